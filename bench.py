@@ -6,8 +6,13 @@ frame (demo scene 1 @1920x1080, reflections on, frozen at time 0) per GPU in the
 job.  Scene data and the frame buffers are resident in HBM when the timed region
 starts.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps, writes the last timed step's frame(s) if
+--dump-outputs is given, and prints the result line.  --full adds what takes runs of its own: the
+correctness gate against the reference's frame, the check of the frames the timed steps produced,
+the kernel's isolated launch time with the roofline figures, and the CPU baseline.
 
 Multi-GPU (quadray-engine_amd/sharding.py, DESIGN.md "Multi-GPU"): every step renders N
 frames; each frame's 8-row tile rows are dealt to the N ranks in contiguous blocks
@@ -218,23 +223,48 @@ def cpu_baseline(workload, rays_per_frame, gpu_frame=None, frames_budget_s=12.0)
                 sample=f"{n} frames of the same workload with oracle/qr_oracle.c (scalar C + OpenMP), median {ms:.3f} ms/frame")
 
 
+DUMP_LIMIT_BYTES = 60 << 20     # all --dump-outputs files together, .npy headers included, stay under 64 MB
+
+
+def dump_outputs(path, frames):
+    """The frames the last timed step left on this rank, as DIR/frame.npy (DIR/frame<f>.npy for several): float32
+    [H, W, 3] of the 8-bit R, G, B channels of the 0x00RRGGBB pixels.  A frame over its share of DUMP_LIMIT_BYTES is
+    cut to a fixed, seeded sample of pixels, [n, 3], with the flat pixel indices beside it (frame*_sample_index.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(frames)
+    for f, fr in enumerate(frames):
+        name = "frame" if len(frames) == 1 else f"frame{f}"
+        px = fr.cpu().numpy().view(np.uint32)
+        rgb = ((px[..., None] >> np.array([16, 8, 0], dtype=np.uint32)) & 0xFF).astype(np.float32)
+        if rgb.nbytes > share:
+            n = share // (3 * 4 + 8)
+            idx = np.sort(np.random.default_rng(0).choice(px.size, n, replace=False))
+            np.save(os.path.join(path, name + "_sample_index.npy"), idx.astype(np.float64))
+            rgb = rgb.reshape(-1, 3)[idx]
+        np.save(os.path.join(path, name + ".npy"), rgb)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=2000, help="timed steps")
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--workload", default="demo1_1080p", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the reference-frame gate, the check of the timed frames, the kernel's isolated launch time with "
+                         "the roofline figures and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame(s) of the last timed step to DIR/*.npy")
     ap.add_argument("--inflight", type=int, default=3, help="steps (frames per GPU) in flight, each on its own streams")
-    ap.add_argument("--min-region-ms", type=float, default=250.0,
-                    help="repeat the --steps pass back to back until the timed region lasts at least this long")
-    ap.add_argument("--repetitions", type=int, default=0, help="passes of --steps inside the timed region (0: from --min-region-ms)")
     ap.add_argument("--split-frame", action="store_true",
                     help="N > 1: ONE frame per step, its 8-row tile rows dealt round-robin over the N ranks and gathered on rank 0 "
                          "(strong scaling: north_star's 'tiles sharded across the GPUs, final image gathered'); default: N frames per step (weak)")
     ap.add_argument("--gather", action="store_true",
                     help="N > 1: gather every frame on rank 0 (north_star's wording) instead of frame f on rank f")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -269,21 +299,23 @@ def main():
     rays_per_frame = rc.total()
     samples_per_frame = rc.primary
 
-    # CORRECTNESS GATE, before anything is timed: the frame of the timed kernel variant must have the
+    # --full: CORRECTNESS GATE, before anything is timed: the frame of the timed kernel variant must have the
     # fingerprint of the reference's frame (tests/golden/manifest.json).  No timing is reported otherwise.
-    want_hash = golden_hash(snap)
-    gate = scn.new_frame()
-    scn.render(gate)
-    torch.cuda.synchronize()
-    frame_check = {"kind": "none: no reference frame exists for this workload", "ok": None}
-    if want_hash is not None:
-        got = qr.frame_hash(gate)
-        frame_check = {"kind": "FNV-1a-64 of the whole frame == the reference's (tests/golden/manifest.json)",
-                       "hash": f"{got:016x}", "ok": got == want_hash}
-        if got != want_hash:
-            print(json.dumps({"error": "rendered frame differs from the reference frame", "workload": args.workload,
-                              "hash": f"{got:016x}", "expected": f"{want_hash:016x}"}), flush=True)
-            raise SystemExit(2)
+    gate, frame_check = None, None
+    if args.full:
+        want_hash = golden_hash(snap)
+        gate = scn.new_frame()
+        scn.render(gate)
+        torch.cuda.synchronize()
+        frame_check = {"kind": "none: no reference frame exists for this workload", "ok": None}
+        if want_hash is not None:
+            got = qr.frame_hash(gate)
+            frame_check = {"kind": "FNV-1a-64 of the whole frame == the reference's (tests/golden/manifest.json)",
+                           "hash": f"{got:016x}", "ok": got == want_hash}
+            if got != want_hash:
+                print(json.dumps({"error": "rendered frame differs from the reference frame", "workload": args.workload,
+                                  "hash": f"{got:016x}", "expected": f"{want_hash:016x}"}), flush=True)
+                raise SystemExit(2)
 
     ex = sharding.FrameExchange(H, W, N, rank)
     # --inflight steps are in flight (one render target set and one HIP stream each), so the long recursion
@@ -368,100 +400,65 @@ def main():
         step(i)
     flush()
     torch.cuda.synchronize()
-    # How long is one pass of --steps?  A region of a millisecond (the driver's --steps 20 at 0.05 ms per step) measures the
-    # ramp and the drain of the launch pipeline, not the steps: the pass is REPEATED back to back inside the one timed region
-    # until the region lasts >= --min-region-ms (0.25 s), HIP events on every stream mark the boundaries between repetitions
-    # (no synchronisation inside the region: the pipeline stays as full as in a long run), and ms_per_step is the MEDIAN
-    # repetition.  The whole region is still bracketed by barrier + synchronize, and its own mean is reported beside it.
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        step(i)
-    flush()
-    torch.cuda.synchronize()
-    probe_ms = (time.perf_counter() - t0) * 1e3
-    if N > 1:
-        # every rank must run the same number of passes (the exchanges are collective): agree on the slowest rank's probe
-        t = torch.tensor([probe_ms], device="cuda", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        probe_ms = float(t.item())
-    R = 1
-    if args.repetitions > 0:
-        R = args.repetitions
-    elif probe_ms < args.min_region_ms:
-        R = int(min(100000, max(3, -(-args.min_region_ms // max(probe_ms, 1e-3)))))
-    all_streams = streams + ([comm] if N > 1 else [])
+    # ONE timed region of exactly --steps steps, barrier + synchronize on both sides, no synchronisation inside (the launch
+    # pipeline stays full); its ramp and drain weigh 1/steps, so short regions read slow: choose --steps from ms_per_step.
     if N > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    marks = [[torch.cuda.Event(enable_timing=True) for _ in all_streams] for _ in range(R + 1)]
     t0 = time.perf_counter()
     state["timed"] = True
-    for e, s_ in zip(marks[0], all_streams):
-        e.record(s_)
-    for r in range(R):
-        for i in range(args.steps):
-            step(r * args.steps + i)
-        flush()
-        for e, s_ in zip(marks[r + 1], all_streams):
-            e.record(s_)
+    for i in range(args.steps):
+        step(i)
+    flush()
     state["timed"] = False
     torch.cuda.synchronize()
     if N > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    dt_region = time.perf_counter() - t0
-    # boundary r = the moment the LAST stream passed its mark (the streams start idle and together: marks[0] are equal within
-    # the time it takes to record them)
-    bounds = [max(marks[0][0].elapsed_time(e) for e in marks[r]) for r in range(R + 1)]
-    # Short passes (the driver's --steps 20 = 0.85 ms) do not end on the same stream each time (20 steps over 3 streams), so single
-    # passes alternate between two lengths; the median is taken over GROUPS of consecutive passes of >= 20 ms each (at least 3
-    # groups, at most 15): per-step time of a group = its span / its steps.
-    per_group = max(1, min(R // 3 if R >= 3 else 1, int(-(-20.0 // max(probe_ms, 1e-3)))))
-    n_groups = R // per_group
-    grp_ms = sorted((bounds[(g + 1) * per_group] - bounds[g * per_group]) / per_group for g in range(n_groups))
-    rep_ms = sorted(bounds[r + 1] - bounds[r] for r in range(R))
-    if n_groups >= 3:
-        dt = grp_ms[n_groups // 2] * 1e-3             # the median group, as the time of ONE pass of --steps steps
-    else:
-        dt = dt_region / R                            # too few passes for a median: the region's own mean
+    dt = time.perf_counter() - t0
     if N > 1:
-        t = torch.tensor([dt, dt_region], device="cuda", dtype=torch.float64)
+        t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, dt_region = float(t[0].item()), float(t[1].item())
-    total_steps = R * args.steps
-    timing = {"repetitions": R, "steps_per_repetition": args.steps, "timed_region_ms": dt_region * 1e3,
-              "ms_per_step_region_mean": dt_region / total_steps * 1e3,
-              "ms_per_step_median_group": dt / args.steps * 1e3,
-              "passes_per_group": per_group, "groups": n_groups,
-              "ms_per_step_min_group": grp_ms[0] / args.steps, "ms_per_step_max_group": grp_ms[-1] / args.steps,
-              "ms_per_step_min_rep": rep_ms[0] / args.steps, "ms_per_step_max_rep": rep_ms[-1] / args.steps,
-              "how": "one timed region (barrier + synchronize on both sides) of `repetitions` back-to-back passes of `steps` steps; "
-                     "HIP events on every launch stream mark the pass boundaries; ms_per_step = median over groups of consecutive passes "
-                     "(>= 20 ms each) of group span / group steps" + ("" if n_groups >= 3 else " (fewer than 3 groups: the region's mean)")}
+        dt = float(t.item())
+    timing = {"timed_region_ms": dt * 1e3,
+              "how": "one timed region of `steps` steps (barrier + synchronize on both sides); ms_per_step = region / steps"}
+    last = (args.steps - 1) % B
 
-    # the frames the TIMED steps produced are checked too: every buffer still in flight at the end
-    ok = True
-    if N > 1:
-        # the assembled frame must equal a whole-frame render of this rank (which passed the gate above)
-        last = (total_steps - 1) % B
+    if args.dump_outputs and rank == 0:
         if split:
-            ok = bool((gate == finals[last][:H]).all().item()) if rank == 0 else True
+            outs = [finals[last][:H]]
+        elif N == 1:
+            outs = [frames[last][0]]
         elif args.gather:
-            ok = all(bool((gate == g).all().item()) for g in gfinals[last]) if rank == 0 else True
+            outs = gfinals[last]
         else:
-            ok = bool((gate == finals[last]).all().item())
-        flag = torch.tensor([1 if ok else 0], device="cuda")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        ok = bool(flag.item())
-    else:
-        for b in range(min(B, total_steps + args.warmup)):
-            ok = ok and bool((gate == frames[b][0]).all().item())
-    frame_check["timed_frames_match"] = ok
-    if not ok:
-        if rank == 0:
-            print(json.dumps({"error": "a frame produced inside the timed region differs from the checked frame",
-                              "workload": args.workload}), flush=True)
-        raise SystemExit(3)
+            outs = [finals[last]]
+        dump_outputs(args.dump_outputs, outs)
+
+    # --full: the frames the TIMED steps produced are checked too: every buffer still in flight at the end
+    ok = None
+    if args.full:
+        ok = True
+        if N > 1:
+            # the assembled frame must equal a whole-frame render of this rank (which passed the gate above)
+            if split:
+                ok = bool((gate == finals[last][:H]).all().item()) if rank == 0 else True
+            elif args.gather:
+                ok = all(bool((gate == g).all().item()) for g in gfinals[last]) if rank == 0 else True
+            else:
+                ok = bool((gate == finals[last]).all().item())
+            flag = torch.tensor([1 if ok else 0], device="cuda")
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            ok = bool(flag.item())
+        else:
+            for b in range(min(B, args.steps + args.warmup)):
+                ok = ok and bool((gate == frames[b][0]).all().item())
+        frame_check["timed_frames_match"] = ok
+        if not ok:
+            if rank == 0:
+                print(json.dumps({"error": "a frame produced inside the timed region differs from the checked frame",
+                                  "workload": args.workload}), flush=True)
+            raise SystemExit(3)
     collective = None
     if N > 1:
         devs = [None] * N
@@ -478,18 +475,19 @@ def main():
             collective.update(exchange_groups=len(ms), exchange_ms_per_group=sum(ms) / len(ms), exchange_ms_per_step=sum(ms) / max(1, steps_x),
                               exchange_ms_max_group=max(ms))
 
-    # dominant-kernel duration: HIP events recorded on the launch stream around full-frame launches
-    scn.set_rows(0, H, 0, 1)
-    scn.set_tile_rows(0, 1)
-    avg_ms, min_ms = scn.render_timed(frames[0][0], max(20, min(args.steps, 200)), stream=compute)
-    torch.cuda.synchronize()
+    if args.full:
+        # dominant-kernel duration: HIP events recorded on the launch stream around full-frame launches
+        scn.set_rows(0, H, 0, 1)
+        scn.set_tile_rows(0, 1)
+        avg_ms, min_ms = scn.render_timed(frames[0][0], max(20, min(args.steps, 200)), stream=compute)
+        torch.cuda.synchronize()
 
     if rank == 0:
-        frames_done = args.steps * (1 if split else N)  # per pass of --steps; dt is the median pass
+        frames_done = args.steps * (1 if split else N)
         total_rays = rays_per_frame * frames_done
         value = total_rays / dt / 1e6
         cpu = None
-        if N == 1 and not args.no_cpu_baseline:
+        if args.full and N == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.workload, rays_per_frame, gpu_frame=gate.cpu().numpy().view("uint32"))
             band = cpu.get("band") if cpu else None
             if band is not None and "gpu_pixels_differ" in band:
@@ -498,94 +496,96 @@ def main():
                 if band["gpu_pixels_differ"] != 0:
                     print(json.dumps({"error": "rendered rows differ from the oracle", "workload": args.workload}), flush=True)
                     raise SystemExit(2)
-        # Which roofline: the path is scalar-per-ray fp32 VALU work -> the VECTOR ALU is the primary
-        # bound; peak = the FMA-counting fp32 vector peak (bit-exactness forbids contraction, so half of it is the most
-        # un-fused arithmetic can reach).  TWO counts of the algorithmic fp32 operations of a frame exist, both with the
-        # weights of SURVEY 8(d) (div and sqrt = 1), and EVERY workload's line carries both with both fractions:
-        #   flops_oracle  the reference's algorithm as the CPU restatement executes it: every element of every list
-        #                 walked, no cull (tests/golden/work.json "deferred"; for a scene the oracle cannot walk whole --
-        #                 config 5 -- its count on a band of rows scaled by rays: "oracle_band", or this run's cpu_baseline band)
-        #   flops_kernel  the same weights added by every lane of the kernel for each step it actually executes
-        #                 (QR_PROF build, tools/gpu_work.py: work.json "kernel"); the culls' own arithmetic is not in it
-        # `achieved` / `frac` use the oracle's count where it covers the whole frame (SURVEY 8(d) defines the figure by the CPU
-        # restatement's counters), else the kernel's, and `basis` says which; achieved_oracle / frac_oracle and achieved_kernel /
-        # frac_kernel always stand beside them.  All over the kernel's mean launch duration measured here with HIP events.
-        work_all = all_work(snap)
-        flops_oracle, oracle_src, flops_kernel, kernel_src = None, None, None, None
-        d = work_all.get("deferred")
-        if d is not None and d.get("rays") == rays_per_frame and "kernel-side" not in d.get("source", ""):
-            flops_oracle, oracle_src = d["flops"], "oracle count of the whole frame, tests/golden/work.json"
-        elif cpu is not None and cpu.get("band"):
-            flops_oracle = int(cpu["band"]["flops"] / max(1, cpu["band"]["rays"]) * rays_per_frame)
-            oracle_src = (f"oracle count on rows {cpu['band']['rows'][0]}..{cpu['band']['rows'][1]} of this run's cpu_baseline, scaled by rays "
-                          "(the oracle walks the LISTS of this scene; the kernel walks grids)")
-        elif work_all.get("oracle_band") is not None:
-            ob = work_all["oracle_band"]
-            flops_oracle = int(ob["flops"] / max(1, ob["rays"]) * rays_per_frame)
-            oracle_src = f"oracle count on rows {ob['rows'][0]}..{ob['rows'][1]} (tests/golden/work.json oracle_band), scaled by rays"
-        k = work_all.get("kernel")
-        if k is not None and k.get("rays") == rays_per_frame:
-            flops_kernel, kernel_src = k["flops"], k.get("source", "kernel-side count") + ", tests/golden/work.json"
-        counters = committed_counters(args.workload)
-        if counters is not None and counters.get("stale"):
-            roofline_stale, counters = counters, None
-        else:
-            roofline_stale = None
-        roofline = dict(bound="valu", achieved=None, peak=VALU_PEAK_TFLOPS, unit="TFLOP/s", frac=None,
-                        basis="flops_oracle" if flops_oracle is not None else ("flops_kernel" if flops_kernel is not None else None),
-                        traffic=(counters or {}).get("hbm_bytes_per_launch"),
-                        kernel=qr.lib().qr_kernel_name().decode(), kernel_avg_ms=avg_ms, kernel_min_ms=min_ms,
-                        flops_oracle=flops_oracle, flops_oracle_source=oracle_src,
-                        flops_kernel=flops_kernel, flops_kernel_source=kernel_src)
-        if roofline_stale is not None:
-            roofline["counters"] = roofline_stale
-        for name, fl in (("oracle", flops_oracle), ("kernel", flops_kernel)):
-            if fl is not None:
-                tf = fl / (avg_ms * 1e-3) / 1e12
-                roofline[f"achieved_{name}"] = tf
-                roofline[f"frac_{name}"] = tf / VALU_PEAK_TFLOPS
-        # headline basis: the oracle's count where it counted the WHOLE frame (every reference scene); where it only has a band of
-        # rows to scale (config 5: its list walk costs 6 000 operations a ray, the kernel's grid walk 26), the kernel's own count
-        whole = flops_oracle is not None and oracle_src.startswith("oracle count of the whole frame")
-        flops = flops_oracle if (whole or flops_kernel is None) else flops_kernel
-        roofline["basis"] = None if flops is None else ("flops_oracle" if flops is flops_oracle else "flops_kernel")
-        if flops is not None:
-            tf = flops / (avg_ms * 1e-3) / 1e12
-            roofline.update(achieved=tf, frac=tf / VALU_PEAK_TFLOPS, flops_per_launch=flops)
-        if counters is not None and counters.get("thread_cycles_valu") and flops_kernel:
-            # how many vector lane-operations the kernel issues per algorithmic operation it executes (SQ_THREAD_CYCLES_VALU of
-            # the committed counter pass of this build / flops_kernel): the overhead factor of the implementation
-            roofline["valu_lane_ops_per_flop"] = counters["thread_cycles_valu"] / flops_kernel
-            if flops_oracle:
-                roofline["valu_lane_ops_per_flop_oracle"] = counters["thread_cycles_valu"] / flops_oracle
-        # the HBM leg, for the record (deliberate correction of SURVEY 8(d): the kernel reads the scene through the
-        # scalar cache, not once per workgroup, so the algorithmic bytes are one frame write + one scene read)
-        alg_bytes = 4 * W * H + int(scn.info.device_bytes)
-        gbs = alg_bytes / (avg_ms * 1e-3) / 1e9
-        roofline["hbm"] = dict(achieved=gbs, peak=HBM_PEAK_GBS, unit="GB/s", frac=gbs / HBM_PEAK_GBS,
-                               algorithmic_bytes_per_launch=alg_bytes)
-        if counters is not None:
-            roofline["counters"] = counters
-            # What actually bounds the kernel: instruction issue.  MI355X_MICROARCH.md: a CDNA4 SIMD is 32 lanes wide and issues a
-            # wave64 VALU instruction every 2 cycles = 1.2 G wave-instructions/s per SIMD at 2.4 GHz, 1024 SIMDs (peak).  What a
-            # SIMD sustains at the renderer's occupancy was measured with tools/ubench/issue_rate.hip (profiles/r04_valu_issue_rate.txt):
-            # 0.94 G/s at 4 waves per SIMD (0.89 at 2, 1.03 at 8; the chip runs at 2.15-2.3 GHz under that load; SALU instructions
-            # share the slot) -- `measured_ceiling`.  The instruction count is the committed counter value (not measured in this
-            # run), the time is this run's: achieved = issued per launch / kernel time; with several launches in flight the
-            # per-frame rate is the one that counts.
-            insts = sum(counters.get(k, 0.0) for k in ("insts_valu", "insts_salu", "insts_smem", "insts_vmem_rd", "insts_vmem_wr"))
-            if insts > 0:
-                peak = 1.2 * 1024
-                ceiling = 0.94 * 1024
-                per_launch = insts / (avg_ms * 1e-3) / 1e9
-                per_frame = insts * args.steps / dt / 1e9       # one frame's worth of instructions per GPU and step (median pass)
-                roofline["issue"] = dict(unit="G wave-instructions/s", peak=peak, measured_ceiling=ceiling, wave_instructions_per_launch=insts,
-                                         achieved_isolated_launch=per_launch, frac_isolated_launch=per_launch / peak,
-                                         achieved_in_flight=per_frame, frac_in_flight=per_frame / peak,
-                                         frac_in_flight_of_measured_ceiling=per_frame / ceiling,
-                                         source="MI355X_MICROARCH.md (peak: SIMD-32, 2 cycles per wave64 VALU), profiles/r04_valu_issue_rate.txt "
-                                                "(measured ceiling), profiles/counters.json (count), this run (time)",
-                                         measured_in_this_run=False)
+        roofline = None
+        if args.full:
+            # Which roofline: the path is scalar-per-ray fp32 VALU work -> the VECTOR ALU is the primary
+            # bound; peak = the FMA-counting fp32 vector peak (bit-exactness forbids contraction, so half of it is the most
+            # un-fused arithmetic can reach).  TWO counts of the algorithmic fp32 operations of a frame exist, both with the
+            # weights of SURVEY 8(d) (div and sqrt = 1), and EVERY workload's line carries both with both fractions:
+            #   flops_oracle  the reference's algorithm as the CPU restatement executes it: every element of every list
+            #                 walked, no cull (tests/golden/work.json "deferred"; for a scene the oracle cannot walk whole --
+            #                 config 5 -- its count on a band of rows scaled by rays: "oracle_band", or this run's cpu_baseline band)
+            #   flops_kernel  the same weights added by every lane of the kernel for each step it actually executes
+            #                 (QR_PROF build, tools/gpu_work.py: work.json "kernel"); the culls' own arithmetic is not in it
+            # `achieved` / `frac` use the oracle's count where it covers the whole frame (SURVEY 8(d) defines the figure by the CPU
+            # restatement's counters), else the kernel's, and `basis` says which; achieved_oracle / frac_oracle and achieved_kernel /
+            # frac_kernel always stand beside them.  All over the kernel's mean launch duration measured here with HIP events.
+            work_all = all_work(snap)
+            flops_oracle, oracle_src, flops_kernel, kernel_src = None, None, None, None
+            d = work_all.get("deferred")
+            if d is not None and d.get("rays") == rays_per_frame and "kernel-side" not in d.get("source", ""):
+                flops_oracle, oracle_src = d["flops"], "oracle count of the whole frame, tests/golden/work.json"
+            elif cpu is not None and cpu.get("band"):
+                flops_oracle = int(cpu["band"]["flops"] / max(1, cpu["band"]["rays"]) * rays_per_frame)
+                oracle_src = (f"oracle count on rows {cpu['band']['rows'][0]}..{cpu['band']['rows'][1]} of this run's cpu_baseline, scaled by rays "
+                              "(the oracle walks the LISTS of this scene; the kernel walks grids)")
+            elif work_all.get("oracle_band") is not None:
+                ob = work_all["oracle_band"]
+                flops_oracle = int(ob["flops"] / max(1, ob["rays"]) * rays_per_frame)
+                oracle_src = f"oracle count on rows {ob['rows'][0]}..{ob['rows'][1]} (tests/golden/work.json oracle_band), scaled by rays"
+            k = work_all.get("kernel")
+            if k is not None and k.get("rays") == rays_per_frame:
+                flops_kernel, kernel_src = k["flops"], k.get("source", "kernel-side count") + ", tests/golden/work.json"
+            counters = committed_counters(args.workload)
+            if counters is not None and counters.get("stale"):
+                roofline_stale, counters = counters, None
+            else:
+                roofline_stale = None
+            roofline = dict(bound="valu", achieved=None, peak=VALU_PEAK_TFLOPS, unit="TFLOP/s", frac=None,
+                            basis="flops_oracle" if flops_oracle is not None else ("flops_kernel" if flops_kernel is not None else None),
+                            traffic=(counters or {}).get("hbm_bytes_per_launch"),
+                            kernel=qr.lib().qr_kernel_name().decode(), kernel_avg_ms=avg_ms, kernel_min_ms=min_ms,
+                            flops_oracle=flops_oracle, flops_oracle_source=oracle_src,
+                            flops_kernel=flops_kernel, flops_kernel_source=kernel_src)
+            if roofline_stale is not None:
+                roofline["counters"] = roofline_stale
+            for name, fl in (("oracle", flops_oracle), ("kernel", flops_kernel)):
+                if fl is not None:
+                    tf = fl / (avg_ms * 1e-3) / 1e12
+                    roofline[f"achieved_{name}"] = tf
+                    roofline[f"frac_{name}"] = tf / VALU_PEAK_TFLOPS
+            # headline basis: the oracle's count where it counted the WHOLE frame (every reference scene); where it only has a band of
+            # rows to scale (config 5: its list walk costs 6 000 operations a ray, the kernel's grid walk 26), the kernel's own count
+            whole = flops_oracle is not None and oracle_src.startswith("oracle count of the whole frame")
+            flops = flops_oracle if (whole or flops_kernel is None) else flops_kernel
+            roofline["basis"] = None if flops is None else ("flops_oracle" if flops is flops_oracle else "flops_kernel")
+            if flops is not None:
+                tf = flops / (avg_ms * 1e-3) / 1e12
+                roofline.update(achieved=tf, frac=tf / VALU_PEAK_TFLOPS, flops_per_launch=flops)
+            if counters is not None and counters.get("thread_cycles_valu") and flops_kernel:
+                # how many vector lane-operations the kernel issues per algorithmic operation it executes (SQ_THREAD_CYCLES_VALU of
+                # the committed counter pass of this build / flops_kernel): the overhead factor of the implementation
+                roofline["valu_lane_ops_per_flop"] = counters["thread_cycles_valu"] / flops_kernel
+                if flops_oracle:
+                    roofline["valu_lane_ops_per_flop_oracle"] = counters["thread_cycles_valu"] / flops_oracle
+            # the HBM leg, for the record (deliberate correction of SURVEY 8(d): the kernel reads the scene through the
+            # scalar cache, not once per workgroup, so the algorithmic bytes are one frame write + one scene read)
+            alg_bytes = 4 * W * H + int(scn.info.device_bytes)
+            gbs = alg_bytes / (avg_ms * 1e-3) / 1e9
+            roofline["hbm"] = dict(achieved=gbs, peak=HBM_PEAK_GBS, unit="GB/s", frac=gbs / HBM_PEAK_GBS,
+                                   algorithmic_bytes_per_launch=alg_bytes)
+            if counters is not None:
+                roofline["counters"] = counters
+                # What actually bounds the kernel: instruction issue.  MI355X_MICROARCH.md: a CDNA4 SIMD is 32 lanes wide and issues a
+                # wave64 VALU instruction every 2 cycles = 1.2 G wave-instructions/s per SIMD at 2.4 GHz, 1024 SIMDs (peak).  What a
+                # SIMD sustains at the renderer's occupancy was measured with tools/ubench/issue_rate.hip (profiles/r04_valu_issue_rate.txt):
+                # 0.94 G/s at 4 waves per SIMD (0.89 at 2, 1.03 at 8; the chip runs at 2.15-2.3 GHz under that load; SALU instructions
+                # share the slot) -- `measured_ceiling`.  The instruction count is the committed counter value (not measured in this
+                # run), the time is this run's: achieved = issued per launch / kernel time; with several launches in flight the
+                # per-frame rate is the one that counts.
+                insts = sum(counters.get(k, 0.0) for k in ("insts_valu", "insts_salu", "insts_smem", "insts_vmem_rd", "insts_vmem_wr"))
+                if insts > 0:
+                    peak = 1.2 * 1024
+                    ceiling = 0.94 * 1024
+                    per_launch = insts / (avg_ms * 1e-3) / 1e9
+                    per_frame = insts * args.steps / dt / 1e9       # one frame's worth of instructions per GPU and step
+                    roofline["issue"] = dict(unit="G wave-instructions/s", peak=peak, measured_ceiling=ceiling, wave_instructions_per_launch=insts,
+                                             achieved_isolated_launch=per_launch, frac_isolated_launch=per_launch / peak,
+                                             achieved_in_flight=per_frame, frac_in_flight=per_frame / peak,
+                                             frac_in_flight_of_measured_ceiling=per_frame / ceiling,
+                                             source="MI355X_MICROARCH.md (peak: SIMD-32, 2 cycles per wave64 VALU), profiles/r04_valu_issue_rate.txt "
+                                                    "(measured ceiling), profiles/counters.json (count), this run (time)",
+                                             measured_in_this_run=False)
         out = {
             "metric": "Mrays/s (primary+secondary)", "value": value, "unit": "Mrays/s",
             "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
@@ -598,13 +598,13 @@ def main():
                        "rays": rc.as_dict(),
                        "parallelism": (f"one frame per step, tile rows round-robin over {N} ranks, gathered on rank 0 per {D} steps" if split else
                                        f"tile-row blocks x{N}, 1 multi-target launch/step, 1 grouped exchange per {D} steps") if N > 1 else "single GPU",
-                       "fps": frames_done / dt, "msamples_per_s": samples_per_frame * frames_done / dt / 1e6,
-                       "frame_check": frame_check, "assembled_frame_matches": ok},
+                       "fps": frames_done / dt, "msamples_per_s": samples_per_frame * frames_done / dt / 1e6},
             "timing": timing,
             "lib": qr.lib().qr_version().decode(),
-            "roofline": roofline,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            out["config"].update(frame_check=frame_check, assembled_frame_matches=ok)
+            out.update(roofline=roofline, cpu_baseline=cpu)
         if collective is not None:
             out["collective"] = collective
         print(json.dumps(out), flush=True)

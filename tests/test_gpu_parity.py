@@ -167,7 +167,7 @@ def test_gpu_two_rank_bench_path_on_one_gpu(ranks, mode):
     env = dict(os.environ, QR_BENCH_SAME_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "7", "--warmup", "2",
-           "--workload", "demo2_1080p_gf_d3", "--no-cpu-baseline"] + mode
+           "--workload", "demo2_1080p_gf_d3", "--full", "--no-cpu-baseline"] + mode
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

@@ -4,10 +4,10 @@ TAG=${1:-r04}
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out; mkdir -p $O
 python3 $R/tools/archive_src.py >/dev/null 2>&1 || true
 cd $R
-python3 bench.py > $O/${TAG}_final_bench_n1.json 2> $O/${TAG}_final_bench_n1.err; tail -c 200 $O/${TAG}_final_bench_n1.json; echo
-python3 bench.py --steps 20 --warmup 5 > $O/${TAG}_final_bench_steps20.json 2>/dev/null
+python3 bench.py --full > $O/${TAG}_final_bench_n1.json 2> $O/${TAG}_final_bench_n1.err; tail -c 200 $O/${TAG}_final_bench_n1.json; echo
+python3 bench.py --steps 20 --warmup 5 --full > $O/${TAG}_final_bench_steps20.json 2>/dev/null
 for w in demo1_1080p_d0 demo2_1080p_gf_d3 demo2_2160p_aa4 swarm_1080p synth10k_4320p; do
-  python3 bench.py --workload $w --steps 100 --warmup 10 > $O/${TAG}_final_bench_$w.json 2> $O/${TAG}_final_bench_$w.err || echo "FAILED $w"
+  python3 bench.py --workload $w --steps 100 --warmup 10 --full > $O/${TAG}_final_bench_$w.json 2> $O/${TAG}_final_bench_$w.err || echo "FAILED $w"
 done
 python3 - <<PY
 import json,os
