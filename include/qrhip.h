@@ -146,6 +146,12 @@ int qr_scene_upload(const void *blob, uint64_t size, int device, qr_device_scene
  */
 #define QR_UPLOAD_REBIN_TILES 1u
 int qr_scene_upload_ex(const void *blob, uint64_t size, int device, uint32_t flags, qr_device_scene **out);
+/*
+ * QR_UPLOAD_RAY_QUERIES also compiles the snapshot's global list (qr_frame.clist) into the image, as a secondary-ray list
+ * (same cells, culls, grids and flags as every other list the walk takes; nothing in it depends on the camera): the list
+ * qr_trace_rays_async / qr_occluded_async walk.  Without the flag the image is what it was before the flag existed.
+ */
+#define QR_UPLOAD_RAY_QUERIES 2u
 int qr_scene_destroy(qr_device_scene *scn);
 
 /*
@@ -167,6 +173,9 @@ typedef struct qr_program_info
     uint32_t n_dda;             /* uniform grids built over long lists                        */
 } qr_program_info;
 int qr_program_stats(const void *blob, uint64_t size, qr_program_info *info);
+/* qr_program_stats with upload flags (QR_UPLOAD_*): reports the image qr_scene_upload_ex would build with them.  Host only,
+ * so a CPU build can compile and verify the ray-query list (QR_UPLOAD_REBIN_TILES needs the GPU and is refused here). */
+int qr_program_stats_ex(const void *blob, uint64_t size, uint32_t flags, qr_program_info *info);
 
 /*
  * Host-only: build per-surface shadow, reflection / refraction and light lists for a snapshot that carries one
@@ -250,6 +259,37 @@ int qr_render_host(qr_device_scene *scn, uint32_t *frame_host, int row_pixels);
  */
 int qr_render_timed(qr_device_scene *scn, void *frame_dev, void *stream,
                     int iters, float *avg_ms, float *min_ms);
+
+/*
+ * Ray queries: what do caller-supplied rays hit?  For picking, collision and visibility probes, a host's own AO / light-probe
+ * passes or any secondary-ray work outside the renderer.  The scene must have been uploaded with QR_UPLOAD_RAY_QUERIES
+ * (else QR_ERR_UNSUP).  The query walks the snapshot's global list (qr_frame.clist) and sees exactly what it holds -- a surface
+ * the engine left out of that list is not there for a query either.  It is the renderer's walk: the same solvers, clippers
+ * and fp32 arithmetic as a primary ray, so a camera ray (quadray-engine_amd/rays.py camera_rays) hits what the pixel shows.
+ *   - A hit counts when tmin < t < tmax (open interval), t in units of |dir| (dir need not be unit length).  tmax = +inf is
+ *     taken as FLT_MAX (the value the engine's cameras use): the two give identical results.
+ *   - Closest hit: of equal t, the surface first in list order wins, as in the renderer (strict depth compare).
+ *   - Occlusion: any hit in the interval on a surface that casts a shadow by the renderer's rule (CHECK_SHAD): light
+ *     surfaces and transparent surfaces that do not refract cast none, per side hit.
+ *   - No self-exclusion: a ray that starts on a surface excludes it through tmin.
+ *   - Path-tracer mode, rebuilt tiles, depth and row selections do not apply; the query runs on the scene's own device
+ *     (QR_DEVICES banding does not apply) and is asynchronous on `stream` (hipStream_t, NULL = default stream).
+ * Arguments: rays_dev, t_out_dev, id_out_dev, occ_out_dev are DEVICE memory of n elements; rays_dev 16-byte aligned.
+ * n == 0 returns QR_OK without a launch; a null pointer, a misaligned rays_dev or n > INT32_MAX give QR_ERR_ARG.
+ */
+typedef struct qr_ray { float org[3]; float tmin; float dir[3]; float tmax; } qr_ray;   /* 32 bytes */
+
+#define QR_TRACE_COHERENT 1u    /* the caller vouches that consecutive rays are neighbours (e.g. 8x8 pixel blocks): packet
+                                   walks are allowed on long lists, as for primary rays.  Results do not depend on it. */
+
+/* closest hit: t_out[i] = t of the hit (tmax when none; FLT_MAX for +inf), id_out[i] = surface_index << 1 | side (-1 = none): the encoding of
+ * qr_render_ids_async */
+int qr_trace_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n,
+                        float *t_out_dev, int32_t *id_out_dev, uint32_t flags, void *stream);
+
+/* occlusion: occ_out[i] = 1 when some hit with tmin < t < tmax casts a shadow (CHECK_SHAD), else 0 */
+int qr_occluded_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n,
+                      uint8_t *occ_out_dev, uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* 3. Misc                                                                   */

@@ -18,9 +18,9 @@ LIB_PATH = os.environ.get("QR_LIB") or os.path.join(_HERE, "libqrhip.so")   # QR
 # every symbol include/qrhip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "qr_render0", "qr_capture_snapshot", "qr_flatten", "qr_free",
-    "qr_scene_upload", "qr_scene_upload_ex", "qr_program_stats", "qr_snapshot_build_lists_c", "qr_scene_destroy", "qr_scene_get_info", "qr_scene_set_depth", "qr_scene_set_pt",
+    "qr_scene_upload", "qr_scene_upload_ex", "qr_program_stats", "qr_program_stats_ex", "qr_snapshot_build_lists_c", "qr_scene_destroy", "qr_scene_get_info", "qr_scene_set_depth", "qr_scene_set_pt",
     "qr_scene_set_rows", "qr_scene_set_tile_rows", "qr_render_async", "qr_render_multi_async", "qr_render_ids_async",
-    "qr_render_count", "qr_render_host", "qr_render_timed",
+    "qr_render_count", "qr_render_host", "qr_render_timed", "qr_trace_rays_async", "qr_occluded_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -29,6 +29,8 @@ ABI_SYMBOLS = [
 
 
 UPLOAD_REBIN_TILES = 1
+UPLOAD_RAY_QUERIES = 2      # also compile the global list for Scene.trace / Scene.occluded
+TRACE_COHERENT = 1          # qr_trace_rays_async / qr_occluded_async flag: consecutive rays are neighbours
 
 
 class QrError(RuntimeError):
@@ -87,6 +89,9 @@ def lib():
     L.qr_scene_upload_ex.argtypes = [vp, cu64, ci, ctypes.c_uint32, ctypes.POINTER(vp)]
     L.qr_scene_destroy.argtypes = [vp]
     L.qr_program_stats.argtypes = [vp, cu64, ctypes.POINTER(ProgramInfo)]
+    L.qr_program_stats_ex.argtypes = [vp, cu64, ctypes.c_uint32, ctypes.POINTER(ProgramInfo)]
+    L.qr_trace_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
+    L.qr_occluded_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
     L.qr_frame_hash.argtypes = [vp, cu64]
@@ -269,24 +274,29 @@ def hierarchy_records_after_apply(blob, nodes, opts):
     return nodes
 
 
-def program_stats(blob):
-    """Validate + compile a snapshot on the host (no GPU): the device image's size and cell counts."""
+def program_stats(blob, flags=0):
+    """Validate + compile a snapshot on the host (no GPU): the device image's size and cell counts.
+    flags: upload flags the image is built with (UPLOAD_RAY_QUERIES; the GPU binning of UPLOAD_REBIN_TILES is refused)."""
     info = ProgramInfo()
     buf = ctypes.create_string_buffer(blob, len(blob))
-    _check(lib().qr_program_stats(buf, len(blob), ctypes.byref(info)))
+    if flags:
+        _check(lib().qr_program_stats_ex(buf, len(blob), flags, ctypes.byref(info)))
+    else:
+        _check(lib().qr_program_stats(buf, len(blob), ctypes.byref(info)))
     return info
 
 
 class Scene:
     """A snapshot resident on one GPU (qr_device_scene)."""
 
-    def __init__(self, blob, device=0, rebin_tiles=False):
+    def __init__(self, blob, device=0, rebin_tiles=False, ray_queries=False):
         """rebin_tiles: rebuild the per-tile lists on the GPU from the camera list
-        (QR_UPLOAD_REBIN_TILES, include/qrhip.h) instead of using the snapshot's."""
+        (QR_UPLOAD_REBIN_TILES, include/qrhip.h) instead of using the snapshot's.
+        ray_queries: also compile the global list for trace() / occluded() (QR_UPLOAD_RAY_QUERIES)."""
         self._h = ctypes.c_void_p()
         self._buf = ctypes.create_string_buffer(blob, len(blob))
-        _check(lib().qr_scene_upload_ex(self._buf, len(blob), device, UPLOAD_REBIN_TILES if rebin_tiles else 0,
-                                        ctypes.byref(self._h)))
+        flags = (UPLOAD_REBIN_TILES if rebin_tiles else 0) | (UPLOAD_RAY_QUERIES if ray_queries else 0)
+        _check(lib().qr_scene_upload_ex(self._buf, len(blob), device, flags, ctypes.byref(self._h)))
         self.device = device
         self.info = SceneInfo()
         _check(lib().qr_scene_get_info(self._h, ctypes.byref(self.info)))
@@ -346,6 +356,39 @@ class Scene:
             _check(lib().qr_render_ids_async(self._h, ctypes.c_void_p(frame.data_ptr()),
                                              ctypes.c_void_p(ids.data_ptr()), sp))
         return frame
+
+    def _rays_arg(self, rays):
+        import torch
+        if not (isinstance(rays, torch.Tensor) and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8
+                and rays.is_contiguous() and rays.is_cuda and rays.device.index == self.device):
+            raise QrError(f"rays must be a contiguous float32 [N, 8] tensor on cuda:{self.device} "
+                          "(org xyz, tmin, dir xyz, tmax per row)")
+        return rays
+
+    def trace(self, rays, stream=None, coherent=False):
+        """Closest hit of every ray (qr_trace_rays_async): rays float32 [N, 8] = (org xyz, tmin, dir xyz, tmax) on the scene's
+        device.  Returns new tensors (t float32 [N]: t of the hit, tmax when none; ids int32 [N]: surface << 1 | side, -1 none).
+        coherent: consecutive rays are neighbours (packet walks on long lists too).  Asynchronous on `stream`."""
+        import torch
+        rays = self._rays_arg(rays)
+        n = rays.shape[0]
+        t = torch.empty(n, dtype=torch.float32, device=rays.device)
+        ids = torch.empty(n, dtype=torch.int32, device=rays.device)
+        _check(lib().qr_trace_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(t.data_ptr()),
+                                         ctypes.c_void_p(ids.data_ptr()), TRACE_COHERENT if coherent else 0,
+                                         self._stream_ptr(stream)))
+        return t, ids
+
+    def occluded(self, rays, stream=None, coherent=False):
+        """Does a surface that casts a shadow (the renderer's rule) lie at tmin < t < tmax on each ray (qr_occluded_async)?
+        Returns a new bool tensor [N].  Asynchronous on `stream`."""
+        import torch
+        rays = self._rays_arg(rays)
+        n = rays.shape[0]
+        occ = torch.empty(n, dtype=torch.uint8, device=rays.device)
+        _check(lib().qr_occluded_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(occ.data_ptr()),
+                                       TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
+        return occ.view(torch.bool)
 
     def render_count(self, frame=None, stream=None):
         if frame is None:

@@ -1047,7 +1047,7 @@ struct Builder
  * tens of thousands of tile chains of two or three elements); compile_list throws Restart at the first chain that is not */
 static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem> &E, const std::vector<int32_t> &T,
                               const qr_frame &frm, const std::vector<BSphere> &bs, QrProgram &out, std::string &err, int sched_blocks,
-                              bool verify, bool assume_short, bool &restart)
+                              bool verify, uint32_t flags, bool assume_short, bool &restart)
 {
     static const bool timing = getenv("QR_COMPILE_TIMING") != nullptr;
     struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
@@ -1206,6 +1206,21 @@ static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem>
         for (int k = 0; k < 3; k++) { b.at<DSurf>(b.o_srf)[n_srf].min[k] = -__builtin_inff(); b.at<DSurf>(b.o_srf)[n_srf].max[k] = __builtin_inff(); }
         b.at<DSurf>(b.o_srf)[n_srf].trn = b.srf_off(n_srf);
         tick("surfaces");
+
+        /* the ray-query list (QR_UPLOAD_RAY_QUERIES): the snapshot's own global list -- never a camera-dependent tile list of the
+         * binning pass -- compiled last, like a secondary-ray list, so that every other record of the image keeps its offset.
+         * It leaves the render path as it is: no box cells for it (the query kernel's walks do not cull on them; a long list
+         * would otherwise restart the build without box cells everywhere) and no say in which kernel instance renders frames. */
+        uint32_t q_off = 0;
+        if (flags & QR_UPLOAD_RAY_QUERIES)
+        {
+            const bool box0 = b.box_ok, long0 = b.any_long;
+            b.box_ok = false;
+            q_off = b.compile_list(v.frame->clist);
+            b.box_ok = box0; b.any_long = long0;
+            if (q_off == 0) q_off = b.alloc(sizeof(CCell), 64);         /* no global list: one END cell, every query misses */
+            tick("query");
+        }
 
         /* wave schedule: one entry {footprint | heaviness << 30, tile-list offset} per wave footprint.
          * heavy = the footprint's tile list holds a reflective or non-opaque surface: those waves can spawn
@@ -1376,8 +1391,10 @@ static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem>
         DevHeader &h = *b.at<DevHeader>(0);
         h.fr = frm;
         h.off_shade = b.o_shd; h.off_tiles = o_til; h.off_order = o_ord; h.n_blocks = (uint32_t)n_waves;
+        h.off_query = q_off;
         b.alloc(64, 64);                    /* tail padding: wide scalar loads of the last record stay inside */
         out.off_order = o_ord; out.n_sched = (uint32_t)n_waves;
+        out.off_query = q_off;
         out.off_srf = b.o_srf; out.off_shade = b.o_shd; out.off_mat = b.o_mat; out.off_lgt = b.o_lgt; out.off_tex = b.o_tex; out.off_tiles = o_til;
         out.n_srf = (uint32_t)n_srf; out.n_mat = (uint32_t)n_mat; out.n_lgt = (uint32_t)n_lgt; out.n_tex = (uint32_t)n_tex; out.n_tiles = (uint32_t)T.size();
         out.off_lists = o_ord + (uint32_t)(n_sched * 8 + 16);
@@ -1401,11 +1418,12 @@ static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem>
 }
 
 int qr_program_build(const qr_scene_view &v, const std::vector<qr_elem> &E, const std::vector<int32_t> &T,
-                     const qr_frame &frm, const std::vector<BSphere> &bs, QrProgram &out, std::string &err, int sched_blocks, bool verify)
+                     const qr_frame &frm, const std::vector<BSphere> &bs, QrProgram &out, std::string &err, int sched_blocks, bool verify,
+                     uint32_t flags)
 {
     bool restart = false;
-    int rc = program_build_once(v, E, T, frm, bs, out, err, sched_blocks, verify, true, restart);
-    if (restart) rc = program_build_once(v, E, T, frm, bs, out, err, sched_blocks, verify, false, restart);
+    int rc = program_build_once(v, E, T, frm, bs, out, err, sched_blocks, verify, flags, true, restart);
+    if (restart) rc = program_build_once(v, E, T, frm, bs, out, err, sched_blocks, verify, flags, false, restart);
     return rc;
 }
 
@@ -1511,7 +1529,9 @@ int qr_program_verify(const QrProgram &p, std::string &err)
     auto vtick = [&](const char *what) { if (!vt) return; struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
         fprintf(stderr, "  verify %-8s %.3f ms\n", what, (t1.tv_sec - vt0.tv_sec) * 1e3 + (t1.tv_nsec - vt0.tv_nsec) * 1e-6); vt0 = t1; };
     const DevHeader *h = (const DevHeader *)b.data();
-    if (h->off_tiles != p.off_tiles || h->off_order != p.off_order || h->off_shade != p.off_shade) return bad("header offsets");
+    if (h->off_tiles != p.off_tiles || h->off_order != p.off_order || h->off_shade != p.off_shade || h->off_query != p.off_query)
+        return bad("header offsets");
+    if (const char *m = check_list(p.off_query)) return bad(m);        /* the ray-query list (0: none) */
     if ((size_t)p.off_tiles + (size_t)p.n_tiles * 4 > limit) return bad("tile array");
     const uint32_t *tl = (const uint32_t *)(b.data() + p.off_tiles);
     /* neighbouring tiles mostly share one program (lists are stored once per content): a head equal to the one just checked
@@ -1617,7 +1637,14 @@ int qr_program_verify(const QrProgram &p, std::string &err)
 /* host-only entry point: validate + compile a snapshot without a device (used by the CPU test-suite) */
 extern "C" int qr_program_stats(const void *blob, uint64_t size, qr_program_info *info)
 {
+    return qr_program_stats_ex(blob, size, 0u, info);
+}
+
+extern "C" int qr_program_stats_ex(const void *blob, uint64_t size, uint32_t flags, qr_program_info *info)
+{
     if (blob == nullptr || info == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (flags & QR_UPLOAD_REBIN_TILES) return qr_fail(QR_ERR_UNSUP, "QR_UPLOAD_REBIN_TILES bins on the GPU: not available to a host-only compile");
+    if (flags & ~QR_UPLOAD_RAY_QUERIES) return qr_fail(QR_ERR_ARG, "unknown upload flags");
     qr_scene_view v;
     const int rc0 = qr_scene_view_init(&v, blob, size);
     if (rc0 != 0) return qr_fail(QR_ERR_ARG, "malformed snapshot (qr_scene_view_init " + std::to_string(rc0) + ")");
@@ -1640,7 +1667,7 @@ extern "C" int qr_program_stats(const void *blob, uint64_t size, qr_program_info
     std::vector<int32_t> T(v.tiles, v.tiles + v.hdr->n_tiles);
     tick("copies");
     QrProgram p;
-    rc = qr_program_build(v, E, T, *v.frame, bs, p, err);
+    rc = qr_program_build(v, E, T, *v.frame, bs, p, err, 0, true, flags);
     if (rc != QR_OK) return qr_fail(rc, err);
     if (const char *dump = getenv("QR_DUMP_IMAGE"))        /* debugging aid: the device image as a file */
         if (FILE *f = fopen(dump, "wb")) { fwrite(p.blob.data(), 1, p.blob.size(), f); fclose(f); }

@@ -8,6 +8,7 @@
  */
 #include "qr_internal.h"
 #include "qr_kernel.hpp"
+#include "qr_query.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -48,6 +49,7 @@ struct qr_device_scene
     size_t n_cells = 0;
     int32_t n_groups = 0;
     bool divk = false;          /* some list is a long hierarchy: launch the kernel instance with the per-lane walk */
+    uint32_t off_query = 0;     /* the ray-query list in the image (QR_UPLOAD_RAY_QUERIES), 0 none */
     /* path-tracer mode (qr_scene_set_pt): what the engine keeps per frame buffer, engine.cpp:2875-2893 */
     bool pt_on = false;
     uint32_t *d_seeds = nullptr; float *d_acc = nullptr;     /* frm_row * frm_h * samples each; d_acc holds r, g, b planes */
@@ -142,7 +144,7 @@ static int build_program(const void *blob, uint64_t size, int device, uint32_t f
         if (rc != QR_OK) return rc;
         phase("rebin");
     }
-    rc = qr_program_build(v, E, T, frm, bsph, prog, err);
+    rc = qr_program_build(v, E, T, frm, bsph, prog, err, 0, true, flags & QR_UPLOAD_RAY_QUERIES);
     if (rc != QR_OK) return qr_fail(rc, err);
     phase("compile");
     hdr = *v.hdr;
@@ -203,6 +205,7 @@ extern "C" int qr_scene_upload_ex(const void *blob, uint64_t size, int device, u
     s->lp.stats = s->d_counters + 4;
     s->fr = frm;
     s->n_cells = n_cells;
+    s->off_query = prog.off_query;
     {
         const char *dv = getenv("QR_DIV");          /* QR_DIV=0 / 1 forces the kernel instance (experiments, tests) */
         s->divk = (dv ? atoi(dv) != 0 : prog.has_long_lists) || prog.has_grids;      /* only that instance knows shadow grids */
@@ -413,6 +416,56 @@ extern "C" int qr_render_async(qr_device_scene *s, void *frame_dev, void *stream
     { const int rc = pt_rows_ok(s); if (rc != QR_OK) return rc; }
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(launch<false>(s, frame_dev, nullptr, (hipStream_t)stream));
+    return QR_OK;
+}
+
+/* ---- ray queries (qr_query.hpp) ---- */
+
+static int query_args(const qr_device_scene *s, const qr_ray *rays, int64_t n, const void *out0, const void *out1, uint32_t flags)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
+    if (flags & ~QR_TRACE_COHERENT) return qr_fail(QR_ERR_ARG, "unknown query flags");
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    if (n == 0) return QR_OK;
+    if (rays == nullptr || out0 == nullptr || out1 == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (((uintptr_t)rays & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays must be 16-byte aligned");
+    return QR_OK;
+}
+
+extern "C" int qr_trace_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,
+                                   float *t_out_dev, int32_t *id_out_dev, uint32_t flags, void *stream)
+{
+    const int rc = query_args(s, rays_dev, n, t_out_dev, id_out_dev, flags);
+    if (rc != QR_OK || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    const f32x4 *r = (const f32x4 *)rays_dev;
+    if (flags & QR_TRACE_COHERENT)
+        hipLaunchKernelGGL((qr_trace_kernel<false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
+                           t_out_dev, id_out_dev, (uint8_t *)nullptr, s->lp.stats);
+    else
+        hipLaunchKernelGGL((qr_trace_kernel<false, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
+                           t_out_dev, id_out_dev, (uint8_t *)nullptr, s->lp.stats);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+extern "C" int qr_occluded_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,
+                                 uint8_t *occ_out_dev, uint32_t flags, void *stream)
+{
+    const int rc = query_args(s, rays_dev, n, occ_out_dev, occ_out_dev, flags);
+    if (rc != QR_OK || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    const f32x4 *r = (const f32x4 *)rays_dev;
+    if (flags & QR_TRACE_COHERENT)
+        hipLaunchKernelGGL((qr_trace_kernel<true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
+                           (float *)nullptr, (int32_t *)nullptr, occ_out_dev, s->lp.stats);
+    else
+        hipLaunchKernelGGL((qr_trace_kernel<true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
+                           (float *)nullptr, (int32_t *)nullptr, occ_out_dev, s->lp.stats);
+    HIP_TRY(hipGetLastError());
     return QR_OK;
 }
 

@@ -38,6 +38,7 @@ struct QrProgram
     qr_frame frm;
     uint32_t off_order = 0, n_sched = 0;
     uint32_t off_srf = 0, off_shade = 0, off_mat = 0, off_lgt = 0, off_tex = 0, off_tiles = 0, off_lists = 0;
+    uint32_t off_query = 0;         /* the ray-query list (DevHeader::off_query), 0 none */
     uint32_t n_srf = 0, n_mat = 0, n_lgt = 0, n_tex = 0, n_tiles = 0;
     QrProgramStats stats = {};
     bool has_grids = false;         /* some light-list entry points at a CGrid: needs the same kernel instance */
@@ -52,7 +53,8 @@ void qr_bound_spheres(const qr_scene_view &v, std::vector<BSphere> &out);
 /* E / T: list cells and tile heads (the snapshot's, or the ones the binning pass built); frm: frame record to use */
 int  qr_program_build(const qr_scene_view &v, const std::vector<qr_elem> &E, const std::vector<int32_t> &T,
                       const qr_frame &frm, const std::vector<BSphere> &bs, QrProgram &out, std::string &err, int sched_blocks = 0,
-                      bool verify = true);      /* verify: walk every offset of the finished image (qr_program_verify) before returning it */
+                      bool verify = true,       /* verify: walk every offset of the finished image (qr_program_verify) before returning it */
+                      uint32_t flags = 0);      /* QR_UPLOAD_RAY_QUERIES: also compile the snapshot's global list for ray queries */
 int  qr_program_verify(const QrProgram &p, std::string &err);
 /* per-surface shadow / reflection / light lists from the global list and the surfaces' bounds (ssort / lsort's role) */
 int  qr_snapshot_build_lists(const qr_scene_view &v, std::vector<uint8_t> &out, std::string &err);

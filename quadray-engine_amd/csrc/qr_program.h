@@ -218,7 +218,8 @@ struct DevHeader
     uint32_t n_blocks;
     uint32_t img_flags;         /* QR_IMG_*                                                                  */
     uint32_t img_bytes;         /* size of the image (the guarded diagnostic build checks cell offsets against it) */
-    uint32_t pad[9];
+    uint32_t off_query;         /* the global list compiled for ray queries (QR_UPLOAD_RAY_QUERIES), with its QR_LISTF_* bits; 0 none */
+    uint32_t pad[8];
 };
 #define QR_IMG_BOXES 1u         /* some cull cell carries a box (QR_OPF_BOX): packet walks prepare the slab test */
 

@@ -5,6 +5,7 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
   * the packet-walk instance qr_render_kernel<false,4,false> (every scene of the reference engine) spills a vector register, uses
     more than 128 VGPRs (4 waves per SIMD) or a private segment above the recursion frames' bytes (QR_MAX_SCRATCH, default 528);
   * the per-lane instance <false,3,true> exceeds 168 VGPRs (3 waves per SIMD) or spills more vector registers than QR_MAX_DIVK_SPILL;
+  * a ray-query instance qr_trace_kernel<SHADOW, COHERENT> spills a vector register or uses more than 128 (occlusion) / 168 VGPRs;
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
 usage: check_kernel_resources.py <file.s> [--print]
 """
@@ -16,6 +17,12 @@ LIMITS = {
     "16qr_render_kernelILb0ELi4ELb0EE": (128, 0, SCR),
     "22qr_render_multi_kernelILi4ELb0EE": (128, 0, SCR),
     "16qr_render_kernelILb0ELi3ELb1EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    # ray queries (qr_query.hpp), with and without QR_TRACE_COHERENT, nothing spilled: occlusion at 4 waves per SIMD; closest hit at
+    # the per-lane render instance's 3 (the hit the hand-over pool carries: 128 registers spilled 35 of them)
+    "15qr_trace_kernelILb0ELb0EE": (168, 0, SCR),
+    "15qr_trace_kernelILb0ELb1EE": (168, 0, SCR),
+    "15qr_trace_kernelILb1ELb0EE": (128, 0, SCR),
+    "15qr_trace_kernelILb1ELb1EE": (128, 0, SCR),
 }
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 
