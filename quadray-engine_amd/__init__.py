@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "qr_scene_upload", "qr_scene_upload_ex", "qr_program_stats", "qr_program_stats_ex", "qr_snapshot_build_lists_c", "qr_scene_destroy", "qr_scene_get_info", "qr_scene_set_depth", "qr_scene_set_pt",
     "qr_scene_set_rows", "qr_scene_set_tile_rows", "qr_render_async", "qr_render_multi_async", "qr_render_ids_async",
     "qr_render_count", "qr_render_host", "qr_render_timed", "qr_trace_rays_async", "qr_occluded_async",
+    "qr_shade_rays_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -92,6 +93,7 @@ def lib():
     L.qr_program_stats_ex.argtypes = [vp, cu64, ctypes.c_uint32, ctypes.POINTER(ProgramInfo)]
     L.qr_trace_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
     L.qr_occluded_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
+    L.qr_shade_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
     L.qr_frame_hash.argtypes = [vp, cu64]
@@ -389,6 +391,21 @@ class Scene:
         _check(lib().qr_occluded_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(occ.data_ptr()),
                                        TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
         return occ.view(torch.bool)
+
+    def shade(self, rays, stream=None, coherent=False, ids=False):
+        """The renderer's colour for every ray (qr_shade_rays_async): rays as for trace(); the first hit walks the ray-query
+        list, everything after it -- shadows, reflection and refraction to the scene's current depth (set_depth) -- is the
+        renderer's.  Returns a new float32 [N, 3] tensor of linear colour, before the frame's output step (rays.pack_colors);
+        with ids=True also the first hit's id (int32 [N], surface << 1 | side, -1 none).  Asynchronous on `stream`."""
+        import torch
+        rays = self._rays_arg(rays)
+        n = rays.shape[0]
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+        hid = torch.empty(n, dtype=torch.int32, device=rays.device) if ids else None
+        _check(lib().qr_shade_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(rgb.data_ptr()),
+                                         ctypes.c_void_p(hid.data_ptr() if ids else None),
+                                         TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
+        return (rgb, hid) if ids else rgb
 
     def render_count(self, frame=None, stream=None):
         if frame is None:

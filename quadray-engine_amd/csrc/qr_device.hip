@@ -469,6 +469,26 @@ extern "C" int qr_occluded_async(qr_device_scene *s, const qr_ray *rays_dev, int
     return QR_OK;
 }
 
+/* ray shading (qr_kernel.hpp qr_shade_rays_kernel): the renderer's colour for caller rays, at the scene's current depth */
+extern "C" int qr_shade_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,
+                                   float *rgb_out_dev, int32_t *id_out_dev, uint32_t flags, void *stream)
+{
+    const int rc = query_args(s, rays_dev, n, rgb_out_dev, rgb_out_dev, flags);
+    if (rc != QR_OK) return rc;
+    if (s->pt_on) return qr_fail(QR_ERR_UNSUP, "scene is in path-tracer mode: caller rays carry no sample seeds");
+    if (n == 0) return QR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    RaysP rp;
+    rp.rays = (const f32x4 *)rays_dev; rp.n = (int32_t)n; rp.pad = 0; rp.rgb = rgb_out_dev;
+    if (flags & QR_TRACE_COHERENT)
+        hipLaunchKernelGGL((qr_shade_rays_kernel<true>), grid, block, 0, (hipStream_t)stream, s->lp, rp, id_out_dev);
+    else
+        hipLaunchKernelGGL((qr_shade_rays_kernel<false>), grid, block, 0, (hipStream_t)stream, s->lp, rp, id_out_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
 /* combined schedules of multi-target launches, keyed by (scene, row range) per target; only the schedule is
  * cached -- recursion depth and frame pointers travel in the kernel arguments of every launch */
 struct MultiSched { uint32_t *d_order; int32_t n; };

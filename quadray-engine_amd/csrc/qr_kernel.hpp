@@ -47,6 +47,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <float.h>
 #include "qr_scene.h"
 #include "qr_program.h"
 
@@ -224,6 +225,13 @@ __device__ __forceinline__ float clamp1(float x) { return x < 1.0f ? x : 1.0f; }
  */
 struct PtParams { u32 *seeds; float *acc_r, *acc_g, *acc_b; float pts_o, pts_u; int eager, pad; };
 
+/*
+ * Ray shading (qr_shade_rays_async; RAYS != 0 instances only): the wave's 64 primary rays come from the caller's qr_ray
+ * array instead of the camera, and its colours leave linear, before the frame's output step.  RAYS = 1: caller rays; 2: caller
+ * rays that the caller vouches are neighbours (QR_TRACE_COHERENT), so that the first round may take packet walks.
+ */
+struct RaysP { const f32x4 *rays; int32_t n; int32_t pad; float *rgb; };
+
 /* one wave = one schedule entry: footprint `ord`, its tile-list program, rendered into `frame` */
 /*
  * The pixel sample a lane stands for and whether this launch owns it, from the schedule word.  Computed where it is needed --
@@ -250,10 +258,16 @@ __device__ __forceinline__ bool pixel_of(u32 ord, int fsaa, const LaunchP &lp, F
     return inside;
 }
 
-template <bool COUNT, bool DIVK, bool PT = false>
+/*
+ * RAYS (ray shading, see RaysP) changes where the wave's rays come from (the caller's array: gw is the workgroup, lane i of it
+ * ray gw * 64 + i), which lanes are inside (i < n), drops the empty-tile exit and the issue-priority schedule, and stores the
+ * linear colour and the first hit's id per ray instead of the frame's output step.  The recursion between them is one piece.
+ */
+template <bool COUNT, bool DIVK, bool PT = false, int RAYS = 0>
 __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, const u32 sched_head, const int gw,
                                             uint32_t *__restrict__ frame, int32_t *__restrict__ ids,
-                                            unsigned long long *__restrict__ counters, const PtParams *ptp = nullptr)
+                                            unsigned long long *__restrict__ counters, const PtParams *ptp = nullptr,
+                                            const RaysP *rp = nullptr)
 {
 #ifdef QR_WAVETIME
     const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
@@ -286,10 +300,10 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
 #if QR_DYN_PRIO
     /* ... and among them the ones that actually do: every traversal round a wave starts raises its priority (2 waves of demo
      * scene 1 at 1080p run 7 rounds, 20 run 6, 12 000 one -- but 3 900 footprints CAN recurse and fill the first generation) */
-    if (ord >> 30) __builtin_amdgcn_s_setprio(1);
+    if constexpr (!RAYS) if (ord >> 30) __builtin_amdgcn_s_setprio(1);
     int prio_round = 0;
 #else
-    if (ord >> 30) { if ((ord >> 30) >= 2) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(2); }
+    if constexpr (!RAYS) if (ord >> 30) { if ((ord >> 30) >= 2) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(2); }
 #endif
     const int px = fsaa == 2 ? (pix & 3) : (pix & 7), py = fsaa == 2 ? (pix >> 2) : (pix >> 3);
     const int x = (int)(ord & 0x3FFFu) * fw + px;
@@ -297,12 +311,17 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     const int group = y >> 3;
     const int frm_w = fr->fr.frm_w;
 
-    bool inside = x < frm_w && y < fr->fr.frm_h && y >= lp.row_begin && y < lp.row_end;
-    if (group < lp.group_first) inside = false;
-    if (lp.group_stride != 1 && (group - lp.group_first) % lp.group_stride != 0) inside = false;
-    if (inside && lp.thnum > 1) inside = (y % lp.thnum) == lp.index;
-    if (!any_lane(inside)) return;                 /* whole wave outside this launch's rows */
-    if (sched_head < 256u)
+    bool inside;
+    if constexpr (RAYS) inside = (u32)gw * 64u + (u32)lane < (u32)rp->n;      /* n > 0: every wave holds a ray */
+    else
+    {
+        inside = x < frm_w && y < fr->fr.frm_h && y >= lp.row_begin && y < lp.row_end;
+        if (group < lp.group_first) inside = false;
+        if (lp.group_stride != 1 && (group - lp.group_first) % lp.group_stride != 0) inside = false;
+        if (inside && lp.thnum > 1) inside = (y % lp.thnum) == lp.index;
+        if (!any_lane(inside)) return;             /* whole wave outside this launch's rows */
+    }
+    if (!RAYS && sched_head < 256u)
     {
         /* empty tiles: no ray of these footprints meets anything; the reference's pipeline ends with colour 0 for such a
          * packet (clamp, sqrt and cvt of 0 are 0), so store it and leave.  The head is the number of footprints of the
@@ -332,8 +351,22 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     const float t_inf = fr->fr.t_max;
 
     u32 rng = 0;                                /* PT: this sample's LCG state */
-    /* primary ray, tracer.cpp:1287-1322; sample offsets engine.cpp:3480-3550 */
     Ray ray;
+    if constexpr (RAYS)
+    {
+        /* the caller's ray, as qr_trace_kernel reads it (qr_query.hpp): two 16-byte loads; lanes past the end read ray 0 and
+         * do not walk.  No originating surface; tmax +inf is taken as FLT_MAX */
+        const u32 i = inside ? (u32)gw * 64u + (u32)lane : 0u;
+        const f32x4 a = rp->rays[2 * (size_t)i], b = rp->rays[2 * (size_t)i + 1];
+        ray.org = {a.x, a.y, a.z}; ray.tmin = a.w;
+        ray.dir = {b.x, b.y, b.z};
+        ray.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;
+        ray.list = inside ? fr->off_query : 0u;
+        ray.osrf = 0; ray.oflg = 0;
+        ray.ploc = {0, 0, 0};
+    }
+    else
+    /* primary ray, tracer.cpp:1287-1322; sample offsets engine.cpp:3480-3550 */
     {
         int ai = 0;
         if (fsaa == 1) ai = (x & 1) * 2 + k;
@@ -453,10 +486,11 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
             wt_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
 #if QR_DYN_PRIO
-            if (prio_round < 3) { prio_round++; if (prio_round == 2) __builtin_amdgcn_s_setprio(2); else if (prio_round == 3) __builtin_amdgcn_s_setprio(3); }
+            if constexpr (!RAYS)
+                if (prio_round < 3) { prio_round++; if (prio_round == 2) __builtin_amdgcn_s_setprio(2); else if (prio_round == 3) __builtin_amdgcn_s_setprio(3); }
 #endif
-            /* coherent: every ray of this round is a primary ray (neighbouring pixels) */
-            const bool coherent = !any_lane(tr && sp != 0);
+            /* coherent: every ray of this round is a primary ray (neighbouring pixels; caller rays only when vouched for) */
+            const bool coherent = (RAYS != 1) && !any_lane(tr && sp != 0);
             traverse<false, DIVK>(B, tr, coherent, ray, h, occ
 #ifdef QR_STATS
                             , cx.stats
@@ -663,7 +697,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     }
 
 #ifdef QR_WAVETIME
-    if (!COUNT && __ffsll((long long)__ballot(true)) - 1 == lane)
+    if (!COUNT && !RAYS && __ffsll((long long)__ballot(true)) - 1 == lane)
     {
         unsigned long long *o = counters + 64 + (size_t)gw * QR_WT_SLOTS;
         o[0] = wt_start; o[1] = wt_mid; o[2] = __builtin_amdgcn_s_memrealtime();
@@ -688,6 +722,17 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
             ptp->acc_r[si] = ar; ptp->acc_g[si] = ag; ptp->acc_b[si] = ab;
             ret = {ar, ag, ab};
         }
+    }
+    if constexpr (RAYS)
+    {
+        /* the linear colour (12 bytes per lane) and the first hit's id: no clamp, reduce, gamma or pack */
+        if (inside)
+        {
+            const size_t i = (size_t)gw * 64u + (size_t)lane;
+            rp->rgb[3 * i] = ret.x; rp->rgb[3 * i + 1] = ret.y; rp->rgb[3 * i + 2] = ret.z;
+            if (ids != nullptr) ids[i] = lds_hit_id[lane];
+        }
+        return;
     }
     QR_FLOPS_M(6 + 2 * fsaa, __popcll(__ballot(inside)));
     /* XX_end 5161-5343: clamp, FSAA reduce, gamma, pack */
@@ -766,6 +811,18 @@ void qr_render_pt_kernel(LaunchP lp, PtParams pt, uint32_t *__restrict__ frame, 
     const u32x2 sched = ((const QR_CONST u32x2 *)lp.order)[gw];
 #pragma clang diagnostic pop
     render_wave<false, false, true>(lp, sched.x, sched.y, gw, frame, nullptr, counters, &pt);
+}
+
+/*
+ * Ray shading (qr_shade_rays_async): one lane per caller ray, 64 per wave, one wave per workgroup; the per-lane walk instance
+ * of the renderer's machine (caller rays may be incoherent, and only it knows shadow grids).  COHERENT: QR_TRACE_COHERENT.
+ */
+template <bool COHERENT>
+__global__ __launch_bounds__(QR_BLOCK, QR_DIVK_WAVES)
+void qr_shade_rays_kernel(LaunchP lp, RaysP rp, int32_t *__restrict__ ids)
+{
+    const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    render_wave<false, true, false, COHERENT ? 2 : 1>(lp, 0u, 0u, gw, nullptr, ids, nullptr, nullptr, &rp);
 }
 
 /*

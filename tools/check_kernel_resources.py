@@ -6,6 +6,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     more than 128 VGPRs (4 waves per SIMD) or a private segment above the recursion frames' bytes (QR_MAX_SCRATCH, default 528);
   * the per-lane instance <false,3,true> exceeds 168 VGPRs (3 waves per SIMD) or spills more vector registers than QR_MAX_DIVK_SPILL;
   * a ray-query instance qr_trace_kernel<SHADOW, COHERENT> spills a vector register or uses more than 128 (occlusion) / 168 VGPRs;
+  * a ray-shading instance qr_shade_rays_kernel<COHERENT> exceeds the per-lane render instance's budget (168 VGPRs,
+    QR_MAX_DIVK_SPILL spilled, 640 B private segment);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
 usage: check_kernel_resources.py <file.s> [--print]
 """
@@ -23,6 +25,9 @@ LIMITS = {
     "15qr_trace_kernelILb0ELb1EE": (168, 0, SCR),
     "15qr_trace_kernelILb1ELb0EE": (128, 0, SCR),
     "15qr_trace_kernelILb1ELb1EE": (128, 0, SCR),
+    # ray shading (qr_kernel.hpp qr_shade_rays_kernel<COHERENT>): the per-lane render instance's machine, held to its budget
+    "20qr_shade_rays_kernelILb0EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "20qr_shade_rays_kernelILb1EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
 }
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 
