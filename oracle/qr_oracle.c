@@ -27,6 +27,7 @@
  */
 #include "qr_scene.h"
 
+#include <float.h>
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -1362,6 +1363,62 @@ int qro_render(const void *blob, uint64_t size, uint32_t *frame, int32_t *ids,
                int threads, uint64_t counts[4])
 {
     return qro_render2(blob, size, frame, ids, depth, row_begin, row_end, index, thnum, threads, counts, 0);
+}
+
+/*
+ * Caller rays (include/qrhip.h qr_trace_rays_async, qr_occluded_async, qr_shade_rays_async), restated with the primary ray's
+ * context of sample(): one context per ray, org / dir / t_min from the caller, t_buf = tmax (+inf taken as FLT_MAX), no
+ * originating surface, the walk of the frame's global list clist.  rays: n x 8 floats in qr_ray layout
+ * (org x, y, z, tmin, dir x, y, z, tmax).  No arithmetic of its own: trace_list and shade do all of it.
+ *   mode 0, trace:     t_out = t_buf after the walk (the hit's t, tmax on a miss), id_out = surface << 1 | side or -1.
+ *                      The final hit is shaded once at depth 0 (deferred): shading does not move t or the id.
+ *   mode 1, occlusion: a FLAG_SHAD walk (the renderer's CHECK_SHAD rule); occ_out = 1 when it ended on a caster.
+ *   mode 2, shade:     rgb_out = the linear colour before clamp1, at `depth` (< 0: the snapshot's), every depth-test
+ *                      winner shaded as the reference does; id_out = the first hit's id.
+ */
+int qro_trace_rays(const void *blob, uint64_t size, const float *rays, int64_t n, int mode, int depth, int threads,
+                   float *t_out, int32_t *id_out, uint8_t *occ_out, float *rgb_out)
+{
+    scene_t S;
+    int rc = qr_scene_view_init(&S.v, blob, size);
+    int64_t i;
+    if (rc != 0) return rc;
+    if (mode < 0 || mode > 2 || n < 0) return -1;
+    S.depth = depth >= 0 ? depth : S.v.frame->depth;
+    (void)threads;
+#ifdef _OPENMP
+    if (threads > 0) omp_set_num_threads(threads);
+#endif
+#pragma omp parallel for schedule(dynamic, 64)
+    for (i = 0; i < n; i++)
+    {
+        const float *q = rays + 8 * i;
+        tracer_t T;
+        ctx_t c;
+        T.s = &S; T.depth = mode == 2 ? S.depth : 0; T.deferred = mode == 0;
+        memset(&T.cnt, 0, sizeof(T.cnt));
+        memset(&c, 0, sizeof(c));
+        c.t_buf = q[7] > FLT_MAX ? FLT_MAX : q[7];
+        c.t_min = q[3];
+        c.org[0] = q[0]; c.org[1] = q[1]; c.org[2] = q[2];
+        c.ray[0] = q[4]; c.ray[1] = q[5]; c.ray[2] = q[6];
+        c.wmask = 0xFFFFFFFFu;
+        c.param_tag = mode == 1 ? 1 : 0;
+        c.param_flg = mode == 1 ? FLAG_SHAD : S.v.frame->ctx_flags;
+        c.param_obj = QR_NULL;
+        c.local_obj = QR_NULL;
+        c.pend_si = QR_NULL;
+        c.hit_id = -1;
+        trace_list(&T, &c, NULL, S.v.frame->clist);
+        if (mode == 0) { t_out[i] = c.t_buf; id_out[i] = c.hit_id; }
+        else if (mode == 1) occ_out[i] = c.c_buf != 0;
+        else
+        {
+            rgb_out[3 * i + 0] = c.col[0]; rgb_out[3 * i + 1] = c.col[1]; rgb_out[3 * i + 2] = c.col[2];
+            id_out[i] = c.hit_id;
+        }
+    }
+    return 0;
 }
 
 int qro_info(const void *blob, uint64_t size, int32_t out[8])

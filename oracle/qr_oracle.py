@@ -27,6 +27,10 @@ def lib():
         L.qro_info.restype = ctypes.c_int
         L.qro_hash.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
         L.qro_hash.restype = ctypes.c_uint64
+        L.qro_trace_rays.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p]
+        L.qro_trace_rays.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -62,3 +66,32 @@ def render(blob, depth=-1, threads=0, want_ids=False, rows=None, index=0, thnum=
 def frame_hash(frame):
     f = np.ascontiguousarray(frame, dtype=np.uint32)
     return int(lib().qro_hash(f.ctypes.data, f.size))
+
+
+_MODES = {"trace": 0, "occluded": 1, "shade": 2}
+
+
+def trace_rays(blob, rays, mode, depth=None, threads=0):
+    """Caller rays (float32 [N, 8], qr_ray layout) against the snapshot's global list, restated on the CPU
+    (qro_trace_rays): the answers of Scene.trace / Scene.occluded / Scene.shade.
+      mode "trace":    (t float32 [N], id int32 [N])
+      mode "occluded": occ bool [N]
+      mode "shade":    (rgb float32 [N, 3] before clamp1, first hit's id int32 [N]) at `depth` (None: the snapshot's)"""
+    r = np.ascontiguousarray(rays, dtype=np.float32)
+    if r.ndim != 2 or r.shape[1] != 8:
+        raise ValueError(f"rays must be [N, 8], got {list(r.shape)}")
+    n = r.shape[0]
+    t = np.zeros(n, dtype=np.float32)
+    ids = np.full(n, -1, dtype=np.int32)
+    occ = np.zeros(n, dtype=np.uint8)
+    rgb = np.zeros((n, 3), dtype=np.float32)
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    rc = lib().qro_trace_rays(buf, len(blob), r.ctypes.data, n, _MODES[mode], -1 if depth is None else int(depth),
+                              threads, t.ctypes.data, ids.ctypes.data, occ.ctypes.data, rgb.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"qro_trace_rays rc={rc}")
+    if mode == "trace":
+        return t, ids
+    if mode == "occluded":
+        return occ.astype(bool)
+    return rgb, ids

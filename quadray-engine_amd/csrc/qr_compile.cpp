@@ -394,6 +394,7 @@ struct Builder
     bool box_ok = false;                    /* every list is short: cull cells may carry boxes (QR_OPF_BOX) */
     bool any_box = false;
     float box_pad = 0.0f;
+    float big = 0.0f;                       /* the scene's largest coordinate: camera origin, finite surface bounds */
 
     Builder(const qr_scene_view &v_, const std::vector<qr_elem> &E_, const std::vector<BSphere> &bs_, int cm, std::vector<uint8_t> &b)
         : v(v_), E(E_), bs(bs_), cull_mode(cm), blob(b), n_srf((int)v_.hdr->n_srf), n_elm((int)E_.size())
@@ -1142,6 +1143,7 @@ static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem>
                     if (bs[i].lo[0] <= bs[i].hi[0])
                         for (int k = 0; k < 3; k++) big = std::max(big, std::max((double)__builtin_fabsf(bs[i].lo[k]), (double)__builtin_fabsf(bs[i].hi[k])));
                 b.box_pad = (float)(2e-6 * big);
+                b.big = (float)big;
             }
             b.box_ok = box_lists && assume_short;       /* the second attempt: compile_list met a chain of QR_LONG_CELLS elements */
         }
@@ -1392,6 +1394,7 @@ static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem>
         h.fr = frm;
         h.off_shade = b.o_shd; h.off_tiles = o_til; h.off_order = o_ord; h.n_blocks = (uint32_t)n_waves;
         h.off_query = q_off;
+        h.reach = 2.0f * b.big;
         b.alloc(64, 64);                    /* tail padding: wide scalar loads of the last record stay inside */
         out.off_order = o_ord; out.n_sched = (uint32_t)n_waves;
         out.off_query = q_off;

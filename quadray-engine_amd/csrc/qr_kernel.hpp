@@ -491,7 +491,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
 #endif
             /* coherent: every ray of this round is a primary ray (neighbouring pixels; caller rays only when vouched for) */
             const bool coherent = (RAYS != 1) && !any_lane(tr && sp != 0);
-            traverse<false, DIVK>(B, tr, coherent, ray, h, occ
+            traverse<false, DIVK, RAYS != 0>(B, tr, coherent, ray, h, occ
 #ifdef QR_STATS
                             , cx.stats
 #endif

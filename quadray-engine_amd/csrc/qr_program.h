@@ -219,7 +219,9 @@ struct DevHeader
     uint32_t img_flags;         /* QR_IMG_*                                                                  */
     uint32_t img_bytes;         /* size of the image (the guarded diagnostic build checks cell offsets against it) */
     uint32_t off_query;         /* the global list compiled for ray queries (QR_UPLOAD_RAY_QUERIES), with its QR_LISTF_* bits; 0 none */
-    uint32_t pad[8];
+    float    reach;             /* twice the scene's largest coordinate (camera origin, finite surface bounds): caller rays whose origin
+                                 * lies beyond it in some coordinate take the walk without culls (qr_walk.hpp traverse, CALLER) */
+    uint32_t pad[7];
 };
 #define QR_IMG_BOXES 1u         /* some cull cell carries a box (QR_OPF_BOX): packet walks prepare the slab test */
 

@@ -46,7 +46,7 @@ void qr_trace_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ ra
     }
     Hit h;
     bool occ = false;
-    traverse<SHADOW, true>(B, active, COHERENT, r, h, occ
+    traverse<SHADOW, true, true>(B, active, COHERENT, r, h, occ
 #ifdef QR_STATS
                            , stats
 #endif

@@ -804,8 +804,10 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
 }
 
 /* BOXC: the walk knows box cull cells (QR_OPF_BOX).  The kernel instance with the per-lane walks is compiled without: images it
- * serves carry none (qr_compile.cpp), and when it is forced onto one (QR_DIV=1) such a cell is simply not culled */
-template <bool SHADOW, bool BOXC>
+ * serves carry none (qr_compile.cpp), and when it is forced onto one (QR_DIV=1) such a cell is simply not culled.
+ * NOCULL (caller rays that the culls were not made for, see traverse): no sphere, box or bounding-volume cull -- every cell is
+ * solved, as the reference walks its list.  Use with BOXC = false. */
+template <bool SHADOW, bool BOXC, bool NOCULL = false>
 __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &h, bool &occluded
 #ifdef QR_STATS
                                           , unsigned long long *stats
@@ -855,6 +857,13 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
          * the walk's only cell load.
          */
         u32x8 c;
+        if constexpr (NOCULL)
+        {
+            QR_GUARD_POS(1, pos, head, return);
+            c = *(const QR_CONST u32x8 *)(B + pos);
+        }
+        else
+        {
 #if QR_ASM_CULL && ((!defined(QR_STATS) && !defined(QR_PROF) && !defined(QR_WAVETIME) && !defined(QR_GUARD)) || defined(QR_GUARD_ASM))
         /* QR_GUARD_ASM (the guard library of the GPU suite): the hand-written loop stays -- the guarded walk runs the product's
          * instructions -- and the cursor is checked before the run loads its first cell and when it hands a cell out (the
@@ -913,6 +922,7 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
             pos = __builtin_amdgcn_readfirstlane(pos + 32);
         }
 #endif
+        }
         const u32 op = c.s0;
         if (op == 0) break;
         const u32 srf_off = c.s1;
@@ -930,7 +940,7 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
             const float R = u2f(c.s7);
             const float ocx = u2f(c.s4) - r.org.x, ocy = u2f(c.s5) - r.org.y, ocz = u2f(c.s6) - r.org.z;
             const float b = __builtin_fmaf(ocz, r.dir.z, __builtin_fmaf(ocy, r.dir.y, ocx * r.dir.x));
-            far = on & (LM(__builtin_fmaf(R, dlen, b) < 0.0f) | LM(__builtin_fmaf(-R, dlen, b) > w.tbd));
+            if constexpr (!NOCULL) far = on & (LM(__builtin_fmaf(R, dlen, b) < 0.0f) | LM(__builtin_fmaf(-R, dlen, b) > w.tbd));
             if (far != 0) { if (lane_of(far)) w.resume = c.s2; }
             full = (on & ~far) != 0;
         }
@@ -1865,7 +1875,16 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
  * DIVK = false is the kernel instance for scenes without long hierarchies (every scene the reference engine
  * prepares): the per-lane walk is compiled out there, which is worth 4 % of instructions through register pressure.
  */
-template <bool SHADOW, bool DIVK>
+/*
+ * CALLER (the ray-query and ray-shading instances): caller rays are not camera rays.  Two kinds are outside what the culls were
+ * made for: a ray with tmin < 0, whose hits at t in (tmin, 0) count -- the culls of the per-lane walks (walk_div, walk_pool,
+ * walk_dda) and the packet walk's sphere, box and bounding-volume culls take a surface behind the origin for a miss -- and a ray
+ * whose origin lies beyond DevHeader::reach in some coordinate, where the culls' rounding slack (sized for origins among the
+ * scene's coordinates) and the grid's entry cell no longer hold.  Such rays stay off the per-lane walks and take the packet walk
+ * without culls (walk_list<..., NOCULL>).  Culls only skip work: that walk solves every surface the reference solves, in list
+ * order, with the same arithmetic.
+ */
+template <bool SHADOW, bool DIVK, bool CALLER = false>
 __device__ __forceinline__ void traverse(BaseP B, bool active, bool coherent, const Ray &r, Hit &h, bool &occluded
 #ifdef QR_STATS
                                          , unsigned long long *stats
@@ -1875,6 +1894,13 @@ __device__ __forceinline__ void traverse(BaseP B, bool active, bool coherent, co
     h.t = r.tmax; h.srf = 0; h.side = 0; h.loc = {0, 0, 0};
     occluded = false;
     lm_t pending = LM(active && r.list != 0);
+    lm_t nocull = 0;                            /* CALLER: the lanes for walk_list<..., NOCULL> */
+    if constexpr (CALLER)
+    {
+        const float reach = c_frm(B)->reach;
+        const float o = __builtin_fmaxf(__builtin_fabsf(r.org.x), __builtin_fmaxf(__builtin_fabsf(r.org.y), __builtin_fabsf(r.org.z)));
+        nocull = LM(r.tmin < 0.0f || !(o <= reach));
+    }
     while (pending != 0)
     {
         const int leader = __ffsll((long long)pending) - 1;
@@ -1886,12 +1912,14 @@ __device__ __forceinline__ void traverse(BaseP B, bool active, bool coherent, co
         if constexpr (DIVK)
         {
         const int n_left = __popcll(pending), n_mine = __popcll(mine);
-        const lm_t can_div = pending & LM((r.list & QR_LISTF_DIV) != 0);
+        lm_t can_div = pending & LM((r.list & QR_LISTF_DIV) != 0);
+        if constexpr (CALLER) can_div &= ~nocull;
         const bool incoherent = n_mine * QR_INCOH_RATIO <= n_left * QR_INCOH_DEN && n_left >= QR_INCOH_MIN;
         const bool long_list = !coherent && (head & QR_LISTF_LONG) != 0 && (head & QR_LISTF_DIV) != 0 && n_mine >= QR_LONG_MIN;
-        if ((incoherent || long_list) && can_div != 0)
+        const lm_t go_c = incoherent ? can_div : (mine & can_div);            /* CALLER: the nocull lanes stay */
+        if ((incoherent || long_list) && (CALLER ? go_c != 0 : can_div != 0))
         {
-            const lm_t go = incoherent ? can_div : mine;
+            const lm_t go = CALLER ? go_c : (incoherent ? can_div : mine);
             pending &= ~go;
 #if QR_DDA
             /* nearest-hit rays on lists that carry a uniform grid */
@@ -1924,7 +1952,16 @@ __device__ __forceinline__ void traverse(BaseP B, bool active, bool coherent, co
         }
         }
         pending &= ~mine;
-        if (lane_of(mine))
+        if (CALLER && (mine & nocull) != 0)
+        {
+            if (lane_of(mine))
+                walk_list<SHADOW, false, true>(B, head & ~31u, r, h, occluded
+#ifdef QR_STATS
+                                               , stats
+#endif
+                                               );
+        }
+        else if (lane_of(mine))
         {
             walk_list<SHADOW, !DIVK>(B, head & ~31u, r, h, occluded
 #ifdef QR_STATS
