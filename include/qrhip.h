@@ -296,8 +296,9 @@ int qr_occluded_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n,
 
 /*
  * Ray shading: the renderer's colour for caller-supplied rays -- what it computes for a primary ray with this origin, direction
- * and interval.  For a host's own cameras (panorama, fisheye, stereo, thin lens, orthographic), more or adaptive samples per
- * pixel, re-shading part of a frame, or probe rays from inside the scene.
+ * and interval.  For a host's own non-pinhole cameras (panorama, fisheye, thin lens, orthographic), more or adaptive samples
+ * per pixel, re-shading part of a frame, or probe rays from inside the scene.  (Whole frames from pinhole cameras:
+ * qr_render_views_async below.)
  *   - The first hit follows the rules of qr_trace_rays_async above: it walks the ray-query list (the scene must have been
  *     uploaded with QR_UPLOAD_RAY_QUERIES, else QR_ERR_UNSUP), a hit counts when tmin < t < tmax, tmax = +inf is taken as
  *     FLT_MAX, and the ray has no originating surface.
@@ -316,6 +317,47 @@ int qr_occluded_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n,
  */
 int qr_shade_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n,
                         float *rgb_out_dev, int32_t *id_out_dev, uint32_t flags, void *stream);
+
+/*
+ * View rendering: whole frames of the resident scene from caller-supplied pinhole cameras, at any frame size, several in one
+ * launch -- a free camera, stereo pairs, cube maps and light probes, thumbnails, a zoomed region at a higher resolution --
+ * without a new snapshot, upload or tile binning, and without the host in the loop.
+ *   - A view is the camera part of the frame record (qr_frame org / dir / hor / ver / t_min): the primary ray of pixel (x, y),
+ *     sample k, is  dir + hor * (x + hor_a[k]) + ver * (y + ver_a[k])  from org, computed in the renderer's operation order.
+ *     quadray-engine_amd/rays.py view_of gives a snapshot's own camera, look_at a pinhole camera from eye / target / up / fov.
+ *   - Everything else is the resident frame record's: FSAA and its sample offsets (pixel units: they hold at any size), clamp,
+ *     colour mask, gamma, ambient, and the scene's current depth (qr_scene_set_depth).  The output step is render()'s.
+ *   - The first hit follows the rules of qr_trace_rays_async: it walks the ray-query list (QR_UPLOAD_RAY_QUERIES, else
+ *     QR_ERR_UNSUP), counts when t_min < t < t_max, t_max = +inf is taken as FLT_MAX, and a view with t_min < 0 or an origin
+ *     far outside the scene is served like such a caller ray.  Secondary rays are the renderer's.
+ *   - views_dev: DEVICE memory, n_views records, 16-byte aligned (an asynchronous call makes no hidden copy).  All views of a
+ *     launch share width x height, 1 .. QR_VIEW_MAX_DIM each; n_views <= QR_VIEW_MAX_VIEWS, and n_views x footprints at most
+ *     QR_VIEW_MAX_WAVES (a footprint is the 8x8, 8x4 or 4x4 pixels one wave renders at FSAA 0, 2x, 4x; 256 views at 4096x4096
+ *     without FSAA).
+ *   - frames_dev: uint32 [n_views][height][width], compact, packed as qr_render_async packs.  ids_dev (NULL = not wanted):
+ *     int32, same shape, the first hit's id as qr_render_ids_async gives it (-1 = none).  depth_dev (NULL = not wanted):
+ *     float32, same shape, the first hit's t, the view's t_max (FLT_MAX for +inf) where there is none.  With FSAA, ids and
+ *     depth are sample 0's.
+ *   - The WHOLE frame of every view is rendered: qr_scene_set_rows, qr_scene_set_tile_rows, index / thnum and QR_DEVICES
+ *     banding do not apply.
+ *   - flags: none defined yet; anything but 0 gives QR_ERR_ARG.  A scene in path-tracer mode gives QR_ERR_UNSUP (its seeds and
+ *     colour planes belong to the snapshot's frame).  A null or misaligned (views 16, outputs 4 bytes) pointer, n_views < 0,
+ *     a size outside the limits give QR_ERR_ARG.  n_views == 0 returns QR_OK without a launch.
+ *   - Asynchronous on `stream`, on the scene's own device.  Non-pinhole cameras and adaptive sampling: qr_shade_rays_async.
+ */
+typedef struct qr_view {      /* 64 bytes, 16-byte aligned; the camera part of qr_frame */
+    float org[3], t_min;      /* ray origin, ctx t_min                                     */
+    float dir[3], t_max;      /* ray(x, y) = dir + hor * (x + hor_a) + ver * (y + ver_a)   */
+    float hor[3], pad0;
+    float ver[3], pad1;
+} qr_view;
+
+#define QR_VIEW_MAX_DIM   16384         /* width, height: the footprint index holds 14 bits per axis (the schedule word's) */
+#define QR_VIEW_MAX_VIEWS 65535         /* the grid's third dimension */
+#define QR_VIEW_MAX_WAVES (1 << 25)     /* n_views x footprints: 2^31 threads in one grid */
+
+int qr_render_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
+                          uint32_t *frames_dev, int32_t *ids_dev, float *depth_dev, uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* 3. Misc                                                                   */

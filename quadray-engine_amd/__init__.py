@@ -94,6 +94,7 @@ def lib():
     L.qr_trace_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
     L.qr_occluded_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_shade_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
+    L.qr_render_views_async.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
     L.qr_frame_hash.argtypes = [vp, cu64]
@@ -406,6 +407,38 @@ class Scene:
                                          ctypes.c_void_p(hid.data_ptr() if ids else None),
                                          TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
         return (rgb, hid) if ids else rgb
+
+    def render_views(self, views, width=None, height=None, frames=None, ids=False, depth=False, stream=None):
+        """Whole frames of the resident scene from caller-supplied cameras (qr_render_views_async): views float32 [N, 16] on the
+        scene's device, one qr_view per row (org xyz, t_min, dir xyz, t_max, hor xyz, 0, ver xyz, 0: rays.view_of, rays.look_at),
+        all rendered at width x height (default: the snapshot's size) in one launch, at the scene's current depth (set_depth)
+        and with the snapshot's FSAA, gamma and output step.  Returns `frames` (int32 [N, H, W] like new_frame; a new tensor
+        unless given), followed by the first hit's ids (int32 [N, H, W], surface << 1 | side, -1 none) with ids=True and the
+        first hit's t (float32 [N, H, W], the view's t_max where none) with depth=True.  Asynchronous on `stream`."""
+        import torch
+        if not (isinstance(views, torch.Tensor) and views.dtype == torch.float32 and views.dim() == 2 and views.shape[1] == 16
+                and views.is_contiguous() and views.is_cuda and views.device.index == self.device):
+            raise QrError(f"views must be a contiguous float32 [N, 16] tensor on cuda:{self.device} "
+                          "(org xyz, t_min, dir xyz, t_max, hor xyz, 0, ver xyz, 0 per row)")
+        w = self.width if width is None else width
+        h = self.height if height is None else height
+        import numbers
+        if not (isinstance(w, numbers.Integral) and isinstance(h, numbers.Integral) and w >= 1 and h >= 1):
+            raise QrError("width and height must be positive integers")
+        w, h = int(w), int(h)
+        n = views.shape[0]
+        if frames is None:
+            frames = torch.empty((n, h, w), dtype=torch.int32, device=views.device)     # every pixel is written
+        elif not (isinstance(frames, torch.Tensor) and frames.dtype == torch.int32 and tuple(frames.shape) == (n, h, w)
+                  and frames.is_contiguous() and frames.is_cuda and frames.device.index == self.device):
+            raise QrError(f"frames must be a contiguous int32 [{n}, {h}, {w}] tensor on cuda:{self.device}")
+        hid = torch.empty((n, h, w), dtype=torch.int32, device=views.device) if ids else None
+        dep = torch.empty((n, h, w), dtype=torch.float32, device=views.device) if depth else None
+        _check(lib().qr_render_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h,
+                                           ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(hid.data_ptr() if ids else None),
+                                           ctypes.c_void_p(dep.data_ptr() if depth else None), 0, self._stream_ptr(stream)))
+        out = (frames,) + ((hid,) if ids else ()) + ((dep,) if depth else ())
+        return out if len(out) > 1 else frames
 
     def render_count(self, frame=None, stream=None):
         if frame is None:

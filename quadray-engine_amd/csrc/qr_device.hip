@@ -489,6 +489,39 @@ extern "C" int qr_shade_rays_async(qr_device_scene *s, const qr_ray *rays_dev, i
     return QR_OK;
 }
 
+/* view rendering (qr_kernel.hpp qr_render_views_kernel): whole frames from caller-supplied cameras, at the scene's current depth */
+extern "C" int qr_render_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                     uint32_t *frames_dev, int32_t *ids_dev, float *depth_dev, uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
+    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
+        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
+    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown view flags");
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    if (s->pt_on) return qr_fail(QR_ERR_UNSUP, "scene is in path-tracer mode: its seeds and colour planes belong to the snapshot's frame");
+    const int fsaa = s->fr.fsaa;
+    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+    const int64_t fcols = (width + fw - 1) / fw, frows = (height + fh - 1) / fh;
+    if ((int64_t)n_views * fcols * frows > (int64_t)QR_VIEW_MAX_WAVES)
+        return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
+    if (n_views == 0) return QR_OK;
+    if (views_dev == nullptr || frames_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (((uintptr_t)views_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "views must be 16-byte aligned");
+    if ((((uintptr_t)frames_dev | (uintptr_t)ids_dev | (uintptr_t)depth_dev) & 3u) != 0) return qr_fail(QR_ERR_ARG, "frames, ids and depth must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)fcols, (unsigned)frows, (unsigned)n_views), block(QR_BLOCK);
+    ViewsP vp;
+    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = depth_dev;
+    /* the instance is chosen as render() chooses its own: per-lane walks only where some list is a long hierarchy or carries a grid */
+    if (s->divk)
+        hipLaunchKernelGGL((qr_render_views_kernel<true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, vp, frames_dev, ids_dev);
+    else
+        hipLaunchKernelGGL((qr_render_views_kernel<false, QR_MIN_WAVES_PER_SIMD>), grid, block, 0, (hipStream_t)stream, s->lp, vp, frames_dev, ids_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
 /* combined schedules of multi-target launches, keyed by (scene, row range) per target; only the schedule is
  * cached -- recursion depth and frame pointers travel in the kernel arguments of every launch */
 struct MultiSched { uint32_t *d_order; int32_t n; };

@@ -232,6 +232,14 @@ struct PtParams { u32 *seeds; float *acc_r, *acc_g, *acc_b; float pts_o, pts_u; 
  */
 struct RaysP { const f32x4 *rays; int32_t n; int32_t pad; float *rgb; };
 
+/*
+ * View rendering (qr_render_views_async; the RAYS = 3 instance): a wave is one footprint of one caller-supplied camera (qr_view,
+ * the camera part of the frame record) at the launch's frame size.  Its rays are the frame's primary rays computed from the view
+ * record instead of the snapshot's, they walk the camera-independent ray-query list as caller rays do (CALLER: a view's t_min
+ * and origin are the caller's), and their colours leave through the frame's output step into frames[view][y][x].
+ */
+struct ViewsP { const qr_view *views; int32_t width, height; float *depth; };
+
 /* one wave = one schedule entry: footprint `ord`, its tile-list program, rendered into `frame` */
 /*
  * The pixel sample a lane stands for and whether this launch owns it, from the schedule word.  Computed where it is needed --
@@ -258,17 +266,35 @@ __device__ __forceinline__ bool pixel_of(u32 ord, int fsaa, const LaunchP &lp, F
     return inside;
 }
 
+/* ... and of a view launch (RAYS = 3): the footprint word holds the workgroup's x | y << 14, the frame is the launch's */
+__device__ __forceinline__ bool pixel_of_view(u32 ord, int fsaa, const ViewsP &vp, int &x, int &y, int &k)
+{
+    asm volatile("" : "+s"(ord));
+    int lane = (int)(threadIdx.x & 63u);
+    asm volatile("" : "+v"(lane));
+    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+    const int pix = lane >> fsaa;
+    k = lane & ((1 << fsaa) - 1);
+    const int px = fsaa == 2 ? (pix & 3) : (pix & 7), py = fsaa == 2 ? (pix >> 2) : (pix >> 3);
+    x = (int)(ord & 0x3FFFu) * fw + px;
+    y = (int)((ord >> 14) & 0x3FFFu) * fh + py;
+    return x < vp.width && y < vp.height;
+}
+
 /*
  * RAYS (ray shading, see RaysP) changes where the wave's rays come from (the caller's array: gw is the workgroup, lane i of it
  * ray gw * 64 + i), which lanes are inside (i < n), drops the empty-tile exit and the issue-priority schedule, and stores the
  * linear colour and the first hit's id per ray instead of the frame's output step.  The recursion between them is one piece.
+ * RAYS = 3 (view rendering, see ViewsP): the frame's own ray arithmetic and output step on the view gw of the launch, footprint
+ * `ord`, the walk and the missing tile schedule of the caller-ray instances; the first hit's t leaves right after the first walk.
  */
 template <bool COUNT, bool DIVK, bool PT = false, int RAYS = 0>
 __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, const u32 sched_head, const int gw,
                                             uint32_t *__restrict__ frame, int32_t *__restrict__ ids,
                                             unsigned long long *__restrict__ counters, const PtParams *ptp = nullptr,
-                                            const RaysP *rp = nullptr)
+                                            const RaysP *rp = nullptr, const ViewsP *vp = nullptr)
 {
+    constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3;
 #ifdef QR_WAVETIME
     const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
     const unsigned long long wt_clk0 = __builtin_amdgcn_s_memtime();      /* shader cycles: with the 100 MHz stamps, the clock the wave ran at */
@@ -309,10 +335,11 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     const int x = (int)(ord & 0x3FFFu) * fw + px;
     const int y = (int)((ord >> 14) & 0x3FFFu) * fh + py;
     const int group = y >> 3;
-    const int frm_w = fr->fr.frm_w;
+    const int frm_w = VIEW ? vp->width : fr->fr.frm_w;
 
     bool inside;
-    if constexpr (RAYS) inside = (u32)gw * 64u + (u32)lane < (u32)rp->n;      /* n > 0: every wave holds a ray */
+    if constexpr (VIEW) inside = x < frm_w && y < vp->height;      /* the grid is the frame's footprints: every wave holds a pixel */
+    else if constexpr (CALLER_RAYS) inside = (u32)gw * 64u + (u32)lane < (u32)rp->n;      /* n > 0: every wave holds a ray */
     else
     {
         inside = x < frm_w && y < fr->fr.frm_h && y >= lp.row_begin && y < lp.row_end;
@@ -352,7 +379,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
 
     u32 rng = 0;                                /* PT: this sample's LCG state */
     Ray ray;
-    if constexpr (RAYS)
+    if constexpr (CALLER_RAYS)
     {
         /* the caller's ray, as qr_trace_kernel reads it (qr_query.hpp): two 16-byte loads; lanes past the end read ray 0 and
          * do not walk.  No originating surface; tmax +inf is taken as FLT_MAX */
@@ -395,6 +422,30 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
         }
         float hs = (float)x + ha; hs = hs + hr;
         float vs = (float)y + va; vs = vs + vr;
+        if constexpr (VIEW)
+        {
+            /* the same operations on the view record: wave-uniform, scalar loads (64 bytes), nothing of it kept in VGPRs.
+             * The first hit walks the ray-query list; t_max +inf is taken as FLT_MAX, as for caller rays */
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+            const QR_CONST qr_view *vw = (const QR_CONST qr_view *)vp->views + gw;
+#pragma clang diagnostic pop
+            float x1 = vw->hor[0] * hs, x2 = vw->hor[1] * hs, x3 = vw->hor[2] * hs;
+            float x4 = vw->ver[0] * vs, x5 = vw->ver[1] * vs, x6 = vw->ver[2] * vs;
+            x1 = x1 + x4; x2 = x2 + x5; x3 = x3 + x6;
+            ray.dir.x = x1 + vw->dir[0];
+            ray.dir.y = x2 + vw->dir[1];
+            ray.dir.z = x3 + vw->dir[2];
+            ray.org.x = vw->org[0]; ray.org.y = vw->org[1]; ray.org.z = vw->org[2];
+            ray.tmin = vw->t_min;
+            const float vt = vw->t_max;
+            ray.tmax = vt > FLT_MAX ? FLT_MAX : vt;
+            ray.osrf = 0; ray.oflg = 0;
+            ray.ploc = {0, 0, 0};
+            ray.list = inside ? fr->off_query : 0u;
+        }
+        else
+        {
         float x1 = fr->fr.hor[0] * hs, x2 = fr->fr.hor[1] * hs, x3 = fr->fr.hor[2] * hs;
         float x4 = fr->fr.ver[0] * vs, x5 = fr->fr.ver[1] * vs, x6 = fr->fr.ver[2] * vs;
         x1 = x1 + x4; x2 = x2 + x5; x3 = x3 + x6;
@@ -414,6 +465,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
         {
             const int tile = (y / fr->fr.tile_h) * fr->fr.tls_row + (x / fr->fr.tile_w);
             ray.list = *(const u32 *)(cx.G + (fr->off_tiles + (u32)tile * 4u));
+        }
         }
     }
 
@@ -502,6 +554,18 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
             wt_trav += __builtin_amdgcn_s_memrealtime() - wt_t0;
             wt_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
+            if constexpr (VIEW)
+            {
+                /* the first hit's t (the view's t_max where there is none), sample 0's: stored here, in the only round whose
+                 * tracing lanes are at level 0, so that nothing waits in a register through the recursion for it */
+                if (vp->depth != nullptr)
+                {
+                    int x_d, y_d, k_d;
+                    const bool in_d = pixel_of_view(ord, fsaa, *vp, x_d, y_d, k_d) && k_d == 0;
+                    if (in_d && tr && sp == 0)
+                        vp->depth[((size_t)gw * (size_t)vp->height + (size_t)y_d) * (size_t)frm_w + (size_t)x_d] = h.t;
+                }
+            }
             const bool got = tr && h.srf != 0 && !QR_KNOB(4);
             if (tr && !got) { ret = {0, 0, 0}; mode = 1; }
             const int hsi = (int)((h.srf - QR_OFF_SRF) >> 7);          /* surface index: DSurf records are 128 B */
@@ -723,7 +787,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
             ret = {ar, ag, ab};
         }
     }
-    if constexpr (RAYS)
+    if constexpr (CALLER_RAYS)
     {
         /* the linear colour (12 bytes per lane) and the first hit's id: no clamp, reduce, gamma or pack */
         if (inside)
@@ -749,7 +813,15 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     }
     /* pixel coordinates and row ownership once more (pixel_of) */
     int x_e, y_e, k_e;
-    const bool inside_e = pixel_of(ord, fsaa, lp, fr, x_e, y_e, k_e) && k_e == 0;
+    bool inside_e;
+    if constexpr (VIEW)
+    {
+        inside_e = pixel_of_view(ord, fsaa, *vp, x_e, y_e, k_e) && k_e == 0;
+        const size_t view_px = (size_t)gw * (size_t)vp->height * (size_t)frm_w;       /* frames[view], ids[view] */
+        frame += view_px;
+        if (ids != nullptr) ids += view_px;
+    }
+    else inside_e = pixel_of(ord, fsaa, lp, fr, x_e, y_e, k_e) && k_e == 0;
     if (inside_e)
     {
         if (fr->fr.ctx_flags & QR_PROP_GAMMA)
@@ -823,6 +895,22 @@ void qr_shade_rays_kernel(LaunchP lp, RaysP rp, int32_t *__restrict__ ids)
 {
     const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
     render_wave<false, true, false, COHERENT ? 2 : 1>(lp, 0u, 0u, gw, nullptr, ids, nullptr, nullptr, &rp);
+}
+
+/*
+ * View rendering (qr_render_views_async): the grid is (footprint columns, footprint rows, views), one wave per workgroup.  The
+ * first round is the frame's: neighbouring pixels of one camera, packet walks.  Two instances, chosen as render() chooses its
+ * own: the per-lane walks for scenes with long hierarchies or grids (the ray-query list of a large scene is long), the packet
+ * walks alone for the others -- demo scene 1 at 1080p: 0.194 ms against 0.258 ms at depth 10, 0.143 against 0.188 at depth 0
+ * (profiles/r07_render_views.txt).
+ */
+template <bool DIVK, int WAVES>
+__global__ __launch_bounds__(QR_BLOCK, WAVES)
+void qr_render_views_kernel(LaunchP lp, ViewsP vp, uint32_t *__restrict__ frames, int32_t *__restrict__ ids)
+{
+    const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
+    const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
+    render_wave<false, DIVK, false, 3>(lp, ord, 0u, view, frames, ids, nullptr, nullptr, nullptr, &vp);
 }
 
 /*

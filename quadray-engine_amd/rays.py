@@ -1,4 +1,4 @@
-"""Ray batches for Scene.trace / Scene.occluded / Scene.shade (include/qrhip.h qr_trace_rays_async, qr_shade_rays_async): one
+"""Ray batches and views for Scene.trace / Scene.occluded / Scene.shade (include/qrhip.h qr_trace_rays_async, qr_shade_rays_async): one
 ray per row of a float32 [N, 8] array, (org x, y, z, tmin, dir x, y, z, tmax) -- the layout of qr_ray.
 
 camera_rays turns a snapshot's camera into such a batch: the primary rays of the render kernel (qr_kernel.hpp, the reference's
@@ -11,6 +11,13 @@ only where the engine's tiles hold other surfaces than its global list):
     ns = 1 << fsaa                                  # the snapshot's FSAA: 0, 1 or 2
     rgb = torch.stack([scn.shade(torch.from_numpy(camera_rays(blob, sample=k)).cuda()) for k in range(ns)])
     frame = pack_colors(rgb.cpu().numpy(), blob)    # uint32 [H, W], 0x00RRGGBB
+
+Whole frames from pinhole cameras do not need that detour: Scene.render_views renders them on the GPU from qr_view records
+(view_of: the snapshot's own camera; look_at: eye / target / up / field of view), at any frame size, and view_rays gives the
+rays it computes.
+
+    views = torch.from_numpy(np.stack([view_of(blob), look_at(eye, target, up, 60.0, 512, 512)])).cuda()
+    frames = scn.render_views(views, 512, 512)      # int32 [2, 512, 512]
 """
 import struct
 
@@ -37,10 +44,64 @@ def camera_rays(blob, sample=0):
     hs = x + hor_a, vs = y + ver_a (plus the zero jitter of a non-path-traced frame), the six products hor * hs and
     ver * vs, their sums, then + dir.  tmin / tmax are the frame's t_min / t_max.  `sample`: which FSAA sub-sample
     (0 .. 2^fsaa - 1) of a frame captured with anti-aliasing."""
+    _, i = frame_record(blob)
+    return view_rays(view_of(blob), int(i[_F_W]), int(i[_F_H]), blob, sample)
+
+
+def view_of(blob):
+    """The snapshot's own camera as a qr_view (include/qrhip.h): float32 [16] = org xyz, t_min, dir xyz, t_max, hor xyz, 0,
+    ver xyz, 0 -- one row of the `views` argument of Scene.render_views."""
+    f, _ = frame_record(blob)
+    v = np.zeros(16, dtype=np.float32)
+    v[0:3], v[3] = f[_F_ORG:_F_ORG + 3], f[_F_TMIN]
+    v[4:7], v[7] = f[_F_DIR:_F_DIR + 3], f[_F_TMAX]
+    v[8:11] = f[_F_HOR:_F_HOR + 3]
+    v[12:15] = f[_F_VER:_F_VER + 3]
+    return v
+
+
+def look_at(eye, target, up, fov_deg, width, height):
+    """A pinhole camera as a qr_view, float32 [16], in the engine's convention: pixel (x, y) looks along
+    dir + hor * x + ver * y with dir = forward - hor * W/2 - ver * H/2, so that the centre of the frame looks at `target`;
+    hor = normalize(forward x up) * s and ver = forward x hor * s with s = tan(fov/2) / (W/2): square pixels, `fov_deg` across
+    the frame's width, x to the right and y downwards for a viewer whose head points along `up`.  Computed in float64 and
+    rounded to float32 once.  t_min = 0, t_max = FLT_MAX."""
+    eye, target, up = (np.asarray(a, dtype=np.float64).reshape(3) for a in (eye, target, up))
+    if not (width >= 1 and height >= 1 and 0.0 < fov_deg < 180.0):
+        raise ValueError("look_at needs width, height >= 1 and 0 < fov_deg < 180")
+    fwd = target - eye
+    n = np.linalg.norm(fwd)
+    if not n > 0.0:
+        raise ValueError("look_at: eye and target coincide")
+    fwd = fwd / n
+    hor = np.cross(fwd, up)
+    n = np.linalg.norm(hor)
+    if not n > 1e-12 * np.linalg.norm(up):
+        raise ValueError("look_at: up is parallel to the viewing direction")
+    hor = hor / n
+    ver = np.cross(fwd, hor)
+    s = np.tan(np.radians(fov_deg) * 0.5) / (width * 0.5)
+    hor, ver = hor * s, ver * s
+    d = fwd - hor * (width * 0.5) - ver * (height * 0.5)
+    v = np.zeros(16, dtype=np.float32)
+    v[0:3], v[3] = eye, 0.0
+    v[4:7], v[7] = d, np.finfo(np.float32).max
+    v[8:11] = hor
+    v[12:15] = ver
+    return v
+
+
+def view_rays(view, width, height, blob, sample=0):
+    """camera_rays for a view (view_of, look_at) and a frame size: the primary rays Scene.render_views computes for the
+    width x height frame of `view`, row-major, float32 [H*W, 8], in the kernel's fp32 operation order.  FSAA and its sample
+    offsets are the snapshot's (`blob`); tmin / tmax are the view's (tmax +inf stays: the ray API takes it as FLT_MAX)."""
+    v = np.asarray(view, dtype=np.float32).reshape(16)
     f, i = frame_record(blob)
-    fsaa, w, h = int(i[_F_FSAA]), int(i[_F_W]), int(i[_F_H])
+    fsaa, w, h = int(i[_F_FSAA]), int(width), int(height)
     if not 0 <= sample < (1 << fsaa):
         raise ValueError(f"sample must be 0..{(1 << fsaa) - 1} for fsaa {fsaa}")
+    if w < 1 or h < 1:
+        raise ValueError("width and height must be at least 1")
     x = np.tile(np.arange(w, dtype=np.float32), h)
     y = np.repeat(np.arange(h, dtype=np.float32), w)
     if fsaa == 0:
@@ -54,12 +115,12 @@ def camera_rays(blob, sample=0):
     vs = (y + f[_F_VERA:_F_VERA + 4][ai]) + zero
     out = np.empty((w * h, 8), dtype=np.float32)
     for k in range(3):
-        a = f[_F_HOR + k] * hs
-        b = f[_F_VER + k] * vs
-        out[:, 4 + k] = (a + b) + f[_F_DIR + k]
-        out[:, k] = f[_F_ORG + k]
-    out[:, 3] = f[_F_TMIN]
-    out[:, 7] = f[_F_TMAX]
+        a = v[8 + k] * hs
+        b = v[12 + k] * vs
+        out[:, 4 + k] = (a + b) + v[4 + k]
+        out[:, k] = v[k]
+    out[:, 3] = v[3]
+    out[:, 7] = v[7]
     return out
 
 

@@ -8,6 +8,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
   * a ray-query instance qr_trace_kernel<SHADOW, COHERENT> spills a vector register or uses more than 128 (occlusion) / 168 VGPRs;
   * a ray-shading instance qr_shade_rays_kernel<COHERENT> exceeds the per-lane render instance's budget (168 VGPRs,
     QR_MAX_DIVK_SPILL spilled, 640 B private segment);
+  * a view-rendering instance qr_render_views_kernel<DIVK, WAVES> exceeds that same budget, or its packet-walk instance
+    <false,4> 128 VGPRs;
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
 usage: check_kernel_resources.py <file.s> [--print]
 """
@@ -28,6 +30,10 @@ LIMITS = {
     # ray shading (qr_kernel.hpp qr_shade_rays_kernel<COHERENT>): the per-lane render instance's machine, held to its budget
     "20qr_shade_rays_kernelILb0EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
     "20qr_shade_rays_kernelILb1EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    # view rendering (qr_kernel.hpp qr_render_views_kernel<DIVK, WAVES>): the same machine on the rays of caller-supplied cameras,
+    # same budget; its packet-walk instance at the packet render instance's 128 registers (4 waves per SIMD)
+    "22qr_render_views_kernelILb0ELi4EE": (128, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "22qr_render_views_kernelILb1ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
 }
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 

@@ -56,4 +56,35 @@ for name, blob in cases.items():
     print(f"{name} frame_ok {int(ok)} rays {counts.as_dict()}", flush=True)
     if not ok:
         rc = 1
+    scn.close()
+
+# view rendering (qr_render_views_kernel) under the same guard: the snapshot's own camera at a quarter of its size in each
+# dimension, on the scenes whose ray-query list is a long hierarchy with a grid (per-lane instance) and on a fixture (packet
+# instance), against the oracle's frame of the snapshot rewritten to that frame with one tile holding the global list.  A guarded
+# walk skips the cell it refuses, so a bad offset shows as a differing frame.  ("view_ok": the cases above are counted by name.)
+spec = importlib.util.spec_from_file_location("qr_rays", os.path.join(ROOT, "quadray-engine_amd", "rays.py"))
+rays = importlib.util.module_from_spec(spec); spec.loader.exec_module(rays)
+for name in ("synth2000_built", "synth10k_built_640", "swarm_demo01_240_mix"):
+    blob = cases[name]
+    f, i = rays.frame_record(blob)
+    w, h = int(i[31]) // 4, int(i[32]) // 4
+    view = rays.view_of(blob)
+    view[8:11] *= np.float32(4.0); view[12:15] *= np.float32(4.0)         # the same field of view
+    b = bytearray(blob)
+    off_frame, off_tiles = (int(x) for x in np.frombuffer(blob, dtype=np.uint32, count=26)[[10, 15]])
+    i[4:7], i[7:10] = view[8:11].view(np.int32), view[12:15].view(np.int32)
+    i[31], i[32], i[33], i[39], i[40] = w, h, w, 0, 1                     # frm_w, frm_h, frm_row, index, thnum
+    i[34], i[35], i[36], i[37] = w, h, 1, 1                               # one tile ...
+    b[off_frame:off_frame + 196] = i.tobytes()
+    b[32:36] = np.uint32(1).tobytes()                                     # ... n_tiles ...
+    b[off_tiles:off_tiles + 4] = i[38:39].tobytes()                       # ... that holds the global list
+    ref, _, _ = qr_oracle.render(bytes(b), threads=16)
+    scn = qr.Scene(blob, rebin_tiles=name.startswith("synth"), ray_queries=True)
+    out = scn.render_views(torch.from_numpy(view[None]).cuda(), w, h)
+    torch.cuda.synchronize()
+    ok = bool((out[0].cpu().numpy().view(np.uint32) == ref).all())
+    print(f"{name} {w}x{h} view_ok {int(ok)}", flush=True)
+    scn.close()
+    if not ok:
+        rc = 1
 sys.exit(rc)
