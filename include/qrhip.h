@@ -359,6 +359,56 @@ typedef struct qr_view {      /* 64 bytes, 16-byte aligned; the camera part of q
 int qr_render_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
                           uint32_t *frames_dev, int32_t *ids_dev, float *depth_dev, uint32_t flags, void *stream);
 
+/*
+ * Hit records: the closest hit of a ray AND the surface point the renderer would shade there -- hit point, normal, texture
+ * colour, material.  What a host needs to bounce, reflect, offset or cosine-weight its own secondary rays (AO, light probes,
+ * path tracing outside the renderer), and, per pixel of a camera, a G-buffer (position, normal, albedo, ids) for deferred passes
+ * or for denoising.  Nothing is lit and no secondary ray is traced: recursion depth and path-tracer mode do not matter, the
+ * calls work in either mode and leave the mode's seeds and colour planes alone.
+ *   - The hit is exactly the one qr_trace_rays_async finds: the ray-query list (QR_UPLOAD_RAY_QUERIES, else QR_ERR_UNSUP),
+ *     tmin < t < tmax, tmax = +inf taken as FLT_MAX, the first in list order among equal t, no self-exclusion.  t and id are
+ *     that call's t_out and id_out, bit for bit.
+ *   - pos: the renderer's hit point, per axis dir * t rounded, then + org (two fp32 operations, no fused multiply-add): the
+ *     origin of the renderer's own secondary rays.
+ *   - nrm: the world-space unit normal shading uses, computed for EVERY hit (whether or not the side's props carry
+ *     QR_PROP_NORMAL): the surface-space normal (a signed axis for planes, the normalised gradient for quadrics), its sign
+ *     flipped on the inner side, through the transposed matrix of the surface's transform node, renormalised unless that
+ *     node is a pure rotation.  Unit length to a few ulp.  A plane without a transform has one component +-1 and two +0.0,
+ *     exactly.  It is the normal of the side the walk names (id & 1).  For planes and for quadrics without a conic term --
+ *     spheres, ellipsoids, cylinders, paraboloids -- that is the side the ray arrives on: the normal faces the incoming ray,
+ *     nrm . dir <= 0 (to rounding at grazing incidence: 1e-5 |dir|), in front of the origin and, with tmin < 0, behind it.
+ *     Two exceptions.  On cones, hyperboloids and hyperbolic cylinders (qr_surface.conic != 0) the solver names the side by the
+ *     order of the roots, which on the surface's second sheet is the far side: there the renderer's normal can face away
+ *     from the ray.  And from an origin hundreds of scene sizes away fp32 no longer resolves the point the normal is taken
+ *     at -- a hit point that rounds onto a quadric's centre or axis has no gradient, and nrm is NaN there, as it is for the
+ *     renderer.  A host that needs a facing normal whatever the surface flips nrm by the sign of nrm . dir.
+ *   - alb: the texture colour shading multiplies light by: the texel's channel & the material's cmask, divided by its clamp,
+ *     squared when the side's props carry QR_PROP_GAMMA; in [0, 1] for the engine's materials.  Light surfaces give it too.
+ *   - mat: qr_surface.mat[side] of the hit side, the index into the snapshot's material table.
+ *   - No hit: t = tmax (FLT_MAX for +inf), id = mat = -1, and pos, nrm, alb are nine +0.0f.
+ * qr_hit_rays_async: rays_dev and hits_dev are DEVICE memory of n elements, both 16-byte aligned.  flags: QR_TRACE_COHERENT
+ * only; results do not depend on it.  n == 0 returns QR_OK without a launch; a null or misaligned pointer, n outside
+ * 0..INT32_MAX or unknown flags give QR_ERR_ARG.
+ * qr_hit_views_async: the rays are those of qr_render_views_async for the same views and size -- the same primary-ray
+ * arithmetic on the view record, the frame's FSAA offsets -- and with FSAA the record is sample 0's, as ids and depth are
+ * there.  hits_dev: qr_hit [n_views][height][width], compact, 16-byte aligned; the WHOLE frame of every view is written
+ * (row selections, tile-row sharding and QR_DEVICES banding do not apply).  The same limits (QR_VIEW_MAX_DIM,
+ * QR_VIEW_MAX_VIEWS, QR_VIEW_MAX_WAVES in qr_render_views_async's footprints); flags: none defined, anything but 0 gives
+ * QR_ERR_ARG, as do a null or misaligned pointer, n_views < 0 or a size outside the limits.  n_views == 0 returns QR_OK
+ * without a launch.
+ * Both are asynchronous on `stream`, on the scene's own device.
+ */
+typedef struct qr_hit {           /* 48 bytes, 16-byte aligned: three 16-byte stores per lane */
+    float pos[3]; float   t;      /* the renderer's hit point (dir * t, then + org, per axis); t as qr_trace_rays_async */
+    float nrm[3]; int32_t id;     /* world-space unit normal as shading uses it; id = surface << 1 | side, -1 none */
+    float alb[3]; int32_t mat;    /* texture colour at the hit as shading uses it; snapshot material index, -1 none */
+} qr_hit;
+
+int qr_hit_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n,
+                      qr_hit *hits_dev, uint32_t flags, void *stream);
+int qr_hit_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
+                       qr_hit *hits_dev, uint32_t flags, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* 3. Misc                                                                   */
 /* ------------------------------------------------------------------------ */

@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "qr_scene_upload", "qr_scene_upload_ex", "qr_program_stats", "qr_program_stats_ex", "qr_snapshot_build_lists_c", "qr_scene_destroy", "qr_scene_get_info", "qr_scene_set_depth", "qr_scene_set_pt",
     "qr_scene_set_rows", "qr_scene_set_tile_rows", "qr_render_async", "qr_render_multi_async", "qr_render_ids_async",
     "qr_render_count", "qr_render_host", "qr_render_timed", "qr_trace_rays_async", "qr_occluded_async",
-    "qr_shade_rays_async",
+    "qr_shade_rays_async", "qr_render_views_async", "qr_hit_rays_async", "qr_hit_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -95,6 +95,8 @@ def lib():
     L.qr_occluded_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_shade_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
     L.qr_render_views_async.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, ctypes.c_uint32, vp]
+    L.qr_hit_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
+    L.qr_hit_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
     L.qr_frame_hash.argtypes = [vp, cu64]
@@ -408,6 +410,48 @@ class Scene:
                                          TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
         return (rgb, hid) if ids else rgb
 
+    def hits(self, rays, stream=None, coherent=False):
+        """Hit records (qr_hit_rays_async): the closest hit of every ray -- the one trace() finds -- and the surface point the
+        renderer would shade there.  rays as for trace().  Returns a new float32 [N, 12] tensor, one qr_hit per row: pos xyz, t,
+        nrm xyz, id, alb xyz, mat -- id (surface << 1 | side) and mat (snapshot material index) are int32 bits in float32 slots,
+        rays.hit_fields splits a record into typed views.  nrm: the world-space unit normal shading uses, facing the incoming
+        ray; alb: the texture colour shading multiplies light by.  A miss has t = tmax, id = mat = -1 and zeros elsewhere.
+        Nothing is lit: depth and path-tracer mode do not matter.  Asynchronous on `stream`."""
+        import torch
+        rays = self._rays_arg(rays)
+        n = rays.shape[0]
+        out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
+        _check(lib().qr_hit_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
+                                       TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
+        return out
+
+    def _views_arg(self, views, width, height):
+        import numbers
+        import torch
+        if not (isinstance(views, torch.Tensor) and views.dtype == torch.float32 and views.dim() == 2 and views.shape[1] == 16
+                and views.is_contiguous() and views.is_cuda and views.device.index == self.device):
+            raise QrError(f"views must be a contiguous float32 [N, 16] tensor on cuda:{self.device} "
+                          "(org xyz, t_min, dir xyz, t_max, hor xyz, 0, ver xyz, 0 per row)")
+        w = self.width if width is None else width
+        h = self.height if height is None else height
+        if not (isinstance(w, numbers.Integral) and isinstance(h, numbers.Integral) and w >= 1 and h >= 1):
+            raise QrError("width and height must be positive integers")
+        return int(w), int(h)
+
+    def view_hits(self, views, width=None, height=None, stream=None):
+        """Hit records of whole frames (qr_hit_views_async): a G-buffer -- position, normal, albedo, ids, materials, depth --
+        of the resident scene from caller-supplied cameras.  views, width, height as for render_views; the rays are the ones
+        it traces (rays.view_rays(view, width, height, blob, sample=0): with FSAA the record is sample 0's, as its ids and
+        depth are).  Returns a new float32 [N, H, W, 12] tensor of qr_hit records (see hits(), rays.hit_fields); every pixel
+        of every view is written.  Asynchronous on `stream`."""
+        import torch
+        w, h = self._views_arg(views, width, height)
+        n = views.shape[0]
+        out = torch.empty((n, h, w, 12), dtype=torch.float32, device=views.device)
+        _check(lib().qr_hit_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(out.data_ptr()),
+                                        0, self._stream_ptr(stream)))
+        return out
+
     def render_views(self, views, width=None, height=None, frames=None, ids=False, depth=False, stream=None):
         """Whole frames of the resident scene from caller-supplied cameras (qr_render_views_async): views float32 [N, 16] on the
         scene's device, one qr_view per row (org xyz, t_min, dir xyz, t_max, hor xyz, 0, ver xyz, 0: rays.view_of, rays.look_at),
@@ -416,16 +460,7 @@ class Scene:
         unless given), followed by the first hit's ids (int32 [N, H, W], surface << 1 | side, -1 none) with ids=True and the
         first hit's t (float32 [N, H, W], the view's t_max where none) with depth=True.  Asynchronous on `stream`."""
         import torch
-        if not (isinstance(views, torch.Tensor) and views.dtype == torch.float32 and views.dim() == 2 and views.shape[1] == 16
-                and views.is_contiguous() and views.is_cuda and views.device.index == self.device):
-            raise QrError(f"views must be a contiguous float32 [N, 16] tensor on cuda:{self.device} "
-                          "(org xyz, t_min, dir xyz, t_max, hor xyz, 0, ver xyz, 0 per row)")
-        w = self.width if width is None else width
-        h = self.height if height is None else height
-        import numbers
-        if not (isinstance(w, numbers.Integral) and isinstance(h, numbers.Integral) and w >= 1 and h >= 1):
-            raise QrError("width and height must be positive integers")
-        w, h = int(w), int(h)
+        w, h = self._views_arg(views, width, height)
         n = views.shape[0]
         if frames is None:
             frames = torch.empty((n, h, w), dtype=torch.int32, device=views.device)     # every pixel is written

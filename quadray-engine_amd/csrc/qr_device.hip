@@ -9,6 +9,7 @@
 #include "qr_internal.h"
 #include "qr_kernel.hpp"
 #include "qr_query.hpp"
+#include "qr_hitrec.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -50,6 +51,7 @@ struct qr_device_scene
     int32_t n_groups = 0;
     bool divk = false;          /* some list is a long hierarchy: launch the kernel instance with the per-lane walk */
     uint32_t off_query = 0;     /* the ray-query list in the image (QR_UPLOAD_RAY_QUERIES), 0 none */
+    uint32_t off_mat = 0;       /* the image's material table: hit records turn DShade::mat back into the snapshot's index */
     /* path-tracer mode (qr_scene_set_pt): what the engine keeps per frame buffer, engine.cpp:2875-2893 */
     bool pt_on = false;
     uint32_t *d_seeds = nullptr; float *d_acc = nullptr;     /* frm_row * frm_h * samples each; d_acc holds r, g, b planes */
@@ -206,6 +208,7 @@ extern "C" int qr_scene_upload_ex(const void *blob, uint64_t size, int device, u
     s->fr = frm;
     s->n_cells = n_cells;
     s->off_query = prog.off_query;
+    s->off_mat = prog.off_mat;
     {
         const char *dv = getenv("QR_DIV");          /* QR_DIV=0 / 1 forces the kernel instance (experiments, tests) */
         s->divk = (dv ? atoi(dv) != 0 : prog.has_long_lists) || prog.has_grids;      /* only that instance knows shadow grids */
@@ -518,6 +521,63 @@ extern "C" int qr_render_views_async(qr_device_scene *s, const qr_view *views_de
         hipLaunchKernelGGL((qr_render_views_kernel<true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, vp, frames_dev, ids_dev);
     else
         hipLaunchKernelGGL((qr_render_views_kernel<false, QR_MIN_WAVES_PER_SIMD>), grid, block, 0, (hipStream_t)stream, s->lp, vp, frames_dev, ids_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+/* ---- hit records (qr_hitrec.hpp): the closest hit of qr_trace_rays_async and the surface point shading would use there ---- */
+
+extern "C" int qr_hit_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,
+                                 qr_hit *hits_dev, uint32_t flags, void *stream)
+{
+    const int rc = query_args(s, rays_dev, n, hits_dev, hits_dev, flags);
+    if (rc != QR_OK || n == 0) return rc;
+    if (((uintptr_t)hits_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "hits must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    const f32x4 *r = (const f32x4 *)rays_dev;
+    const ViewsP vp = {};
+    if (flags & QR_TRACE_COHERENT)
+        hipLaunchKernelGGL((qr_hit_kernel<false, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
+                           vp, s->off_mat, (f32x4 *)hits_dev, s->lp.stats);
+    else
+        hipLaunchKernelGGL((qr_hit_kernel<false, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
+                           vp, s->off_mat, (f32x4 *)hits_dev, s->lp.stats);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+extern "C" int qr_hit_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                  qr_hit *hits_dev, uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
+    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
+        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
+    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown view flags");
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    {
+        /* the limit of qr_render_views_async, in its footprints (the frame's FSAA), so that a size it takes is taken here too */
+        const int fsaa = s->fr.fsaa;
+        const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+        if ((int64_t)n_views * ((width + fw - 1) / fw) * ((height + fh - 1) / fh) > (int64_t)QR_VIEW_MAX_WAVES)
+            return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
+    }
+    if (n_views == 0) return QR_OK;
+    if (views_dev == nullptr || hits_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if ((((uintptr_t)views_dev | (uintptr_t)hits_dev) & 15u) != 0) return qr_fail(QR_ERR_ARG, "views and hits must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    /* one lane per pixel: 8x8 footprints at every FSAA (never more workgroups than the limit above allows) */
+    const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
+    ViewsP vp;
+    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
+    const f32x4 *none = nullptr;
+    if (s->divk)
+        hipLaunchKernelGGL((qr_hit_kernel<true, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
+                           vp, s->off_mat, (f32x4 *)hits_dev, s->lp.stats);
+    else
+        hipLaunchKernelGGL((qr_hit_kernel<true, false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
+                           vp, s->off_mat, (f32x4 *)hits_dev, s->lp.stats);
     HIP_TRY(hipGetLastError());
     return QR_OK;
 }

@@ -12,6 +12,9 @@ only where the engine's tiles hold other surfaces than its global list):
     rgb = torch.stack([scn.shade(torch.from_numpy(camera_rays(blob, sample=k)).cuda()) for k in range(ns)])
     frame = pack_colors(rgb.cpu().numpy(), blob)    # uint32 [H, W], 0x00RRGGBB
 
+Scene.hits / Scene.view_hits return hit records (qr_hit: position, t, normal, id, albedo, material); hit_fields splits them into
+typed views, offset_rays and reflect_rays build a host's own secondary rays from them.
+
 Whole frames from pinhole cameras do not need that detour: Scene.render_views renders them on the GPU from qr_view records
 (view_of: the snapshot's own camera; look_at: eye / target / up / field of view), at any frame size, and view_rays gives the
 rays it computes.
@@ -163,3 +166,52 @@ def pack_colors(rgb, blob):
     q = _cvt_near(c) & np.int64(np.uint32(i[_F_CMASK]))
     p = (q[:, 0] << 16) | (q[:, 1] << 8) | q[:, 2]
     return (p & np.int64(0xFFFFFFFF)).astype(np.uint32).reshape(h, w)
+
+
+# ---- hit records (include/qrhip.h qr_hit; Scene.hits, Scene.view_hits): float32 [..., 12] = pos xyz, t, nrm xyz, id, alb xyz, mat ----
+
+def hit_fields(h):
+    """Typed VIEWS (no copies) of hit records h, a float32 [..., 12] torch tensor or numpy array: the tuple
+    (pos [..., 3], t [...], nrm [..., 3], id [...], alb [..., 3], mat [...]) with id and mat viewed as int32
+    (id = surface << 1 | side, mat = snapshot material index; both -1 on a miss)."""
+    if h.shape[-1] != 12 or "float32" not in str(h.dtype):
+        raise ValueError(f"hit records are float32 [..., 12], got {h.dtype} {list(h.shape)}")
+    if isinstance(h, np.ndarray):
+        i = h.view(np.int32)
+    else:
+        import torch
+        i = h.view(torch.int32)
+    return h[..., 0:3], h[..., 3], h[..., 4:7], i[..., 7], h[..., 8:11], i[..., 11]
+
+
+def _secondary(hits, dirs, eps):
+    import torch
+    pos, _, _, hid, _, _ = hit_fields(hits)
+    n = hits.shape[0]
+    out = torch.empty((n, 8), dtype=torch.float32, device=hits.device)
+    out[:, 0:3] = pos
+    out[:, 3] = eps
+    out[:, 4:7] = dirs
+    tmin = out[:, 3]
+    out[:, 7] = torch.where(hid >= 0, torch.full_like(tmin, float("inf")), tmin)      # a miss: tmax = tmin, the interval is empty
+    return out
+
+
+def offset_rays(hits, dirs, eps):
+    """Secondary rays that leave hit points: hits float32 [N, 12] (Scene.hits), dirs float32 [N, 3] on the same device.
+    Returns float32 [N, 8] qr_ray rows: origin = pos, direction = dirs, tmin = eps (the step off the surface, in units of
+    |dir|: no self-exclusion in the ray API), tmax = +inf; rows of misses get tmax = tmin and hit nothing.
+    A helper for a host's own passes (AO, probes); NOT the renderer's bit-exact children: those start at tmin 0 with the
+    originating surface excluded, which the ray API does not offer."""
+    return _secondary(hits, dirs, eps)
+
+
+def reflect_rays(rays, hits, eps):
+    """Mirror rays: rays float32 [N, 8] (the rays that gave `hits`), hits float32 [N, 12].  Direction d - 2 (d . n) n with the
+    incoming direction d as given (not normalised) and the record's normal n, in plain float32 torch arithmetic; origin,
+    tmin = eps and the rows of misses as offset_rays.  NOT the renderer's bit-exact reflection children (it normalises d first,
+    in its own operation order, and excludes the originating surface instead of stepping off it)."""
+    _, _, nrm, _, _, _ = hit_fields(hits)
+    d = rays[:, 4:7]
+    dn = (d * nrm).sum(dim=1, keepdim=True)
+    return _secondary(hits, d - 2.0 * dn * nrm, eps)

@@ -10,6 +10,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     QR_MAX_DIVK_SPILL spilled, 640 B private segment);
   * a view-rendering instance qr_render_views_kernel<DIVK, WAVES> exceeds that same budget, or its packet-walk instance
     <false,4> 128 VGPRs;
+  * a hit-record instance qr_hit_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more than
+    168 VGPRs (128: the view instance with packet walks only);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
 usage: check_kernel_resources.py <file.s> [--print]
 """
@@ -34,6 +36,13 @@ LIMITS = {
     # same budget; its packet-walk instance at the packet render instance's 128 registers (4 waves per SIMD)
     "22qr_render_views_kernelILb0ELi4EE": (128, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
     "22qr_render_views_kernelILb1ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    # hit records (qr_hitrec.hpp qr_hit_kernel<VIEW, DIVK, COHERENT>): a walk and one surface point, no recursion: nothing spilled and
+    # no private segment at all; caller rays and views of scenes with long lists at the closest-hit query's 168 registers, views of
+    # the others at the packet instances' 128
+    "13qr_hit_kernelILb0ELb1ELb0EE": (168, 0, 0),
+    "13qr_hit_kernelILb0ELb1ELb1EE": (168, 0, 0),
+    "13qr_hit_kernelILb1ELb1ELb1EE": (168, 0, 0),
+    "13qr_hit_kernelILb1ELb0ELb1EE": (128, 0, 0),
 }
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 
