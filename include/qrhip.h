@@ -360,6 +360,39 @@ int qr_render_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_
                           uint32_t *frames_dev, int32_t *ids_dev, float *depth_dev, uint32_t flags, void *stream);
 
 /*
+ * View accumulation: ONE frame that is the sum -- and, scaled, the mean -- of many views of the resident scene, in one launch:
+ * supersampling beyond the frame's FSAA (sub-pixel-shifted copies of a camera: rays.py jitter_view), depth of field (pinhole
+ * cameras spread over a lens that share a focus plane: thin_lens_views), progressive refinement of a still image (a few more
+ * views per launch, QR_MEAN_RESUME).  The sum is taken in linear fp32 colour, before gamma and the rounding to 8 bits, and no
+ * per-view frame or colour plane ever reaches memory.
+ *   - Per view: for each pixel p and each view v, in array order, c_v is the linear pixel colour of that view: the arithmetic of
+ *     qr_render_views_async up to and including the FSAA reduce of the output step -- clamp1 (x < 1 ? x : 1) of every sample;
+ *     with FSAA every sample * 0.5 and samples added pairwise, for 4x once more * 0.5 and added.  The sample offsets are the
+ *     resident frame's; the first hit, the depth, t_min < 0 and far origins are served as a view launch serves them.
+ *   - The sum: s = c_0 without QR_MEAN_RESUME, s = sum_dev[p] with it; then s = s + c_v for every remaining view (with
+ *     QR_MEAN_RESUME: every view): one fp32 add per channel and view, in order, never fused or reassociated.  A sequence of
+ *     views cut into several resumed launches therefore gives the same bits as one launch.
+ *   - sum_dev: required, float32 [height][width][3], compact, 4-byte aligned: receives s (and is read only with QR_MEAN_RESUME).
+ *     frame_dev: optional (NULL = not wanted), uint32 [height][width]: the rest of qr_render_async's output step applied to
+ *     s * scale (one fp32 multiply): the square root under QR_PROP_GAMMA, * clamp, round to nearest even, & cmask, packed.
+ *     scale: computed by the caller, normally 1.0f / (float)total_views; finite and > 0, ignored when frame_dev is NULL.
+ *   - views_dev, width, height as for qr_render_views_async: 1 .. QR_VIEW_MAX_DIM each, n_views <= QR_VIEW_MAX_VIEWS; row
+ *     selections, tile-row sharding and QR_DEVICES banding do not apply.  Needs QR_UPLOAD_RAY_QUERIES (else QR_ERR_UNSUP); a
+ *     scene in path-tracer mode gives QR_ERR_UNSUP.
+ *   - flags: QR_MEAN_RESUME only.  n_views == 0 returns QR_OK without a launch and writes nothing.  A null or misaligned
+ *     (views 16, outputs 4 bytes) pointer, n_views < 0, a size outside the limits, unknown flags, or a scale that is not finite
+ *     and > 0 while a frame is wanted give QR_ERR_ARG.
+ *   - Parallelism: the launch has one wave per footprint of the ONE frame (8x8, 8x4, 4x4 pixels at FSAA 0, 2x, 4x) and that
+ *     wave renders all n_views views one after the other -- splitting views across waves would break the summation order.  A
+ *     small frame with many views therefore does not fill the GPU (480x270 without FSAA: about 2000 waves); there
+ *     qr_render_views_async, which has n_views x footprints waves, is the faster way to the same rays.
+ *   - Asynchronous on `stream`, on the scene's own device; no hidden copy.
+ */
+#define QR_MEAN_RESUME 1u               /* qr_render_views_mean_async: start from sum_dev instead of the first view's colour */
+int qr_render_views_mean_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
+                               float *sum_dev, uint32_t *frame_dev, float scale, uint32_t flags, void *stream);
+
+/*
  * Hit records: the closest hit of a ray AND the surface point the renderer would shade there -- hit point, normal, texture
  * colour, material.  What a host needs to bounce, reflect, offset or cosine-weight its own secondary rays (AO, light probes,
  * path tracing outside the renderer), and, per pixel of a camera, a G-buffer (position, normal, albedo, ids) for deferred passes

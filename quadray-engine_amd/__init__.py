@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "qr_scene_upload", "qr_scene_upload_ex", "qr_program_stats", "qr_program_stats_ex", "qr_snapshot_build_lists_c", "qr_scene_destroy", "qr_scene_get_info", "qr_scene_set_depth", "qr_scene_set_pt",
     "qr_scene_set_rows", "qr_scene_set_tile_rows", "qr_render_async", "qr_render_multi_async", "qr_render_ids_async",
     "qr_render_count", "qr_render_host", "qr_render_timed", "qr_trace_rays_async", "qr_occluded_async",
-    "qr_shade_rays_async", "qr_render_views_async", "qr_hit_rays_async", "qr_hit_views_async",
+    "qr_shade_rays_async", "qr_render_views_async", "qr_render_views_mean_async", "qr_hit_rays_async", "qr_hit_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
 UPLOAD_REBIN_TILES = 1
 UPLOAD_RAY_QUERIES = 2      # also compile the global list for Scene.trace / Scene.occluded
 TRACE_COHERENT = 1          # qr_trace_rays_async / qr_occluded_async flag: consecutive rays are neighbours
+MEAN_RESUME = 1             # qr_render_views_mean_async flag: the sum starts from the `sum` buffer's contents
 
 
 class QrError(RuntimeError):
@@ -95,6 +96,7 @@ def lib():
     L.qr_occluded_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_shade_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
     L.qr_render_views_async.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, ctypes.c_uint32, vp]
+    L.qr_render_views_mean_async.argtypes = [vp, vp, ci, ci, ci, vp, vp, ctypes.c_float, ctypes.c_uint32, vp]
     L.qr_hit_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_hit_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
@@ -474,6 +476,47 @@ class Scene:
                                            ctypes.c_void_p(dep.data_ptr() if depth else None), 0, self._stream_ptr(stream)))
         out = (frames,) + ((hid,) if ids else ()) + ((dep,) if depth else ())
         return out if len(out) > 1 else frames
+
+    def render_views_mean(self, views, width=None, height=None, sum=None, frame=True, scale=None, resume=False, stream=None):
+        """One frame that is the mean of many views (qr_render_views_mean_async): views, width, height as for render_views; every
+        view's linear pixel colour (render_views' arithmetic up to and including the FSAA reduce) is added in array order, one
+        fp32 add per channel and view, into `sum` (float32 [H, W, 3]; a new tensor unless given), and with frame=True (or an
+        int32 [H, W] tensor to fill) the rest of the output step is applied to sum * scale.  scale=None: float32(1) /
+        float32(n_views).  resume=True: the sum starts from the contents of `sum` (required then, as is `scale` when a frame is
+        wanted: 1 / the number of views added so far, this call's included) -- views cut into several resumed calls give the bits
+        of one call.  Returns (frame or None, sum).  One wave renders a footprint of all views: meant for full-size frames.
+        Asynchronous on `stream`."""
+        import numpy as np
+        import torch
+        w, h = self._views_arg(views, width, height)
+        n = views.shape[0]
+        if resume and sum is None:
+            raise QrError("resume=True needs the `sum` tensor of the earlier calls")
+        if sum is None:
+            sum = torch.empty((h, w, 3), dtype=torch.float32, device=views.device)      # every pixel is written
+        elif not (isinstance(sum, torch.Tensor) and sum.dtype == torch.float32 and tuple(sum.shape) == (h, w, 3)
+                  and sum.is_contiguous() and sum.is_cuda and sum.device.index == self.device):
+            raise QrError(f"sum must be a contiguous float32 [{h}, {w}, 3] tensor on cuda:{self.device}")
+        if frame is True:
+            frame = torch.empty((h, w), dtype=torch.int32, device=views.device)
+        elif frame is False or frame is None:
+            frame = None
+        elif not (isinstance(frame, torch.Tensor) and frame.dtype == torch.int32 and tuple(frame.shape) == (h, w)
+                  and frame.is_contiguous() and frame.is_cuda and frame.device.index == self.device):
+            raise QrError(f"frame must be True, False or a contiguous int32 [{h}, {w}] tensor on cuda:{self.device}")
+        if frame is not None:
+            if scale is None:
+                if resume:
+                    raise QrError("resume=True with a frame needs `scale`: 1 / the number of views added so far")
+                scale = np.float32(1) / np.float32(max(n, 1))
+            scale = float(np.float32(scale))
+            if not (np.isfinite(scale) and scale > 0.0):
+                raise QrError("scale must be finite and greater than 0")
+        _check(lib().qr_render_views_mean_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(sum.data_ptr()),
+                                                ctypes.c_void_p(frame.data_ptr() if frame is not None else None),
+                                                scale if frame is not None else 1.0, MEAN_RESUME if resume else 0,
+                                                self._stream_ptr(stream)))
+        return frame, sum
 
     def render_count(self, frame=None, stream=None):
         if frame is None:

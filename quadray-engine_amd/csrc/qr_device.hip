@@ -13,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstring>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #if defined(__SSE2__)
@@ -521,6 +522,43 @@ extern "C" int qr_render_views_async(qr_device_scene *s, const qr_view *views_de
         hipLaunchKernelGGL((qr_render_views_kernel<true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, vp, frames_dev, ids_dev);
     else
         hipLaunchKernelGGL((qr_render_views_kernel<false, QR_MIN_WAVES_PER_SIMD>), grid, block, 0, (hipStream_t)stream, s->lp, vp, frames_dev, ids_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+/* view accumulation (qr_kernel.hpp qr_views_mean_kernel): the sum and the mean frame of many views of one frame, in one launch */
+extern "C" int qr_render_views_mean_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                          float *sum_dev, uint32_t *frame_dev, float scale, uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
+    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
+        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
+    if ((flags & ~QR_MEAN_RESUME) != 0u) return qr_fail(QR_ERR_ARG, "unknown view accumulation flags");
+    if (frame_dev != nullptr && !(std::isfinite(scale) && scale > 0.0f))
+        return qr_fail(QR_ERR_ARG, "scale must be finite and greater than 0 when a frame is wanted");
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    if (s->pt_on) return qr_fail(QR_ERR_UNSUP, "scene is in path-tracer mode: its seeds and colour planes belong to the snapshot's frame");
+    if (n_views == 0) return QR_OK;
+    if (views_dev == nullptr || sum_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (((uintptr_t)views_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "views must be 16-byte aligned");
+    if ((((uintptr_t)sum_dev | (uintptr_t)frame_dev) & 3u) != 0) return qr_fail(QR_ERR_ARG, "sum and frame must be 4-byte aligned");
+    const int fsaa = s->fr.fsaa;
+    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+    HIP_TRY(hipSetDevice(s->device));
+    /* one wave per footprint of the ONE frame, whatever n_views is (at most 4096 x 4096 workgroups: QR_VIEW_MAX_DIM) */
+    const dim3 grid((unsigned)((width + fw - 1) / fw), (unsigned)((height + fh - 1) / fh), 1u), block(QR_BLOCK);
+    ViewsP vp;
+    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
+    const uint32_t resume = flags & QR_MEAN_RESUME;
+    if (frame_dev == nullptr) scale = 1.0f;
+    /* the instance is chosen as qr_render_views_async chooses its own */
+    if (s->divk)
+        hipLaunchKernelGGL((qr_views_mean_kernel<true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, vp, n_views,
+                           sum_dev, frame_dev, scale, resume);
+    else
+        hipLaunchKernelGGL((qr_views_mean_kernel<false, QR_MIN_WAVES_PER_SIMD>), grid, block, 0, (hipStream_t)stream, s->lp, vp, n_views,
+                           sum_dev, frame_dev, scale, resume);
     HIP_TRY(hipGetLastError());
     return QR_OK;
 }

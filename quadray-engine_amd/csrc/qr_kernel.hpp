@@ -287,14 +287,18 @@ __device__ __forceinline__ bool pixel_of_view(u32 ord, int fsaa, const ViewsP &v
  * linear colour and the first hit's id per ray instead of the frame's output step.  The recursion between them is one piece.
  * RAYS = 3 (view rendering, see ViewsP): the frame's own ray arithmetic and output step on the view gw of the launch, footprint
  * `ord`, the walk and the missing tile schedule of the caller-ray instances; the first hit's t leaves right after the first walk.
+ * RAYS = 4 (view accumulation, qr_views_mean_kernel): RAYS = 3 up to and including the FSAA reduce; the reduced linear colour is
+ * handed back in `mean_out` (sample 0's lane holds the pixel's) and nothing is stored.  The caller runs it once per view: everything
+ * a wave sets up -- rays, recursion stack, mode, counters -- is set up here, on every call, and nothing is read from an earlier one.
  */
 template <bool COUNT, bool DIVK, bool PT = false, int RAYS = 0>
 __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, const u32 sched_head, const int gw,
                                             uint32_t *__restrict__ frame, int32_t *__restrict__ ids,
                                             unsigned long long *__restrict__ counters, const PtParams *ptp = nullptr,
-                                            const RaysP *rp = nullptr, const ViewsP *vp = nullptr)
+                                            const RaysP *rp = nullptr, const ViewsP *vp = nullptr, V3 *mean_out = nullptr)
 {
-    constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3;
+    constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3 || RAYS == 4, MEAN = RAYS == 4;
+    (void)mean_out;
 #ifdef QR_WAVETIME
     const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
     const unsigned long long wt_clk0 = __builtin_amdgcn_s_memtime();      /* shader cycles: with the 100 MHz stamps, the clock the wave ran at */
@@ -811,6 +815,11 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
         cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
         cr = cr + __shfl_down(cr, 2); cg = cg + __shfl_down(cg, 2); cb = cb + __shfl_down(cb, 2);
     }
+    if constexpr (MEAN)
+    {
+        *mean_out = {cr, cg, cb};
+        return;
+    }
     /* pixel coordinates and row ownership once more (pixel_of) */
     int x_e, y_e, k_e;
     bool inside_e;
@@ -911,6 +920,73 @@ void qr_render_views_kernel(LaunchP lp, ViewsP vp, uint32_t *__restrict__ frames
     const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
     const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
     render_wave<false, DIVK, false, 3>(lp, ord, 0u, view, frames, ids, nullptr, nullptr, nullptr, &vp);
+}
+
+/*
+ * View accumulation (qr_render_views_mean_async): the grid is the footprints of ONE frame, one wave per workgroup; the wave renders
+ * its footprint from every view of the launch in array order (a wave-uniform loop: the view record comes through scalar loads,
+ * as in a view launch) and keeps the running sum of the reduced linear colours -- one fp32 add per channel and view, in order,
+ * never fused (-ffp-contract=off) -- for the lanes that hold sample 0 (in LDS between views, see below).  The sum is stored once,
+ * after the loop, with the optional packed pixel (the rest of the output step on sum * scale): 12 to 16 bytes of global traffic per pixel
+ * however many views there are.  QR_MEAN_RESUME: the sum starts from sum[p] instead of the first view's colour.  One wave per
+ * footprint whatever n_views is: a small frame does not fill the machine (include/qrhip.h).  Instances as the view launch's.
+ */
+template <bool DIVK, int WAVES>
+__global__ __launch_bounds__(QR_BLOCK, WAVES)
+void qr_views_mean_kernel(LaunchP lp, ViewsP vp, int n_views, float *__restrict__ sum, uint32_t *__restrict__ frame,
+                          float scale, u32 resume)
+{
+    const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
+    /* the running sum waits in LDS while a view is rendered (768 B per wave): live in registers across render_wave it cost the
+     * per-lane instance 13 more spilled registers (26: over its budget) and the packet instance 7 */
+    __shared__ float lds_sum[3][64];
+    const int lane = (int)(threadIdx.x & 63u);
+    if (resume)
+    {
+        const int fsaa_r = c_frm((BaseP)lp.B)->fr.fsaa;
+        int x_r, y_r, k_r;
+        if (pixel_of_view(ord, fsaa_r, vp, x_r, y_r, k_r) && k_r == 0)
+        {
+            const float *p = sum + 3 * ((size_t)y_r * (size_t)vp.width + (size_t)x_r);
+            lds_sum[0][lane] = p[0]; lds_sum[1][lane] = p[1]; lds_sum[2][lane] = p[2];
+        }
+    }
+    V3 s = {0.0f, 0.0f, 0.0f};
+#pragma nounroll
+    for (int v = 0; v < n_views; v++)
+    {
+        V3 c;
+        render_wave<false, DIVK, false, 4>(lp, ord, 0u, __builtin_amdgcn_readfirstlane(v), nullptr, nullptr, nullptr, nullptr,
+                                           nullptr, &vp, &c);
+        int lane_s = (int)(threadIdx.x & 63u);
+        asm volatile("" : "+v"(lane_s));            /* not an address register kept alive through the view */
+        if (v == 0 && !resume) s = c;
+        else
+        {
+            s.x = lds_sum[0][lane_s] + c.x; s.y = lds_sum[1][lane_s] + c.y; s.z = lds_sum[2][lane_s] + c.z;
+        }
+        if (v + 1 < n_views) { lds_sum[0][lane_s] = s.x; lds_sum[1][lane_s] = s.y; lds_sum[2][lane_s] = s.z; }
+    }
+    const FrmP fr = c_frm((BaseP)lp.B);
+    int x_e, y_e, k_e;
+    if (pixel_of_view(ord, fr->fr.fsaa, vp, x_e, y_e, k_e) && k_e == 0)
+    {
+        const size_t px = (size_t)y_e * (size_t)vp.width + (size_t)x_e;
+        sum[3 * px] = s.x; sum[3 * px + 1] = s.y; sum[3 * px + 2] = s.z;
+        if (frame != nullptr)
+        {
+            /* the rest of XX_end on the scaled sum: gamma, scale, round, mask, pack */
+            float cr = s.x * scale, cg = s.y * scale, cb = s.z * scale;
+            if (fr->fr.ctx_flags & QR_PROP_GAMMA)
+            {
+                asm volatile("" ::: "memory");
+                cr = __builtin_sqrtf(cr); cg = __builtin_sqrtf(cg); cb = __builtin_sqrtf(cb);
+            }
+            const float cl = fr->fr.clamp; const u32 cmask = fr->fr.cmask;
+            cr = cr * cl; cg = cg * cl; cb = cb * cl;
+            frame[px] = (((u32)cvt_near(cr) & cmask) << 16) | (((u32)cvt_near(cg) & cmask) << 8) | ((u32)cvt_near(cb) & cmask);
+        }
+    }
 }
 
 /*

@@ -21,6 +21,13 @@ rays it computes.
 
     views = torch.from_numpy(np.stack([view_of(blob), look_at(eye, target, up, 60.0, 512, 512)])).cuda()
     frames = scn.render_views(views, 512, 512)      # int32 [2, 512, 512]
+
+Scene.render_views_mean gives ONE frame that is the mean of many views, summed in linear fp32 colour on the GPU: jitter_view
+(sub-pixel-shifted copies: supersampling) and thin_lens_views (depth of field) make such view sets; reduce_colors, pack_linear and
+mean_of_views state its arithmetic in numpy.
+
+    views = torch.from_numpy(np.stack([jitter_view(view_of(blob), dx, dy) for dx, dy in offsets])).cuda()
+    frame, sum = scn.render_views_mean(views)       # int32 [H, W], float32 [H, W, 3]
 """
 import struct
 
@@ -166,6 +173,117 @@ def pack_colors(rgb, blob):
     q = _cvt_near(c) & np.int64(np.uint32(i[_F_CMASK]))
     p = (q[:, 0] << 16) | (q[:, 1] << 8) | q[:, 2]
     return (p & np.int64(0xFFFFFFFF)).astype(np.uint32).reshape(h, w)
+
+
+# ---- view accumulation (include/qrhip.h qr_render_views_mean_async; Scene.render_views_mean): the contract in numpy ----
+
+def reduce_colors(rgb, blob):
+    """The first half of the output step, up to and including the FSAA reduce, for linear colours of any number of pixels:
+    rgb float32 [ns, P, 3] (sample k in row k; ns = 2^fsaa of the snapshot) or [P, 3] at fsaa 0.  Returns float32 [P, 3]: the
+    linear pixel colour qr_render_views_mean_async adds per view.  One IEEE fp32 operation per step, as in pack_colors: clamp1
+    of each sample, every sample * 0.5 and samples (0, 1), (2, 3) added, for 4x once more * 0.5 and the two sums added."""
+    _, i = frame_record(blob)
+    fsaa = int(i[_F_FSAA])
+    ns = 1 << fsaa
+    c = np.asarray(rgb)
+    if c.ndim == 2:
+        c = c[None]
+    if c.dtype != np.float32 or c.ndim != 3 or c.shape[0] != ns or c.shape[2] != 3:
+        raise ValueError(f"rgb must be float32 [P, 3] or [{ns}, P, 3] for this snapshot (fsaa {fsaa}), got {c.dtype} {list(c.shape)}")
+    one, half = np.float32(1.0), np.float32(0.5)
+    c = np.where(c < one, c, one)                           # clamp1: NaN gives 1 as well
+    if fsaa >= 1:
+        c = c * half
+        c = np.stack([c[0] + c[1]] if fsaa == 1 else [c[0] + c[1], c[2] + c[3]])
+    if fsaa >= 2:
+        c = c * half
+        c = (c[0] + c[1])[None]
+    return c[0]
+
+
+def pack_linear(lin, blob, width, height):
+    """The second half of the output step for linear pixel colours lin, float32 [height * width, 3] (or [height, width, 3]): the
+    square root when ctx_flags holds QR_PROP_GAMMA, * clamp, round to nearest even, & cmask, packed as r << 16 | g << 8 | b.
+    Returns the uint32 [height, width] frame.  pack_linear(reduce_colors(rgb, blob), blob, W, H) is pack_colors(rgb, blob)."""
+    f, i = frame_record(blob)
+    w, h = int(width), int(height)
+    c = np.asarray(lin)
+    if c.dtype != np.float32 or c.size != w * h * 3 or c.shape[-1] != 3:
+        raise ValueError(f"lin must be float32 [{w * h}, 3], got {c.dtype} {list(c.shape)}")
+    c = c.reshape(w * h, 3)
+    if int(i[_F_FLAGS]) & PROP_GAMMA:
+        with np.errstate(invalid="ignore"):
+            c = np.sqrt(c)
+    c = c * f[_F_CLAMP]
+    q = _cvt_near(c) & np.int64(np.uint32(i[_F_CMASK]))
+    p = (q[:, 0] << 16) | (q[:, 1] << 8) | q[:, 2]
+    return (p & np.int64(0xFFFFFFFF)).astype(np.uint32).reshape(h, w)
+
+
+def mean_of_views(colours, blob, width, height, scale, start=None):
+    """The contract of qr_render_views_mean_async in numpy: colours is the per-view list of reduce_colors results (float32
+    [height * width, 3] each, in view order).  s = colours[0] (start=None) or `start` (the sum of an earlier call: the resumed
+    launch), then s = s + c for every remaining view -- one fp32 add per channel and view, in order.  Returns (frame, sum):
+    sum float32 [height, width, 3], frame = pack_linear(sum * float32(scale)) (one fp32 multiply), uint32 [height, width]."""
+    w, h = int(width), int(height)
+    cs = [np.asarray(c) for c in colours]
+    for c in cs:
+        if c.dtype != np.float32 or c.shape != (w * h, 3):
+            raise ValueError(f"every view's colours must be float32 [{w * h}, 3], got {c.dtype} {list(c.shape)}")
+    if start is None:
+        if not cs:
+            raise ValueError("mean_of_views needs a view or a start")
+        s, rest = cs[0].copy(), cs[1:]
+    else:
+        s = np.asarray(start)
+        if s.dtype != np.float32 or s.size != w * h * 3:
+            raise ValueError(f"start must be float32 [{h}, {w}, 3], got {s.dtype} {list(s.shape)}")
+        s, rest = s.reshape(w * h, 3).copy(), cs
+    for c in rest:
+        s = s + c
+    frame = pack_linear(s * np.float32(scale), blob, w, h)
+    return frame, s.reshape(h, w, 3)
+
+
+def jitter_view(view, dx, dy):
+    """The view shifted by a sub-pixel offset: pixel (x, y) of the result looks where (x + dx, y + dy) of `view` looks --
+    dir + hor * dx + ver * dy, computed in float64 and rounded to float32 once; everything else kept.  An offset of (0, 0)
+    returns the same bits.  N such copies through Scene.render_views_mean supersample a frame beyond the scene's FSAA."""
+    v = np.asarray(view, dtype=np.float32).reshape(16).copy()
+    if dx == 0 and dy == 0:
+        return v
+    d, hor, ver = (v[a:a + 3].astype(np.float64) for a in (4, 8, 12))
+    v[4:7] = d + hor * np.float64(dx) + ver * np.float64(dy)
+    return v
+
+
+def thin_lens_views(eye, target, up, fov_deg, width, height, aperture, focus, n, seed):
+    """n pinhole views (float32 [n, 16]) that sample a thin lens: look_at(eye, target, up, fov_deg, width, height) with the
+    origin moved by an offset on the disc of diameter `aperture` around `eye`, perpendicular to the viewing direction (uniform
+    over its area, numpy default_rng(seed): deterministic), and `dir` moved by -offset / focus, so that all views see the same
+    point of the plane at distance `focus` (along the viewing direction) through the same pixel: that plane stays sharp in
+    their mean (Scene.render_views_mean), everything else blurs with the aperture.  Float64, rounded to float32 once.
+    aperture = 0 gives n copies of look_at, bit for bit."""
+    base = look_at(eye, target, up, fov_deg, width, height)
+    if not (n >= 0 and aperture >= 0.0 and focus > 0.0):
+        raise ValueError("thin_lens_views needs n >= 0, aperture >= 0 and focus > 0")
+    out = np.tile(base, (int(n), 1))
+    if aperture == 0:
+        return out
+    eye, target, up = (np.asarray(a, dtype=np.float64).reshape(3) for a in (eye, target, up))
+    fwd = (target - eye) / np.linalg.norm(target - eye)
+    uh = np.cross(fwd, up)
+    uh = uh / np.linalg.norm(uh)
+    uv = np.cross(fwd, uh)
+    s = np.tan(np.radians(fov_deg) * 0.5) / (width * 0.5)
+    d = fwd - uh * s * (width * 0.5) - uv * s * (height * 0.5)
+    rng = np.random.default_rng(seed)
+    r = 0.5 * aperture * np.sqrt(rng.uniform(0.0, 1.0, int(n)))
+    phi = rng.uniform(0.0, 2.0 * np.pi, int(n))
+    off = (r * np.cos(phi))[:, None] * uh + (r * np.sin(phi))[:, None] * uv
+    out[:, 0:3] = eye + off
+    out[:, 4:7] = d - off / np.float64(focus)
+    return out
 
 
 # ---- hit records (include/qrhip.h qr_hit; Scene.hits, Scene.view_hits): float32 [..., 12] = pos xyz, t, nrm xyz, id, alb xyz, mat ----

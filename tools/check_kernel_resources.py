@@ -10,6 +10,7 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     QR_MAX_DIVK_SPILL spilled, 640 B private segment);
   * a view-rendering instance qr_render_views_kernel<DIVK, WAVES> exceeds that same budget, or its packet-walk instance
     <false,4> 128 VGPRs;
+  * a view-accumulation instance qr_views_mean_kernel<DIVK, WAVES> exceeds the budget of the view-rendering instance it mirrors;
   * a hit-record instance qr_hit_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more than
     168 VGPRs (128: the view instance with packet walks only);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
@@ -36,6 +37,10 @@ LIMITS = {
     # same budget; its packet-walk instance at the packet render instance's 128 registers (4 waves per SIMD)
     "22qr_render_views_kernelILb0ELi4EE": (128, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
     "22qr_render_views_kernelILb1ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    # view accumulation (qr_kernel.hpp qr_views_mean_kernel<DIVK, WAVES>): the view instances' machine run once per view, the sum
+    # of the views live in three more registers across it: held to the view instances' budgets
+    "20qr_views_mean_kernelILb0ELi4EE": (128, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "20qr_views_mean_kernelILb1ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
     # hit records (qr_hitrec.hpp qr_hit_kernel<VIEW, DIVK, COHERENT>): a walk and one surface point, no recursion: nothing spilled and
     # no private segment at all; caller rays and views of scenes with long lists at the closest-hit query's 168 registers, views of
     # the others at the packet instances' 128
