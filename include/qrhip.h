@@ -442,6 +442,48 @@ int qr_hit_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n,
 int qr_hit_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
                        qr_hit *hits_dev, uint32_t flags, void *stream);
 
+/*
+ * Occlusion fans: from every surface point a fan of K visibility rays along ONE direction table, in one launch -- ambient
+ * occlusion, sky and sun visibility, soft-shadow masks for a host's own lights, openness of lightmap texels and probes.  What a
+ * host would otherwise build from qr_hit_views_async, N x K qr_ray rows of its own and qr_occluded_async; here the hit stays in
+ * registers, no ray reaches memory and one count (and, if wanted, one bit per direction) per point leaves.
+ *   - Each element has a surface point pos, a normal nrm and an id (id < 0: a miss).  dirs_dev: k records, 1 <= k <=
+ *     QR_FAN_MAX_DIRS, DEVICE memory, 16-byte aligned, the same for every element; directions need not be unit length.
+ *     eps: the tmin of every fan ray, in units of |dir| (the step off the surface: there is no self-exclusion); reach: the tmax,
+ *     +inf taken as FLT_MAX.  Both must not be NaN.
+ *   - For direction d = dirs[j]: dot = (nrm.x * d.x + nrm.y * d.y) + nrm.z * d.z -- three fp32 products, two fp32 adds in that
+ *     order, never fused.  Without QR_FAN_FLIP the direction is TRACED iff 0 < dot (the renderer's rule for lights); otherwise
+ *     the surface itself blocks it: closed, no walk.  With QR_FAN_FLIP every direction is traced, as -d where dot < 0 and as d
+ *     otherwise (a two-sided fan: the hemisphere above the surface whichever way the normal points).  A NaN dot decides as these
+ *     comparisons do: closed without the flag, traced as d with it.
+ *   - A traced direction is OPEN iff qr_occluded_async answers 0 for the ray (pos, eps, +-d, reach): the same list, the same
+ *     shadow rule (light surfaces and transparent surfaces that do not refract cast none), the same interval rules.
+ *   - open_dev: int32 per element: the number of open directions, -1 for a miss.  mask_dev (NULL = not wanted): uint32
+ *     [ceil(k / 32)][elements]: bit j & 31 of plane j >> 5 is set iff direction j is open; bits of closed or untraced
+ *     directions, bits past k and every bit of a miss are 0.  Both 4-byte aligned.
+ *   - Recursion depth and path-tracer mode do not matter (nothing is lit).  Needs QR_UPLOAD_RAY_QUERIES (else QR_ERR_UNSUP).
+ * qr_fan_rays_async: an element is the first hit of ray i, exactly qr_hit_rays_async's pos, nrm, id; n elements; flags
+ * QR_TRACE_COHERENT | QR_FAN_FLIP.  qr_fan_views_async: an element is a pixel, exactly qr_hit_views_async's record (sample 0's
+ * under FSAA), elements [n_views][height][width]; flags QR_FAN_FLIP; the limits of qr_hit_views_async apply.  qr_fan_hits_async:
+ * pos, nrm, id are read from caller-supplied qr_hit records (16-byte aligned; t, alb, mat are not read) -- second-bounce AO,
+ * lightmap texels, any points with normals; no first walk; n elements; flags QR_FAN_FLIP.
+ * A null or misaligned pointer, unknown flags, k outside 1..QR_FAN_MAX_DIRS, a NaN eps or reach, n outside 0..INT32_MAX give
+ * QR_ERR_ARG; n == 0 (n_views == 0) returns QR_OK without a launch.  Asynchronous on `stream`, on the scene's own device; results
+ * do not depend on QR_TRACE_COHERENT.
+ */
+typedef struct qr_fan_dir { float dir[3]; float pad; } qr_fan_dir;     /* 16 bytes; pad is ignored */
+
+#define QR_FAN_MAX_DIRS 1024
+#define QR_FAN_FLIP 2u          /* trace every direction, mirrored into the normal's hemisphere (-d where nrm . d < 0) */
+
+int qr_fan_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+                      float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream);
+int qr_fan_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
+                       const qr_fan_dir *dirs_dev, int k, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
+                       uint32_t flags, void *stream);
+int qr_fan_hits_async(qr_device_scene *scn, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+                      float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* 3. Misc                                                                   */
 /* ------------------------------------------------------------------------ */

@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "qr_scene_set_rows", "qr_scene_set_tile_rows", "qr_render_async", "qr_render_multi_async", "qr_render_ids_async",
     "qr_render_count", "qr_render_host", "qr_render_timed", "qr_trace_rays_async", "qr_occluded_async",
     "qr_shade_rays_async", "qr_render_views_async", "qr_render_views_mean_async", "qr_hit_rays_async", "qr_hit_views_async",
+    "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -33,6 +34,8 @@ UPLOAD_REBIN_TILES = 1
 UPLOAD_RAY_QUERIES = 2      # also compile the global list for Scene.trace / Scene.occluded
 TRACE_COHERENT = 1          # qr_trace_rays_async / qr_occluded_async flag: consecutive rays are neighbours
 MEAN_RESUME = 1             # qr_render_views_mean_async flag: the sum starts from the `sum` buffer's contents
+FAN_FLIP = 2                # qr_fan_*_async flag: every direction is traced, mirrored into the normal's hemisphere
+FAN_MAX_DIRS = 1024         # QR_FAN_MAX_DIRS
 
 
 class QrError(RuntimeError):
@@ -99,6 +102,10 @@ def lib():
     L.qr_render_views_mean_async.argtypes = [vp, vp, ci, ci, ci, vp, vp, ctypes.c_float, ctypes.c_uint32, vp]
     L.qr_hit_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_hit_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_uint32, vp]
+    cf = ctypes.c_float
+    L.qr_fan_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    L.qr_fan_hits_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    L.qr_fan_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
     L.qr_frame_hash.argtypes = [vp, cu64]
@@ -453,6 +460,77 @@ class Scene:
         _check(lib().qr_hit_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(out.data_ptr()),
                                         0, self._stream_ptr(stream)))
         return out
+
+    def _fan_args(self, dirs, eps, reach, shape, mask):
+        """(dirs as a contiguous float32 [K, 4] tensor, K, eps, reach, open, mask or None) of an occlusion-fan call whose
+        elements have `shape`"""
+        import math
+        import torch
+        if not (isinstance(dirs, torch.Tensor) and dirs.dtype == torch.float32 and dirs.dim() == 2 and dirs.shape[1] in (3, 4)
+                and dirs.is_cuda and dirs.device.index == self.device):
+            raise QrError(f"dirs must be a float32 [K, 3] or [K, 4] tensor on cuda:{self.device}")
+        k = dirs.shape[0]
+        if not 1 <= k <= FAN_MAX_DIRS:
+            raise QrError(f"dirs must hold 1..{FAN_MAX_DIRS} directions, got {k}")
+        if eps is None or math.isnan(eps) or math.isnan(reach):
+            raise QrError("eps (the step off the surface, in units of |dir|) is required; eps and reach must not be NaN")
+        if dirs.shape[1] == 3:
+            d4 = torch.zeros((k, 4), dtype=torch.float32, device=dirs.device)
+            d4[:, 0:3] = dirs
+        else:
+            d4 = dirs.contiguous()
+        opn = torch.empty(shape, dtype=torch.int32, device=dirs.device)                 # every element is written
+        msk = torch.empty(((k + 31) // 32,) + tuple(shape), dtype=torch.int32, device=dirs.device) if mask else None
+        return d4, k, float(eps), float(reach), opn, msk
+
+    def occlusion(self, rays, dirs, eps, reach=float("inf"), flip=False, mask=False, coherent=False, stream=None):
+        """Occlusion fans from the first hits of caller rays (qr_fan_rays_async): for every ray, the surface point hits() gives
+        (pos, nrm, id) and from it one visibility ray per row of `dirs` (float32 [K, 3] or [K, 4] on the scene's device, K <=
+        1024, shared by all rays; [K, 3] is padded), in ONE launch: no hit record and no fan ray reaches memory.  Direction k is
+        traced iff 0 < nrm . dirs[k] (flip=True: always, as -dirs[k] where the dot product is negative) and is open iff
+        occluded() answers False for the ray (pos, eps, +-dirs[k], reach); rays.fan_rays states the composition exactly.
+        Returns open (int32 [N]: the number of open directions, -1 where the ray hits nothing); with mask=True (open, mask):
+        mask int32 [ceil(K / 32), N], bit k & 31 of plane k >> 5 set iff direction k is open (rays.fan_bits unpacks it).
+        eps: the step off the surface in units of |dir| (there is no self-exclusion).  coherent: as for trace(); results do not
+        depend on it.  Nothing is lit: depth and path-tracer mode do not matter.  Asynchronous on `stream`."""
+        rays = self._rays_arg(rays)
+        n = rays.shape[0]
+        d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, (n,), mask)
+        _check(lib().qr_fan_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
+                                       ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
+                                       (TRACE_COHERENT if coherent else 0) | (FAN_FLIP if flip else 0), self._stream_ptr(stream)))
+        return (opn, msk) if mask else opn
+
+    def view_occlusion(self, views, dirs, width=None, height=None, eps=None, reach=float("inf"), flip=False, mask=False, stream=None):
+        """Occlusion fans from every pixel of caller-supplied cameras (qr_fan_views_async): ambient occlusion or sky visibility
+        of whole frames in one launch.  views, width, height as for view_hits -- the surface point of a pixel is its record there
+        (sample 0's under FSAA) -- dirs, eps (required), reach, flip, mask as for occlusion().  Returns open int32 [N, H, W]
+        (-1 where the pixel shows nothing), with mask=True (open, mask int32 [ceil(K / 32), N, H, W]).  Asynchronous on `stream`."""
+        w, h = self._views_arg(views, width, height)
+        n = views.shape[0]
+        d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, (n, h, w), mask)
+        _check(lib().qr_fan_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
+                                        ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
+                                        FAN_FLIP if flip else 0, self._stream_ptr(stream)))
+        return (opn, msk) if mask else opn
+
+    def hit_occlusion(self, hits, dirs, eps, reach=float("inf"), flip=False, mask=False, stream=None):
+        """Occlusion fans from caller-supplied hit records (qr_fan_hits_async): hits float32 [..., 12] on the scene's device,
+        contiguous (hits(), view_hits(), or a host's own points: pos in columns 0:3, nrm in 4:7, the int32 bits of an id >= 0 in
+        column 7; the rest is not read) -- second-bounce AO, lightmap texels, probes.  No first walk.  dirs, eps, reach, flip,
+        mask as for occlusion().  Returns open int32 [...] (-1 where id < 0), with mask=True (open, mask int32
+        [ceil(K / 32), ...]).  Asynchronous on `stream`."""
+        import torch
+        if not (isinstance(hits, torch.Tensor) and hits.dtype == torch.float32 and hits.dim() >= 2 and hits.shape[-1] == 12
+                and hits.is_contiguous() and hits.is_cuda and hits.device.index == self.device):
+            raise QrError(f"hits must be a contiguous float32 [..., 12] tensor on cuda:{self.device} (qr_hit records)")
+        shape = tuple(hits.shape[:-1])
+        n = hits.numel() // 12
+        d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, shape, mask)
+        _check(lib().qr_fan_hits_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
+                                       ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
+                                       FAN_FLIP if flip else 0, self._stream_ptr(stream)))
+        return (opn, msk) if mask else opn
 
     def render_views(self, views, width=None, height=None, frames=None, ids=False, depth=False, stream=None):
         """Whole frames of the resident scene from caller-supplied cameras (qr_render_views_async): views float32 [N, 16] on the

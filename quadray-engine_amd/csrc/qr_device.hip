@@ -10,6 +10,7 @@
 #include "qr_kernel.hpp"
 #include "qr_query.hpp"
 #include "qr_hitrec.hpp"
+#include "qr_fan.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -616,6 +617,113 @@ extern "C" int qr_hit_views_async(qr_device_scene *s, const qr_view *views_dev, 
     else
         hipLaunchKernelGGL((qr_hit_kernel<true, false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
                            vp, s->off_mat, (f32x4 *)hits_dev, s->lp.stats);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+/* ---- occlusion fans (qr_fan.hpp): per surface point, how many directions of a shared table are open ---- */
+
+/* what the three entry points check alike, before the element count decides whether anything is launched */
+static int fan_args(const qr_device_scene *s, int k, float eps, float reach, uint32_t flags, uint32_t allowed)
+{
+    if (flags & ~allowed) return qr_fail(QR_ERR_ARG, "unknown fan flags");
+    if (k < 1 || k > QR_FAN_MAX_DIRS) return qr_fail(QR_ERR_ARG, "direction count must be 1.." + std::to_string(QR_FAN_MAX_DIRS));
+    if (std::isnan(eps) || std::isnan(reach)) return qr_fail(QR_ERR_ARG, "eps and reach must not be NaN");
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    return QR_OK;
+}
+
+/* ... and once there are elements: src is the ray, view or record array */
+static int fan_ptrs(const void *src, const qr_fan_dir *dirs, const int32_t *open, const uint32_t *mask)
+{
+    if (src == nullptr || dirs == nullptr || open == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if ((((uintptr_t)src | (uintptr_t)dirs) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays, views, hits and dirs must be 16-byte aligned");
+    if ((((uintptr_t)open | (uintptr_t)mask) & 3u) != 0) return qr_fail(QR_ERR_ARG, "open and mask must be 4-byte aligned");
+    return QR_OK;
+}
+
+static FanP fan_params(const qr_fan_dir *dirs, int k, float eps, float reach, int32_t *open, uint32_t *mask, uint32_t flags, uint64_t elems)
+{
+    FanP fp;
+    fp.dirs = dirs; fp.k = k; fp.flip = flags & QR_FAN_FLIP;
+    fp.eps = eps; fp.reach = reach > FLT_MAX ? FLT_MAX : reach;     /* +inf is taken as FLT_MAX, as in qr_trace_kernel */
+    fp.open = open; fp.mask = mask; fp.elems = elems;
+    return fp;
+}
+
+extern "C" int qr_fan_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+                                 float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
+    { const int rc = fan_args(s, k, eps, reach, flags, QR_TRACE_COHERENT | QR_FAN_FLIP); if (rc != QR_OK) return rc; }
+    if (n == 0) return QR_OK;
+    { const int rc = fan_ptrs(rays_dev, dirs_dev, open_dev, mask_dev); if (rc != QR_OK) return rc; }
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    const f32x4 *r = (const f32x4 *)rays_dev;
+    const ViewsP vp = {};
+    const FanP fp = fan_params(dirs_dev, k, eps, reach, open_dev, mask_dev, flags, (uint64_t)n);
+    if (flags & QR_TRACE_COHERENT)
+        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_RAYS, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r,
+                           (int32_t)n, vp, fp, s->lp.stats);
+    else
+        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_RAYS, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r,
+                           (int32_t)n, vp, fp, s->lp.stats);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+extern "C" int qr_fan_hits_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+                                 float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "record count must be 0..INT32_MAX");
+    { const int rc = fan_args(s, k, eps, reach, flags, QR_FAN_FLIP); if (rc != QR_OK) return rc; }
+    if (n == 0) return QR_OK;
+    { const int rc = fan_ptrs(hits_dev, dirs_dev, open_dev, mask_dev); if (rc != QR_OK) return rc; }
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    const ViewsP vp = {};
+    const FanP fp = fan_params(dirs_dev, k, eps, reach, open_dev, mask_dev, flags, (uint64_t)n);
+    hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_HITS, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob,
+                       (const f32x4 *)hits_dev, (int32_t)n, vp, fp, s->lp.stats);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+extern "C" int qr_fan_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                  const qr_fan_dir *dirs_dev, int k, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
+                                  uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
+    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
+        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
+    { const int rc = fan_args(s, k, eps, reach, flags, QR_FAN_FLIP); if (rc != QR_OK) return rc; }
+    {
+        /* the limit of qr_hit_views_async, in qr_render_views_async's footprints (the frame's FSAA) */
+        const int fsaa = s->fr.fsaa;
+        const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+        if ((int64_t)n_views * ((width + fw - 1) / fw) * ((height + fh - 1) / fh) > (int64_t)QR_VIEW_MAX_WAVES)
+            return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
+    }
+    if (n_views == 0) return QR_OK;
+    { const int rc = fan_ptrs(views_dev, dirs_dev, open_dev, mask_dev); if (rc != QR_OK) return rc; }
+    HIP_TRY(hipSetDevice(s->device));
+    /* one lane per pixel: 8x8 footprints at every FSAA, as qr_hit_views_async */
+    const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
+    ViewsP vp;
+    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
+    const FanP fp = fan_params(dirs_dev, k, eps, reach, open_dev, mask_dev, flags, (uint64_t)n_views * (uint64_t)width * (uint64_t)height);
+    const f32x4 *none = nullptr;
+    /* the instance is chosen as qr_hit_views_async chooses its own */
+    if (s->divk)
+        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_VIEW, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
+                           vp, fp, s->lp.stats);
+    else
+        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_VIEW, false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
+                           vp, fp, s->lp.stats);
     HIP_TRY(hipGetLastError());
     return QR_OK;
 }

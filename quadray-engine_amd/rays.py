@@ -13,7 +13,9 @@ only where the engine's tiles hold other surfaces than its global list):
     frame = pack_colors(rgb.cpu().numpy(), blob)    # uint32 [H, W], 0x00RRGGBB
 
 Scene.hits / Scene.view_hits return hit records (qr_hit: position, t, normal, id, albedo, material); hit_fields splits them into
-typed views, offset_rays and reflect_rays build a host's own secondary rays from them.
+typed views, offset_rays and reflect_rays build a host's own secondary rays from them.  Fans of many visibility rays per hit
+(ambient occlusion, sky visibility) need no rays: Scene.occlusion / view_occlusion / hit_occlusion trace a shared direction table
+(sphere_dirs) from every hit in one launch; fan_rays states what they trace, fan_bits unpacks their masks.
 
 Whole frames from pinhole cameras do not need that detour: Scene.render_views renders them on the GPU from qr_view records
 (view_of: the snapshot's own camera; look_at: eye / target / up / field of view), at any frame size, and view_rays gives the
@@ -319,8 +321,10 @@ def offset_rays(hits, dirs, eps):
     """Secondary rays that leave hit points: hits float32 [N, 12] (Scene.hits), dirs float32 [N, 3] on the same device.
     Returns float32 [N, 8] qr_ray rows: origin = pos, direction = dirs, tmin = eps (the step off the surface, in units of
     |dir|: no self-exclusion in the ray API), tmax = +inf; rows of misses get tmax = tmin and hit nothing.
-    A helper for a host's own passes (AO, probes); NOT the renderer's bit-exact children: those start at tmin 0 with the
-    originating surface excluded, which the ray API does not offer."""
+    A helper for a host's own passes with one direction per hit (probes, a bounce); NOT the renderer's bit-exact children: those
+    start at tmin 0 with the originating surface excluded, which the ray API does not offer.  Ambient occlusion and other fans of
+    many directions per hit need no rays at all: Scene.occlusion / Scene.view_occlusion / Scene.hit_occlusion trace them from
+    the hit in one launch (fan_rays states what they trace)."""
     return _secondary(hits, dirs, eps)
 
 
@@ -333,3 +337,83 @@ def reflect_rays(rays, hits, eps):
     d = rays[:, 4:7]
     dn = (d * nrm).sum(dim=1, keepdim=True)
     return _secondary(hits, d - 2.0 * dn * nrm, eps)
+
+
+# ---- occlusion fans (include/qrhip.h qr_fan_*_async; Scene.occlusion, Scene.view_occlusion, Scene.hit_occlusion) ----
+
+def fan_rays(hits, dirs, eps, reach=float("inf"), flip=False):
+    """The rays an occlusion fan traces, as a composition of the ray API: hits float32 [N, 12] (Scene.hits, or view_hits
+    reshaped), dirs float32 [K, 3] or [K, 4] (the fourth column is ignored), numpy arrays or torch tensors on one device.
+    Returns (rays float32 [N, K, 8], traced bool [N, K]).
+
+    For hit i and direction d = dirs[k]:  dot = (nrm.x * d.x + nrm.y * d.y) + nrm.z * d.z -- three float32 products and two
+    float32 adds in that order, nothing fused.  flip=False: the ray is (pos, eps, d, reach) and it is traced iff the record is
+    a hit (id >= 0) and 0 < dot: the renderer's rule for lights; otherwise the surface itself closes the direction.
+    flip=True: the ray is (pos, eps, -d, reach) where dot < 0 and (pos, eps, d, reach) otherwise, and every direction of a
+    hit is traced.  A NaN dot decides as these comparisons do (closed without flip, traced as d with it).  Rows of misses are
+    filled the same way and never traced.  Direction k of element i is OPEN iff it is traced and Scene.occluded answers False
+    for its ray; Scene.occlusion counts the open directions (-1 for a miss) and sets bit k & 31 of mask plane k >> 5."""
+    pos, _, nrm, hid, _, _ = hit_fields(hits)
+    if hits.ndim != 2:
+        raise ValueError(f"hits must be [N, 12], got {list(hits.shape)}")
+    if dirs.ndim != 2 or dirs.shape[1] not in (3, 4) or "float32" not in str(dirs.dtype):
+        raise ValueError(f"dirs must be float32 [K, 3] or [K, 4], got {dirs.dtype} {list(dirs.shape)}")
+    n, k = hits.shape[0], dirs.shape[0]
+    d = dirs[:, 0:3]
+    if isinstance(hits, np.ndarray):
+        where, full = np.where, (lambda shape, dt: np.empty(shape, dtype=dt))
+        f32, bool_ = np.float32, np.bool_
+        ctx = np.errstate(invalid="ignore", over="ignore")
+    else:
+        import contextlib
+        import torch
+        where, full = torch.where, (lambda shape, dt: torch.empty(shape, dtype=dt, device=hits.device))
+        f32, bool_ = torch.float32, torch.bool
+        ctx = contextlib.nullcontext()
+    with ctx:
+        p0 = nrm[:, 0:1] * d[:, 0][None, :]
+        p1 = nrm[:, 1:2] * d[:, 1][None, :]
+        p2 = nrm[:, 2:3] * d[:, 2][None, :]
+        dot = (p0 + p1) + p2                                    # [N, K]
+        rays = full((n, k, 8), f32)
+        traced = full((n, k), bool_)
+        rays[:, :, 0:3] = pos[:, None, :]
+        rays[:, :, 3] = eps
+        rays[:, :, 7] = reach
+        hit = (hid >= 0)[:, None]
+        if flip:
+            neg = (dot < 0)[:, :, None]
+            rays[:, :, 4:7] = where(neg, -d[None, :, :], d[None, :, :])
+            traced[:, :] = hit
+        else:
+            rays[:, :, 4:7] = d[None, :, :]
+            traced[:, :] = hit & (0 < dot)
+    return rays, traced
+
+
+def fan_bits(mask, k):
+    """The mask planes of an occlusion fan as booleans: mask int32 or uint32 [ceil(k / 32), ...] (numpy array or torch tensor, as
+    Scene.occlusion(..., mask=True) returns it) -> bool [..., k]: entry j is bit j & 31 of plane j >> 5."""
+    k = int(k)
+    if k < 1 or mask.ndim < 1 or mask.shape[0] != (k + 31) // 32:
+        raise ValueError(f"a mask of {k} directions has {(k + 31) // 32} planes, got shape {list(mask.shape)}")
+    cols = [((mask[j >> 5] >> (j & 31)) & 1) != 0 for j in range(k)]
+    if isinstance(mask, np.ndarray):
+        return np.stack(cols, axis=-1)
+    import torch
+    return torch.stack(cols, dim=-1)
+
+
+def sphere_dirs(n):
+    """n directions on a Fibonacci sphere, float32 [n, 3], unit length: with i = arange(n) + 0.5, z = 1 - 2 i / n,
+    phi = i * pi * (3 - sqrt(5)), s = sqrt(1 - z^2), the direction is (s cos phi, s sin phi, z).  Computed in float64 and
+    rounded to float32 once.  A direction table for Scene.occlusion: with flip=True every point sees all n mirrored into its
+    own hemisphere; without, about half of them lie above any surface."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("sphere_dirs needs n >= 1")
+    i = np.arange(n, dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * i / n
+    phi = i * np.pi * (3.0 - np.sqrt(5.0))
+    s = np.sqrt(1.0 - z * z)
+    return np.stack([s * np.cos(phi), s * np.sin(phi), z], axis=1).astype(np.float32)

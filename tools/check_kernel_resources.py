@@ -13,6 +13,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
   * a view-accumulation instance qr_views_mean_kernel<DIVK, WAVES> exceeds the budget of the view-rendering instance it mirrors;
   * a hit-record instance qr_hit_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more than
     168 VGPRs (128: the view instance with packet walks only);
+  * an occlusion-fan instance qr_fan_kernel<SRC, DIVK, COHERENT> spills a vector register, has a private segment, or uses more
+    than 168 VGPRs (128: the view instance with packet walks only and the instance that reads caller records);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
 usage: check_kernel_resources.py <file.s> [--print]
 """
@@ -48,6 +50,15 @@ LIMITS = {
     "13qr_hit_kernelILb0ELb1ELb1EE": (168, 0, 0),
     "13qr_hit_kernelILb1ELb1ELb1EE": (168, 0, 0),
     "13qr_hit_kernelILb1ELb0ELb1EE": (128, 0, 0),
+    # occlusion fans (qr_fan.hpp qr_fan_kernel<SRC, DIVK, COHERENT>; SRC 0 caller rays, 1 views, 2 caller records): a first walk and
+    # one surface point as a hit-record instance, then the occlusion query's walk in a loop with point, normal, count and mask
+    # word live across it: nothing spilled, no private segment; the hit-record instances' registers where there is a first
+    # walk, the occlusion query's 128 (4 waves per SIMD) where there is none
+    "13qr_fan_kernelILi0ELb1ELb0EE": (168, 0, 0),
+    "13qr_fan_kernelILi0ELb1ELb1EE": (168, 0, 0),
+    "13qr_fan_kernelILi1ELb1ELb1EE": (168, 0, 0),
+    "13qr_fan_kernelILi1ELb0ELb1EE": (128, 0, 0),
+    "13qr_fan_kernelILi2ELb1ELb0EE": (128, 0, 0),
 }
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 
