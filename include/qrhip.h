@@ -484,6 +484,44 @@ int qr_fan_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_vie
 int qr_fan_hits_async(qr_device_scene *scn, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
                       float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream);
 
+/*
+ * Hit layers: the first k hits along a ray, in order, in one launch -- picking through glass and x-ray selection, thickness and
+ * entry / exit pairs of a solid, order-independent transparency, CSG inspection, layered depth images for reprojection, "how many
+ * surfaces lie between A and B".  What a host would otherwise loop over qr_trace_rays_async, reading the rays again for every
+ * layer and rewriting tmin in between; here the ray stays in registers and only the answers leave.
+ *   - For a ray (org, tmin, dir, tmax) and k layers, 1 <= k <= QR_LAYER_MAX: layer 0 is exactly what qr_trace_rays_async
+ *     answers for the ray; layer j + 1 is what it answers for (org, t_j, dir, tmax), where t_j is layer j's t, bit for bit, used
+ *     as the new tmin with no epsilon (a hit counts when tmin < t < tmax and a query ray has no self-exclusion, so the next hit
+ *     is the same ray from t_j on).
+ *   - A ray ENDS at the first layer that is a miss.  count_dev (required): int32 per element, the number of hits found, 0..k;
+ *     count == k means "there may be more".  Every layer from `count` on holds the miss values: t = tmax (FLT_MAX for +inf),
+ *     id = -1, and the miss record of qr_hit_rays_async.  All k planes are always written in full: no memset is needed.
+ *   - Consequences.  t is strictly increasing over a ray's hits.  Surfaces whose t is bit-equal collapse to the one that is
+ *     first in list order (the others are not at t > t_j); hits a few ulp apart are both kept.  Resuming is exact: k1 layers,
+ *     then k2 layers on the rays (org, t of the last layer found, dir, tmax) -- and (org, tmax, dir, tmax), an empty interval,
+ *     for a ray that has ended: quadray-engine_amd/rays.py next_rays -- give the bits of one call with k1 + k2.
+ *   - t_dev (float32), id_dev (int32, surface_index << 1 | side as qr_trace_rays_async) and hits_dev (qr_hit) are each optional
+ *     (NULL = not wanted) and laid out plane-major, [k][elements], so that a wave's stores are contiguous; a call with none of
+ *     them is valid ("how many surfaces does this ray cross", up to k).  Layer j's qr_hit is exactly qr_hit_rays_async's record
+ *     for the ray (org, t_{j-1}, dir, tmax) (layer 0: the ray itself).
+ *   - Nothing is lit: recursion depth and path-tracer mode do not matter.  Needs QR_UPLOAD_RAY_QUERIES (else QR_ERR_UNSUP).
+ * qr_layer_rays_async: n elements, one per qr_ray; flags: QR_TRACE_COHERENT only; results do not depend on it.
+ * qr_layer_views_async: elements are [n_views][height][width], the rays are those of qr_hit_views_async (sample 0's under
+ * FSAA), the same limits apply (QR_VIEW_MAX_DIM, QR_VIEW_MAX_VIEWS, QR_VIEW_MAX_WAVES); flags: none defined, anything but 0
+ * gives QR_ERR_ARG.
+ * A null rays_dev / views_dev / count_dev, a misaligned pointer (rays, views and hits 16 bytes, count, t and id 4), k outside
+ * 1..QR_LAYER_MAX, n outside 0..INT32_MAX, a size outside the limits or unknown flags give QR_ERR_ARG; n == 0 (n_views == 0)
+ * returns QR_OK without a launch.  Asynchronous on `stream`, on the scene's own device.
+ */
+#define QR_LAYER_MAX 64
+
+int qr_layer_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n, int k,
+                        int32_t *count_dev, float *t_dev, int32_t *id_dev, qr_hit *hits_dev,
+                        uint32_t flags, void *stream);
+int qr_layer_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height, int k,
+                         int32_t *count_dev, float *t_dev, int32_t *id_dev, qr_hit *hits_dev,
+                         uint32_t flags, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* 3. Misc                                                                   */
 /* ------------------------------------------------------------------------ */

@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "qr_scene_set_rows", "qr_scene_set_tile_rows", "qr_render_async", "qr_render_multi_async", "qr_render_ids_async",
     "qr_render_count", "qr_render_host", "qr_render_timed", "qr_trace_rays_async", "qr_occluded_async",
     "qr_shade_rays_async", "qr_render_views_async", "qr_render_views_mean_async", "qr_hit_rays_async", "qr_hit_views_async",
-    "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async",
+    "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async", "qr_layer_rays_async", "qr_layer_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -36,6 +36,7 @@ TRACE_COHERENT = 1          # qr_trace_rays_async / qr_occluded_async flag: cons
 MEAN_RESUME = 1             # qr_render_views_mean_async flag: the sum starts from the `sum` buffer's contents
 FAN_FLIP = 2                # qr_fan_*_async flag: every direction is traced, mirrored into the normal's hemisphere
 FAN_MAX_DIRS = 1024         # QR_FAN_MAX_DIRS
+LAYER_MAX = 64              # QR_LAYER_MAX: the most layers of one qr_layer_*_async call
 
 
 class QrError(RuntimeError):
@@ -106,6 +107,8 @@ def lib():
     L.qr_fan_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
     L.qr_fan_hits_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
     L.qr_fan_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    L.qr_layer_rays_async.argtypes = [vp, vp, ctypes.c_int64, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
+    L.qr_layer_views_async.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
     L.qr_frame_hash.argtypes = [vp, cu64]
@@ -531,6 +534,59 @@ class Scene:
                                        ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
                                        FAN_FLIP if flip else 0, self._stream_ptr(stream)))
         return (opn, msk) if mask else opn
+
+    def _layer_args(self, k, shape, t, ids, hits, device):
+        """(k, count, t or None, ids or None, hits or None) of a hit-layer call whose elements have `shape`"""
+        import numbers
+        import torch
+        if not (isinstance(k, numbers.Integral) and 1 <= k <= LAYER_MAX):
+            raise QrError(f"k must be an integer 1..{LAYER_MAX} (layers), got {k!r}")
+        k = int(k)
+        shape = tuple(shape)
+        cnt = torch.empty(shape, dtype=torch.int32, device=device)                      # every element of every plane is written
+        tt = torch.empty((k,) + shape, dtype=torch.float32, device=device) if t else None
+        ii = torch.empty((k,) + shape, dtype=torch.int32, device=device) if ids else None
+        hh = torch.empty((k,) + shape + (12,), dtype=torch.float32, device=device) if hits else None
+        return k, cnt, tt, ii, hh
+
+    @staticmethod
+    def _layer_out(cnt, tt, ii, hh, hits):
+        return (cnt, tt, ii, hh) if hits else (cnt, tt, ii)
+
+    def trace_layers(self, rays, k, t=True, ids=True, hits=False, coherent=False, stream=None):
+        """The first k hits along every ray, in order, in ONE launch (qr_layer_rays_async): picking through glass, thickness and
+        entry / exit pairs, order-independent transparency, "how many surfaces lie between A and B".  rays as for trace(); k:
+        1..LAYER_MAX.  Layer 0 is exactly trace()'s answer for the ray; layer j + 1 is its answer for the same ray with tmin = t
+        of layer j, bit for bit, no epsilon (rays.layers_of states the composition).  A ray ends at its first miss.
+        Returns (count, t, ids) or, with hits=True, (count, t, ids, hits): count int32 [N]: hits found, 0..k (k: there may be
+        more); t float32 [k, N] and ids int32 [k, N]: plane j is layer j, with the miss values t = tmax (FLT_MAX for +inf),
+        id = -1 from layer `count` on; hits float32 [k, N, 12]: layer j's qr_hit record (see hits()), the miss record from
+        layer `count` on.  t=False / ids=False: that output is not computed and None stands in its place.  t is strictly
+        increasing over a ray's hits; surfaces at bit-equal t collapse to the first in list order.  rays.next_rays(rays, t[-1],
+        ids[-1]) gives the rays that resume where this call stopped: k1 layers, then k2 on them, equal one call with k1 + k2.
+        coherent: as for trace(); results do not depend on it.  Nothing is lit: depth and path-tracer mode do not matter.
+        Asynchronous on `stream`."""
+        rays = self._rays_arg(rays)
+        n = rays.shape[0]
+        k, cnt, tt, ii, hh = self._layer_args(k, (n,), t, ids, hits, rays.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else None)
+        _check(lib().qr_layer_rays_async(self._h, ptr(rays), n, k, ptr(cnt), ptr(tt), ptr(ii), ptr(hh),
+                                         TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
+        return self._layer_out(cnt, tt, ii, hh, hits)
+
+    def view_layers(self, views, k, width=None, height=None, t=True, ids=True, hits=False, stream=None):
+        """The first k hits behind every pixel of caller-supplied cameras (qr_layer_views_async): layered depth images, x-ray
+        views, thickness maps.  views, width, height as for view_hits -- the rays are the ones it traces, sample 0's under FSAA
+        -- k, t, ids, hits as for trace_layers().  Returns (count int32 [N, H, W], t float32 [k, N, H, W], ids int32
+        [k, N, H, W]) and, with hits=True, hits float32 [k, N, H, W, 12].  Layer 0 is view_hits' answer.  Asynchronous on
+        `stream`."""
+        w, h = self._views_arg(views, width, height)
+        n = views.shape[0]
+        k, cnt, tt, ii, hh = self._layer_args(k, (n, h, w), t, ids, hits, views.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else None)
+        _check(lib().qr_layer_views_async(self._h, ptr(views), n, w, h, k, ptr(cnt), ptr(tt), ptr(ii), ptr(hh),
+                                          0, self._stream_ptr(stream)))
+        return self._layer_out(cnt, tt, ii, hh, hits)
 
     def render_views(self, views, width=None, height=None, frames=None, ids=False, depth=False, stream=None):
         """Whole frames of the resident scene from caller-supplied cameras (qr_render_views_async): views float32 [N, 16] on the

@@ -11,6 +11,7 @@
 #include "qr_query.hpp"
 #include "qr_hitrec.hpp"
 #include "qr_fan.hpp"
+#include "qr_layers.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -724,6 +725,94 @@ extern "C" int qr_fan_views_async(qr_device_scene *s, const qr_view *views_dev, 
     else
         hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_VIEW, false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
                            vp, fp, s->lp.stats);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+/* ---- hit layers (qr_layers.hpp): the first k hits along a ray, in order ---- */
+
+/* what the two entry points check alike, before the element count decides whether anything is launched */
+static int layer_args(const qr_device_scene *s, int k, uint32_t flags, uint32_t allowed)
+{
+    if (flags & ~allowed) return qr_fail(QR_ERR_ARG, "unknown layer flags");
+    if (k < 1 || k > QR_LAYER_MAX) return qr_fail(QR_ERR_ARG, "layer count must be 1.." + std::to_string(QR_LAYER_MAX));
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    return QR_OK;
+}
+
+/* ... and once there are elements: src is the ray or view array; t, id and hits may be null */
+static int layer_ptrs(const void *src, const int32_t *count, const float *t, const int32_t *id, const qr_hit *hits)
+{
+    if (src == nullptr || count == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if ((((uintptr_t)src | (uintptr_t)hits) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays, views and hits must be 16-byte aligned");
+    if ((((uintptr_t)count | (uintptr_t)t | (uintptr_t)id) & 3u) != 0) return qr_fail(QR_ERR_ARG, "count, t and id must be 4-byte aligned");
+    return QR_OK;
+}
+
+static LayerP layer_params(const qr_device_scene *s, int k, int32_t *count, float *t, int32_t *id, qr_hit *hits, uint64_t elems)
+{
+    LayerP lp;
+    lp.k = k; lp.off_mat = s->off_mat;
+    lp.count = count; lp.t = t; lp.id = id; lp.hits = (f32x4 *)hits; lp.elems = elems;
+    return lp;
+}
+
+extern "C" int qr_layer_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, int k,
+                                   int32_t *count_dev, float *t_dev, int32_t *id_dev, qr_hit *hits_dev,
+                                   uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
+    { const int rc = layer_args(s, k, flags, QR_TRACE_COHERENT); if (rc != QR_OK) return rc; }
+    if (n == 0) return QR_OK;
+    { const int rc = layer_ptrs(rays_dev, count_dev, t_dev, id_dev, hits_dev); if (rc != QR_OK) return rc; }
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    const f32x4 *r = (const f32x4 *)rays_dev;
+    const ViewsP vp = {};
+    const LayerP lp = layer_params(s, k, count_dev, t_dev, id_dev, hits_dev, (uint64_t)n);
+    if (flags & QR_TRACE_COHERENT)
+        hipLaunchKernelGGL((qr_layer_kernel<false, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
+                           vp, lp, s->lp.stats);
+    else
+        hipLaunchKernelGGL((qr_layer_kernel<false, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
+                           vp, lp, s->lp.stats);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+extern "C" int qr_layer_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height, int k,
+                                    int32_t *count_dev, float *t_dev, int32_t *id_dev, qr_hit *hits_dev,
+                                    uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
+    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
+        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
+    { const int rc = layer_args(s, k, flags, 0u); if (rc != QR_OK) return rc; }
+    {
+        /* the limit of qr_hit_views_async, in qr_render_views_async's footprints (the frame's FSAA) */
+        const int fsaa = s->fr.fsaa;
+        const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+        if ((int64_t)n_views * ((width + fw - 1) / fw) * ((height + fh - 1) / fh) > (int64_t)QR_VIEW_MAX_WAVES)
+            return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
+    }
+    if (n_views == 0) return QR_OK;
+    { const int rc = layer_ptrs(views_dev, count_dev, t_dev, id_dev, hits_dev); if (rc != QR_OK) return rc; }
+    HIP_TRY(hipSetDevice(s->device));
+    /* one lane per pixel: 8x8 footprints at every FSAA, as qr_hit_views_async */
+    const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
+    ViewsP vp;
+    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
+    const LayerP lp = layer_params(s, k, count_dev, t_dev, id_dev, hits_dev, (uint64_t)n_views * (uint64_t)width * (uint64_t)height);
+    const f32x4 *none = nullptr;
+    /* the instance is chosen as qr_hit_views_async chooses its own */
+    if (s->divk)
+        hipLaunchKernelGGL((qr_layer_kernel<true, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
+                           vp, lp, s->lp.stats);
+    else
+        hipLaunchKernelGGL((qr_layer_kernel<true, false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
+                           vp, lp, s->lp.stats);
     HIP_TRY(hipGetLastError());
     return QR_OK;
 }

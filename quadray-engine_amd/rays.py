@@ -15,7 +15,9 @@ only where the engine's tiles hold other surfaces than its global list):
 Scene.hits / Scene.view_hits return hit records (qr_hit: position, t, normal, id, albedo, material); hit_fields splits them into
 typed views, offset_rays and reflect_rays build a host's own secondary rays from them.  Fans of many visibility rays per hit
 (ambient occlusion, sky visibility) need no rays: Scene.occlusion / view_occlusion / hit_occlusion trace a shared direction table
-(sphere_dirs) from every hit in one launch; fan_rays states what they trace, fan_bits unpacks their masks.
+(sphere_dirs) from every hit in one launch; fan_rays states what they trace, fan_bits unpacks their masks.  Scene.trace_layers /
+Scene.view_layers give the first k hits along a ray, in order, in one launch; layers_of states them as a composition of trace(),
+next_rays builds the rays that resume a layered ray where a call stopped.
 
 Whole frames from pinhole cameras do not need that detour: Scene.render_views renders them on the GPU from qr_view records
 (view_of: the snapshot's own camera; look_at: eye / target / up / field of view), at any frame size, and view_rays gives the
@@ -417,3 +419,64 @@ def sphere_dirs(n):
     phi = i * np.pi * (3.0 - np.sqrt(5.0))
     s = np.sqrt(1.0 - z * z)
     return np.stack([s * np.cos(phi), s * np.sin(phi), z], axis=1).astype(np.float32)
+
+
+# ---- hit layers (include/qrhip.h qr_layer_*_async; Scene.trace_layers, Scene.view_layers) ----
+
+def next_rays(rays, t, ids):
+    """The rays that continue behind a hit: rays float32 [N, 8], t float32 [N] and ids int32 [N] as Scene.trace answers for them
+    (or the last plane of Scene.trace_layers), numpy arrays or torch tensors on one device.  Returns a new float32 [N, 8]:
+    where ids >= 0 the same ray with tmin = t, bit for bit, no epsilon -- a hit counts when tmin < t' < tmax and the ray API
+    has no self-exclusion, so its closest hit is the NEXT surface along the ray; where the ray ended (ids < 0) tmin = tmax
+    (+inf taken as FLT_MAX): an empty interval, so that every later call answers a miss with t = tmax.  Origin, direction and
+    tmax are kept.  k1 layers, then k2 layers on next_rays(rays, t[k1 - 1], ids[k1 - 1]), are one call with k1 + k2."""
+    if rays.ndim != 2 or rays.shape[1] != 8 or "float32" not in str(rays.dtype):
+        raise ValueError(f"rays must be float32 [N, 8], got {rays.dtype} {list(rays.shape)}")
+    if tuple(t.shape) != (rays.shape[0],) or tuple(ids.shape) != (rays.shape[0],) or "float32" not in str(t.dtype):
+        raise ValueError(f"t (float32) and ids must be [N] for rays [N, 8], got {list(t.shape)} and {list(ids.shape)}")
+    flt_max = float(np.finfo(np.float32).max)
+    if isinstance(rays, np.ndarray):
+        out = rays.copy()
+        tmax = rays[:, 7]
+        end = np.where(tmax > np.float32(flt_max), np.float32(flt_max), tmax)
+        out[:, 3] = np.where(ids >= 0, t, end)
+    else:
+        import torch
+        out = rays.clone()
+        tmax = rays[:, 7]
+        end = torch.where(tmax > flt_max, torch.full_like(tmax, flt_max), tmax)
+        out[:, 3] = torch.where(ids >= 0, t, end)
+    return out
+
+
+def layers_of(trace, rays, k):
+    """What Scene.trace_layers computes, as a composition of closest-hit queries: trace is any callable with Scene.trace's
+    signature on numpy arrays -- trace(rays float32 [M, 8]) -> (t float32 [M], ids int32 [M]), a miss answered as t = tmax
+    (FLT_MAX for +inf), id = -1 -- rays float32 [N, 8] (numpy), 1 <= k.  Returns (count int32 [N], t float32 [k, N], ids int32
+    [k, N]).
+
+    Layer 0 is trace(rays); layer j + 1 is trace(next_rays(layer j's rays, t_j, ids_j)): the same ray with tmin = t_j, bit for
+    bit.  A ray ends at its first miss: from that layer on its planes hold t = tmax (FLT_MAX for +inf), id = -1 -- what trace
+    answers for next_rays' empty interval, so ended rays are not handed to trace again -- and count is the number of hits
+    found, 0..k."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    k = int(k)
+    if rays.ndim != 2 or rays.shape[1] != 8 or k < 1:
+        raise ValueError(f"layers_of needs rays [N, 8] and k >= 1, got {list(rays.shape)} and k = {k}")
+    n = rays.shape[0]
+    flt_max = np.finfo(np.float32).max
+    end = np.where(rays[:, 7] > flt_max, flt_max, rays[:, 7]).astype(np.float32)
+    t = np.tile(end, (k, 1))
+    ids = np.full((k, n), -1, dtype=np.int32)
+    cur = rays
+    alive = np.arange(n)
+    for j in range(k):
+        if len(alive) == 0:
+            break
+        tj, ij = trace(cur)
+        tj, ij = np.asarray(tj, dtype=np.float32), np.asarray(ij, dtype=np.int32)
+        t[j, alive], ids[j, alive] = tj, ij
+        hit = ij >= 0
+        cur = next_rays(cur, tj, ij)[hit]
+        alive = alive[hit]
+    return (ids >= 0).sum(axis=0).astype(np.int32), t, ids

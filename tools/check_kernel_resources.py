@@ -15,6 +15,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     168 VGPRs (128: the view instance with packet walks only);
   * an occlusion-fan instance qr_fan_kernel<SRC, DIVK, COHERENT> spills a vector register, has a private segment, or uses more
     than 168 VGPRs (128: the view instance with packet walks only and the instance that reads caller records);
+  * a hit-layer instance qr_layer_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more
+    than 168 VGPRs (128: the view instance with packet walks only);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
 usage: check_kernel_resources.py <file.s> [--print]
 """
@@ -59,6 +61,13 @@ LIMITS = {
     "13qr_fan_kernelILi1ELb1ELb1EE": (168, 0, 0),
     "13qr_fan_kernelILi1ELb0ELb1EE": (128, 0, 0),
     "13qr_fan_kernelILi2ELb1ELb0EE": (128, 0, 0),
+    # hit layers (qr_layers.hpp qr_layer_kernel<VIEW, DIVK, COHERENT>): a hit-record instance's walk and surface point in a loop over
+    # the layers, with the ray, the count and the alive flag live across it: nothing spilled, no private segment, and no more
+    # registers than the hit-record instance each one mirrors
+    "15qr_layer_kernelILb0ELb1ELb0EE": (168, 0, 0),
+    "15qr_layer_kernelILb0ELb1ELb1EE": (168, 0, 0),
+    "15qr_layer_kernelILb1ELb1ELb1EE": (168, 0, 0),
+    "15qr_layer_kernelILb1ELb0ELb1EE": (128, 0, 0),
 }
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 
