@@ -24,6 +24,14 @@
  * reference (oracle/_ref/qr_ref, built from /root/reference by oracle/Makefile)
  * for demo01-03 and test01-18; the committed fixtures under tests/golden/ are
  * those frames (tests/golden/make_golden.py is the generating script).
+ *
+ * PATH TRACER (RT_FEAT_PT, tracer.cpp:1008-1057, 1112-1136, 1168-1176, 1218-1285,
+ * 2339-2703, 3192-3198, 3428-3466, 3612-3616, 5176-5219): restated inside the same
+ * shade() / sample() / pixel(), switched by tracer_t.pt; entry point qro_render_pt.
+ * In the reference's order it is pinned bit-for-bit against the reference's own
+ * path-traced frames (tests/golden/pt, tests/golden/make_pt_golden.py,
+ * tests/test_pt_oracle.py); in the fast kernel's order (DESIGN.md 4 "Path-tracer
+ * instance", order of draws) it is what Scene.set_pt(True) frames are held to.
  */
 #include "qr_scene.h"
 
@@ -86,6 +94,10 @@ static inline int32_t cvt_near(float x)      /* cvnps: round half to even */
 /* state                                                                     */
 /* ------------------------------------------------------------------------ */
 
+/* path tracer: what the engine keeps per frame buffer (engine.cpp:2875-2893, 3670-3700): one LCG state and three
+ * colour planes per pixel sample, slot (y * frm_row + x) * samples + k (tracer.cpp:1168-1176, 5182-5188) */
+typedef struct pt_state_t { u32 *seeds; float *pl[3]; float pts_o, pts_u; float *mean; } pt_state_t;
+
 typedef struct counts_t { uint64_t primary, shadow, reflect, refract, flops; } counts_t;
 
 /*
@@ -143,9 +155,66 @@ typedef struct tracer_t
     int depth;              /* inf_DEPTH, decremented around child packets */
     int deferred;           /* shade only the final hit of a list walk (see qro_render) */
     counts_t cnt;
+    const pt_state_t *pts;  /* path tracer: the frame buffer's planes, or NULL */
+    /* path-tracer mode (RT_FEAT_PT; qro_render_pt): 0 off, 1 the reference's order of draws, 2 the fast kernel's
+     * (DESIGN.md 4 "Path-tracer instance", the numbered order of draws) */
+    int pt;
+    u32 rng;                /* this sample's LCG state (inf_PRNGS slot) */
+    uint64_t st[6];         /* roulette draws, deaths, bounces sampled, splits to reflection, to refraction, TIR skips */
+    int top;                /* inf_DEPTH of the primary context: level = top - depth (trace only) */
+    float *trace;           /* debug: (level, stage, value) per number drawn, or NULL */
+    int trace_n, trace_cap;
 } tracer_t;
 
 static void trace_list(tracer_t *T, ctx_t *c, const float *parent_loc, int head);
+
+/* ------------------------------------------------------------------------ */
+/* path tracer: generator and power series, tracer.cpp:1008-1057             */
+/* ------------------------------------------------------------------------ */
+
+#define RT_STACK_DEPTH 10   /* tracer.h:46: the roulette and the split compare inf_DEPTH with it, not with the scene's depth */
+
+enum { PT_DRAW_JITTER_H = 0, PT_DRAW_JITTER_V = 1, PT_DRAW_ROULETTE = 2, PT_DRAW_BOUNCE_R = 3, PT_DRAW_BOUNCE_PHI = 4,
+       PT_DRAW_SPLIT = 5 };
+
+/* GET_RANDOM 1013-1027, LCG24 (engine.cpp:867-873): the state advances, bits 8..31 / 2^24 are the number.  A lane whose
+ * TMASK is empty neither draws nor stores (mmvpx_st): the callers below draw only for live lanes */
+static float pt_random(tracer_t *T, int stage)
+{
+    float r;
+    T->rng = T->rng * 214013u + 2531011u;
+    r = (float)(int32_t)((T->rng >> 8) & 0xFFFFFFu);
+    r = r / ((float)(int32_t)0xFFFFFF + 1.0f);
+    if (T->trace != NULL && T->trace_n < T->trace_cap)
+    {
+        float *o = T->trace + 3 * T->trace_n++;
+        o[0] = (float)(T->top - T->depth); o[1] = (float)stage; o[2] = r;
+    }
+    return r;
+}
+
+/* sinps_rr / cosps_rr 1029-1057.  fmaps3ld is ONE rounding on the targets the pinned reference binary is built for
+ * (vfmadd231ps, RT_SIMD_COMPAT_FMA 1): fmaf, the only fused operations in this file.  Constants engine.cpp:894-900. */
+static float pt_sin(float xs)
+{
+    float t1 = xs * xs, xd = xs;
+    xs = xd * t1;
+    xd = fmaf(xs, (float)-0.1666666666666666666666666666666666666666666, xd); xs = xs * t1;
+    xd = fmaf(xs, (float)+0.0083333333333333333333333333333333333333333, xd); xs = xs * t1;
+    xd = fmaf(xs, (float)-0.0001984126984126984126984126984126984126984, xd); xs = xs * t1;
+    xd = fmaf(xs, (float)+0.0000027557319223985890652557319223985890652, xd);
+    return xd;
+}
+static float pt_cos(float xs)
+{
+    float t1 = xs * xs, xd = 1.0f;
+    xs = xd * t1;
+    xd = fmaf(xs, -0.5f, xd); xs = xs * t1;
+    xd = fmaf(xs, (float)+0.0416666666666666666666666666666666666666666, xd); xs = xs * t1;
+    xd = fmaf(xs, (float)-0.0013888888888888888888888888888888888888888, xd); xs = xs * t1;
+    xd = fmaf(xs, (float)+0.0000248015873015873015873015873015873015873, xd);
+    return xd;
+}
 
 /* ------------------------------------------------------------------------ */
 /* helpers on surfaces                                                       */
@@ -398,6 +467,10 @@ static int shade(tracer_t *T, ctx_t *c, int si, int side, int kind)
     const qr_material *mt;
     int props;
     float x0, x1, x2, x3, x4, x5, x6, x7;
+    /* path tracer: ctx_F_PRB (the roulette's survivors, all ones otherwise), ctx_M_RFL; kernel order: the pending bounce */
+    u32 f_prb = 0xFFFFFFFFu, m_rfl;
+    int pt_bounce = 0;
+    float pt_dir[3] = { 0.0f, 0.0f, 0.0f }, pt_w[3] = { 0.0f, 0.0f, 0.0f };
 
     /* FETCH_PROP 597-604 */
     c->local_flg = side | s->props[side];
@@ -530,6 +603,102 @@ static int shade(tracer_t *T, ctx_t *c, int si, int side, int kind)
         }
     }
 
+    /* ---------------- path tracer: 2339-2703 (instead of the lights) ---------------- */
+    if (T->pt)
+    {
+        float b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;
+        if (props & QR_PROP_DIFFUSE)
+        {
+            /* Russian roulette 2352-2396: from inf_DEPTH <= RT_STACK_DEPTH - 5 on */
+            if (T->depth <= RT_STACK_DEPTH - 5)
+            {
+                x4 = c->tex[0];
+                x4 = x4 > c->tex[1] ? x4 : c->tex[1];       /* maxps */
+                x4 = x4 > c->tex[2] ? x4 : c->tex[2];
+                x0 = pt_random(T, PT_DRAW_ROULETTE);
+                T->st[0]++;
+                f_prb &= clt(x0, x4);
+                if (f_prb == 0) T->st[1]++;                  /* PT_chk -> PT_mix */
+                else
+                {
+                    x5 = 1.0f / x4;
+                    c->tex[0] = c->tex[0] * x5; c->tex[1] = c->tex[1] * x5; c->tex[2] = c->tex[2] * x5;
+                }
+            }
+            if (f_prb != 0)
+            {
+                float u1, u2, u3, v1, v2, v3;
+                /* PT_cnt 2398-2534: basis u = normalize(nrm x ray), v = nrm x u; cosine-weighted direction */
+                x1 = c->nrm[0]; x2 = c->nrm[1]; x3 = c->nrm[2];
+                x4 = c->ray[0]; x5 = c->ray[1]; x6 = c->ray[2];
+                x0 = x2 * x6; x7 = x3 * x5; u1 = x0 - x7;
+                x0 = x3 * x4; x7 = x1 * x6; u2 = x0 - x7;
+                x0 = x1 * x5; x7 = x2 * x4; u3 = x0 - x7;
+                x4 = u1; x5 = u2; x6 = u3;
+                x1 = x4 * x4; x2 = x5 * x5; x3 = x6 * x6;
+                x1 = x1 + x2; x1 = x1 + x3;
+                x0 = rsq(x1);
+                x4 = x4 * x0; x5 = x5 * x0; x6 = x6 * x0;
+                u1 = x4; u2 = x5; u3 = x6;
+                x1 = c->nrm[0]; x2 = c->nrm[1]; x3 = c->nrm[2];
+                x0 = x2 * x6; x7 = x3 * x5; v1 = x0 - x7;
+                x0 = x3 * x4; x7 = x1 * x6; v2 = x0 - x7;
+                x0 = x1 * x5; x7 = x2 * x4; v3 = x0 - x7;
+                x0 = pt_random(T, PT_DRAW_BOUNCE_R);
+                x6 = x0; x0 = 1.0f - x6;
+                x6 = sqrtf(x6); x0 = sqrtf(x0);
+                x1 = x1 * x0; x2 = x2 * x0; x3 = x3 * x0;
+                x0 = pt_random(T, PT_DRAW_BOUNCE_PHI);
+                T->st[2]++;
+                x0 = x0 + x0;
+                x0 = x0 * (float)3.14159265358979323846;    /* mat_GPC10 = RT_PI, object.cpp:4130 */
+                x0 = x0 - (float)3.14159265358979323846;
+                x4 = pt_cos(x0); x4 = x4 * x6;
+                x5 = u1 * x4; x1 = x1 + x5;
+                x5 = u2 * x4; x2 = x2 + x5;
+                x5 = u3 * x4; x3 = x3 + x5;
+                x4 = pt_sin(x0); x4 = x4 * x6;
+                x5 = v1 * x4; x1 = x1 + x5;
+                x5 = v2 * x4; x2 = x2 + x5;
+                x5 = v3 * x4; x3 = x3 + x5;
+                c->nw[0] = x1; c->nw[1] = x2; c->nw[2] = x3;
+                if (T->pt == 2)
+                {
+                    /* kernel order (order of draws, item 5): the bounce's subtree comes LAST; its weight is
+                     * kept as (tex * l_dff), times the TR_mix factor once that is known */
+                    pt_bounce = 1;
+                    pt_dir[0] = x1; pt_dir[1] = x2; pt_dir[2] = x3;
+                    pt_w[0] = c->tex[0] * mt->l_dff; pt_w[1] = c->tex[1] * mt->l_dff; pt_w[2] = c->tex[2] * mt->l_dff;
+                }
+                else if (T->depth != 0)
+                {
+                    /* 2548-2609: the bounce's subtree at once, tag 4, the surface's own side list */
+                    ctx_t ch;
+                    memset(&ch, 0, sizeof(ch));
+                    ch.param_flg = c->local_flg;            /* | RT_FLAG_PASS_BACK (0) */
+                    ch.param_obj = si;
+                    ch.param_tag = 4;
+                    ch.wmask = 0xFFFFFFFFu;
+                    ch.t_buf = fr->t_max;
+                    ch.t_min = 0.0f;
+                    ch.org[0] = c->hit[0]; ch.org[1] = c->hit[1]; ch.org[2] = c->hit[2];
+                    ch.ray[0] = c->nw[0];  ch.ray[1] = c->nw[1];  ch.ray[2] = c->nw[2];
+                    ch.local_obj = QR_NULL; ch.pend_si = QR_NULL;
+                    ch.hit_id = -1;
+                    T->depth -= 1;
+                    trace_list(T, &ch, &c->nrm[3], s->lst[side * 2 + 1]);
+                    T->depth += 1;
+                    b1 = ch.col[0] * mt->l_dff; b2 = ch.col[1] * mt->l_dff; b3 = ch.col[2] * mt->l_dff;
+                    b1 = b1 * c->tex[0]; b2 = b2 * c->tex[1]; b3 = b3 * c->tex[2];
+                }
+            }
+        }
+        /* PT_mix 2685-2699: self-emission */
+        c->col[0] = b1 + mt->emis[0];
+        c->col[1] = b2 + mt->emis[1];
+        c->col[2] = b3 + mt->emis[2];
+    }
+    else
     /* ---------------- lights: 2709-3179 ---------------- */
     if (props & QR_PROP_LIGHT)
     {
@@ -700,10 +869,12 @@ static int shade(tracer_t *T, ctx_t *c, int si, int side, int kind)
     /* ---------------- transparency: 3185-3598 ---------------- */
     {
         float c_trn = mt->c_trn, c_rfl = mt->c_rfl;     /* ctx_C_TRN / ctx_C_RFL */
-        u32 m_trn = 0xFFFFFFFFu;
+        u32 m_trn;
         float r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;         /* Xmm1..3 into TR_mix */
 
-        if (!(props & QR_PROP_OPAQUE))
+        /* 3192-3198: ctx_F_PRB is the lane mask of this block and of the reflections (all ones outside the path tracer) */
+        m_trn = f_prb; m_rfl = f_prb;
+        if (f_prb != 0 && !(props & QR_PROP_OPAQUE))
         {
             int do_rfi = (props & QR_PROP_REFRACT) || (props & QR_PROP_FRESNEL);
             int tir_all = 0;
@@ -735,6 +906,7 @@ static int shade(tracer_t *T, ctx_t *c, int si, int side, int kind)
                         c_trn = 0.0f;
                         c_rfl = mt->c_rfl + mt->c_trn;
                         tir_all = 1;
+                        if (T->pt && T->depth <= RT_STACK_DEPTH - 2) T->st[5]++;     /* no split, no number drawn */
                     }
                 }
                 if (!tir_all)
@@ -784,6 +956,29 @@ static int shade(tracer_t *T, ctx_t *c, int si, int side, int kind)
                     f = u2f(f2u(f) | u);
                     c_trn = mt->c_trn - f;
                     c_rfl = mt->c_rfl + f;
+                    /* Fresnel split 3428-3466: from inf_DEPTH <= RT_STACK_DEPTH - 2 on ONE of the two children is followed,
+                     * the reflection with probability P = 0.25 + 0.5 c_rfl / (c_trn + c_rfl), weights over the probabilities */
+                    if (T->pt && T->depth <= RT_STACK_DEPTH - 2)
+                    {
+                        x4 = c_trn; x5 = c_rfl;
+                        x0 = pt_random(T, PT_DRAW_SPLIT);
+                        x6 = x5;
+                        x7 = x4 + x5;
+                        x5 = x5 / x7;
+                        x7 = 0.5f;
+                        x5 = x5 * x7;
+                        x7 = x7 * x7;
+                        x7 = x7 + x5;
+                        m_trn &= cge(x0, x7);
+                        m_rfl &= clt(x0, x7);
+                        if (m_rfl != 0) T->st[3]++; else T->st[4]++;
+                        x5 = x4;
+                        x2 = 1.0f - x7;
+                        x5 = x5 / x2;
+                        x6 = x6 / x7;
+                        c_trn = fand(x5, m_trn);
+                        c_rfl = fand(x6, m_rfl);
+                    }
                 }
                 /* TR_frn 3468-3552 */
                 if (m_trn != 0 && T->depth != 0)
@@ -820,10 +1015,10 @@ static int shade(tracer_t *T, ctx_t *c, int si, int side, int kind)
         c->col[2] = r3 + c->col[2] * x0;
 
         /* ---------------- reflections: 3604-3930 ---------------- */
-        if ((props & QR_PROP_REFLECT) ||
-            (!(props & QR_PROP_OPAQUE) && (props & QR_PROP_FRESNEL)))
+        if (m_rfl != 0 && ((props & QR_PROP_REFLECT) ||
+            (!(props & QR_PROP_OPAQUE) && (props & QR_PROP_FRESNEL))))
         {
-            /* RF_ini */
+            /* RF_ini; 3612-3616: nothing for a lane outside ctx_M_RFL */
             FL(T, 24);
             x1 = c->ray[0]; x4 = c->nrm[0]; x7 = x1 * x1; x0 = x7;
             x2 = c->ray[1]; x5 = c->nrm[1]; x7 = x2 * x2; x0 = x0 + x7;
@@ -916,6 +1111,35 @@ static int shade(tracer_t *T, ctx_t *c, int si, int side, int kind)
             c->col[0] = r1 + c->col[0];
             c->col[1] = r2 + c->col[1];
             c->col[2] = r3 + c->col[2];
+        }
+
+        /* kernel order, item 5: the bounce's subtree after the node's other children; the node's colour is linear in
+         * what the bounce returns, weight (tex * l_dff) * TR_mix factor */
+        if (pt_bounce && T->depth != 0)
+        {
+            ctx_t ch;
+            x0 = 1.0f - mt->c_trn;
+            x0 = x0 - mt->c_rfl;
+            x0 = fand(x0, cle(0.0f, x0));
+            memset(&ch, 0, sizeof(ch));
+            ch.param_flg = c->local_flg;
+            ch.param_obj = si;
+            ch.param_tag = 4;
+            ch.wmask = 0xFFFFFFFFu;
+            ch.t_buf = fr->t_max;
+            ch.t_min = 0.0f;
+            ch.org[0] = c->hit[0]; ch.org[1] = c->hit[1]; ch.org[2] = c->hit[2];
+            ch.ray[0] = pt_dir[0]; ch.ray[1] = pt_dir[1]; ch.ray[2] = pt_dir[2];
+            ch.local_obj = QR_NULL; ch.pend_si = QR_NULL;
+            ch.hit_id = -1;
+            T->depth -= 1;
+            trace_list(T, &ch, &c->nrm[3], s->lst[side * 2 + 1]);
+            T->depth += 1;
+            x1 = pt_w[0] * x0; x2 = pt_w[1] * x0; x3 = pt_w[2] * x0;
+            x1 = ch.col[0] * x1; x2 = ch.col[1] * x2; x3 = ch.col[2] * x3;
+            c->col[0] = c->col[0] + x1;
+            c->col[1] = c->col[1] + x2;
+            c->col[2] = c->col[2] + x3;
         }
     }
     return 0;
@@ -1221,6 +1445,7 @@ static void sample(tracer_t *T, int x, int y, int k, float col[3], int *hit_id)
     const qr_frame *fr = v->frame;
     ctx_t c;
     float hs, vs, x1, x2, x3, x4, x5, x6;
+    float hr = 0.0f, vr = 0.0f;                     /* hor_r / ver_r, 1215-1216 */
     int ai = 0, tile;
 
     if (fr->fsaa == 1) ai = (x & 1) * 2 + k;        /* engine.cpp:3489-3510 */
@@ -1238,10 +1463,28 @@ static void sample(tracer_t *T, int x, int y, int k, float col[3], int *hit_id)
     c.pend_si = QR_NULL;
     c.hit_id = -1;
 
+    if (T->pt)
+    {
+        /* tent-filter jitter of the sample position 1218-1285: two numbers, horizontal first; halved, and once more
+         * under FSAA */
+        int j;
+        for (j = 0; j < 2; j++)
+        {
+            float u = pt_random(T, j == 0 ? PT_DRAW_JITTER_H : PT_DRAW_JITTER_V), a, b;
+            u = u + u;
+            a = sqrtf(u); a = a - 1.0f;
+            b = 2.0f - u; b = sqrtf(b); b = 1.0f - b;
+            a = fsel(clt(u, 1.0f), a, b);
+            a = a * 0.5f;
+            if (fr->fsaa != 0) a = a * 0.5f;
+            if (j == 0) hr = a; else vr = a;
+        }
+    }
+
     /* primary ray 1287-1322 */
     FL(T, 16);
-    hs = (float)x + fr->hor_a[ai]; hs = hs + 0.0f;
-    vs = (float)y + fr->ver_a[ai]; vs = vs + 0.0f;
+    hs = (float)x + fr->hor_a[ai]; hs = hs + hr;
+    vs = (float)y + fr->ver_a[ai]; vs = vs + vr;
     x1 = fr->hor[0] * hs; x2 = fr->hor[1] * hs; x3 = fr->hor[2] * hs;
     x4 = fr->ver[0] * vs; x5 = fr->ver[1] * vs; x6 = fr->ver[2] * vs;
     x1 = x1 + x4; x2 = x2 + x5; x3 = x3 + x6;
@@ -1270,8 +1513,26 @@ static u32 pixel(tracer_t *T, int x, int y, int *hit_id)
     for (k = 0; k < ns; k++)
     {
         int h;
+        size_t slot = 0;
+        if (T->pt)
+        {
+            slot = ((size_t)y * (size_t)fr->frm_row + (size_t)x) * (size_t)ns + (size_t)k;
+            T->rng = T->pts->seeds[slot];
+        }
         sample(T, x, y, k, s[k], &h);
         if (k == 0) id = h;
+        if (T->pt)
+        {
+            /* XX_end 5176-5219: the sample's state goes back, the planes keep the running mean, the frame shows it */
+            T->pts->seeds[slot] = T->rng;
+            for (ch = 0; ch < 3; ch++)
+            {
+                float a = s[k][ch] * T->pts->pts_o, b = T->pts->pl[ch][slot] * T->pts->pts_u;
+                a = a + b;
+                T->pts->pl[ch][slot] = a;
+                s[k][ch] = a;
+            }
+        }
         for (ch = 0; ch < 3; ch++) s[k][ch] = clamp1(s[k][ch]);
     }
     FL(T, 6 + 2 * fr->fsaa);
@@ -1287,6 +1548,8 @@ static u32 pixel(tracer_t *T, int x, int y, int *hit_id)
             col[ch] = p0 * 0.5f + p1 * 0.5f;
         }
     }
+    if (T->pt && T->pts->mean != NULL)
+        for (ch = 0; ch < 3; ch++) T->pts->mean[((size_t)y * (size_t)fr->frm_w + (size_t)x) * 3 + (size_t)ch] = col[ch];
     /* FRAME_SIMD 988-1006 */
     for (ch = 0; ch < 3; ch++)
     {
@@ -1341,8 +1604,8 @@ int qro_render2(const void *blob, uint64_t size, uint32_t *frame, int32_t *ids,
         tracer_t T;
         int x;
         if ((y % thnum) != index) continue;
+        memset(&T, 0, sizeof(T));
         T.s = &S; T.depth = S.depth; T.deferred = deferred;
-        memset(&T.cnt, 0, sizeof(T.cnt));
         for (x = 0; x < w; x++)
         {
             int id;
@@ -1395,8 +1658,8 @@ int qro_trace_rays(const void *blob, uint64_t size, const float *rays, int64_t n
         const float *q = rays + 8 * i;
         tracer_t T;
         ctx_t c;
+        memset(&T, 0, sizeof(T));
         T.s = &S; T.depth = mode == 2 ? S.depth : 0; T.deferred = mode == 0;
-        memset(&T.cnt, 0, sizeof(T.cnt));
         memset(&c, 0, sizeof(c));
         c.t_buf = q[7] > FLT_MAX ? FLT_MAX : q[7];
         c.t_min = q[3];
@@ -1419,6 +1682,126 @@ int qro_trace_rays(const void *blob, uint64_t size, const float *rays, int64_t n
         }
     }
     return 0;
+}
+
+/*
+ * Path tracer (RT_FEAT_PT): `n_frames` accumulated frames of the snapshot from fresh seeds (rt_Scene::reset_pseed,
+ * engine.cpp:3651-3685: a 48-bit LCG walks over the slots, each keeps the low 32 bits) and zeroed colour planes;
+ * frame_out receives the last packed frame.  depth < 0 keeps the snapshot's.
+ *   order 0, reference: every depth-test winner is shaded at once -- stage 1 (roulette, bounce direction), the bounce's
+ *                       subtree, the Fresnel-split draw, the refraction subtree, the reflection subtree; a later, closer
+ *                       hit shades again and overwrites.  Pinned to the reference's own frames (tests/golden/pt).
+ *   order 1, kernel:    numbers are drawn for the final hit of a walk only, children in the order of DESIGN.md 4
+ *                       "Path-tracer instance", the numbered order of draws.
+ * Streams are per sample, so rows run in parallel and the result does not depend on `threads`.
+ * mean_out (optional) float[h][w][3]: the pixel's linear colour after the FSAA reduce, before gamma and packing.
+ * stats_out (optional) uint64[6], over all samples and frames: roulette draws, roulette deaths, bounce directions
+ * sampled, Fresnel splits resolved to reflection, to refraction, splits skipped by total inner reflection.
+ */
+static int pt_alloc(const scene_t *S, pt_state_t *P)
+{
+    const size_t n = (size_t)S->v.frame->frm_row * (size_t)S->v.frame->frm_h * ((size_t)1 << S->v.frame->fsaa);
+    uint64_t seed = 1;
+    size_t k;
+    memset(P, 0, sizeof(*P));
+    if (S->v.frame->frm_row < S->v.frame->frm_w || n == 0) return -1;
+    P->seeds = (u32 *)malloc(n * sizeof(u32));
+    P->pl[0] = (float *)calloc(3 * n, sizeof(float));
+    if (P->seeds == NULL || P->pl[0] == NULL) { free(P->seeds); free(P->pl[0]); return -2; }
+    P->pl[1] = P->pl[0] + n; P->pl[2] = P->pl[0] + 2 * n;
+    for (k = 0; k < n; k++)
+    {
+        seed = (seed * 25214903917ull + 11ull) & 0x0000FFFFFFFFFFFFull;
+        P->seeds[k] = (u32)seed;
+    }
+    return 0;
+}
+
+int qro_render_pt(const void *blob, uint64_t size, int n_frames, int depth, int order, int threads,
+                  uint32_t *frame_out, float *mean_out, uint64_t *stats_out)
+{
+    scene_t S;
+    pt_state_t P;
+    int rc = qr_scene_view_init(&S.v, blob, size);
+    int y, w, h, f;
+    float pts_c = 0.0f;
+    uint64_t s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
+    if (rc != 0) return rc;
+    if (n_frames < 1 || order < 0 || order > 1) return -1;
+    S.depth = depth >= 0 ? depth : S.v.frame->depth;
+    w = S.v.frame->frm_w; h = S.v.frame->frm_h;
+    rc = pt_alloc(&S, &P);
+    if (rc != 0) return rc;
+    P.mean = mean_out;
+    (void)threads;
+#ifdef _OPENMP
+    if (threads > 0) omp_set_num_threads(threads);
+#endif
+    for (f = 0; f < n_frames; f++)
+    {
+        /* 1112-1136: sample count, its reciprocal and the complement */
+        pts_c = pts_c + 1.0f;
+        P.pts_o = 1.0f / pts_c;
+        P.pts_u = 1.0f - P.pts_o;
+#pragma omp parallel for schedule(dynamic, 4) reduction(+:s0,s1,s2,s3,s4,s5)
+        for (y = 0; y < h; y++)
+        {
+            tracer_t T;
+            int x;
+            memset(&T, 0, sizeof(T));
+            T.s = &S; T.depth = S.depth; T.top = S.depth; T.deferred = order == 1; T.pt = order == 1 ? 2 : 1; T.pts = &P;
+            for (x = 0; x < w; x++)
+            {
+                int id;
+                frame_out[(size_t)y * w + x] = pixel(&T, x, y, &id);
+            }
+            s0 += T.st[0]; s1 += T.st[1]; s2 += T.st[2]; s3 += T.st[3]; s4 += T.st[4]; s5 += T.st[5];
+        }
+    }
+    if (stats_out) { stats_out[0] = s0; stats_out[1] = s1; stats_out[2] = s2; stats_out[3] = s3; stats_out[4] = s4; stats_out[5] = s5; }
+    free(P.seeds); free(P.pl[0]);
+    return 0;
+}
+
+/*
+ * Debug aid: the numbers ONE sample (pixel x, y, sub-sample k) draws over `n_frames` frames, as (level, stage, value)
+ * triples in drawing order -- level = recursion level of the context that drew, stage = PT_DRAW_* (0 / 1 jitter,
+ * 2 roulette, 3 / 4 bounce, 5 Fresnel split).  Only that sample is rendered: streams are per sample.  Returns the number
+ * of triples (at most `cap` are written), < 0 on error.  col_out (optional) float[3]: the sample's running mean.
+ */
+int qro_pt_trace_sample(const void *blob, uint64_t size, int n_frames, int depth, int order, int x, int y, int k,
+                        float *out, int cap, float *col_out)
+{
+    scene_t S;
+    pt_state_t P;
+    tracer_t T;
+    int rc = qr_scene_view_init(&S.v, blob, size);
+    int f, ch, ns;
+    size_t slot;
+    float pts_c = 0.0f, mean[3] = { 0.0f, 0.0f, 0.0f };
+    if (rc != 0) return rc;
+    ns = 1 << S.v.frame->fsaa;
+    if (n_frames < 1 || order < 0 || order > 1 || cap < 0) return -1;
+    if (x < 0 || x >= S.v.frame->frm_w || y < 0 || y >= S.v.frame->frm_h || k < 0 || k >= ns) return -1;
+    S.depth = depth >= 0 ? depth : S.v.frame->depth;
+    rc = pt_alloc(&S, &P);
+    if (rc != 0) return rc;
+    slot = ((size_t)y * (size_t)S.v.frame->frm_row + (size_t)x) * (size_t)ns + (size_t)k;
+    memset(&T, 0, sizeof(T));
+    T.s = &S; T.depth = S.depth; T.top = S.depth; T.deferred = order == 1; T.pt = order == 1 ? 2 : 1; T.pts = &P;
+    T.rng = P.seeds[slot];
+    T.trace = out; T.trace_cap = out != NULL ? cap : 0;
+    for (f = 0; f < n_frames; f++)
+    {
+        float col[3];
+        int id;
+        pts_c = pts_c + 1.0f;
+        sample(&T, x, y, k, col, &id);
+        for (ch = 0; ch < 3; ch++) mean[ch] = col[ch] * (1.0f / pts_c) + mean[ch] * (1.0f - 1.0f / pts_c);
+    }
+    if (col_out) { col_out[0] = mean[0]; col_out[1] = mean[1]; col_out[2] = mean[2]; }
+    free(P.seeds); free(P.pl[0]);
+    return T.trace_n;
 }
 
 int qro_info(const void *blob, uint64_t size, int32_t out[8])

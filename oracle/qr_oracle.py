@@ -31,6 +31,13 @@ def lib():
                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p]
         L.qro_trace_rays.restype = ctypes.c_int
+        L.qro_render_pt.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.qro_render_pt.restype = ctypes.c_int
+        L.qro_pt_trace_sample.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                          ctypes.c_void_p]
+        L.qro_pt_trace_sample.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -95,3 +102,46 @@ def trace_rays(blob, rays, mode, depth=None, threads=0):
     if mode == "occluded":
         return occ.astype(bool)
     return rgb, ids
+
+
+_PT_ORDERS = {"reference": 0, "kernel": 1}
+PT_STATS = ("roulette_draws", "roulette_deaths", "bounces", "split_reflect", "split_refract", "split_tir_skipped")
+PT_STAGES = ("jitter_h", "jitter_v", "roulette", "bounce_r", "bounce_phi", "split")
+
+
+def render_pt(blob, frames, depth=-1, order="reference", threads=0, want_mean=False, want_stats=False):
+    """Path tracer on the CPU (qro_render_pt): `frames` accumulated frames from fresh seeds, the last packed frame.
+    order "reference": every depth-test winner is shaded at once, as the reference does (pinned to tests/golden/pt);
+    order "kernel": numbers are drawn for the final hit of a walk only, children in the fast kernel's order
+    ("Path-tracer instance").  The result does not depend on `threads`.
+    Returns the frame uint32 [h, w]; with want_mean / want_stats a tuple (frame[, mean float32 [h, w, 3]][, stats dict
+    with the keys PT_STATS, counted over all samples and frames])."""
+    i = info(blob)
+    w, h = i["w"], i["h"]
+    frame = np.zeros((h, w), dtype=np.uint32)
+    mean = np.zeros((h, w, 3), dtype=np.float32) if want_mean else None
+    stats = (ctypes.c_uint64 * 6)()
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    rc = lib().qro_render_pt(buf, len(blob), int(frames), int(depth), _PT_ORDERS[order], int(threads), frame.ctypes.data,
+                             mean.ctypes.data if want_mean else None, stats)
+    if rc != 0:
+        raise RuntimeError(f"qro_render_pt rc={rc}")
+    out = [frame]
+    if want_mean:
+        out.append(mean)
+    if want_stats:
+        out.append(dict(zip(PT_STATS, (int(v) for v in stats))))
+    return frame if len(out) == 1 else tuple(out)
+
+
+def pt_trace_sample(blob, frames, x, y, k=0, depth=-1, order="kernel", cap=4096):
+    """Debug aid (qro_pt_trace_sample): the numbers one sample draws over `frames` frames, in drawing order, as a list of
+    (level, stage name, value), and the sample's running-mean colour float32 [3]."""
+    out = np.zeros((cap, 3), dtype=np.float32)
+    col = np.zeros(3, dtype=np.float32)
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    n = lib().qro_pt_trace_sample(buf, len(blob), int(frames), int(depth), _PT_ORDERS[order], int(x), int(y), int(k),
+                                  out.ctypes.data, cap, col.ctypes.data)
+    if n < 0:
+        raise RuntimeError(f"qro_pt_trace_sample rc={n}")
+    return [(int(l), PT_STAGES[int(s)], float(v)) for l, s, v in out[:n]], col

@@ -590,7 +590,9 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
             {
                 const bool can_spawn = (depth - sp) != 0;
                 /* PT: one more flag in front of the surface index: the node has a diffuse bounce to follow LAST (the
-                 * node's colour is linear in its children: rfl c_rfl + trn c_trn + x0 (bounce l_dff tex + emission)) */
+                 * node's colour is linear in its children: rfl c_rfl + trn c_trn + x0 (bounce l_dff tex + emission)).
+                 * Children and colour association: DESIGN.md 4 "Path-tracer instance", order of draws, items 4 and 5,
+                 * which the oracle's kernel order (qro_render_pt) restates */
                 const bool has_pt = PT && o.want_pt && can_spawn;
                 const int meta = PT ? ((hsi << 5) | (has_pt ? 16 : 0) | (h.side << 3) | (o.want_rf ? 4 : 0))
                                     : ((hsi << 4) | (h.side << 3) | (o.want_rf ? 4 : 0));

@@ -329,7 +329,9 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
     if constexpr (PT)
     {
         /* path tracer, tracer.cpp:2339-2690: no light loop; the local colour is the material's emission, a diffuse
-         * surface samples one bounce over the cosine-weighted hemisphere */
+         * surface samples one bounce over the cosine-weighted hemisphere.  With pt_stage 0 the numbers of this call come in
+         * the order of DESIGN.md 4 "Path-tracer instance", order of draws, item 3: roulette, bounce radius and angle here,
+         * the Fresnel split further down; the oracle's kernel order (qro_render_pt) restates that list */
         le = 0;
         col = {0, 0, 0};
         if (act)

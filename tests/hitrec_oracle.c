@@ -47,8 +47,8 @@ int qrh_hit_rays(const void *blob, uint64_t size, const float *rays, int64_t n, 
         hitrec_t *o = out + i;
         tracer_t T;
         ctx_t c;
+        memset(&T, 0, sizeof(T));       /* path-tracer mode off (T.pt) */
         T.s = &S; T.depth = 0; T.deferred = 1;
-        memset(&T.cnt, 0, sizeof(T.cnt));
         memset(&c, 0, sizeof(c));
         c.t_buf = q[7] > FLT_MAX ? FLT_MAX : q[7];
         c.t_min = q[3];
