@@ -393,6 +393,50 @@ int qr_render_views_mean_async(qr_device_scene *scn, const qr_view *views_dev, i
                                float *sum_dev, uint32_t *frame_dev, float scale, uint32_t flags, void *stream);
 
 /*
+ * Path-traced views: progressive path-traced frames of the resident scene from caller-supplied cameras, at any frame size,
+ * several in one launch -- a free camera, a stereo pair, a cube-map light probe or a thumbnail of the path-traced picture.
+ * What the engine keeps per frame buffer in path-tracer mode (qr_scene_set_pt: one generator state and three running-mean
+ * colour planes per pixel sample) lives here in memory the CALLER owns, one block per view; a launch adds `samples` more
+ * samples to every pixel sample of every view and writes the packed running-mean frames.
+ *   - After qr_pt_views_reset and N accumulated samples, view j holds exactly what qr_scene_set_pt(scn, 1) followed by N calls
+ *     of qr_render_async gives on the snapshot whose camera is view j and whose frm_w = frm_row = width, frm_h = height: the
+ *     tent-filter jitter, the order of draws, the bounces, and the running mean  col * o + mean * u  with  o = 1.0f / (float)n,
+ *     u = 1.0f - o  for sample number n (1-based, counted from the reset), never fused.
+ *   - Seeds: qr_pt_views_reset fills the seed plane of EVERY view as rt_Scene::reset_pseed fills a frame's (a 48-bit LCG
+ *     walks over the slots from seed 1, each slot keeps the low 32 bits), so all views of a state start from the same
+ *     numbers: by definition, a view is a snapshot of its own.  Views with decorrelated noise: edit the seed planes.
+ *   - The state, QR_PT_VIEWS_STATE_WORDS planes of 32-bit words per view:
+ *         state[view][plane][slot],  slot = (y * width + x) * samples_per_pixel + k,  slots = width * height * samples_per_pixel
+ *     plane 0: uint32 generator states; planes 1, 2, 3: float32 running means of r, g, b (linear, unclamped).
+ *     samples_per_pixel is 1, 2 or 4 (the resident frame's FSAA).  qr_pt_views_state_bytes gives the size (n_views * 4 * slots *
+ *     4 bytes).  The state and the number of samples in it are all there is: a copy of the bytes, continued with the same
+ *     calls, gives the same bits (checkpoints), and `samples = a + b` gives the bits of two launches with a, then b.
+ *   - done: the number of samples the state already holds (0 after a reset); the caller keeps it.  samples: 1 ..
+ *     QR_PT_VIEWS_MAX_SAMPLES, all in ONE launch: a wave loops over the samples of its footprint with the generator states and
+ *     the means on chip, and reads and writes the state once.  done >= 0 and done + samples < 2^24.
+ *   - The first hit of the primary ray follows qr_render_views_async (the ray-query list, QR_UPLOAD_RAY_QUERIES, the view's
+ *     t_min / t_max); everything after it is the path tracer's.  FSAA, gamma, clamp and mask are the resident frame's, the depth
+ *     is the scene's at the time of the call (qr_scene_set_depth).
+ *   - frames_dev: required, uint32 [n_views][height][width], the packed running mean.  mean_dev (NULL = not wanted): float32
+ *     [n_views][height][width][3], the pixel's linear colour after clamp1 and the FSAA reduce, before gamma and packing.
+ *   - Independent of the scene's own path-tracer mode: works whether qr_scene_set_pt is on or off, and never touches the
+ *     scene's seed and colour planes or its frame counter.  A snapshot captured outside path-tracer mode has no emitters.
+ *   - Limits as qr_render_views_async's (QR_VIEW_MAX_DIM, QR_VIEW_MAX_VIEWS, QR_VIEW_MAX_WAVES), and n_views * slots at most
+ *     2^30.  A size or count outside them, unknown flags (none defined), a null or misaligned (views 16, others 4 bytes)
+ *     pointer, samples or done outside their ranges give QR_ERR_ARG, a scene without ray-query list QR_ERR_UNSUP; a refused
+ *     call launches nothing and changes nothing.  n_views == 0 returns QR_OK without a launch.
+ *   - qr_pt_views_reset is SYNCHRONOUS, like qr_scene_set_pt: it waits for the device, fills the state and returns when it is
+ *     filled.  qr_pt_views_async is asynchronous on `stream`, on the scene's own device; no hidden copy.
+ */
+#define QR_PT_VIEWS_MAX_SAMPLES 512     /* samples of one qr_pt_views_async launch */
+#define QR_PT_VIEWS_STATE_WORDS 4       /* 32-bit planes per view: generator state, mean r, g, b */
+int qr_pt_views_state_bytes(qr_device_scene *scn, int n_views, int width, int height, uint64_t *bytes_out);
+int qr_pt_views_reset(qr_device_scene *scn, int n_views, int width, int height, void *state_dev);
+int qr_pt_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
+                      void *state_dev, int done, int samples, uint32_t *frames_dev, float *mean_dev,
+                      uint32_t flags, void *stream);
+
+/*
  * Hit records: the closest hit of a ray AND the surface point the renderer would shade there -- hit point, normal, texture
  * colour, material.  What a host needs to bounce, reflect, offset or cosine-weight its own secondary rays (AO, light probes,
  * path tracing outside the renderer), and, per pixel of a camera, a G-buffer (position, normal, albedo, ids) for deferred passes

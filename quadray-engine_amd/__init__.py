@@ -21,7 +21,8 @@ ABI_SYMBOLS = [
     "qr_scene_upload", "qr_scene_upload_ex", "qr_program_stats", "qr_program_stats_ex", "qr_snapshot_build_lists_c", "qr_scene_destroy", "qr_scene_get_info", "qr_scene_set_depth", "qr_scene_set_pt",
     "qr_scene_set_rows", "qr_scene_set_tile_rows", "qr_render_async", "qr_render_multi_async", "qr_render_ids_async",
     "qr_render_count", "qr_render_host", "qr_render_timed", "qr_trace_rays_async", "qr_occluded_async",
-    "qr_shade_rays_async", "qr_render_views_async", "qr_render_views_mean_async", "qr_hit_rays_async", "qr_hit_views_async",
+    "qr_shade_rays_async", "qr_render_views_async", "qr_render_views_mean_async",
+    "qr_pt_views_state_bytes", "qr_pt_views_reset", "qr_pt_views_async", "qr_hit_rays_async", "qr_hit_views_async",
     "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async", "qr_layer_rays_async", "qr_layer_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
@@ -36,6 +37,8 @@ TRACE_COHERENT = 1          # qr_trace_rays_async / qr_occluded_async flag: cons
 MEAN_RESUME = 1             # qr_render_views_mean_async flag: the sum starts from the `sum` buffer's contents
 FAN_FLIP = 2                # qr_fan_*_async flag: every direction is traced, mirrored into the normal's hemisphere
 FAN_MAX_DIRS = 1024         # QR_FAN_MAX_DIRS
+PT_VIEWS_MAX_SAMPLES = 512  # QR_PT_VIEWS_MAX_SAMPLES: the most samples of one qr_pt_views_async launch
+PT_VIEWS_STATE_WORDS = 4    # QR_PT_VIEWS_STATE_WORDS: 32-bit planes per view of a path-traced view state
 LAYER_MAX = 64              # QR_LAYER_MAX: the most layers of one qr_layer_*_async call
 
 
@@ -101,6 +104,9 @@ def lib():
     L.qr_shade_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
     L.qr_render_views_async.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_render_views_mean_async.argtypes = [vp, vp, ci, ci, ci, vp, vp, ctypes.c_float, ctypes.c_uint32, vp]
+    L.qr_pt_views_state_bytes.argtypes = [vp, ci, ci, ci, ctypes.POINTER(cu64)]
+    L.qr_pt_views_reset.argtypes = [vp, ci, ci, ci, vp]
+    L.qr_pt_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.c_uint32, vp]
     L.qr_hit_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_hit_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_uint32, vp]
     cf = ctypes.c_float
@@ -652,6 +658,13 @@ class Scene:
                                                 self._stream_ptr(stream)))
         return frame, sum
 
+    def pt_views(self, views, width=None, height=None, state=None, samples=0):
+        """Progressive path-traced frames from caller-supplied cameras (qr_pt_views_async): returns a PtViews accumulator for
+        `views` (as for render_views) at width x height.  state=None: a new state tensor, reset (every view starts from the
+        seed plane rays.pt_seeds gives, means 0).  state=<tensor>, samples=<count>: continue a checkpoint -- an int32
+        [N, 4, H * W * samples_per_pixel] tensor on the scene's device holding `samples` samples."""
+        return PtViews(self, views, width, height, state, samples)
+
     def render_count(self, frame=None, stream=None):
         if frame is None:
             frame = self.new_frame()
@@ -672,6 +685,78 @@ class Scene:
             out = np.zeros((self.height, self.width), dtype=np.uint32)
         _check(lib().qr_render_host(self._h, out.ctypes.data_as(ctypes.c_void_p), self.width if row_pixels is None else row_pixels))
         return out
+
+
+class PtViews:
+    """A path-traced accumulation over caller cameras (Scene.pt_views; include/qrhip.h qr_pt_views_async).
+
+    state: int32 [N, 4, H * W * samples_per_pixel] on the scene's device -- per view the generator states (plane 0) and the
+    float32 running means of r, g, b (planes 1..3, bits in int32 slots), slot (y * W + x) * samples_per_pixel + k.
+    samples: how many samples the state holds.  step() adds more; the state and `samples` are all there is to checkpoint.
+    The scene's own path-tracer mode (set_pt) neither matters nor is touched."""
+
+    def __init__(self, scene, views, width=None, height=None, state=None, samples=0):
+        import torch
+        w, h = scene._views_arg(views, width, height)
+        self.scene, self.views, self.width, self.height = scene, views, w, h
+        n = views.shape[0]
+        nbytes = ctypes.c_uint64()
+        _check(lib().qr_pt_views_state_bytes(scene._h, n, w, h, ctypes.byref(nbytes)))
+        self.slots = (w * h) << scene.info.fsaa
+        shape = (n, PT_VIEWS_STATE_WORDS, self.slots)
+        assert nbytes.value == 4 * n * PT_VIEWS_STATE_WORDS * self.slots
+        if state is None:
+            if samples != 0:
+                raise QrError("a new state holds no samples: pass the state tensor that holds them")
+            self.state = torch.empty(shape, dtype=torch.int32, device=views.device)
+            self.samples = 0
+            self.reset()
+        else:
+            if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == shape
+                    and state.is_contiguous() and state.is_cuda and state.device.index == scene.device):
+                raise QrError(f"state must be a contiguous int32 {list(shape)} tensor on cuda:{scene.device}")
+            if not (isinstance(samples, int) and samples >= 0):
+                raise QrError("samples must be the non-negative number of samples the state holds")
+            self.state, self.samples = state, samples
+
+    def reset(self):
+        """Restart the accumulation: seeds as rays.pt_seeds in every view, means 0, samples 0.  Synchronous (qr_pt_views_reset)."""
+        _check(lib().qr_pt_views_reset(self.scene._h, self.views.shape[0], self.width, self.height,
+                                       ctypes.c_void_p(self.state.data_ptr())))
+        self.samples = 0
+
+    def clone(self):
+        """A checkpoint: an accumulator with a copy of the state (on the current stream) that continues independently."""
+        return PtViews(self.scene, self.views, self.width, self.height, self.state.clone(), self.samples)
+
+    def step(self, samples=1, frames=None, mean=False, stream=None):
+        """Add `samples` (1 .. PT_VIEWS_MAX_SAMPLES) samples to every pixel sample of every view in ONE launch and return the
+        packed running-mean frames (int32 [N, H, W]; a new tensor unless given); with mean=True (or a float32 [N, H, W, 3]
+        tensor to fill) also the pixels' linear colours after the FSAA reduce, before gamma and packing: (frames, mean).
+        The scene's current depth (set_depth) applies.  Asynchronous on `stream`."""
+        import torch
+        n, h, w, dev = self.views.shape[0], self.height, self.width, self.scene.device
+        if frames is None:
+            frames = torch.empty((n, h, w), dtype=torch.int32, device=self.views.device)    # every pixel is written
+        elif not (isinstance(frames, torch.Tensor) and frames.dtype == torch.int32 and tuple(frames.shape) == (n, h, w)
+                  and frames.is_contiguous() and frames.is_cuda and frames.device.index == dev):
+            raise QrError(f"frames must be a contiguous int32 [{n}, {h}, {w}] tensor on cuda:{dev}")
+        if mean is True:
+            mean = torch.empty((n, h, w, 3), dtype=torch.float32, device=self.views.device)
+        elif mean is False or mean is None:
+            mean = None
+        elif not (isinstance(mean, torch.Tensor) and mean.dtype == torch.float32 and tuple(mean.shape) == (n, h, w, 3)
+                  and mean.is_contiguous() and mean.is_cuda and mean.device.index == dev):
+            raise QrError(f"mean must be True, False or a contiguous float32 [{n}, {h}, {w}, 3] tensor on cuda:{dev}")
+        if not isinstance(samples, int):
+            raise QrError("samples must be an integer")
+        _check(lib().qr_pt_views_async(self.scene._h, ctypes.c_void_p(self.views.data_ptr()), n, w, h,
+                                       ctypes.c_void_p(self.state.data_ptr()), self.samples, samples,
+                                       ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(mean.data_ptr() if mean is not None else None),
+                                       0, Scene._stream_ptr(stream)))
+        if n > 0:
+            self.samples += samples
+        return (frames, mean) if mean is not None else frames
 
 
 class MultiRender:

@@ -565,6 +565,96 @@ extern "C" int qr_render_views_mean_async(qr_device_scene *s, const qr_view *vie
     return QR_OK;
 }
 
+/* ---- path-traced views (qr_kernel.hpp qr_pt_views_kernel): progressive frames from caller cameras, state in the caller's memory ---- */
+
+/* the checks every entry point of the feature shares: sizes and the view launch's limits; *slots: words of one plane of one view */
+static int pt_views_dims(const qr_device_scene *s, int n_views, int width, int height, uint64_t *slots)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
+    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
+        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
+    const int fsaa = s->fr.fsaa;
+    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+    const int64_t fcols = (width + fw - 1) / fw, frows = (height + fh - 1) / fh;
+    if ((int64_t)n_views * fcols * frows > (int64_t)QR_VIEW_MAX_WAVES)
+        return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
+    *slots = ((uint64_t)width * (uint64_t)height) << fsaa;
+    if ((uint64_t)n_views * *slots > ((uint64_t)1 << 30))
+        return qr_fail(QR_ERR_ARG, "more than 2^30 pixel samples of path-tracer state in one launch");
+    return QR_OK;
+}
+
+extern "C" int qr_pt_views_state_bytes(qr_device_scene *s, int n_views, int width, int height, uint64_t *bytes_out)
+{
+    uint64_t slots = 0;
+    const int rc = pt_views_dims(s, n_views, width, height, &slots);
+    if (rc != QR_OK) return rc;
+    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    *bytes_out = (uint64_t)n_views * QR_PT_VIEWS_STATE_WORDS * slots * sizeof(uint32_t);
+    return QR_OK;
+}
+
+/* the seed plane of qr_scene_set_pt (rt_Scene::reset_pseed) for every view, running means 0: synchronous, as qr_scene_set_pt is */
+extern "C" int qr_pt_views_reset(qr_device_scene *s, int n_views, int width, int height, void *state_dev)
+{
+    uint64_t slots = 0;
+    const int rc = pt_views_dims(s, n_views, width, height, &slots);
+    if (rc != QR_OK) return rc;
+    if (n_views == 0) return QR_OK;
+    if (state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (((uintptr_t)state_dev & 3u) != 0) return qr_fail(QR_ERR_ARG, "state must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<uint32_t> seeds(slots);
+    unsigned long long seed = 1;
+    for (uint64_t k = 0; k < slots; k++)
+    {
+        seed = (seed * 25214903917ull + 11ull) & 0x0000FFFFFFFFFFFFull;
+        seeds[k] = (uint32_t)seed;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t *st = (uint32_t *)state_dev;
+    for (int v = 0; v < n_views; v++, st += QR_PT_VIEWS_STATE_WORDS * slots)
+    {
+        HIP_TRY(hipMemcpy(st, seeds.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(st + slots, 0, 3 * slots * sizeof(uint32_t)));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return QR_OK;
+}
+
+extern "C" int qr_pt_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                 void *state_dev, int done, int samples, uint32_t *frames_dev, float *mean_dev,
+                                 uint32_t flags, void *stream)
+{
+    uint64_t slots = 0;
+    const int rc = pt_views_dims(s, n_views, width, height, &slots);
+    if (rc != QR_OK) return rc;
+    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown path-traced view flags");
+    if (samples < 1 || samples > QR_PT_VIEWS_MAX_SAMPLES)
+        return qr_fail(QR_ERR_ARG, "samples must be 1.." + std::to_string(QR_PT_VIEWS_MAX_SAMPLES));
+    if (done < 0 || (int64_t)done + (int64_t)samples >= ((int64_t)1 << 24))
+        return qr_fail(QR_ERR_ARG, "done must be 0 or more and done + samples below 2^24 (the sample number is exact in fp32)");
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    if (n_views == 0) return QR_OK;
+    if (views_dev == nullptr || state_dev == nullptr || frames_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (((uintptr_t)views_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "views must be 16-byte aligned");
+    if ((((uintptr_t)state_dev | (uintptr_t)frames_dev | (uintptr_t)mean_dev) & 3u) != 0)
+        return qr_fail(QR_ERR_ARG, "state, frames and mean must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const int fsaa = s->fr.fsaa;
+    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+    const dim3 grid((unsigned)((width + fw - 1) / fw), (unsigned)((height + fh - 1) / fh), (unsigned)n_views), block(QR_BLOCK);
+    ViewsP vp;
+    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
+    PtViewsP pv;
+    pv.state = (uint32_t *)state_dev; pv.done = done; pv.samples = samples; pv.mean = mean_dev;
+    /* one instance, as the scene's own path tracer has one: the packet walks (shade<..., PT> exists for them alone) */
+    hipLaunchKernelGGL(qr_pt_views_kernel, grid, block, 0, (hipStream_t)stream, s->lp, vp, pv, frames_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
 /* ---- hit records (qr_hitrec.hpp): the closest hit of qr_trace_rays_async and the surface point shading would use there ---- */
 
 extern "C" int qr_hit_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,

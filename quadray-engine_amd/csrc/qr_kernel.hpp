@@ -240,6 +240,15 @@ struct RaysP { const f32x4 *rays; int32_t n; int32_t pad; float *rgb; };
  */
 struct ViewsP { const qr_view *views; int32_t width, height; float *depth; };
 
+/*
+ * Path-traced views (qr_pt_views_async; the RAYS = 5 instance, PT = true): the accumulation of PtParams for every view of a view
+ * launch, in memory the caller owns.  state: per view four planes of width * height * samples-per-pixel 32-bit words -- the LCG
+ * states, then the running means of r, g, b -- slot (y * width + x) * samples-per-pixel + k (include/qrhip.h).  done: samples the
+ * state holds; samples: how many this launch adds; mean: optional float [view][y][x][3], the pixel's linear colour after the FSAA
+ * reduce.
+ */
+struct PtViewsP { u32 *state; int32_t done, samples; float *mean; };
+
 /* one wave = one schedule entry: footprint `ord`, its tile-list program, rendered into `frame` */
 /*
  * The pixel sample a lane stands for and whether this launch owns it, from the schedule word.  Computed where it is needed --
@@ -290,15 +299,22 @@ __device__ __forceinline__ bool pixel_of_view(u32 ord, int fsaa, const ViewsP &v
  * RAYS = 4 (view accumulation, qr_views_mean_kernel): RAYS = 3 up to and including the FSAA reduce; the reduced linear colour is
  * handed back in `mean_out` (sample 0's lane holds the pixel's) and nothing is stored.  The caller runs it once per view: everything
  * a wave sets up -- rays, recursion stack, mode, counters -- is set up here, on every call, and nothing is read from an earlier one.
+ * RAYS = 5 (path-traced views, qr_pt_views_kernel; PT = true): ONE path-tracer sample of the view's footprint.  The view's ray
+ * set-up and first walk (RAYS = 3) around the path tracer's jitter, shading and bounces; the sample's generator state comes in and
+ * goes out through `rng_io`, its colour leaves in `mean_out` before the running mean, and nothing is read from or written to
+ * global memory for it: the caller keeps the state between samples.  Always the deferred order (no eager machine).
  */
 template <bool COUNT, bool DIVK, bool PT = false, int RAYS = 0>
 __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, const u32 sched_head, const int gw,
                                             uint32_t *__restrict__ frame, int32_t *__restrict__ ids,
                                             unsigned long long *__restrict__ counters, const PtParams *ptp = nullptr,
-                                            const RaysP *rp = nullptr, const ViewsP *vp = nullptr, V3 *mean_out = nullptr)
+                                            const RaysP *rp = nullptr, const ViewsP *vp = nullptr, V3 *mean_out = nullptr,
+                                            u32 *rng_io = nullptr)
 {
-    constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3 || RAYS == 4, MEAN = RAYS == 4;
-    (void)mean_out;
+    constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3 || RAYS == 4 || RAYS == 5, MEAN = RAYS == 4;
+    constexpr bool PTV = RAYS == 5;
+    static_assert(!PTV || PT, "the path-traced view instance is a path-tracer instance");
+    (void)mean_out; (void)rng_io;
 #ifdef QR_WAVETIME
     const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
     const unsigned long long wt_clk0 = __builtin_amdgcn_s_memtime();      /* shader cycles: with the 100 MHz stamps, the clock the wave ran at */
@@ -413,8 +429,12 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
         if constexpr (PT)
         {
             /* tent-filter jitter of the sample position, tracer.cpp:1218-1285 */
-            if (inside && ptp->eager != 3)
+            bool jitter;
+            if constexpr (PTV) jitter = inside; else jitter = inside && ptp->eager != 3;
+            if (jitter)
             {
+                if constexpr (PTV) rng = *rng_io;       /* the caller's: slot (y * width + x) * ns + k of the view's state */
+                else
                 rng = ptp->seeds[((size_t)y * fr->fr.frm_row + x) * ns + k];     /* the engine's slot: row stride frm_row (tracer.cpp:1168-1176) */
                 float a = pt_random(rng); a = a + a;
                 hr = a < 1.0f ? __builtin_sqrtf(a) - 1.0f : 1.0f - __builtin_sqrtf(2.0f - a);
@@ -516,7 +536,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     QR_FLOPS_M(16, __popcll(__ballot(inside)));             /* primary ray */
 
     bool eager_done = false;
-    if constexpr (PT)
+    if constexpr (PT && !PTV)
     {
         if (ptp->eager)
         {
@@ -558,7 +578,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
             wt_trav += __builtin_amdgcn_s_memrealtime() - wt_t0;
             wt_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
-            if constexpr (VIEW)
+            if constexpr (VIEW && !PTV)
             {
                 /* the first hit's t (the view's t_max where there is none), sample 0's: stored here, in the only round whose
                  * tracing lanes are at level 0, so that nothing waits in a register through the recursion for it */
@@ -779,7 +799,14 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
              | ((unsigned long long)wt_push << 40);
     }
 #endif
-    if constexpr (PT)
+    if constexpr (PTV)
+    {
+        /* the sample's colour and the generator's state go back to the caller's loop: the running mean is taken there */
+        *mean_out = ret;
+        *rng_io = rng;
+        return;
+    }
+    if constexpr (PT && !PTV)
     {
         /* 5176-5219: running mean of the samples in the colour planes; the frame shows the mean so far */
         if (inside)
@@ -988,6 +1015,92 @@ void qr_views_mean_kernel(LaunchP lp, ViewsP vp, int n_views, float *__restrict_
             cr = cr * cl; cg = cg * cl; cb = cb * cl;
             frame[px] = (((u32)cvt_near(cr) & cmask) << 16) | (((u32)cvt_near(cg) & cmask) << 8) | ((u32)cvt_near(cb) & cmask);
         }
+    }
+}
+
+/*
+ * Path-traced views (qr_pt_views_async): the grid is (footprint columns, footprint rows, views), one wave per workgroup, as in a
+ * view launch; the wave adds pv.samples samples to its footprint in a wave-uniform loop.  What the engine keeps per pixel sample
+ * (PtParams: one LCG state, three running means) is read from the caller's state once, waits in LDS while a sample is traced
+ * (1 KB per wave: nothing of it is live in registers through the recursion but the generator's state, which the path tracer
+ * carries anyway), and is written back once, after the last sample; then the frame's output step runs once on the means.  The
+ * weights of sample n (1-based, counted from the state's reset) are 1.0f / (float)n and 1.0f - that: IEEE division, the bits of
+ * the host's (qr_device.hip launch<>); wave-uniform.  The path-tracer instance's walks and launch bound.
+ */
+__global__ __launch_bounds__(QR_BLOCK, 3)
+void qr_pt_views_kernel(LaunchP lp, ViewsP vp, PtViewsP pv, uint32_t *__restrict__ frames)
+{
+    const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
+    const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
+    __shared__ u32 lds_rng[64];
+    __shared__ float lds_acc[3][64];
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    const FrmP fr = c_frm((BaseP)lp.B);
+#pragma clang diagnostic pop
+    const int fsaa = fr->fr.fsaa;
+    const size_t slots = (size_t)vp.width * (size_t)vp.height << fsaa;      /* of one view, of one plane */
+    u32 *const st = pv.state + (size_t)view * 4u * slots;
+    const int lane = (int)(threadIdx.x & 63u);
+    {
+        int x_r, y_r, k_r;
+        if (pixel_of_view(ord, fsaa, vp, x_r, y_r, k_r))
+        {
+            const size_t si = (((size_t)y_r * (size_t)vp.width + (size_t)x_r) << fsaa) + (size_t)k_r;
+            lds_rng[lane] = st[si];
+            lds_acc[0][lane] = u2f(st[slots + si]); lds_acc[1][lane] = u2f(st[2 * slots + si]); lds_acc[2][lane] = u2f(st[3 * slots + si]);
+        }
+    }
+    V3 m = {0.0f, 0.0f, 0.0f};
+#pragma nounroll
+    for (int s = 0; s < pv.samples; s++)
+    {
+        int lane_s = (int)(threadIdx.x & 63u);
+        asm volatile("" : "+v"(lane_s));            /* not an address register kept alive through the sample */
+        u32 rng = lds_rng[lane_s];
+        V3 c;
+        render_wave<false, false, true, 5>(lp, ord, 0u, view, nullptr, nullptr, nullptr, nullptr, nullptr, &vp, &c, &rng);
+        asm volatile("" : "+v"(lane_s));
+        /* 5176-5219: running mean of the samples; lanes outside the frame carry zeros and a state nobody reads */
+        const float pts_o = 1.0f / (float)(pv.done + s + 1), pts_u = 1.0f - pts_o;
+        m.x = c.x * pts_o + lds_acc[0][lane_s] * pts_u;
+        m.y = c.y * pts_o + lds_acc[1][lane_s] * pts_u;
+        m.z = c.z * pts_o + lds_acc[2][lane_s] * pts_u;
+        lds_rng[lane_s] = rng;
+        if (s + 1 < pv.samples) { lds_acc[0][lane_s] = m.x; lds_acc[1][lane_s] = m.y; lds_acc[2][lane_s] = m.z; }
+    }
+    int x_e, y_e, k_e;
+    const bool inside_e = pixel_of_view(ord, fsaa, vp, x_e, y_e, k_e);
+    if (inside_e)
+    {
+        const size_t si = (((size_t)y_e * (size_t)vp.width + (size_t)x_e) << fsaa) + (size_t)k_e;
+        st[si] = lds_rng[lane];
+        st[slots + si] = f2u(m.x); st[2 * slots + si] = f2u(m.y); st[3 * slots + si] = f2u(m.z);
+    }
+    /* XX_end 5161-5343 on the means: clamp, FSAA reduce, gamma, pack (render_wave's output step) */
+    float cr = clamp1(m.x), cg = clamp1(m.y), cb = clamp1(m.z);
+    if (fsaa >= 1)
+    {
+        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
+        cr = cr + __shfl_down(cr, 1); cg = cg + __shfl_down(cg, 1); cb = cb + __shfl_down(cb, 1);
+    }
+    if (fsaa >= 2)
+    {
+        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
+        cr = cr + __shfl_down(cr, 2); cg = cg + __shfl_down(cg, 2); cb = cb + __shfl_down(cb, 2);
+    }
+    if (inside_e && k_e == 0)
+    {
+        const size_t px = ((size_t)view * (size_t)vp.height + (size_t)y_e) * (size_t)vp.width + (size_t)x_e;
+        if (pv.mean != nullptr) { pv.mean[3 * px] = cr; pv.mean[3 * px + 1] = cg; pv.mean[3 * px + 2] = cb; }
+        if (fr->fr.ctx_flags & QR_PROP_GAMMA)
+        {
+            asm volatile("" ::: "memory");
+            cr = __builtin_sqrtf(cr); cg = __builtin_sqrtf(cg); cb = __builtin_sqrtf(cb);
+        }
+        const float cl = fr->fr.clamp; const u32 cmask = fr->fr.cmask;
+        cr = cr * cl; cg = cg * cl; cb = cb * cl;
+        frames[px] = (((u32)cvt_near(cr) & cmask) << 16) | (((u32)cvt_near(cg) & cmask) << 8) | ((u32)cvt_near(cb) & cmask);
     }
 }
 

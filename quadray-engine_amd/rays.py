@@ -32,6 +32,9 @@ mean_of_views state its arithmetic in numpy.
 
     views = torch.from_numpy(np.stack([jitter_view(view_of(blob), dx, dy) for dx, dy in offsets])).cuda()
     frame, sum = scn.render_views_mean(views)       # int32 [H, W], float32 [H, W, 3]
+
+Scene.pt_views accumulates path-traced frames of such views in a state tensor the caller owns; pt_seeds gives the seed plane
+every view starts from and pt_random the generator's step, so that a host can predict, edit or checkpoint a state.
 """
 import struct
 
@@ -288,6 +291,41 @@ def thin_lens_views(eye, target, up, fov_deg, width, height, aperture, focus, n,
     out[:, 0:3] = eye + off
     out[:, 4:7] = d - off / np.float64(focus)
     return out
+
+
+# ---- path-traced views (include/qrhip.h qr_pt_views_async; Scene.pt_views): the generator and its seeds in numpy ----
+
+def pt_seeds(width, height, samples_per_pixel=1):
+    """The seed plane a path-traced accumulation starts from (qr_scene_set_pt, qr_pt_views_reset; the reference's
+    rt_Scene::reset_pseed): uint32 [width * height * samples_per_pixel].  A 48-bit LCG, x <- (x * 25214903917 + 11) mod 2^48
+    from x = 1, walks over the slots and each slot keeps the low 32 bits of its x; pixel (x, y), sample k has slot
+    (y * width + x) * samples_per_pixel + k.  Every view of a Scene.pt_views state starts from this same plane (plane 0 of
+    its block of the state tensor)."""
+    n = int(width) * int(height) * int(samples_per_pixel)
+    if n < 1:
+        raise ValueError("pt_seeds needs width, height and samples_per_pixel >= 1")
+    m48 = np.uint64((1 << 48) - 1)
+    # a[k - 1], c[k - 1]: k steps are x -> a * x + c (mod 2^48; uint64 products wrap mod 2^64, which 2^48 divides)
+    a = np.array([25214903917], dtype=np.uint64)
+    c = np.array([11], dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        while len(a) < n:
+            am, cm = a[-1], c[-1]
+            a, c = np.concatenate([a, (a * am) & m48]), np.concatenate([c, (a * cm + c) & m48])
+        x = (a[:n] + c[:n]) & m48
+    return (x & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
+def pt_random(state):
+    """One step of the path tracer's generator (qr_shade.hpp pt_random) on uint32 states of any shape: returns (new states,
+    the numbers drawn as float32 in [0, 1)): s <- s * 214013 + 2531011 (mod 2^32), value = ((s >> 8) & 0xFFFFFF) / 2^24.
+    A sample's first two draws are its horizontal and vertical jitter ("Order of draws")."""
+    s = np.asarray(state, dtype=np.uint32)
+    with np.errstate(over="ignore"):
+        s = (s.astype(np.uint64) * np.uint64(214013) + np.uint64(2531011)).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    s = s.astype(np.uint32)
+    v = ((s >> np.uint32(8)) & np.uint32(0xFFFFFF)).astype(np.float32) / np.float32(16777216.0)
+    return s, v
 
 
 # ---- hit records (include/qrhip.h qr_hit; Scene.hits, Scene.view_hits): float32 [..., 12] = pos xyz, t, nrm xyz, id, alb xyz, mat ----
