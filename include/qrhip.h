@@ -437,6 +437,54 @@ int qr_pt_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_view
                       uint32_t flags, void *stream);
 
 /*
+ * Path-traced rays: progressive path-tracer samples for caller-supplied rays -- the path-traced twin of qr_shade_rays_async,
+ * for what a pinhole view cannot say: a host's own camera (fisheye, panorama, thin lens), light-probe and lightmap rays, an
+ * adaptive sampler that sends more samples only where the picture is still noisy.  The accumulation lives in memory the CALLER
+ * owns; a launch adds `samples` more samples to every ray.
+ *   - The state, QR_PT_RAYS_STATE_WORDS planes of n 32-bit words:  state[plane][i],  ray i is column i.
+ *     plane 0: uint32 generator (LCG) states; planes 1, 2, 3: float32 running means of r, g, b (linear, unclamped).
+ *     qr_pt_rays_state_bytes gives the size (4 * n * 4 bytes).  The host may read and edit it.  The state and the number of
+ *     samples in it are all there is: a copy of the bytes, continued with the same calls, gives the same bits (checkpoints).
+ *   - qr_pt_rays_reset: plane 0 = the engine's seeds of slots 0 .. n - 1 (the 48-bit LCG of qr_pt_views_reset from seed 1, each
+ *     slot keeps the low 32 bits; rays.py pt_seeds(n, 1, 1)), means 0.  The camera rays of a W x H x samples-per-pixel frame sent
+ *     in slot order so start from the seed plane of qr_pt_views_async.  SYNCHRONOUS, like qr_pt_views_reset.
+ *   - One sample of ray i, sample number m (1-based, counted from the reset), in this order:
+ *       1. rng = state[0][i].
+ *       2. With a spread: two numbers are drawn, horizontal first, each through the renderer's tent filter
+ *              u = u + u;  a = u < 1 ? sqrt(u) - 1 : 1 - sqrt(2 - u);  a = a * 0.5
+ *          (no further halving: caller rays have no FSAA), giving h and v; then per component c
+ *              a = du[c] * h;  b = dv[c] * v;  a = a + b;  dir[c] = dir[c] + a
+ *          every step one IEEE fp32 operation, never fused.  Without a spread nothing is drawn before the walk.
+ *       3. The ray walks the ray-query list with its own tmin / tmax (tmax above FLT_MAX is taken as FLT_MAX, as for
+ *          qr_shade_rays_async); everything after the first hit is the path tracer's, in the kernel's order of draws
+ *          (DESIGN.md 4), at the scene's current depth (qr_scene_set_depth).
+ *       4. mean = col * o + mean * u  per channel with  o = 1.0f / (float)m,  u = 1.0f - o,  never fused; state[0][i] = rng.
+ *   - qr_ray_spread: du xyz, pad, dv xyz, pad, 32 bytes, 16-byte aligned; the pad words are ignored.  For a pinhole camera du
+ *     and dv are the view's hor and ver, the change of direction per pixel step.  spread_dev = NULL: no jitter.
+ *   - done: the number of samples the state already holds (0 after a reset); the caller keeps it.  samples: 1 ..
+ *     QR_PT_RAYS_MAX_SAMPLES, all in ONE launch: a wave loops over the samples of its 64 rays with the generator states and the
+ *     means on chip, and reads and writes the state once.  done >= 0 and done + samples < 2^24.  `samples = a + b` gives the
+ *     bits of two launches with a, then b, state included.
+ *   - The rays and the spread may be different in every call: the state belongs to the accumulation, not to a ray set.
+ *   - rgb_dev: optional (NULL = not wanted), float32 [n][3], the running means after the call, before any clamp (rays.py
+ *     pack_colors applies the frame's output step, as for qr_shade_rays_async).
+ *   - Independent of the scene's own path-tracer mode (qr_scene_set_pt), which it never touches.  A snapshot captured outside
+ *     path-tracer mode has no emitters.
+ *   - QR_ERR_UNSUP for a scene without ray-query list (QR_UPLOAD_RAY_QUERIES).  QR_ERR_ARG for samples or done outside their
+ *     ranges, any flag (none is defined: rays are never taken as neighbours, there is no QR_TRACE_COHERENT here), a null
+ *     rays_dev or state_dev, rays_dev or spread_dev not 16-byte aligned, state_dev or rgb_dev not 4-byte aligned, n outside
+ *     0..INT32_MAX; a refused call launches nothing and changes nothing.  n == 0 returns QR_OK without a launch.
+ *   - qr_pt_rays_async is asynchronous on `stream`, on the scene's own device; no hidden copy.
+ */
+#define QR_PT_RAYS_MAX_SAMPLES 512      /* samples of one qr_pt_rays_async launch */
+#define QR_PT_RAYS_STATE_WORDS 4        /* 32-bit planes of n words: generator state, mean r, g, b */
+typedef struct qr_ray_spread { float du[3], pad0, dv[3], pad1; } qr_ray_spread;         /* 32 bytes */
+int qr_pt_rays_state_bytes(qr_device_scene *scn, int64_t n, uint64_t *bytes_out);
+int qr_pt_rays_reset(qr_device_scene *scn, int64_t n, void *state_dev);
+int qr_pt_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
+                     void *state_dev, int done, int samples, float *rgb_dev, uint32_t flags, void *stream);
+
+/*
  * Hit records: the closest hit of a ray AND the surface point the renderer would shade there -- hit point, normal, texture
  * colour, material.  What a host needs to bounce, reflect, offset or cosine-weight its own secondary rays (AO, light probes,
  * path tracing outside the renderer), and, per pixel of a camera, a G-buffer (position, normal, albedo, ids) for deferred passes

@@ -22,7 +22,8 @@ ABI_SYMBOLS = [
     "qr_scene_set_rows", "qr_scene_set_tile_rows", "qr_render_async", "qr_render_multi_async", "qr_render_ids_async",
     "qr_render_count", "qr_render_host", "qr_render_timed", "qr_trace_rays_async", "qr_occluded_async",
     "qr_shade_rays_async", "qr_render_views_async", "qr_render_views_mean_async",
-    "qr_pt_views_state_bytes", "qr_pt_views_reset", "qr_pt_views_async", "qr_hit_rays_async", "qr_hit_views_async",
+    "qr_pt_views_state_bytes", "qr_pt_views_reset", "qr_pt_views_async",
+    "qr_pt_rays_state_bytes", "qr_pt_rays_reset", "qr_pt_rays_async", "qr_hit_rays_async", "qr_hit_views_async",
     "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async", "qr_layer_rays_async", "qr_layer_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
@@ -39,6 +40,8 @@ FAN_FLIP = 2                # qr_fan_*_async flag: every direction is traced, mi
 FAN_MAX_DIRS = 1024         # QR_FAN_MAX_DIRS
 PT_VIEWS_MAX_SAMPLES = 512  # QR_PT_VIEWS_MAX_SAMPLES: the most samples of one qr_pt_views_async launch
 PT_VIEWS_STATE_WORDS = 4    # QR_PT_VIEWS_STATE_WORDS: 32-bit planes per view of a path-traced view state
+PT_RAYS_MAX_SAMPLES = 512   # QR_PT_RAYS_MAX_SAMPLES: the most samples of one qr_pt_rays_async launch
+PT_RAYS_STATE_WORDS = 4     # QR_PT_RAYS_STATE_WORDS: 32-bit planes of a path-traced ray state
 LAYER_MAX = 64              # QR_LAYER_MAX: the most layers of one qr_layer_*_async call
 
 
@@ -107,6 +110,9 @@ def lib():
     L.qr_pt_views_state_bytes.argtypes = [vp, ci, ci, ci, ctypes.POINTER(cu64)]
     L.qr_pt_views_reset.argtypes = [vp, ci, ci, ci, vp]
     L.qr_pt_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.c_uint32, vp]
+    L.qr_pt_rays_state_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
+    L.qr_pt_rays_reset.argtypes = [vp, ctypes.c_int64, vp]
+    L.qr_pt_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ci, ci, vp, ctypes.c_uint32, vp]
     L.qr_hit_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_hit_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_uint32, vp]
     cf = ctypes.c_float
@@ -665,6 +671,12 @@ class Scene:
         [N, 4, H * W * samples_per_pixel] tensor on the scene's device holding `samples` samples."""
         return PtViews(self, views, width, height, state, samples)
 
+    def pt_rays(self, n, state=None, samples=0):
+        """Progressive path-traced samples for caller rays (qr_pt_rays_async): returns a PtRays accumulator for `n` rays.
+        state=None: a new state tensor, reset (ray i starts from seed i of rays.pt_seeds(n, 1, 1), means 0).  state=<tensor>,
+        samples=<count>: continue a checkpoint -- an int32 [4, n] tensor on the scene's device holding `samples` samples."""
+        return PtRays(self, n, state, samples)
+
     def render_count(self, frame=None, stream=None):
         if frame is None:
             frame = self.new_frame()
@@ -757,6 +769,80 @@ class PtViews:
         if n > 0:
             self.samples += samples
         return (frames, mean) if mean is not None else frames
+
+
+class PtRays:
+    """A path-traced accumulation over caller rays (Scene.pt_rays; include/qrhip.h qr_pt_rays_async).
+
+    state: int32 [4, N] on the scene's device -- the generator states (plane 0) and the float32 running means of r, g, b
+    (planes 1..3, bits in int32 slots), ray i in column i; the host may edit it.  samples: how many samples the state holds.
+    step() adds more; the state and `samples` are all there is to checkpoint.  The state belongs to the accumulation, not to a
+    ray set: rays and spread may differ from step to step.  The scene's own path-tracer mode (set_pt) neither matters nor is
+    touched."""
+
+    def __init__(self, scene, n, state=None, samples=0):
+        import torch
+        if not (isinstance(n, int) and n >= 0):
+            raise QrError("n must be the non-negative number of rays")
+        self.scene, self.n = scene, n
+        nbytes = ctypes.c_uint64()
+        _check(lib().qr_pt_rays_state_bytes(scene._h, n, ctypes.byref(nbytes)))
+        shape = (PT_RAYS_STATE_WORDS, n)
+        assert nbytes.value == 4 * PT_RAYS_STATE_WORDS * n
+        if state is None:
+            if samples != 0:
+                raise QrError("a new state holds no samples: pass the state tensor that holds them")
+            self.state = torch.empty(shape, dtype=torch.int32, device=f"cuda:{scene.device}")
+            self.samples = 0
+            self.reset()
+        else:
+            if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == shape
+                    and state.is_contiguous() and state.is_cuda and state.device.index == scene.device):
+                raise QrError(f"state must be a contiguous int32 {list(shape)} tensor on cuda:{scene.device}")
+            if not (isinstance(samples, int) and samples >= 0):
+                raise QrError("samples must be the non-negative number of samples the state holds")
+            self.state, self.samples = state, samples
+
+    def reset(self):
+        """Restart the accumulation: seeds as rays.pt_seeds(n, 1, 1), means 0, samples 0.  Synchronous (qr_pt_rays_reset)."""
+        _check(lib().qr_pt_rays_reset(self.scene._h, self.n, ctypes.c_void_p(self.state.data_ptr())))
+        self.samples = 0
+
+    def clone(self):
+        """A checkpoint: an accumulator with a copy of the state (on the current stream) that continues independently."""
+        return PtRays(self.scene, self.n, self.state.clone(), self.samples)
+
+    def step(self, rays, samples=1, spread=None, rgb=True, stream=None):
+        """Add `samples` (1 .. PT_RAYS_MAX_SAMPLES) path-tracer samples to every ray in ONE launch: rays float32 [N, 8] as for
+        Scene.trace; spread: None or float32 [N, 8] = (du xyz, pad, dv xyz, pad), along which every sample's direction is
+        jittered (rays.pt_jitter, rays.spread_rays).  Returns the running means after the call, float32 [N, 3] linear colour
+        before any clamp (a new tensor with rgb=True, or the given tensor filled), or None with rgb=False.  The scene's
+        current depth (set_depth) applies.  Asynchronous on `stream`."""
+        import torch
+        n, dev = self.n, self.scene.device
+        rays = self.scene._rays_arg(rays)
+        if rays.shape[0] != n:
+            raise QrError(f"this accumulation holds {n} rays, got {rays.shape[0]}")
+        if spread is not None and not (isinstance(spread, torch.Tensor) and spread.dtype == torch.float32
+                                       and tuple(spread.shape) == (n, 8) and spread.is_contiguous() and spread.is_cuda
+                                       and spread.device.index == dev):
+            raise QrError(f"spread must be None or a contiguous float32 [{n}, 8] tensor on cuda:{dev} (du xyz, pad, dv xyz, pad per row)")
+        if rgb is True:
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+        elif rgb is False or rgb is None:
+            rgb = None
+        elif not (isinstance(rgb, torch.Tensor) and rgb.dtype == torch.float32 and tuple(rgb.shape) == (n, 3)
+                  and rgb.is_contiguous() and rgb.is_cuda and rgb.device.index == dev):
+            raise QrError(f"rgb must be True, False or a contiguous float32 [{n}, 3] tensor on cuda:{dev}")
+        if not isinstance(samples, int):
+            raise QrError("samples must be an integer")
+        _check(lib().qr_pt_rays_async(self.scene._h, ctypes.c_void_p(rays.data_ptr()),
+                                      ctypes.c_void_p(spread.data_ptr() if spread is not None else None), n,
+                                      ctypes.c_void_p(self.state.data_ptr()), self.samples, samples,
+                                      ctypes.c_void_p(rgb.data_ptr() if rgb is not None else None), 0, Scene._stream_ptr(stream)))
+        if n > 0:
+            self.samples += samples
+        return rgb
 
 
 class MultiRender:

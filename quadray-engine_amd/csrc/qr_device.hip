@@ -655,6 +655,75 @@ extern "C" int qr_pt_views_async(qr_device_scene *s, const qr_view *views_dev, i
     return QR_OK;
 }
 
+/* ---- path-traced rays (qr_kernel.hpp qr_pt_rays_kernel): progressive samples for caller rays, state in the caller's memory ---- */
+
+/* the checks every entry point of the feature shares: the scene and the ray count of query_args */
+static int pt_rays_dims(const qr_device_scene *s, int64_t n)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
+    return QR_OK;
+}
+
+extern "C" int qr_pt_rays_state_bytes(qr_device_scene *s, int64_t n, uint64_t *bytes_out)
+{
+    const int rc = pt_rays_dims(s, n);
+    if (rc != QR_OK) return rc;
+    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    *bytes_out = (uint64_t)n * QR_PT_RAYS_STATE_WORDS * sizeof(uint32_t);
+    return QR_OK;
+}
+
+/* the seeds of slots 0 .. n - 1 of qr_scene_set_pt's plane (rt_Scene::reset_pseed), running means 0: synchronous, as qr_pt_views_reset is */
+extern "C" int qr_pt_rays_reset(qr_device_scene *s, int64_t n, void *state_dev)
+{
+    const int rc = pt_rays_dims(s, n);
+    if (rc != QR_OK) return rc;
+    if (n == 0) return QR_OK;
+    if (state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (((uintptr_t)state_dev & 3u) != 0) return qr_fail(QR_ERR_ARG, "state must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<uint32_t> seeds((size_t)n);
+    unsigned long long seed = 1;
+    for (int64_t k = 0; k < n; k++)
+    {
+        seed = (seed * 25214903917ull + 11ull) & 0x0000FFFFFFFFFFFFull;
+        seeds[(size_t)k] = (uint32_t)seed;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t *st = (uint32_t *)state_dev;
+    HIP_TRY(hipMemcpy(st, seeds.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(st + n, 0, 3 * (size_t)n * sizeof(uint32_t)));
+    HIP_TRY(hipDeviceSynchronize());
+    return QR_OK;
+}
+
+extern "C" int qr_pt_rays_async(qr_device_scene *s, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
+                                void *state_dev, int done, int samples, float *rgb_dev, uint32_t flags, void *stream)
+{
+    const int rc = pt_rays_dims(s, n);
+    if (rc != QR_OK) return rc;
+    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown path-traced ray flags");
+    if (samples < 1 || samples > QR_PT_RAYS_MAX_SAMPLES)
+        return qr_fail(QR_ERR_ARG, "samples must be 1.." + std::to_string(QR_PT_RAYS_MAX_SAMPLES));
+    if (done < 0 || (int64_t)done + (int64_t)samples >= ((int64_t)1 << 24))
+        return qr_fail(QR_ERR_ARG, "done must be 0 or more and done + samples below 2^24 (the sample number is exact in fp32)");
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    if (n == 0) return QR_OK;
+    if (rays_dev == nullptr || state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if ((((uintptr_t)rays_dev | (uintptr_t)spread_dev) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays and spread must be 16-byte aligned");
+    if ((((uintptr_t)state_dev | (uintptr_t)rgb_dev) & 3u) != 0) return qr_fail(QR_ERR_ARG, "state and rgb must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    PtRaysP pr;
+    pr.rays = (const f32x4 *)rays_dev; pr.spread = (const f32x4 *)spread_dev; pr.n = (int32_t)n; pr.pad = 0; pr.rgb = rgb_dev;
+    /* one instance, as the scene's own path tracer has one: the packet walks (shade<..., PT> exists for them alone); rays are
+     * never taken as neighbours */
+    hipLaunchKernelGGL(qr_pt_rays_kernel, grid, block, 0, (hipStream_t)stream, s->lp, pr, (uint32_t *)state_dev, done, samples);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
 /* ---- hit records (qr_hitrec.hpp): the closest hit of qr_trace_rays_async and the surface point shading would use there ---- */
 
 extern "C" int qr_hit_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,

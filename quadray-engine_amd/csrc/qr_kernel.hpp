@@ -249,6 +249,14 @@ struct ViewsP { const qr_view *views; int32_t width, height; float *depth; };
  */
 struct PtViewsP { u32 *state; int32_t done, samples; float *mean; };
 
+/*
+ * Path-traced rays (qr_pt_rays_async; the RAYS = 6 instance, PT = true): caller rays as in RaysP, and per ray an optional spread
+ * (qr_ray_spread, two 16-byte words: du xyz, pad, dv xyz, pad; nullptr: none) along which every sample's direction is jittered.
+ * rgb: optional float [n][3], the running means after the launch.  The accumulation itself (state, done, samples) is the
+ * kernel's own argument: qr_pt_rays_kernel.
+ */
+struct PtRaysP { const f32x4 *rays; const f32x4 *spread; int32_t n; int32_t pad; float *rgb; };
+
 /* one wave = one schedule entry: footprint `ord`, its tile-list program, rendered into `frame` */
 /*
  * The pixel sample a lane stands for and whether this launch owns it, from the schedule word.  Computed where it is needed --
@@ -303,18 +311,25 @@ __device__ __forceinline__ bool pixel_of_view(u32 ord, int fsaa, const ViewsP &v
  * set-up and first walk (RAYS = 3) around the path tracer's jitter, shading and bounces; the sample's generator state comes in and
  * goes out through `rng_io`, its colour leaves in `mean_out` before the running mean, and nothing is read from or written to
  * global memory for it: the caller keeps the state between samples.  Always the deferred order (no eager machine).
+ * RAYS = 6 (path-traced rays, qr_pt_rays_kernel; PT = true): ONE path-tracer sample of the wave's 64 caller rays (PtRaysP; gw is
+ * the workgroup, lane i of it ray gw * 64 + i).  The ray -- and its spread, when there is one -- is read again on every call and not
+ * kept across the recursion; with a spread the sample first draws two numbers and moves the direction along du and dv by the
+ * tent filter's values.  Rays are never taken as neighbours (the first round is RAYS = 1's), there is no empty-tile exit, no
+ * priority schedule, no id and no depth; state and colour travel as for RAYS = 5 (`rng_io`, `mean_out`), and a lane past n draws
+ * nothing.
  */
 template <bool COUNT, bool DIVK, bool PT = false, int RAYS = 0>
 __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, const u32 sched_head, const int gw,
                                             uint32_t *__restrict__ frame, int32_t *__restrict__ ids,
                                             unsigned long long *__restrict__ counters, const PtParams *ptp = nullptr,
                                             const RaysP *rp = nullptr, const ViewsP *vp = nullptr, V3 *mean_out = nullptr,
-                                            u32 *rng_io = nullptr)
+                                            u32 *rng_io = nullptr, const PtRaysP *pr = nullptr)
 {
     constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3 || RAYS == 4 || RAYS == 5, MEAN = RAYS == 4;
-    constexpr bool PTV = RAYS == 5;
+    constexpr bool PTV = RAYS == 5, PTR = RAYS == 6;
     static_assert(!PTV || PT, "the path-traced view instance is a path-tracer instance");
-    (void)mean_out; (void)rng_io;
+    static_assert(!PTR || PT, "the path-traced ray instance is a path-tracer instance");
+    (void)mean_out; (void)rng_io; (void)pr;
 #ifdef QR_WAVETIME
     const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
     const unsigned long long wt_clk0 = __builtin_amdgcn_s_memtime();      /* shader cycles: with the 100 MHz stamps, the clock the wave ran at */
@@ -360,6 +375,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     bool inside;
     if constexpr (VIEW) inside = x < frm_w && y < vp->height;      /* the grid is the frame's footprints: every wave holds a pixel */
     else if constexpr (CALLER_RAYS) inside = (u32)gw * 64u + (u32)lane < (u32)rp->n;      /* n > 0: every wave holds a ray */
+    else if constexpr (PTR) inside = (u32)gw * 64u + (u32)lane < (u32)pr->n;
     else
     {
         inside = x < frm_w && y < fr->fr.frm_h && y >= lp.row_begin && y < lp.row_end;
@@ -399,7 +415,40 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
 
     u32 rng = 0;                                /* PT: this sample's LCG state */
     Ray ray;
-    if constexpr (CALLER_RAYS)
+    if constexpr (PTR)
+    {
+        /* the caller's ray as below, then the sample's jitter along the ray's spread: two draws, horizontal first, through the
+         * tent filter of the frame's samples (tracer.cpp:1218-1285) without the FSAA halving -- caller rays have none; every
+         * step one fp32 operation (-ffp-contract=off).  Lanes past the end read ray 0 and spread 0, draw nothing and do not walk */
+        const u32 i = inside ? (u32)gw * 64u + (u32)lane : 0u;
+        const f32x4 a = pr->rays[2 * (size_t)i], b = pr->rays[2 * (size_t)i + 1];
+        ray.org = {a.x, a.y, a.z}; ray.tmin = a.w;
+        ray.dir = {b.x, b.y, b.z};
+        ray.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;
+        ray.list = inside ? fr->off_query : 0u;
+        ray.osrf = 0; ray.oflg = 0;
+        ray.ploc = {0, 0, 0};
+        if (inside) rng = *rng_io;              /* the caller's: column i of the state's plane 0 */
+        if (pr->spread != nullptr)
+        {
+            const f32x4 du = pr->spread[2 * (size_t)i], dv = pr->spread[2 * (size_t)i + 1];
+            if (inside)
+            {
+                float u = pt_random(rng); u = u + u;
+                float hr = u < 1.0f ? __builtin_sqrtf(u) - 1.0f : 1.0f - __builtin_sqrtf(2.0f - u);
+                float v = pt_random(rng); v = v + v;
+                float vr = v < 1.0f ? __builtin_sqrtf(v) - 1.0f : 1.0f - __builtin_sqrtf(2.0f - v);
+                hr = hr * 0.5f; vr = vr * 0.5f;
+                float x1 = du.x * hr, x2 = du.y * hr, x3 = du.z * hr;
+                float x4 = dv.x * vr, x5 = dv.y * vr, x6 = dv.z * vr;
+                x1 = x1 + x4; x2 = x2 + x5; x3 = x3 + x6;
+                ray.dir.x = ray.dir.x + x1;
+                ray.dir.y = ray.dir.y + x2;
+                ray.dir.z = ray.dir.z + x3;
+            }
+        }
+    }
+    else if constexpr (CALLER_RAYS)
     {
         /* the caller's ray, as qr_trace_kernel reads it (qr_query.hpp): two 16-byte loads; lanes past the end read ray 0 and
          * do not walk.  No originating surface; tmax +inf is taken as FLT_MAX */
@@ -536,7 +585,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     QR_FLOPS_M(16, __popcll(__ballot(inside)));             /* primary ray */
 
     bool eager_done = false;
-    if constexpr (PT && !PTV)
+    if constexpr (PT && !PTV && !PTR)
     {
         if (ptp->eager)
         {
@@ -566,7 +615,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
                 if (prio_round < 3) { prio_round++; if (prio_round == 2) __builtin_amdgcn_s_setprio(2); else if (prio_round == 3) __builtin_amdgcn_s_setprio(3); }
 #endif
             /* coherent: every ray of this round is a primary ray (neighbouring pixels; caller rays only when vouched for) */
-            const bool coherent = (RAYS != 1) && !any_lane(tr && sp != 0);
+            const bool coherent = (RAYS != 1 && RAYS != 6) && !any_lane(tr && sp != 0);
             traverse<false, DIVK, RAYS != 0>(B, tr, coherent, ray, h, occ
 #ifdef QR_STATS
                             , cx.stats
@@ -799,14 +848,14 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
              | ((unsigned long long)wt_push << 40);
     }
 #endif
-    if constexpr (PTV)
+    if constexpr (PTV || PTR)
     {
         /* the sample's colour and the generator's state go back to the caller's loop: the running mean is taken there */
         *mean_out = ret;
         *rng_io = rng;
         return;
     }
-    if constexpr (PT && !PTV)
+    if constexpr (PT && !PTV && !PTR)
     {
         /* 5176-5219: running mean of the samples in the colour planes; the frame shows the mean so far */
         if (inside)
@@ -1101,6 +1150,60 @@ void qr_pt_views_kernel(LaunchP lp, ViewsP vp, PtViewsP pv, uint32_t *__restrict
         const float cl = fr->fr.clamp; const u32 cmask = fr->fr.cmask;
         cr = cr * cl; cg = cg * cl; cb = cb * cl;
         frames[px] = (((u32)cvt_near(cr) & cmask) << 16) | (((u32)cvt_near(cg) & cmask) << 8) | ((u32)cvt_near(cb) & cmask);
+    }
+}
+
+/*
+ * Path-traced rays (qr_pt_rays_async): one lane per caller ray, 64 per wave, one wave per workgroup, as in ray shading; the wave
+ * adds `samples` samples to its rays in the wave-uniform loop of qr_pt_views_kernel.  state: four planes of n 32-bit words --
+ * the LCG states, then the running means of r, g, b -- ray i is column i (include/qrhip.h).  It is read once before the first
+ * sample, waits in LDS while a sample is traced (1 KB per wave: nothing of it is live in registers through the recursion but the
+ * generator's state, which the path tracer carries anyway) and is written once after the last, with the optional rgb; the ray
+ * and its spread are read again by every sample.  The weights of sample number done + s + 1 are those of qr_pt_views_kernel.
+ * A lane past n reads and writes nothing.  The path-tracer instance's walks (packet walks only) and launch bound.
+ */
+__global__ __launch_bounds__(QR_BLOCK, 3)
+void qr_pt_rays_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, int done, int samples)
+{
+    const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    __shared__ u32 lds_rng[64];
+    __shared__ float lds_acc[3][64];
+    const size_t n = (size_t)(u32)pr.n;
+    const int lane = (int)(threadIdx.x & 63u);
+    {
+        const size_t i = (size_t)(u32)gw * 64u + (size_t)lane;
+        if (i < n)
+        {
+            lds_rng[lane] = state[i];
+            lds_acc[0][lane] = u2f(state[n + i]); lds_acc[1][lane] = u2f(state[2 * n + i]); lds_acc[2][lane] = u2f(state[3 * n + i]);
+        }
+    }
+    V3 m = {0.0f, 0.0f, 0.0f};
+#pragma nounroll
+    for (int s = 0; s < samples; s++)
+    {
+        int lane_s = (int)(threadIdx.x & 63u);
+        asm volatile("" : "+v"(lane_s));            /* not an address register kept alive through the sample */
+        u32 rng = lds_rng[lane_s];
+        V3 c;
+        render_wave<false, false, true, 6>(lp, 0u, 0u, gw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &c, &rng, &pr);
+        asm volatile("" : "+v"(lane_s));
+        /* the running mean of qr_pt_views_kernel; lanes past n carry zeros and a state nobody reads */
+        const float pts_o = 1.0f / (float)(done + s + 1), pts_u = 1.0f - pts_o;
+        m.x = c.x * pts_o + lds_acc[0][lane_s] * pts_u;
+        m.y = c.y * pts_o + lds_acc[1][lane_s] * pts_u;
+        m.z = c.z * pts_o + lds_acc[2][lane_s] * pts_u;
+        lds_rng[lane_s] = rng;
+        if (s + 1 < samples) { lds_acc[0][lane_s] = m.x; lds_acc[1][lane_s] = m.y; lds_acc[2][lane_s] = m.z; }
+    }
+    int lane_e = (int)(threadIdx.x & 63u);
+    asm volatile("" : "+v"(lane_e));
+    const size_t i_e = (size_t)(u32)gw * 64u + (size_t)lane_e;
+    if (i_e < n)
+    {
+        state[i_e] = lds_rng[lane_e];
+        state[n + i_e] = f2u(m.x); state[2 * n + i_e] = f2u(m.y); state[3 * n + i_e] = f2u(m.z);
+        if (pr.rgb != nullptr) { pr.rgb[3 * i_e] = m.x; pr.rgb[3 * i_e + 1] = m.y; pr.rgb[3 * i_e + 2] = m.z; }
     }
 }
 

@@ -35,6 +35,16 @@ mean_of_views state its arithmetic in numpy.
 
 Scene.pt_views accumulates path-traced frames of such views in a state tensor the caller owns; pt_seeds gives the seed plane
 every view starts from and pt_random the generator's step, so that a host can predict, edit or checkpoint a state.
+
+Scene.pt_rays is the same accumulation for caller rays (include/qrhip.h qr_pt_rays_async): path-traced samples for a host's own
+camera, probe or lightmap rays, or more samples only where a picture is still noisy.  Its state is int32 [4, N], ray i in
+column i, reset to pt_seeds(N, 1, 1).  An optional spread per ray (du, dv: the change of direction per pixel step) jitters every
+sample's direction through the renderer's tent filter: pt_jitter gives the two draws and spread_rays the rays they make.
+pt_view_rays gives the rays ONE path-traced sample of a pinhole view traces (Scene.pt_views, set_pt + render), in slot order:
+
+    acc = scn.pt_rays(n)                            # state: seeds of slots 0 .. n - 1, means 0
+    rgb = acc.step(rays, samples=16, spread=spread) # float32 [n, 3]: running means after 16 samples, before any clamp
+    rgb = acc.step(other_rays, samples=4)           # the state belongs to the accumulation, not to a ray set
 """
 import struct
 
@@ -326,6 +336,89 @@ def pt_random(state):
     s = s.astype(np.uint32)
     v = ((s >> np.uint32(8)) & np.uint32(0xFFFFFF)).astype(np.float32) / np.float32(16777216.0)
     return s, v
+
+
+# ---- path-traced rays (include/qrhip.h qr_pt_rays_async; Scene.pt_rays): the jitter and the rays of a sample in numpy ----
+
+def _pt_tent(u):
+    """the renderer's tent filter on numbers in [0, 1) (qr_kernel.hpp, tracer.cpp:1218-1285): float32 in [-0.5, 0.5)"""
+    one, two, half = np.float32(1.0), np.float32(2.0), np.float32(0.5)
+    u = np.asarray(u, dtype=np.float32)
+    u = u + u
+    with np.errstate(invalid="ignore"):
+        a = np.sqrt(u) - one
+        b = one - np.sqrt(two - u)
+    return np.where(u < one, a, b) * half
+
+
+def pt_jitter(states):
+    """The two numbers a path-traced sample draws before its walk ("Order of draws", item 1), through the tent
+    filter: returns (states after the two draws, h, v), uint32 and float32 of the shape of `states`.  Horizontal first.  Per
+    number u = u + u; a = u < 1 ? sqrt(u) - 1 : 1 - sqrt(2 - u); a = a * 0.5 -- one IEEE fp32 operation per step.  A frame
+    with FSAA halves both once more (pt_view_rays); caller rays (qr_pt_rays_async with a spread) do not."""
+    s, u = pt_random(states)
+    h = _pt_tent(u)
+    s, u = pt_random(s)
+    v = _pt_tent(u)
+    return s, h, v
+
+
+def spread_rays(rays, spread, h, v):
+    """The rays qr_pt_rays_async traces for `rays` float32 [N, 8] with `spread` float32 [N, 8] (du xyz, pad, dv xyz, pad) and
+    the jitter h, v (float32 [N], pt_jitter): per component a = du * h; b = dv * v; a = a + b; dir = dir + a, one IEEE fp32
+    operation per step.  Origin, tmin and tmax are kept.  Returns a new float32 [N, 8] array."""
+    r = np.array(rays, dtype=np.float32, copy=True)
+    sp = np.asarray(spread, dtype=np.float32)
+    h, v = np.asarray(h, dtype=np.float32), np.asarray(v, dtype=np.float32)
+    if r.ndim != 2 or r.shape[1] != 8 or sp.shape != r.shape or h.shape != r.shape[:1] or v.shape != r.shape[:1]:
+        raise ValueError("spread_rays needs rays [N, 8], spread [N, 8], h [N] and v [N]")
+    for k in range(3):
+        a = sp[:, k] * h
+        b = sp[:, 4 + k] * v
+        a = a + b
+        r[:, 4 + k] = r[:, 4 + k] + a
+    return r
+
+
+def pt_view_rays(view, width, height, blob, states):
+    """The rays ONE path-traced sample of a view traces (Scene.pt_views; set_pt + render on the snapshot rewritten to the view):
+    returns (rays float32 [W * H * ns, 8] in slot order -- slot (y * W + x) * ns + k, ns = 2^fsaa of the snapshot --, states
+    after the two jitter draws, uint32 [W * H * ns]).  `states`: the slots' generator states before the sample (pt_seeds(W, H,
+    ns) for the first).  view_rays' arithmetic with hs = (x + hor_a) + hr, vs = (y + ver_a) + vr, where hr, vr are pt_jitter's
+    values, halved once more when the snapshot has FSAA."""
+    vw = np.asarray(view, dtype=np.float32).reshape(16)
+    f, i = frame_record(blob)
+    fsaa, w, h = int(i[_F_FSAA]), int(width), int(height)
+    ns = 1 << fsaa
+    if w < 1 or h < 1:
+        raise ValueError("width and height must be at least 1")
+    st = np.asarray(states, dtype=np.uint32)
+    if st.shape != (w * h * ns,):
+        raise ValueError(f"states must be uint32 [{w * h * ns}] (width * height * samples per pixel)")
+    xi = np.repeat(np.tile(np.arange(w), h), ns)
+    x = xi.astype(np.float32)
+    y = np.repeat(np.arange(h, dtype=np.float32), w * ns)
+    k = np.tile(np.arange(ns), w * h)
+    if fsaa == 0:
+        ai = np.zeros(w * h, dtype=np.int64)
+    elif fsaa == 1:
+        ai = (xi & 1) * 2 + k
+    else:
+        ai = k
+    st, hr, vr = pt_jitter(st)
+    if fsaa != 0:
+        hr, vr = hr * np.float32(0.5), vr * np.float32(0.5)
+    hs = (x + f[_F_HORA:_F_HORA + 4][ai]) + hr
+    vs = (y + f[_F_VERA:_F_VERA + 4][ai]) + vr
+    out = np.empty((w * h * ns, 8), dtype=np.float32)
+    for c in range(3):
+        a = vw[8 + c] * hs
+        b = vw[12 + c] * vs
+        out[:, 4 + c] = (a + b) + vw[4 + c]
+        out[:, c] = vw[c]
+    out[:, 3] = vw[3]
+    out[:, 7] = vw[7]
+    return out, st
 
 
 # ---- hit records (include/qrhip.h qr_hit; Scene.hits, Scene.view_hits): float32 [..., 12] = pos xyz, t, nrm xyz, id, alb xyz, mat ----
