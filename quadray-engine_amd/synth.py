@@ -118,6 +118,146 @@ class _Builder:
         return cells[0] if cells else NULL
 
 
+def _lights(b, box):
+    """the four lights above the corners of the box"""
+    top = box + 10.0
+    return [b.light((-0.4 * box, -0.4 * box, top), (1.0, 1.0, 1.0)),
+            b.light((0.4 * box, -0.4 * box, top), (0.9, 0.9, 1.0)),
+            b.light((0.4 * box, 0.4 * box, top), (1.0, 0.9, 0.9)),
+            b.light((-0.4 * box, 0.4 * box, top), (0.9, 1.0, 0.9))]
+
+
+def _bound(spheres):
+    """(centre, radius) of a sphere holding the given spheres (centre of their box)"""
+    cs = np.array([m[0] for m in spheres]); rs = np.array([m[1] for m in spheres])
+    c = 0.5 * ((cs - rs[:, None]).min(0) + (cs + rs[:, None]).max(0))
+    r = float((np.linalg.norm(cs - c, axis=1) + rs).max()) * 1.0001 + 1e-4
+    return c, r
+
+
+def _array(b, member_cells, spheres):
+    """prefix a bounding-volume element to a run of cells; returns (cells, (centre, radius))"""
+    c, r = _bound(spheres)
+    bs = b.surface(TAG_BOUND, (0, 0, 0), c, sci=(1, 1, 1, np.float32(r) * np.float32(r)), real=False)
+    head = b.cell(bs, data=member_cells[-1], kind=1)
+    return [head] + member_cells, (c, r)
+
+
+def _tree(b, obj, ks, leaf):
+    """median-split bounding-volume tree over the objects ks of obj [(surface index, sphere centre, radius)], written
+    depth-first as nested arrays: the reference's array list format is a flattened BVH with skip links (elm_DATA = last
+    element).  Returns (cells, (centre, radius))."""
+    if len(ks) <= leaf:
+        cells = [b.cell(obj[k][0]) for k in ks]
+        sph = [(obj[k][1], obj[k][2]) for k in ks]
+        return _array(b, cells, sph) if len(ks) > 1 else (cells, sph[0])
+    cs = np.array([obj[k][1] for k in ks])
+    axis = int(np.argmax(cs.max(0) - cs.min(0)))
+    order = [ks[i] for i in np.argsort(cs[:, axis], kind="stable")]
+    l_cells, l_sph = _tree(b, obj, order[:len(order) // 2], leaf)
+    r_cells, r_sph = _tree(b, obj, order[len(order) // 2:], leaf)
+    return _array(b, l_cells + r_cells, [l_sph, r_sph])
+
+
+def _sides(r, lp):
+    """Which side of surface record r a light at lp is entered on (2 outer, 1 inner, 3 both) -- the engine's rule
+    (RT_OPTS_2SIDED: lsort -> bbox_side -> clip_side, engine.cpp:2503-2533, rtgeom.cpp:939-995; the same rule as light_sides
+    in csrc/qr_compile.cpp): the sign of the quadric form at the light (margin 1e-4); a convex surface seen from inside shows
+    its inner side only; from outside the outer side only, unless the surface is concave-capable with holes or the light
+    stands outside its clip box."""
+    f = r.view(np.float32)
+    tag = int(r[37].view(np.int32)) if hasattr(r[37], "view") else int(np.int32(r[37]))
+    loc = (lp - f[0:3]).astype(np.float32)
+    if tag == 0:
+        k = (int(r[23]) >> 4) & 3
+        d = -loc[k] if (int(r[23]) >> 10) & 1 else loc[k]
+    else:
+        sci, scj = f[24:28], f[28:31]
+        dcj = np.float32(loc[0] * (scj[0] + scj[0]) + loc[1] * (scj[1] + scj[1]) + loc[2] * (scj[2] + scj[2]))
+        dci = np.float32(loc[0] * loc[0] * sci[0] + loc[1] * loc[1] * sci[1] + loc[2] * loc[2] * sci[2])
+        d = np.float32(dci - dcj - sci[3])
+    c = 2 if d > 1e-4 else (0 if d >= -1e-4 else 1)
+    if c == 0:
+        return 3
+    if tag == 0:
+        return c
+    if tag not in (3, 5, 7, 8) and c == 1:
+        return c
+    mm = int(r[7]) & 63
+    if mm == 0:
+        return c
+    for a in range(3):
+        cmin = f[4 + a] + f[a] if mm & (1 << a) else -np.inf
+        cmax = f[8 + a] + f[a] if mm & (1 << (3 + a)) else np.inf
+        if lp[a] - 1e-4 <= cmin or lp[a] + 1e-4 >= cmax:
+            return 3
+    return c
+
+
+def _light_lists(b, shared, lpos32, r, cells):
+    """cells: one (light, shadow list) per light -> heads of the outer and the inner light list of surface r; equal lists
+    are one list (`shared`: every light on the global shadow list: shared by all)"""
+    out = []
+    for want in (2, 1):
+        key = tuple((l, sh) for (l, sh), lp in zip(cells, lpos32) if _sides(r, lp) & want)
+        if key not in shared:
+            shared[key] = b.link([b.cell(l, data=sh) for l, sh in key]) if key else NULL
+        out.append(shared[key])
+    return out
+
+
+def _frame(width, height, depth, fsaa, gamma, box, glist):
+    """qr_frame: the camera outside a corner of the box, looking at its centre; a single whole-frame tile"""
+    eye = np.array([-0.95 * box, -1.25 * box, 0.9 * box + 1.5])
+    target = np.array([0.0, 0.0, 0.45 * box])
+    fwd = target - eye; fwd /= np.linalg.norm(fwd)
+    right = np.cross(fwd, [0.0, 0.0, 1.0]); right /= np.linalg.norm(right)
+    down = np.cross(fwd, right)
+    pov = 1.0
+    step = 1.0 / width                                            # image plane one unit wide at distance pov
+    hor = right * step; ver = down * step
+    tl = fwd * pov - hor * (0.5 * width) - ver * (0.5 * height)
+
+    fr = np.zeros(49, dtype=np.uint32)                             # qr_frame: 41 used dwords + pad[8]
+    ff = fr.view(np.float32)
+    ff[0] = np.finfo(np.float32).max
+    ff[1:4] = tl; ff[4:7] = hor; ff[7:10] = ver
+    if fsaa == 2:                                                  # engine.cpp:3525-3546 style 4x pattern
+        ff[10:14] = (-0.25 - 0.08, 0.25 - 0.08, -0.25 + 0.08, 0.25 + 0.08)
+        ff[14:18] = (-0.25 + 0.08, -0.25 - 0.08, 0.25 + 0.08, 0.25 - 0.08)
+    ff[18] = 255.0; fr[19] = 255
+    ff[20] = 0.15; ff[21:24] = (0.15, 0.15, 0.15)
+    ff[24] = pov; ff[25:28] = eye
+    fr[28] = P_GAMMA if gamma else 0
+    fr[29] = depth; fr[30] = fsaa
+    fr[31:34] = (width, height, width)
+    fr[34:38] = (width, height, 1, 1)                              # a single whole-frame tile
+    fr[38] = glist; fr[39] = 0; fr[40] = 1
+    return fr
+
+
+def _serialise(b, fr, glist):
+    """the snapshot bytes of a builder's records, frame fr and the single tile's list glist"""
+    def pad16(x):
+        return (x + 15) & ~15
+    srf = np.array(b.srf, dtype=np.uint32); mat = np.array(b.mat, dtype=np.uint32)
+    lgt = np.array(b.lgt, dtype=np.uint32); elm = np.array(b.elm, dtype=np.int32)
+    tiles = np.array([glist], dtype=np.int32); tex = np.array(b.texels, dtype=np.uint32)
+    o_frame = 128
+    o_srf = pad16(o_frame + fr.nbytes); o_mat = pad16(o_srf + srf.nbytes); o_lgt = pad16(o_mat + mat.nbytes)
+    o_elm = pad16(o_lgt + lgt.nbytes); o_tiles = pad16(o_elm + elm.nbytes); o_tex = pad16(o_tiles + tiles.nbytes)
+    total = pad16(o_tex + tex.nbytes)
+    hdr = struct.pack("<4I6I7I5I10I", MAGIC, VERSION, total, 128,
+                      len(srf), len(mat), len(lgt), len(elm), 1, len(tex),
+                      o_frame, o_srf, o_mat, o_lgt, o_elm, o_tiles, o_tex,
+                      fr.nbytes, 256, 128, 64, 16, *([0] * 10))
+    blob = bytearray(total)
+    blob[0:128] = hdr
+    for off, arr in ((o_frame, fr), (o_srf, srf), (o_mat, mat), (o_lgt, lgt), (o_elm, elm), (o_tiles, tiles), (o_tex, tex)):
+        blob[off:off + arr.nbytes] = arr.tobytes()
+    return bytes(blob)
+
+
 def make_scene(n_objects=10000, width=7680, height=4320, depth=4, seed=12345, box=100.0, gamma=False, fsaa=0,
                hierarchy=True, leaf=16, shadow_lists=True):
     """Return the snapshot bytes of the synthetic scene.  hierarchy=False writes one flat list without
@@ -185,94 +325,22 @@ def make_scene(n_objects=10000, width=7680, height=4320, depth=4, seed=12345, bo
             bc, br = (p[0], p[1], p[2] + 0.5 * r), float(np.sqrt(r * r + 0.25 * r * r))
         obj.append((s, np.array(bc, dtype=np.float64), br))
 
-    # lights
-    top = box + 10.0
-    lights = [b.light((-0.4 * box, -0.4 * box, top), (1.0, 1.0, 1.0)),
-              b.light((0.4 * box, -0.4 * box, top), (0.9, 0.9, 1.0)),
-              b.light((0.4 * box, 0.4 * box, top), (1.0, 0.9, 0.9)),
-              b.light((-0.4 * box, 0.4 * box, top), (0.9, 1.0, 0.9))]
+    lights = _lights(b, box)
 
     # ---- the hierarchical list ------------------------------------------------------------------
-    def bound(spheres):
-        """(centre, radius) of a sphere holding the given spheres (centre of their box)"""
-        cs = np.array([m[0] for m in spheres]); rs = np.array([m[1] for m in spheres])
-        c = 0.5 * ((cs - rs[:, None]).min(0) + (cs + rs[:, None]).max(0))
-        r = float((np.linalg.norm(cs - c, axis=1) + rs).max()) * 1.0001 + 1e-4
-        return c, r
-
-    def array(member_cells, spheres):
-        """prefix a bounding-volume element to a run of cells; returns (cells, (centre, radius))"""
-        c, r = bound(spheres)
-        bs = b.surface(TAG_BOUND, (0, 0, 0), c, sci=(1, 1, 1, np.float32(r) * np.float32(r)), real=False)
-        head = b.cell(bs, data=member_cells[-1], kind=1)
-        return [head] + member_cells, (c, r)
-
-    def build(ks):
-        """median-split bounding-volume tree over the objects ks, written depth-first as nested arrays:
-        the reference's array list format is a flattened BVH with skip links (elm_DATA = last element)"""
-        if len(ks) <= leaf:
-            cells = [b.cell(obj[k][0]) for k in ks]
-            sph = [(obj[k][1], obj[k][2]) for k in ks]
-            return array(cells, sph) if len(ks) > 1 else (cells, sph[0])
-        cs = np.array([obj[k][1] for k in ks])
-        axis = int(np.argmax(cs.max(0) - cs.min(0)))
-        order = [ks[i] for i in np.argsort(cs[:, axis], kind="stable")]
-        l_cells, l_sph = build(order[:len(order) // 2])
-        r_cells, r_sph = build(order[len(order) // 2:])
-        return array(l_cells + r_cells, [l_sph, r_sph])
-
     top_cells = [b.cell(ground)]
     if hierarchy and obj:
-        top_cells += build(list(range(len(obj))))[0]
+        top_cells += _tree(b, obj, list(range(len(obj))), leaf)[0]
     else:
         top_cells += [b.cell(o[0]) for o in obj]
     glist = b.link(top_cells)
 
     # light lists.  Default: one light list for everything, every light's shadow list is the global list.
-    # Which side of a surface a light is entered on is the engine's rule (RT_OPTS_2SIDED: lsort -> bbox_side -> clip_side,
-    # engine.cpp:2503-2533, rtgeom.cpp:939-995; the same rule as light_sides in csrc/qr_compile.cpp): the sign of the
-    # quadric form at the light (margin 1e-4); a convex surface seen from inside shows its inner side only; from outside
-    # the outer side only, unless the surface is concave-capable with holes or the light stands outside its clip box.
+    # Which side of a surface a light is entered on: _sides.
     lpos32 = [b.lgt[l].view(np.float32)[1:4].copy() for l in lights]
 
-    def sides(r, lp):
-        f = r.view(np.float32)
-        tag = int(r[37].view(np.int32)) if hasattr(r[37], "view") else int(np.int32(r[37]))
-        loc = (lp - f[0:3]).astype(np.float32)
-        if tag == 0:
-            k = (int(r[23]) >> 4) & 3
-            d = -loc[k] if (int(r[23]) >> 10) & 1 else loc[k]
-        else:
-            sci, scj = f[24:28], f[28:31]
-            dcj = np.float32(loc[0] * (scj[0] + scj[0]) + loc[1] * (scj[1] + scj[1]) + loc[2] * (scj[2] + scj[2]))
-            dci = np.float32(loc[0] * loc[0] * sci[0] + loc[1] * loc[1] * sci[1] + loc[2] * loc[2] * sci[2])
-            d = np.float32(dci - dcj - sci[3])
-        c = 2 if d > 1e-4 else (0 if d >= -1e-4 else 1)
-        if c == 0:
-            return 3
-        if tag == 0:
-            return c
-        if tag not in (3, 5, 7, 8) and c == 1:
-            return c
-        mm = int(r[7]) & 63
-        if mm == 0:
-            return c
-        for a in range(3):
-            cmin = f[4 + a] + f[a] if mm & (1 << a) else -np.inf
-            cmax = f[8 + a] + f[a] if mm & (1 << (3 + a)) else np.inf
-            if lp[a] - 1e-4 <= cmin or lp[a] + 1e-4 >= cmax:
-                return 3
-        return c
-
     def light_lists(r, cells):
-        """cells: one (light, shadow list) per light -> heads of the outer and the inner light list of surface r"""
-        out = []
-        for want in (2, 1):
-            key = tuple((l, sh) for (l, sh), lp in zip(cells, lpos32) if sides(r, lp) & want)
-            if key not in shared:                     # equal lists are one list (every light on the global shadow list: shared by all)
-                shared[key] = b.link([b.cell(l, data=sh) for l, sh in key]) if key else NULL
-            out.append(shared[key])
-        return out
+        return _light_lists(b, shared, lpos32, r, cells)
 
     shared = {}
 
@@ -308,49 +376,4 @@ def make_scene(n_objects=10000, width=7680, height=4320, depth=4, seed=12345, bo
             lo, li_ = light_lists(b.srf[s], [(l, int(heads[k, li])) for li, l in enumerate(lights)])
             b.srf[s][44] = np.uint32(lo & 0xFFFFFFFF); b.srf[s][46] = np.uint32(li_ & 0xFFFFFFFF)
 
-    # ---- camera: outside a corner of the box, looking at its centre ------------------------------
-    eye = np.array([-0.95 * box, -1.25 * box, 0.9 * box + 1.5])
-    target = np.array([0.0, 0.0, 0.45 * box])
-    fwd = target - eye; fwd /= np.linalg.norm(fwd)
-    right = np.cross(fwd, [0.0, 0.0, 1.0]); right /= np.linalg.norm(right)
-    down = np.cross(fwd, right)
-    pov = 1.0
-    step = 1.0 / width                                            # image plane one unit wide at distance pov
-    hor = right * step; ver = down * step
-    tl = fwd * pov - hor * (0.5 * width) - ver * (0.5 * height)
-
-    fr = np.zeros(49, dtype=np.uint32)                             # qr_frame: 41 used dwords + pad[8]
-    ff = fr.view(np.float32)
-    ff[0] = np.finfo(np.float32).max
-    ff[1:4] = tl; ff[4:7] = hor; ff[7:10] = ver
-    if fsaa == 2:                                                  # engine.cpp:3525-3546 style 4x pattern
-        ff[10:14] = (-0.25 - 0.08, 0.25 - 0.08, -0.25 + 0.08, 0.25 + 0.08)
-        ff[14:18] = (-0.25 + 0.08, -0.25 - 0.08, 0.25 + 0.08, 0.25 - 0.08)
-    ff[18] = 255.0; fr[19] = 255
-    ff[20] = 0.15; ff[21:24] = (0.15, 0.15, 0.15)
-    ff[24] = pov; ff[25:28] = eye
-    fr[28] = P_GAMMA if gamma else 0
-    fr[29] = depth; fr[30] = fsaa
-    fr[31:34] = (width, height, width)
-    fr[34:38] = (width, height, 1, 1)                              # a single whole-frame tile
-    fr[38] = glist; fr[39] = 0; fr[40] = 1
-
-    # ---- serialise ------------------------------------------------------------------------------
-    def pad16(x):
-        return (x + 15) & ~15
-    srf = np.array(b.srf, dtype=np.uint32); mat = np.array(b.mat, dtype=np.uint32)
-    lgt = np.array(b.lgt, dtype=np.uint32); elm = np.array(b.elm, dtype=np.int32)
-    tiles = np.array([glist], dtype=np.int32); tex = np.array(b.texels, dtype=np.uint32)
-    o_frame = 128
-    o_srf = pad16(o_frame + fr.nbytes); o_mat = pad16(o_srf + srf.nbytes); o_lgt = pad16(o_mat + mat.nbytes)
-    o_elm = pad16(o_lgt + lgt.nbytes); o_tiles = pad16(o_elm + elm.nbytes); o_tex = pad16(o_tiles + tiles.nbytes)
-    total = pad16(o_tex + tex.nbytes)
-    hdr = struct.pack("<4I6I7I5I10I", MAGIC, VERSION, total, 128,
-                      len(srf), len(mat), len(lgt), len(elm), 1, len(tex),
-                      o_frame, o_srf, o_mat, o_lgt, o_elm, o_tiles, o_tex,
-                      fr.nbytes, 256, 128, 64, 16, *([0] * 10))
-    blob = bytearray(total)
-    blob[0:128] = hdr
-    for off, arr in ((o_frame, fr), (o_srf, srf), (o_mat, mat), (o_lgt, lgt), (o_elm, elm), (o_tiles, tiles), (o_tex, tex)):
-        blob[off:off + arr.nbytes] = arr.tobytes()
-    return bytes(blob)
+    return _serialise(b, _frame(width, height, depth, fsaa, gamma, box, glist), glist)

@@ -1,0 +1,283 @@
+"""A crowd of engine-authored surfaces for the large-scene walks (walk_div, walk_pool, walk_dda, the shadow grids) and the
+per-surface bounds behind them: what quadray-engine_amd/synth.py never draws.
+
+synth.make_scene writes four shapes (tags 1-4), one axis map (0x024) and three min/max patterns.  make_crowd writes the same
+kind of snapshot -- same camera, lights, ground plane, single whole-frame tile, global list only (synth's shadow_lists=False)
+-- but every object is a DONOR: the 64-dword surface record of an untransformed, unclipped (trnode == NULL, clip == NULL), real
+surface taken as the engine wrote it from the snapshots under tests/golden/ (SOURCES), with only these fields rewritten:
+  pos                      drawn from synth._Rng
+  min / max, scj, sci.w    multiplied by s, s, s*s for a uniform scale s = 2^k (exact in fp32, so the engine's box stays the
+                           box of the scaled shape bit for bit); k brings the donor's box to the radius synth would draw
+  mat / props              synth's plain / metal / glass in turn; with `textured` the plain PLANE members take one of two
+                           materials transplanted with their texel ranges (a 256x256 texture of demo03_160, a 2x2 one of
+                           test15_160).  Planes only: texture coordinates are written by the plane's material code alone
+                           (oracle/qr_oracle.c, PL_mat), a textured quadric would show what the last plane hit left there
+  lst                      light lists by synth._sides over the global list
+For a record without its own transform (has_trm == 0) every other field is relative to pos (oracle/qr_oracle.c clip():
+hit - pos against min / max; qr_sides.cpp: bmin = min + pos) or is a pure shape coefficient: d_eps, t_eps, axes, conic,
+srf_t, c_def, smask stay as the engine set them.
+
+DONORS holds one record per (tag, axis map, min/max pattern, conic, solver types) whose engine box is finite, tags in turn so
+that any run of nine objects holds every tag 0..8; object i takes DONORS[i % len(DONORS)].  The four fixture surfaces with an
+open box (two endless cylinders with minmax == 0, two endless plane strips: test07_160*) are OPEN_DONORS: `unbounded` appends
+that many of them.  No donor is left out.
+
+hierarchy=True writes synth's median-split array tree over the members whose clip box, with what the shape adds to it
+(clip_sphere), is closed; a member's bounding sphere is that box's circumsphere.  Members without one go to the top level, in
+front of the tree.
+"""
+import gzip
+import importlib.util
+import os
+import struct
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+# in this order: the first record of a kind is its donor
+SOURCES = ("lists/test15_160", "lists/test15_160_j9", "lists/test16_160", "demo03_160", "lists/swarm_demo01_240_mix",
+           "demo02_160", "lists/test05_160_j1", "lists/test05_160_j14", "lists/test06_160", "lists/test06_160_j2",
+           "lists/test07_160", "lists/test07_160_j3", "lists/test08_160", "lists/test08_160_j4", "test09_160_j11",
+           "lists/test10_160_j6", "lists/test18_160", "lists/test18_160_j18", "lists/swarm_demo02_200_mix_gf")
+TEXTURES = (("demo03_160", 256), ("lists/test15_160", 2))       # (snapshot, texture width): the first such textured material
+
+_CACHE = {}
+
+
+def synth():
+    if "synth" not in _CACHE:
+        spec = importlib.util.spec_from_file_location("qr_synth", os.path.join(ROOT, "quadray-engine_amd", "synth.py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        _CACHE["synth"] = mod
+    return _CACHE["synth"]
+
+
+def _snapshot(name):
+    """(surfaces uint32 [n, 64], materials uint32 [n, 32], texels uint32 [n]) of a fixture"""
+    with open(os.path.join(GOLDEN, name + ".qrs.gz"), "rb") as f:
+        blob = gzip.decompress(f.read())
+    h = struct.unpack_from("<26I", blob, 0)
+    srf = np.frombuffer(blob, dtype=np.uint32, count=h[4] * 64, offset=h[11]).reshape(h[4], 64)
+    mat = np.frombuffer(blob, dtype=np.uint32, count=h[5] * 32, offset=h[12]).reshape(h[5], 32)
+    tex = np.frombuffer(blob, dtype=np.uint32, count=h[9], offset=h[16])
+    return srf, mat, tex
+
+
+def _is_open(rec):
+    f = rec.view(np.float32)
+    return bool((np.abs(f[4:7]) > 1e30).any() or (np.abs(f[8:11]) > 1e30).any())
+
+
+def donor_key(rec):
+    i = rec.view(np.int32)
+    return (int(i[37]), int(rec[23]), int(rec[7]) & 63, int(i[11]), int(i[34]), int(i[35]), int(i[36]))
+
+
+def harvest():
+    """(DONORS, OPEN_DONORS): lists of (record uint32 [64], (snapshot, surface index))"""
+    if "donors" in _CACHE:
+        return _CACHE["donors"]
+    seen, by_tag, opened = set(), {}, []
+    for name in SOURCES:
+        srf = _snapshot(name)[0]
+        si = srf.view(np.int32)
+        for r in range(len(srf)):
+            tag = int(si[r, 37])
+            if not 0 <= tag < 9 or si[r, 38] != -1 or si[r, 39] != -1 or si[r, 15] != 0 or si[r, 19] != 0:
+                continue
+            key = donor_key(srf[r])
+            if key in seen:
+                continue
+            seen.add(key)
+            d = (srf[r].copy(), (name, r))
+            if _is_open(srf[r]):
+                opened.append(d)
+            else:
+                by_tag.setdefault(tag, []).append(d)
+    table = []
+    for k in range(max(len(v) for v in by_tag.values())):         # tags in turn; the rare ones (6, 7, 8) come first
+        for tag in sorted(by_tag):
+            if k < len(by_tag[tag]):
+                table.append(by_tag[tag][k])
+    _CACHE["donors"] = (table, opened)
+    return _CACHE["donors"]
+
+
+def _textures():
+    """[(material record uint32 [32], its texels)] of TEXTURES"""
+    if "tex" not in _CACHE:
+        out = []
+        for name, width in TEXTURES:
+            srf, mat, tex = _snapshot(name)
+            si = srf.view(np.int32)
+            for r in range(len(srf)):
+                m = int(si[r, 40])
+                if 0 <= int(si[r, 37]) < 9 and si[r, 42] & synth().P_TEXTURE and mat[m, 4] == width - 1:
+                    n = int(mat[m, 4]) + (int(mat[m, 5]) << int(mat[m, 6] & 31)) + 1
+                    t0 = int(mat[m].view(np.int32)[7])
+                    assert 0 <= t0 and t0 + n <= len(tex)
+                    out.append((mat[m].copy(), tex[t0:t0 + n].copy()))
+                    break
+            else:
+                raise RuntimeError(f"no textured material of width {width} in {name}")
+        _CACHE["tex"] = out
+    return _CACHE["tex"]
+
+
+def _extent(rec):
+    """half-diagonal of the finite part of the engine's box of a donor record"""
+    f = rec.view(np.float32)
+    h = [0.5 * (float(f[8 + a]) - float(f[4 + a])) for a in range(3) if abs(f[4 + a]) < 1e30 and abs(f[8 + a]) < 1e30]
+    return float(np.sqrt(sum(x * x for x in h)))
+
+
+def _placed(rec, pos, radius):
+    """the donor record at pos, scaled by the power of two that brings its box nearest to `radius`"""
+    r = rec.copy()
+    f = r.view(np.float32)
+    ext = _extent(rec)
+    k = int(np.clip(np.round(np.log2(radius / ext)), -10, 3)) if ext > 0 else 0
+    s = np.float32(2.0 ** k)
+    f[0:3] = pos
+    for a in range(3):
+        if abs(f[4 + a]) < 1e30:
+            f[4 + a] *= s
+        if abs(f[8 + a]) < 1e30:
+            f[8 + a] *= s
+    f[28:31] *= s
+    f[27] *= s * s
+    return r
+
+
+def clip_sphere(r):
+    """(centre float64 [3], radius) of a sphere that holds the visible part of placed record r, or None when its clip box and
+    shape do not close it in: the clip box, a plane's normal axis at 0, and for a quadric without linear terms on an axis a
+    with sci_a > 0:  sci_a x_a^2 <= sci_w + sum over the other axes b with sci_b < 0 of -sci_b max(x_b^2)  (a clipped
+    cylinder's, cone's or hyperboloid's waist; an ellipsoid's half-axes)"""
+    f = r.view(np.float32)
+    mm = int(r[7]) & 63
+    tag = int(r.view(np.int32)[37])
+    sci, scj = f[24:28].astype(np.float64), f[28:31]
+    lo, hi = np.empty(3), np.empty(3)
+    for a in range(3):
+        lo[a] = float(f[4 + a]) if mm & (1 << a) else -np.inf
+        hi[a] = float(f[8 + a]) if mm & (8 << a) else np.inf
+        if tag == 0 and a == (int(r[23]) >> 4) & 3:
+            lo[a], hi[a] = min(max(lo[a], 0.0), hi[a]), max(min(hi[a], 0.0), lo[a])
+    if tag != 0 and not scj.any():
+        for _ in range(2):
+            for a in range(3):
+                if not sci[a] > 0:
+                    continue
+                rhs = sci[3]
+                for b in range(3):
+                    if b != a and sci[b] < 0:
+                        rhs += -sci[b] * max(lo[b] * lo[b], hi[b] * hi[b])
+                if np.isfinite(rhs):
+                    e = float(np.sqrt(max(rhs, 0.0) / sci[a])) * 1.0005 + 1e-4
+                    lo[a], hi[a] = max(lo[a], -e), min(hi[a], e)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        return None
+    hi = np.maximum(hi, lo)
+    c = f[0:3].astype(np.float64) + 0.5 * (lo + hi)
+    return c, float(np.linalg.norm(0.5 * (hi - lo))) * 1.0001 + 1e-4
+
+
+def make_crowd(n_objects, width, height, depth, box, seed, hierarchy=True, unbounded=0, textured=True, fsaa=0, gamma=False,
+               leaf=16):
+    """Snapshot bytes in synth.make_scene's layout (see the module's text)."""
+    S = synth()
+    donors, opened = harvest()
+    if not 0 <= unbounded <= len(opened):
+        raise ValueError(f"unbounded: 0..{len(opened)}")
+    rng = S._Rng(seed)
+    b = S._Builder()
+
+    palette = [0xD04040, 0x40B040, 0x4060D0, 0xD0C040, 0xB050C0, 0x40C0C0]
+    plain = [b.material(c) for c in palette]
+    metal = [b.material(c, l_dff=0.5, l_spc=0.5, l_pow=512, c_rfl=0.5, ext_2=81.0) for c in palette]
+    glass_o = [b.material(c, c_trn=0.5, c_rfr=0.67) for c in palette]
+    glass_i = [b.material(c, c_trn=0.5, c_rfr=1.5) for c in palette]
+    ground_m = b.material(0x909090)
+    inner_plain = b.material(0x808080)
+    tex_m = []
+    if textured:
+        for rec, texels in _textures():
+            m = rec.copy()
+            m[7] = len(b.texels)
+            b.texels.extend(int(t) for t in texels)
+            b.mat.append(m)
+            tex_m.append(len(b.mat) - 1)
+
+    g = S.P_GAMMA if gamma else 0
+    PR_PLAIN = S.P_DIFFUSE | S.P_OPAQUE | S.P_NORMAL | g
+    PR_METAL = S.P_SPECULAR | S.P_DIFFUSE | S.P_REFLECT | S.P_OPAQUE | S.P_NORMAL | S.P_METAL | g
+    PR_GLASS = S.P_REFRACT | S.P_DIFFUSE | S.P_NORMAL | g
+    PR_TEX = PR_PLAIN | S.P_TEXTURE
+
+    half = 0.75 * box
+    ground = b.surface(S.TAG_PLANE, (1, 1, 1), (0.0, 0.0, 0.0), mn=(-half, -half, 0.0), mx=(half, half, 0.0),
+                       minmax_t=0x1B, mats=(ground_m, inner_plain), props=(PR_PLAIN, PR_PLAIN))
+
+    n = n_objects
+    cx = (rng.real(n) - np.float32(0.5)) * np.float32(box)
+    cy = (rng.real(n) - np.float32(0.5)) * np.float32(box)
+    cz = rng.real(n) * np.float32(box) + np.float32(1.5)
+    rad = rng.real(n) * np.float32(0.8) + np.float32(0.2)
+    ox = (rng.real(4) - np.float32(0.5)) * np.float32(box)          # the open members: always drawn, so that `unbounded`
+    oy = (rng.real(4) - np.float32(0.5)) * np.float32(box)          # changes nothing else
+    oz = rng.real(4) * np.float32(box) + np.float32(1.5)
+    orad = rng.real(4) * np.float32(0.8) + np.float32(0.2)
+    picks = [(donors[i % len(donors)][0], (cx[i], cy[i], cz[i]), rad[i]) for i in range(n)]
+    picks += [(opened[k][0], (ox[k], oy[k], oz[k]), orad[k]) for k in range(unbounded)]
+
+    obj, loose = [], []           # (surface index, sphere centre, radius) of members with a closed clip box; the others
+    for i, (rec, pos, radius) in enumerate(picks):
+        r = _placed(rec, np.array(pos, dtype=np.float32), float(radius))
+        m, pi = i % 3, (i // 3) % len(palette)
+        if m == 0 and tex_m and int(r[37]) == S.TAG_PLANE:
+            mats, props = (tex_m[(i // 3) % len(tex_m)], inner_plain), (PR_TEX, PR_PLAIN)
+        elif m == 0:
+            mats, props = (plain[pi], inner_plain), (PR_PLAIN, PR_PLAIN)
+        elif m == 1:
+            mats, props = (metal[pi], inner_plain), (PR_METAL, PR_PLAIN)
+        else:
+            mats, props = (glass_o[pi], glass_i[pi]), (PR_GLASS, PR_GLASS)
+        r[40:42] = np.array(mats, dtype=np.int32).view(np.uint32)
+        r[42:44] = np.array(props, dtype=np.int32).view(np.uint32)
+        r[44:48] = np.uint32(0xFFFFFFFF)
+        b.srf.append(r)
+        s = len(b.srf) - 1
+        sph = clip_sphere(r)
+        if sph is None:
+            loose.append(s)
+        else:
+            obj.append((s, sph[0], sph[1]))
+
+    lights = S._lights(b, box)
+
+    top_cells = [b.cell(ground)]
+    if hierarchy and obj:
+        top_cells += [b.cell(s) for s in loose]
+        top_cells += S._tree(b, obj, list(range(len(obj))), leaf)[0]
+    else:
+        top_cells += [b.cell(s) for s in range(ground + 1, ground + 1 + len(picks))]
+    glist = b.link(top_cells)
+
+    lpos32 = [b.lgt[l].view(np.float32)[1:4].copy() for l in lights]
+    shared = {}
+    for r in b.srf:
+        if int(r[37]) < S.TAG_BOUND:
+            lo, li = S._light_lists(b, shared, lpos32, r, [(l, glist) for l in lights])
+            r[44:48] = np.array([lo, glist, li, glist], dtype=np.int32).view(np.uint32)
+    return S._serialise(b, S._frame(width, height, depth, fsaa, gamma, box, glist), glist)
+
+
+# the crowds of the GPU tests (tests/test_crowd.py, _rayset.SCENES and the other entry points' parameter lists)
+HIER = dict(n_objects=220, width=160, height=90, depth=4, box=14.0, seed=11)
+DENSE = dict(n_objects=400, width=160, height=90, depth=5, box=8.0, seed=12, hierarchy=False)
+OPEN = dict(n_objects=500, width=97, height=61, depth=4, box=18.0, seed=13, unbounded=4, fsaa=2, gamma=True)
+COVER = dict(n_objects=400, width=160, height=90, depth=4, box=16.0, seed=11)      # the coverage test's crowd

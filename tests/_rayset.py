@@ -16,6 +16,8 @@ Every generator is deterministic (seeded by zlib.crc32 of the scene name) and re
   probe      rays that start at earlier hit points, hemisphere directions, tmin 0 or 1e-4 * t (AO and light probes)
   mixed      all of them concatenated and shuffled (an odd count)
 
+The crowd_* scenes hold engine-authored surfaces of every tag, axis map and min/max pattern the fixtures have (tests/_crowd.py).
+
 The scenes (SCENES) and how each is uploaded (environment of the image build) live here as well, so that the CPU coverage
 test and the GPU tests see the same query lists.
 """
@@ -45,6 +47,9 @@ SCENES = {
     "synth_flat": ("synth_flat", {}),
     "synth_flat_dda": ("synth_flat", DDA_ENV),
     "synth_dense_dda": ("dense", DDA_ENV),
+    "crowd_hier": ("crowd_hier", {}),
+    "crowd_flat_dda": ("crowd_flat", DDA_ENV),
+    "crowd_dense_dda": ("crowd_dense", DDA_ENV),
 }
 FAMILIES = ["axis", "near_axis", "grid", "interval", "scale", "far", "probe", "mixed"]
 
@@ -68,10 +73,19 @@ def scene_blob(name):
         elif kind in ("synth", "synth_flat"):
             from test_ray_query import SYNTH_SMALL
             b = _synth_mod().make_scene(hierarchy=kind == "synth", **SYNTH_SMALL)
-        else:                                   # the dense cloud of test_synth.py (seed 4): many equal depths
+        elif kind == "dense":                   # the dense cloud of test_synth.py (seed 4): many equal depths
             from qr_loader import load_package
             kw = dict(n_objects=900, width=320, height=180, depth=6, box=9.0, seed=4)
             b = load_package().build_lists(_synth_mod().make_scene(shadow_lists=False, **kw))
+        else:                                   # engine-authored surfaces of every kind (tests/_crowd.py)
+            import _crowd
+            if kind == "crowd_hier":            # a long hierarchy: hand-over walk
+                b = _crowd.make_crowd(**_crowd.HIER)
+            elif kind == "crowd_flat":          # a flat list with four unbounded members, a grid over it
+                b = _crowd.make_crowd(**dict(_crowd.OPEN, hierarchy=False))
+            else:                               # dense, built lists: list order decides between equal depths
+                from qr_loader import load_package
+                b = load_package().build_lists(_crowd.make_crowd(**_crowd.DENSE))
         _BLOBS[name] = b
     return _BLOBS[name]
 

@@ -344,7 +344,7 @@ def test_gpu_layers_camera_rays(qr, oracle, rays_mod, helper, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ORIGIN_CASES + ["synth_small_dda"])
+@pytest.mark.parametrize("name", ORIGIN_CASES + ["synth_small_dda", "crowd_flat_dda"])
 def test_gpu_layers_edge_families(qr, oracle, rays_mod, helper, name, tmp_path):
     """the adversarial families of tests/_rayset.py (the grid family on the scene whose query list carries a uniform grid) at
     k = 4; on synth_small the far family once more at k = 64, where the count saturates"""

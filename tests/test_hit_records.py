@@ -360,9 +360,10 @@ def _rs_scene(qr, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ORIGIN_CASES + ["synth_small_dda"])
+@pytest.mark.parametrize("name", ORIGIN_CASES + ["synth_small_dda", "crowd_flat_dda"])
 def test_gpu_hits_edge_families(qr, oracle, rays_mod, helper, name, tmp_path):
-    """the adversarial families of tests/_rayset.py (the grid family on the scene whose query list carries a uniform grid)"""
+    """the adversarial families of tests/_rayset.py (the grid family on the scenes whose query list carries a uniform grid;
+    crowd_flat_dda: records on every surface kind, axis map and a textured plane of tests/_crowd.py)"""
     blob = RS.scene_blob(name)
     off, img = RS.query_image(qr, name, tmp_path)
     scn = _rs_scene(qr, name)

@@ -303,6 +303,31 @@ def test_gpu_ray_occlusion_families(qr, oracle, rays_mod, helper):
 
 
 @pytest.mark.gpu
+def test_gpu_ray_occlusion_on_a_grid_list(qr, oracle, rays_mod, helper, tmp_path):
+    """fans over a list with a uniform grid and four unbounded members (crowd_flat_dda, tests/_crowd.py): first hits of the
+    grid family -- rays on cell faces, sparse waves -- and of the mixed family carry the fans, so that the fan rounds' idle
+    lanes are what walk_dda's segment split hands work to"""
+    name = "crowd_flat_dda"
+    blob = RS.scene_blob(name)
+    off, img = RS.query_image(qr, name, tmp_path)
+    g = RS.dda_grid(off, img)
+    assert g is not None
+    dirs = _dirs16(rays_mod)
+    scn = _rs_scene(qr, name)
+    try:
+        for label, rays in (("grid", RS.grid(blob, name, g)), ("mixed", RS.mixed(blob, name, oracle, g, RS.reach_of(img)))):
+            hits = helper(blob, rays)
+            assert (_fields(hits)[3] >= 0).sum() > 100, label
+            for flip in (False, True):
+                want_o, want_m = _truth(oracle, rays_mod, blob, hits, dirs, EPS, REACH, flip)
+                for coherent in (False, True):
+                    opn, msk = _occlusion(scn, rays, dirs, flip=flip, coherent=coherent)
+                    _same(f"{name} {label} flip={flip} coherent={coherent}", opn, msk, want_o, want_m)
+    finally:
+        scn.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 130])
 def test_gpu_ray_occlusion_batch_sizes(qr, oracle, rays_mod, helper, n):
     """partial waves, with and without `coherent`; nothing is written past the end of open or of a mask plane"""

@@ -29,7 +29,7 @@ from test_pt_views import SCENES, _base, _bits, _cams, _fsaa, _rays_mod, _size
 ASM = TPV.ASM
 GUARD_LIB = TPV.GUARD_LIB
 GUARD_CASE = ("patched:demo02_160_gf_aa4", 2, 3)            # scene, view, samples
-FAMILY_SCENES = ["demo01_160", "test05_160_j14", "synth_small"]
+FAMILY_SCENES = ["demo01_160", "test05_160_j14", "synth_small", "crowd_hier"]
 ARG, UNSUP = -1, -3
 W = H = 64
 # the seeded view the single-view tests use: one that test_inputs_discriminate shows to be lit and sensitive to the spread, the

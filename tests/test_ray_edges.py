@@ -133,6 +133,11 @@ def test_query_lists_cover_the_walks(images):
     assert flags["synth_small"] == RS.LISTF_DIV | RS.LISTF_LONG | RS.LISTF_WORLD
     assert flags["synth_flat"] == RS.LISTF_DIV | RS.LISTF_WORLD
     assert flags["demo01_160"] == 0 and flags["swarm_demo01_240"] == 0
+    # engine-authored surfaces of every kind (tests/_crowd.py) on the hand-over walk, and under a grid: a flat list with four
+    # unbounded members, a dense one with built lists
+    assert flags["crowd_hier"] == RS.LISTF_DIV | RS.LISTF_LONG | RS.LISTF_WORLD
+    assert flags["crowd_flat_dda"] == RS.LISTF_DIV | RS.LISTF_WORLD | RS.LISTF_DDA
+    assert flags["crowd_dense_dda"] == RS.LISTF_DIV | RS.LISTF_WORLD | RS.LISTF_DDA
 
 
 @pytest.mark.parametrize("name", sorted(RS.SCENES))

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import _rayq
+import _rayset as RS
 from conftest import ROOT, load_blob, load_frame
 from test_ray_query import NON_PT_SMALL, ORIGIN_CASES, _blob
 
@@ -200,7 +201,7 @@ _DEPTHS = {}
 
 
 def _seeded_views(rays_mod, name, n=8):
-    base = _blob(name)
+    base = RS.scene_blob(name) if name.startswith("crowd_") else _blob(name)      # a crowd of tests/_crowd.py, or a fixture
     return base, [rays_mod.view_of(c) for c in _rayq.random_cameras(base, seed=zlib.crc32(name.encode()), n=n)]
 
 
@@ -277,7 +278,7 @@ def _behind_and_far(rays_mod, name, w, h):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["demo01_160", "synth_small", "swarm_demo01_240", "demo01_160_gf_aa4"])
+@pytest.mark.parametrize("name", ["demo01_160", "synth_small", "swarm_demo01_240", "demo01_160_gf_aa4", "crowd_flat_dda"])
 def test_gpu_views_behind_and_far_are_caller_rays(qr, oracle, rays_mod, name):
     """A view is caller input: with t_min < 0 or an origin beyond `reach` its rays behave as they do for shade -- the oracle's
     caller-ray restatement (oracle.trace_rays) of the view's rays, packed by the frame's output step, is the view's frame; its
@@ -285,7 +286,11 @@ def test_gpu_views_behind_and_far_are_caller_rays(qr, oracle, rays_mod, name):
     w, h = 67, 45
     base, views = _behind_and_far(rays_mod, name, w, h)
     ns = 1 << int(_rayq.frame_words(base)[0][30])
-    scn = qr.Scene(base, ray_queries=True)
+    if name in RS.SCENES:                       # crowd_flat_dda: engine-authored surfaces of every kind under a uniform grid
+        with RS.upload_env(name):
+            scn = qr.Scene(base, ray_queries=True)
+    else:
+        scn = qr.Scene(base, ray_queries=True)
     f, ids, dep = _render(scn, views, w, h)
     scn.close()
     hit = []

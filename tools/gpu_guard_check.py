@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The QR_STATS + QR_GUARD build (every cell offset of the per-lane walks checked before it is loaded, csrc/qr_walk.hpp
 QR_GUARD_POS) on scenes that drive walk_div / walk_pool / walk_dda hard: synthetic crowds with built lists, the 10 000-object
-scene at a small size, a swarm fixture.  Prints one line per case: "<case> guard_bad 0 frame_ok 1"; exit code 1 on any bad
+scene at a small size, a swarm fixture, a dense crowd of engine-authored surfaces (tests/_crowd.py).  Prints one line per case: "<case> guard_bad 0 frame_ok 1"; exit code 1 on any bad
 offset or frame.  Build: make -C quadray-engine_amd/csrc guard.  (GPU box; run by tests/test_synth.py in a child process.)"""
 import gzip, importlib.util, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,13 +36,17 @@ cases = {
 # a dense cloud with lowered grid thresholds (every list of 64 members gets its uniform grid, the plane its shadow grids): an image of
 # ~300 MB, i.e. valid cell offsets beyond the 256 MB bound the guard had until round 3
 cases["dense490_low_thresholds"] = qr.build_lists(synth.make_scene(shadow_lists=False, n_objects=490, width=320, height=180, depth=6, box=5.96, seed=20076))
+# engine-authored surfaces of every kind, axis map and min/max pattern the fixtures hold (tests/_crowd.py), dense, built lists
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _crowd
+cases["crowd400_dense_low_thresholds"] = qr.build_lists(_crowd.make_crowd(**_crowd.DENSE))
 rc = 0
 for name, blob in cases.items():
     low = name.endswith("low_thresholds")
     if low:
         os.environ.update({"QR_DDA": "64", "QR_GRID": "64"})
     try:
-        scn = qr.Scene(blob, rebin_tiles=name.startswith("synth"))
+        scn = qr.Scene(blob, rebin_tiles=name.startswith(("synth", "crowd")))
     finally:
         if low:
             del os.environ["QR_DDA"], os.environ["QR_GRID"]
