@@ -485,6 +485,65 @@ int qr_pt_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, const qr_ray_
                      void *state_dev, int done, int samples, float *rgb_dev, uint32_t flags, void *stream);
 
 /*
+ * Adaptive path-traced rays: qr_pt_rays_async with a sample count and a noise estimate PER RAY in the caller-owned state, and a
+ * stop rule evaluated on chip before every sample.  Rays that have converged retire; a wave leaves when none of its rays is left.
+ * The specification in numpy is rays.py pt_adapt_fold (the rule alone: pt_adapt_open).
+ *   - The state, QR_PT_ADAPT_STATE_WORDS planes of n 32-bit words:  state[plane][i],  ray i is column i.
+ *       plane 0      uint32   LCG state
+ *       planes 1..3  float32  running means of r, g, b, exactly as qr_pt_rays_async keeps them
+ *       plane 4      uint32   the number of samples m this ray holds
+ *       planes 5..7  float32  M2 of r, g, b: the sum of squared deviations from the mean, Welford's
+ *     qr_pt_adapt_state_bytes gives the size (8 * n * 4 bytes).  qr_pt_adapt_reset writes plane 0 as qr_pt_rays_reset does and
+ *     sets every other plane to 0; it is SYNCHRONOUS.  The state is all there is: there is no `done` argument.  The host may
+ *     read it, edit it, copy it and continue from it.
+ *   - One call: every ray gets up to `samples` candidate samples, 1 .. QR_PT_ADAPT_MAX_SAMPLES.  Before each candidate ray i
+ *     decides on its own column whether to take it:
+ *         take = m < max_samples && (m < min_samples || m < 2 || !conv)
+ *         lim  = (float)m * (float)(m - 1);   lim = lim * tol2;            two fp32 multiplies
+ *         conv = M2r <= lim && M2g <= lim && M2b <= lim                     a NaN never converges
+ *     A ray that does not take a candidate takes none later in that call, because its state did not change; its eight state
+ *     words are left as they are, bit for bit.
+ *   - A taken sample is exactly one sample of qr_pt_rays_async, steps 1 to 3 of its text above: the spread jitter if any, the
+ *     walk, and the kernel's order of draws at the scene's current depth.  Then, every line one IEEE fp32 operation, never
+ *     fused, the quotient correctly rounded:
+ *         m = m + 1;  o = 1.0f / (float)m;  u = 1.0f - o
+ *         per channel:  d1 = col - mean;  a = col * o;  b = mean * u;  mean = a + b;  d2 = col - mean;  p = d1 * d2;  M2 = M2 + p
+ *         state[0][i] = rng
+ *   - tol2 is the SQUARED tolerance on the standard error of the mean, in linear colour units: M2 / (m (m - 1)) is the variance
+ *     of the mean.  min_samples and max_samples are per-ray totals since the reset, not per call.
+ *   - Why Welford's M2 and not the running mean of x * x: mean(x * x) - mean * mean cancels in fp32 exactly where a pixel is
+ *     quiet -- where the rule has to decide -- and can come out negative by far more than rounding; M2 is a sum of products
+ *     d1 * d2 of the sample's deviation from the mean before and after the update, which subtracts nothing: a ray whose samples
+ *     are all equal holds M2 = 0 exactly after its first two, and at most a few ulp^2 of its colour squared later.
+ *   - Consequences the tests rest on:
+ *       (a) with min_samples >= max_samples (the call accepts min_samples == max_samples), the first four planes after any
+ *           sequence of calls are the bits qr_pt_rays_async gives for the same rays and sample totals;
+ *       (b) samples = a + b gives the bits of two calls with a, then b;
+ *       (c) a ray's result depends on nothing but its own column, ray and spread: not on its neighbours, not on n, not on its
+ *           position in the wave.
+ *   - rgb_dev: optional (NULL = not wanted), float32 [n][3]: the means after the call, for every ray, taken or not.
+ *   - open_dev: optional, ONE uint32 that the caller zeroes.  The call adds the number of rays that would still take a sample
+ *     under the same rule evaluated on the final state: one vector atomic add per wave, from one lane, of the ballot's
+ *     population count; waves with a count of 0 skip it.  A host loops "step until open == 0" without reading the state back.
+ *   - Cost: one wave holds 64 consecutive rays and runs as long as its slowest ray; the others' lanes idle.  That is inherent
+ *     to one wave per 64 rays.  What a caller can do: sort or compact the rays (with their state columns) by whether they are
+ *     still open between calls -- consequence (c) makes that exact.
+ *   - QR_ERR_ARG: samples outside 1 .. QR_PT_ADAPT_MAX_SAMPLES; min_samples < 0, max_samples < 1, min_samples > max_samples or
+ *     max_samples >= 2^24 (the count is exact in fp32); tol2 negative, NaN or infinite; any flag (none is defined); a null
+ *     rays_dev or state_dev; rays_dev or spread_dev not 16-byte aligned; state_dev, rgb_dev or open_dev not 4-byte aligned;
+ *     n outside 0..INT32_MAX.  QR_ERR_UNSUP for a scene without ray-query list (QR_UPLOAD_RAY_QUERIES).  A refused call
+ *     launches nothing and changes nothing.  n == 0 returns QR_OK without a launch.
+ *   - Independent of the scene's own path-tracer mode.  Asynchronous on `stream`, on the scene's own device; no hidden copy.
+ */
+#define QR_PT_ADAPT_MAX_SAMPLES 512      /* candidate samples of one launch */
+#define QR_PT_ADAPT_STATE_WORDS 8        /* planes of n 32-bit words */
+int qr_pt_adapt_state_bytes(qr_device_scene *scn, int64_t n, uint64_t *bytes_out);
+int qr_pt_adapt_reset(qr_device_scene *scn, int64_t n, void *state_dev);
+int qr_pt_adapt_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
+                           void *state_dev, int samples, int min_samples, int max_samples, float tol2,
+                           float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream);
+
+/*
  * Hit records: the closest hit of a ray AND the surface point the renderer would shade there -- hit point, normal, texture
  * colour, material.  What a host needs to bounce, reflect, offset or cosine-weight its own secondary rays (AO, light probes,
  * path tracing outside the renderer), and, per pixel of a camera, a G-buffer (position, normal, albedo, ids) for deferred passes

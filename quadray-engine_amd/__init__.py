@@ -23,7 +23,8 @@ ABI_SYMBOLS = [
     "qr_render_count", "qr_render_host", "qr_render_timed", "qr_trace_rays_async", "qr_occluded_async",
     "qr_shade_rays_async", "qr_render_views_async", "qr_render_views_mean_async",
     "qr_pt_views_state_bytes", "qr_pt_views_reset", "qr_pt_views_async",
-    "qr_pt_rays_state_bytes", "qr_pt_rays_reset", "qr_pt_rays_async", "qr_hit_rays_async", "qr_hit_views_async",
+    "qr_pt_rays_state_bytes", "qr_pt_rays_reset", "qr_pt_rays_async",
+    "qr_pt_adapt_state_bytes", "qr_pt_adapt_reset", "qr_pt_adapt_rays_async", "qr_hit_rays_async", "qr_hit_views_async",
     "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async", "qr_layer_rays_async", "qr_layer_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
@@ -42,6 +43,8 @@ PT_VIEWS_MAX_SAMPLES = 512  # QR_PT_VIEWS_MAX_SAMPLES: the most samples of one q
 PT_VIEWS_STATE_WORDS = 4    # QR_PT_VIEWS_STATE_WORDS: 32-bit planes per view of a path-traced view state
 PT_RAYS_MAX_SAMPLES = 512   # QR_PT_RAYS_MAX_SAMPLES: the most samples of one qr_pt_rays_async launch
 PT_RAYS_STATE_WORDS = 4     # QR_PT_RAYS_STATE_WORDS: 32-bit planes of a path-traced ray state
+PT_ADAPT_MAX_SAMPLES = 512  # QR_PT_ADAPT_MAX_SAMPLES: the most candidate samples of one qr_pt_adapt_rays_async launch
+PT_ADAPT_STATE_WORDS = 8    # QR_PT_ADAPT_STATE_WORDS: 32-bit planes of an adaptive path-traced ray state
 LAYER_MAX = 64              # QR_LAYER_MAX: the most layers of one qr_layer_*_async call
 
 
@@ -113,6 +116,9 @@ def lib():
     L.qr_pt_rays_state_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
     L.qr_pt_rays_reset.argtypes = [vp, ctypes.c_int64, vp]
     L.qr_pt_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ci, ci, vp, ctypes.c_uint32, vp]
+    L.qr_pt_adapt_state_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
+    L.qr_pt_adapt_reset.argtypes = [vp, ctypes.c_int64, vp]
+    L.qr_pt_adapt_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ci, ci, ci, ctypes.c_float, vp, vp, ctypes.c_uint32, vp]
     L.qr_hit_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_hit_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_uint32, vp]
     cf = ctypes.c_float
@@ -677,6 +683,13 @@ class Scene:
         samples=<count>: continue a checkpoint -- an int32 [4, n] tensor on the scene's device holding `samples` samples."""
         return PtRays(self, n, state, samples)
 
+    def pt_adaptive(self, n, min_samples, max_samples, tol, state=None):
+        """Adaptive path-traced samples for caller rays (qr_pt_adapt_rays_async): returns a PtAdaptive accumulator for `n` rays
+        that keeps a sample count and a noise estimate per ray and stops a ray once the standard error of its mean is at most
+        `tol` in every channel (linear colour units), between `min_samples` and `max_samples` samples per ray since the reset.
+        state=None: a new state tensor, reset.  state=<tensor>: continue from an int32 [8, n] tensor on the scene's device."""
+        return PtAdaptive(self, n, min_samples, max_samples, tol, state)
+
     def render_count(self, frame=None, stream=None):
         if frame is None:
             frame = self.new_frame()
@@ -843,6 +856,108 @@ class PtRays:
         if n > 0:
             self.samples += samples
         return rgb
+
+
+class PtAdaptive:
+    """An adaptive path-traced accumulation over caller rays (Scene.pt_adaptive; include/qrhip.h qr_pt_adapt_rays_async).
+
+    state: int32 [8, N] on the scene's device, ray i in column i -- plane 0 the generator states, planes 1..3 the float32
+    running means of r, g, b (as PtRays keeps them), plane 4 the number of samples the ray holds, planes 5..7 Welford's M2 of
+    r, g, b (float32 bits in int32 slots).  counts: a view of plane 4.  The state is all there is: the host may read it, edit
+    it, copy it and continue from it.  tol2: float32(tol) * float32(tol), the squared tolerance the stop rule uses
+    (rays.pt_adapt_open states the rule, rays.pt_adapt_fold the update).  A wave of 64 consecutive rays runs as long as its
+    slowest ray: sort or compact rays and state columns by what is still open between steps where that matters -- a ray's
+    result depends on nothing but its own column, ray and spread."""
+
+    def __init__(self, scene, n, min_samples, max_samples, tol, state=None):
+        import numpy as np
+        import torch
+        if not (isinstance(n, int) and n >= 0):
+            raise QrError("n must be the non-negative number of rays")
+        if not (isinstance(min_samples, int) and isinstance(max_samples, int)
+                and 0 <= min_samples <= max_samples and 1 <= max_samples < (1 << 24)):
+            raise QrError("min_samples and max_samples must be integers, 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24")
+        try:
+            t = np.float32(tol)
+        except (TypeError, ValueError):
+            raise QrError("tol must be a number") from None
+        with np.errstate(over="ignore", invalid="ignore"):
+            tol2 = t * t
+        if not (t >= 0 and np.isfinite(tol2)):
+            raise QrError("tol must be a finite number, 0 or more, whose square is finite in float32")
+        self.scene, self.n, self.min_samples, self.max_samples = scene, n, min_samples, max_samples
+        self.tol, self.tol2 = float(t), tol2
+        nbytes = ctypes.c_uint64()
+        _check(lib().qr_pt_adapt_state_bytes(scene._h, n, ctypes.byref(nbytes)))
+        shape = (PT_ADAPT_STATE_WORDS, n)
+        assert nbytes.value == 4 * PT_ADAPT_STATE_WORDS * n
+        if state is None:
+            self.state = torch.empty(shape, dtype=torch.int32, device=f"cuda:{scene.device}")
+            self.reset()
+        else:
+            if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == shape
+                    and state.is_contiguous() and state.is_cuda and state.device.index == scene.device):
+                raise QrError(f"state must be a contiguous int32 {list(shape)} tensor on cuda:{scene.device}")
+            self.state = state
+
+    @property
+    def counts(self):
+        """plane 4 of the state (a view): the number of samples every ray holds"""
+        return self.state[4]
+
+    def reset(self):
+        """Restart the accumulation: seeds as rays.pt_seeds(n, 1, 1), every other plane 0.  Synchronous (qr_pt_adapt_reset)."""
+        _check(lib().qr_pt_adapt_reset(self.scene._h, self.n, ctypes.c_void_p(self.state.data_ptr())))
+
+    def clone(self):
+        """A checkpoint: an accumulator with a copy of the state (on the current stream) that continues independently."""
+        return PtAdaptive(self.scene, self.n, self.min_samples, self.max_samples, self.tol, self.state.clone())
+
+    def step(self, rays, samples=1, spread=None, rgb=True, open=False, stream=None):
+        """Offer every ray up to `samples` (1 .. PT_ADAPT_MAX_SAMPLES) candidate samples in ONE launch; a ray takes them while the
+        stop rule on its own column lets it.  rays, spread and rgb as for PtRays.step; rgb holds the means of every ray, taken
+        or not.  open: False, True (a new one-element int32 tensor) or a one-element int32 / uint32 tensor on the scene's
+        device; step zeroes it on `stream` and the launch adds the number of rays that would still take a sample.  Returns rgb,
+        or (rgb, open) when open is wanted.  The scene's current depth applies.  Asynchronous on `stream`."""
+        import torch
+        n, dev = self.n, self.scene.device
+        rays = self.scene._rays_arg(rays)
+        if rays.shape[0] != n:
+            raise QrError(f"this accumulation holds {n} rays, got {rays.shape[0]}")
+        if spread is not None and not (isinstance(spread, torch.Tensor) and spread.dtype == torch.float32
+                                       and tuple(spread.shape) == (n, 8) and spread.is_contiguous() and spread.is_cuda
+                                       and spread.device.index == dev):
+            raise QrError(f"spread must be None or a contiguous float32 [{n}, 8] tensor on cuda:{dev} (du xyz, pad, dv xyz, pad per row)")
+        if rgb is True:
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+        elif rgb is False or rgb is None:
+            rgb = None
+        elif not (isinstance(rgb, torch.Tensor) and rgb.dtype == torch.float32 and tuple(rgb.shape) == (n, 3)
+                  and rgb.is_contiguous() and rgb.is_cuda and rgb.device.index == dev):
+            raise QrError(f"rgb must be True, False or a contiguous float32 [{n}, 3] tensor on cuda:{dev}")
+        opent = None
+        if open is True:
+            opent = torch.empty((1,), dtype=torch.int32, device=rays.device)
+        elif not (open is False or open is None):
+            if not (isinstance(open, torch.Tensor) and open.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
+                    and open.numel() == 1 and open.is_contiguous() and open.is_cuda and open.device.index == dev):
+                raise QrError(f"open must be True, False or a one-element int32 or uint32 tensor on cuda:{dev}")
+            opent = open
+        if not isinstance(samples, int):
+            raise QrError("samples must be an integer")
+        if not 1 <= samples <= PT_ADAPT_MAX_SAMPLES:
+            raise QrError(f"samples must be 1..{PT_ADAPT_MAX_SAMPLES}")
+        if opent is not None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                opent.zero_()
+        _check(lib().qr_pt_adapt_rays_async(self.scene._h, ctypes.c_void_p(rays.data_ptr()),
+                                            ctypes.c_void_p(spread.data_ptr() if spread is not None else None), n,
+                                            ctypes.c_void_p(self.state.data_ptr()), samples, self.min_samples, self.max_samples,
+                                            ctypes.c_float(float(self.tol2)),
+                                            ctypes.c_void_p(rgb.data_ptr() if rgb is not None else None),
+                                            ctypes.c_void_p(opent.data_ptr() if opent is not None else None), 0,
+                                            Scene._stream_ptr(stream)))
+        return (rgb, opent) if opent is not None else rgb
 
 
 class MultiRender:

@@ -724,6 +724,56 @@ extern "C" int qr_pt_rays_async(qr_device_scene *s, const qr_ray *rays_dev, cons
     return QR_OK;
 }
 
+/* ---- adaptive path-traced rays (qr_kernel.hpp qr_pt_adapt_kernel): per-ray counts, Welford's M2 and a stop rule on chip ---- */
+
+extern "C" int qr_pt_adapt_state_bytes(qr_device_scene *s, int64_t n, uint64_t *bytes_out)
+{
+    const int rc = pt_rays_dims(s, n);
+    if (rc != QR_OK) return rc;
+    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    *bytes_out = (uint64_t)n * QR_PT_ADAPT_STATE_WORDS * sizeof(uint32_t);
+    return QR_OK;
+}
+
+/* plane 0 as qr_pt_rays_reset writes it, every other plane 0: synchronous */
+extern "C" int qr_pt_adapt_reset(qr_device_scene *s, int64_t n, void *state_dev)
+{
+    const int rc = qr_pt_rays_reset(s, n, state_dev);
+    if (rc != QR_OK || n == 0) return rc;
+    HIP_TRY(hipMemset((uint32_t *)state_dev + QR_PT_RAYS_STATE_WORDS * (size_t)n, 0,
+                      (QR_PT_ADAPT_STATE_WORDS - QR_PT_RAYS_STATE_WORDS) * (size_t)n * sizeof(uint32_t)));
+    HIP_TRY(hipDeviceSynchronize());
+    return QR_OK;
+}
+
+extern "C" int qr_pt_adapt_rays_async(qr_device_scene *s, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
+                                      void *state_dev, int samples, int min_samples, int max_samples, float tol2,
+                                      float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream)
+{
+    const int rc = pt_rays_dims(s, n);
+    if (rc != QR_OK) return rc;
+    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown adaptive path-traced ray flags");
+    if (samples < 1 || samples > QR_PT_ADAPT_MAX_SAMPLES)
+        return qr_fail(QR_ERR_ARG, "samples must be 1.." + std::to_string(QR_PT_ADAPT_MAX_SAMPLES));
+    if (min_samples < 0 || max_samples < 1 || min_samples > max_samples || max_samples >= (1 << 24))
+        return qr_fail(QR_ERR_ARG, "min_samples and max_samples must be 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24 (the count is exact in fp32)");
+    if (!(tol2 >= 0.0f) || tol2 > FLT_MAX) return qr_fail(QR_ERR_ARG, "tol2 must be a finite number, 0 or more");
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    if (n == 0) return QR_OK;
+    if (rays_dev == nullptr || state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if ((((uintptr_t)rays_dev | (uintptr_t)spread_dev) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays and spread must be 16-byte aligned");
+    if ((((uintptr_t)state_dev | (uintptr_t)rgb_dev | (uintptr_t)open_dev) & 3u) != 0)
+        return qr_fail(QR_ERR_ARG, "state, rgb and open must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    PtRaysP pr;
+    pr.rays = (const f32x4 *)rays_dev; pr.spread = (const f32x4 *)spread_dev; pr.n = (int32_t)n; pr.pad = 0; pr.rgb = rgb_dev;
+    hipLaunchKernelGGL(qr_pt_adapt_kernel, grid, block, 0, (hipStream_t)stream, s->lp, pr, (uint32_t *)state_dev, samples,
+                       min_samples, max_samples, tol2, open_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
 /* ---- hit records (qr_hitrec.hpp): the closest hit of qr_trace_rays_async and the surface point shading would use there ---- */
 
 extern "C" int qr_hit_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,

@@ -317,19 +317,22 @@ __device__ __forceinline__ bool pixel_of_view(u32 ord, int fsaa, const ViewsP &v
  * tent filter's values.  Rays are never taken as neighbours (the first round is RAYS = 1's), there is no empty-tile exit, no
  * priority schedule, no id and no depth; state and colour travel as for RAYS = 5 (`rng_io`, `mean_out`), and a lane past n draws
  * nothing.
+ * RAYS = 7 (adaptive path-traced rays, qr_pt_adapt_kernel; PT = true): RAYS = 6 with one difference: a lane is inside only when
+ * its ray also takes this sample (`take`, the stop rule of include/qrhip.h evaluated by the caller's loop).  A lane that does not
+ * is a lane past n: it draws nothing, walks nothing and stays out of every ballot.
  */
 template <bool COUNT, bool DIVK, bool PT = false, int RAYS = 0>
 __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, const u32 sched_head, const int gw,
                                             uint32_t *__restrict__ frame, int32_t *__restrict__ ids,
                                             unsigned long long *__restrict__ counters, const PtParams *ptp = nullptr,
                                             const RaysP *rp = nullptr, const ViewsP *vp = nullptr, V3 *mean_out = nullptr,
-                                            u32 *rng_io = nullptr, const PtRaysP *pr = nullptr)
+                                            u32 *rng_io = nullptr, const PtRaysP *pr = nullptr, const bool take = true)
 {
     constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3 || RAYS == 4 || RAYS == 5, MEAN = RAYS == 4;
-    constexpr bool PTV = RAYS == 5, PTR = RAYS == 6;
+    constexpr bool PTV = RAYS == 5, PTR = RAYS == 6 || RAYS == 7, PTA = RAYS == 7;
     static_assert(!PTV || PT, "the path-traced view instance is a path-tracer instance");
     static_assert(!PTR || PT, "the path-traced ray instance is a path-tracer instance");
-    (void)mean_out; (void)rng_io; (void)pr;
+    (void)mean_out; (void)rng_io; (void)pr; (void)take;
 #ifdef QR_WAVETIME
     const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
     const unsigned long long wt_clk0 = __builtin_amdgcn_s_memtime();      /* shader cycles: with the 100 MHz stamps, the clock the wave ran at */
@@ -375,6 +378,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     bool inside;
     if constexpr (VIEW) inside = x < frm_w && y < vp->height;      /* the grid is the frame's footprints: every wave holds a pixel */
     else if constexpr (CALLER_RAYS) inside = (u32)gw * 64u + (u32)lane < (u32)rp->n;      /* n > 0: every wave holds a ray */
+    else if constexpr (PTA) inside = (u32)gw * 64u + (u32)lane < (u32)pr->n && take;
     else if constexpr (PTR) inside = (u32)gw * 64u + (u32)lane < (u32)pr->n;
     else
     {
@@ -615,7 +619,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
                 if (prio_round < 3) { prio_round++; if (prio_round == 2) __builtin_amdgcn_s_setprio(2); else if (prio_round == 3) __builtin_amdgcn_s_setprio(3); }
 #endif
             /* coherent: every ray of this round is a primary ray (neighbouring pixels; caller rays only when vouched for) */
-            const bool coherent = (RAYS != 1 && RAYS != 6) && !any_lane(tr && sp != 0);
+            const bool coherent = (RAYS != 1 && RAYS != 6 && RAYS != 7) && !any_lane(tr && sp != 0);
             traverse<false, DIVK, RAYS != 0>(B, tr, coherent, ray, h, occ
 #ifdef QR_STATS
                             , cx.stats
@@ -1204,6 +1208,105 @@ void qr_pt_rays_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, int done
         state[i_e] = lds_rng[lane_e];
         state[n + i_e] = f2u(m.x); state[2 * n + i_e] = f2u(m.y); state[3 * n + i_e] = f2u(m.z);
         if (pr.rgb != nullptr) { pr.rgb[3 * i_e] = m.x; pr.rgb[3 * i_e + 1] = m.y; pr.rgb[3 * i_e + 2] = m.z; }
+    }
+}
+
+/*
+ * Adaptive path-traced rays (qr_pt_adapt_rays_async): qr_pt_rays_kernel with a sample count and a noise estimate per ray and a
+ * stop rule evaluated on chip.  state: eight planes of n 32-bit words -- the LCG states, the running means of r, g, b, the count
+ * m of samples the ray holds, Welford's M2 (sum of squared deviations) of r, g, b -- ray i is column i (include/qrhip.h).  All
+ * eight words are read once and wait in LDS (2 KB per wave); nothing of them is live in registers through a sample but the
+ * generator's state.  Before every candidate sample each lane evaluates the rule on its own column:
+ *     take = m < max && (m < min || m < 2 || !(M2r <= lim && M2g <= lim && M2b <= lim)),  lim = ((float)m * (float)(m - 1)) * tol2
+ * (per-lane data, so vector compares; only the ballot is scalar).  A lane that does not take a candidate takes none later in the
+ * launch -- its column did not change -- and is out of the sample like a lane past n (render_wave RAYS = 7); the wave leaves the
+ * loop when no lane is left, so a wave runs as long as its slowest ray.  The update is Welford's, one fp32 operation per step
+ * (-ffp-contract=off), the division IEEE.  The state is written back once, by the lanes that took a sample (their count is no
+ * longer the one in memory: no flag is carried through the samples); rgb by every lane
+ * below n; `open` gets ONE vector atomic add per wave, from its first lane, of the number of lanes the rule on the final
+ * state still lets take, and none when that number is 0.
+ */
+__global__ __launch_bounds__(QR_BLOCK, 3)
+void qr_pt_adapt_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, int samples, int min_samples, int max_samples, float tol2,
+                        u32 *__restrict__ open)
+{
+    const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    __shared__ u32 lds_st[QR_PT_ADAPT_STATE_WORDS][64];
+    const size_t n = (size_t)(u32)pr.n;
+    const int lane = (int)(threadIdx.x & 63u);
+    const size_t i = (size_t)(u32)gw * 64u + (size_t)lane;
+    /* lanes past n hold m = max_samples: the rule never lets them take */
+    {
+        u32 w[QR_PT_ADAPT_STATE_WORDS] = {0u, 0u, 0u, 0u, (u32)max_samples, 0u, 0u, 0u};
+        if (i < n)
+        {
+#pragma unroll
+            for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) w[p] = state[(size_t)p * n + i];
+        }
+#pragma unroll
+        for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) lds_st[p][lane] = w[p];
+    }
+    auto rule = [&](int l) -> bool {
+        /* four LDS reads, then vector compares whose lane masks are combined as scalars: no branch */
+        const u32 m = lds_st[4][l];
+        const float m2r = u2f(lds_st[5][l]), m2g = u2f(lds_st[6][l]), m2b = u2f(lds_st[7][l]);
+        float lim = (float)m * (float)(m - 1u);
+        lim = lim * tol2;
+        const bool conv = m2r <= lim && m2g <= lim && m2b <= lim;
+        return m < (u32)max_samples && (m < (u32)min_samples || m < 2u || !conv);
+    };
+#pragma nounroll
+    for (int s = 0; s < samples; s++)
+    {
+        int lane_s = (int)(threadIdx.x & 63u);
+        asm volatile("" : "+v"(lane_s));            /* not an address register kept alive through the sample */
+        const bool take = rule(lane_s);
+        if (!any_lane(take)) break;
+        u32 rng = lds_st[0][lane_s];
+        V3 c;
+        render_wave<false, false, true, 7>(lp, 0u, 0u, gw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &c, &rng, &pr, take);
+        asm volatile("" : "+v"(lane_s));
+        if (take)
+        {
+            const u32 m = lds_st[4][lane_s] + 1u;
+            const float o = 1.0f / (float)m, u = 1.0f - o;
+            lds_st[4][lane_s] = m;
+            lds_st[0][lane_s] = rng;
+            const float col[3] = {c.x, c.y, c.z};
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++)
+            {
+                const float mean = u2f(lds_st[1 + ch][lane_s]);
+                const float d1 = col[ch] - mean;
+                const float a = col[ch] * o, b = mean * u;
+                const float mn = a + b;
+                const float d2 = col[ch] - mn;
+                const float p = d1 * d2;
+                lds_st[1 + ch][lane_s] = f2u(mn);
+                lds_st[5 + ch][lane_s] = f2u(u2f(lds_st[5 + ch][lane_s]) + p);
+            }
+        }
+    }
+    int lane_e = (int)(threadIdx.x & 63u);
+    asm volatile("" : "+v"(lane_e));
+    const size_t i_e = (size_t)(u32)gw * 64u + (size_t)lane_e;
+    if (i_e < n)
+    {
+        /* a ray that took a sample holds more than it came with: the count in memory says which columns to write */
+        if (lds_st[4][lane_e] != state[4 * n + i_e])
+        {
+#pragma unroll
+            for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) state[(size_t)p * n + i_e] = lds_st[p][lane_e];
+        }
+        if (pr.rgb != nullptr)
+        {
+            pr.rgb[3 * i_e] = u2f(lds_st[1][lane_e]); pr.rgb[3 * i_e + 1] = u2f(lds_st[2][lane_e]); pr.rgb[3 * i_e + 2] = u2f(lds_st[3][lane_e]);
+        }
+    }
+    if (open != nullptr)
+    {
+        const unsigned long long still = __ballot(rule(lane_e));
+        if (still != 0ull && lane_e == 0) atomicAdd(open, (u32)__popcll(still));
     }
 }
 

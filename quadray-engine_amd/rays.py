@@ -45,6 +45,15 @@ pt_view_rays gives the rays ONE path-traced sample of a pinhole view traces (Sce
     acc = scn.pt_rays(n)                            # state: seeds of slots 0 .. n - 1, means 0
     rgb = acc.step(rays, samples=16, spread=spread) # float32 [n, 3]: running means after 16 samples, before any clamp
     rgb = acc.step(other_rays, samples=4)           # the state belongs to the accumulation, not to a ray set
+
+Scene.pt_adaptive is pt_rays with a sample count and a noise estimate per ray (include/qrhip.h qr_pt_adapt_rays_async): the state
+is int32 [8, N] -- pt_rays' four planes, then the count m and Welford's M2 of r, g, b -- and a stop rule on that column decides
+before every sample whether the ray takes it.  pt_adapt_open states the rule and pt_adapt_fold the update, in float32 numpy:
+
+    acc = scn.pt_adaptive(n, min_samples=4, max_samples=64, tol=0.01)
+    while True:
+        rgb, still = acc.step(rays, samples=8, spread=spread, open=True)    # up to 8 more samples where the rule asks for them
+        if int(still) == 0: break                                            # acc.counts: samples per ray
 """
 import struct
 
@@ -419,6 +428,75 @@ def pt_view_rays(view, width, height, blob, states):
     out[:, 3] = vw[3]
     out[:, 7] = vw[7]
     return out, st
+
+
+# ---- adaptive path-traced rays (include/qrhip.h qr_pt_adapt_rays_async; Scene.pt_adaptive): the rule and the update in numpy ----
+
+def _pt_adapt_state(state):
+    st = np.ascontiguousarray(state)
+    if st.ndim != 2 or st.shape[0] != 8 or st.dtype.itemsize != 4:
+        raise ValueError("an adaptive state is [8, N] of 32-bit words")
+    return st.view(np.uint32)
+
+
+def pt_adapt_open(state, min_samples, max_samples, tol2):
+    """The stop rule of qr_pt_adapt_rays_async on a state [8, N] (uint32 or int32): bool [N], True where the ray would take one
+    more sample.  Per ray, with m = plane 4 (unsigned) and M2 = planes 5..7 (float32):
+        lim = float32(m) * float32(m - 1);  lim = lim * tol2                 (two fp32 multiplies; m - 1 wraps for m = 0, unused)
+        conv = M2r <= lim and M2g <= lim and M2b <= lim                      (a NaN never converges)
+        take = m < max_samples and (m < min_samples or m < 2 or not conv)"""
+    st = _pt_adapt_state(state)
+    m = st[4]
+    with np.errstate(over="ignore", invalid="ignore"):
+        lim = m.astype(np.float32) * (m - np.uint32(1)).astype(np.float32)
+        lim = lim * np.float32(tol2)
+        m2 = st[5:8].view(np.float32)
+        conv = (m2[0] <= lim) & (m2[1] <= lim) & (m2[2] <= lim)
+    return (m < np.uint32(max_samples)) & ((m < np.uint32(min_samples)) | (m < np.uint32(2)) | ~conv)
+
+
+def pt_adapt_fold(state, cols, rngs, min_samples, max_samples, tol2):
+    """The specification of one qr_pt_adapt_rays_async call, given what every candidate sample WOULD give: cols float32 [N, S, 3],
+    the colours of the S consecutive samples of every ray from the state's generator word, and rngs uint32 [N, S], the generator
+    word after each.  A ray's candidate sequence does not depend on how many it takes -- it keeps a prefix -- so this is exact.
+    Before each candidate the rule (pt_adapt_open) decides; a ray that takes it is updated, one IEEE fp32 operation per step:
+        m = m + 1;  o = 1 / float32(m);  u = 1 - o
+        per channel:  d1 = col - mean;  a = col * o;  b = mean * u;  mean = a + b;  d2 = col - mean;  p = d1 * d2;  M2 = M2 + p
+        plane 0 = the generator word after the sample
+    Returns (state' uint32 [8, N], rgb float32 [N, 3] = the means of every ray, open = the number of rays the rule would still
+    let take a sample on state')."""
+    st = _pt_adapt_state(state).copy()
+    n = st.shape[1]
+    cols = np.asarray(cols, dtype=np.float32)
+    rngs = np.asarray(rngs, dtype=np.uint32)
+    if cols.ndim != 3 or cols.shape[0] != n or cols.shape[2] != 3 or rngs.shape != cols.shape[:2]:
+        raise ValueError("pt_adapt_fold needs cols [N, S, 3] and rngs [N, S] for a state [8, N]")
+    one = np.float32(1.0)
+    mean, m2 = st[1:4].view(np.float32), st[5:8].view(np.float32)
+    taken = np.zeros(n, dtype=np.int64)                 # candidates taken so far in this call: a prefix
+    with np.errstate(over="ignore", invalid="ignore"):
+        for s in range(cols.shape[1]):
+            t = np.nonzero(pt_adapt_open(st, min_samples, max_samples, tol2) & (taken == s))[0]
+            if len(t) == 0:
+                break
+            taken[t] += 1
+            m = st[4, t] + np.uint32(1)
+            o = one / m.astype(np.float32)
+            u = one - o
+            for ch in range(3):
+                c, mu = cols[t, s, ch], mean[ch, t]
+                d1 = c - mu
+                a = c * o
+                b = mu * u
+                mu = a + b
+                d2 = c - mu
+                p = d1 * d2
+                mean[ch, t] = mu
+                m2[ch, t] = m2[ch, t] + p
+            st[4, t] = m
+            st[0, t] = rngs[t, s]
+    rgb = np.ascontiguousarray(mean.T).copy()
+    return st, rgb, int(pt_adapt_open(st, min_samples, max_samples, tol2).sum())
 
 
 # ---- hit records (include/qrhip.h qr_hit; Scene.hits, Scene.view_hits): float32 [..., 12] = pos xyz, t, nrm xyz, id, alb xyz, mat ----

@@ -14,6 +14,7 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
   * the path-traced view kernel qr_pt_views_kernel exceeds 168 VGPRs (3 waves per SIMD, its launch bound), spills a vector
     register or has a larger private segment than the scene's own path-tracer kernel (2128 B);
   * the path-traced ray kernel qr_pt_rays_kernel exceeds that same budget;
+  * the adaptive path-traced ray kernel qr_pt_adapt_kernel exceeds that same budget;
   * a hit-record instance qr_hit_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more than
     168 VGPRs (128: the view instance with packet walks only);
   * an occlusion-fan instance qr_fan_kernel<SRC, DIVK, COHERENT> spills a vector register, has a private segment, or uses more
@@ -54,6 +55,8 @@ LIMITS = {
     "18qr_pt_views_kernel7LaunchP": (168, 0, 2128),
     # path-traced rays (qr_kernel.hpp qr_pt_rays_kernel): the same instance and sample loop on caller rays: the same budget
     "17qr_pt_rays_kernel": (168, 0, 2128),
+    # adaptive path-traced rays (qr_kernel.hpp qr_pt_adapt_kernel): that kernel with per-ray counts and a stop rule: the same budget
+    "18qr_pt_adapt_kernel": (168, 0, 2128),
     # hit records (qr_hitrec.hpp qr_hit_kernel<VIEW, DIVK, COHERENT>): a walk and one surface point, no recursion: nothing spilled and
     # no private segment at all; caller rays and views of scenes with long lists at the closest-hit query's 168 registers, views of
     # the others at the packet instances' 128
