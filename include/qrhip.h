@@ -526,8 +526,8 @@ int qr_pt_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, const qr_ray_
  *     under the same rule evaluated on the final state: one vector atomic add per wave, from one lane, of the ballot's
  *     population count; waves with a count of 0 skip it.  A host loops "step until open == 0" without reading the state back.
  *   - Cost: one wave holds 64 consecutive rays and runs as long as its slowest ray; the others' lanes idle.  That is inherent
- *     to one wave per 64 rays.  What a caller can do: sort or compact the rays (with their state columns) by whether they are
- *     still open between calls -- consequence (c) makes that exact.
+ *     to one wave per 64 rays.  What a caller does about it: qr_pt_adapt_open_list_async lists the open rays on chip and
+ *     qr_pt_adapt_list_rays_async steps the listed rays, 64 of them per wave (below) -- consequence (c) makes that exact.
  *   - QR_ERR_ARG: samples outside 1 .. QR_PT_ADAPT_MAX_SAMPLES; min_samples < 0, max_samples < 1, min_samples > max_samples or
  *     max_samples >= 2^24 (the count is exact in fp32); tol2 negative, NaN or infinite; any flag (none is defined); a null
  *     rays_dev or state_dev; rays_dev or spread_dev not 16-byte aligned; state_dev, rgb_dev or open_dev not 4-byte aligned;
@@ -542,6 +542,51 @@ int qr_pt_adapt_reset(qr_device_scene *scn, int64_t n, void *state_dev);
 int qr_pt_adapt_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
                            void *state_dev, int samples, int min_samples, int max_samples, float tol2,
                            float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream);
+
+/*
+ * Open lists and indexed adaptive steps: compaction on chip.  qr_pt_adapt_open_list_async writes the indices of the rays the stop
+ * rule would still let take a sample; qr_pt_adapt_list_rays_async is qr_pt_adapt_rays_async on the rays of such a list, 64 LISTED
+ * rays per wave instead of 64 consecutive ones, so that waves hold open rays only.  By consequence (c) above the state after
+ * "list, then indexed step" is bit for bit the state after the plain step.  Nothing is read back to the host in between.
+ *   qr_pt_adapt_open_list_async
+ *   - evaluates the rule of qr_pt_adapt_rays_async (the `take` expression above; rays.py pt_adapt_open) on every column of
+ *     state_dev and writes index_dev[0 .. count) = the indices of the open rays in ASCENDING order, *count_dev = their number:
+ *     np.flatnonzero(pt_adapt_open(state)) (rays.py pt_adapt_open_list).  index_dev has room for n entries; the entries from
+ *     count on are NOT written.  The state is only read.
+ *   - The list is a function of the state alone -- no atomic append, the same bytes every time -- and no workgroup waits for
+ *     another: three launches on `stream` (a count per block of QR_PT_OPEN_BLOCK rays; one workgroup that turns the counts into
+ *     offsets, QR_PT_OPEN_CHUNK at a time, and stores the total; a scatter by block offset, wave offset and the lane's rank in
+ *     its wave's ballot).
+ *   - work_dev: qr_pt_adapt_list_work_bytes(n) bytes of 4-byte words (one per block), the caller's; its contents after the call
+ *     are unspecified.  The same buffer may serve every call on one stream.
+ *   qr_pt_adapt_list_rays_async
+ *   - List position p is served iff p < min(cap, *count_dev).  *count_dev is read ON CHIP when the launch runs: the count an
+ *     open list wrote earlier on the stream, or any word the caller set.  cap is the host's upper bound on it and sizes the grid
+ *     (min(cap, n) / 64 waves, rounded up; a wave whose first position is not below the count leaves at once): the `open` a host
+ *     read back after a step is exactly the next open list's length; a host that knows nothing passes n.
+ *   - The ray at position p is i = index_dev[p]: its qr_ray, its spread row, its state column and its rgb row are all addressed
+ *     by i; n is the size of those arrays as in the plain call.  An entry i >= n is skipped: nothing is read or written for it.
+ *     Entries must be distinct; a duplicate leaves that column's state unspecified and harms nothing else.
+ *   - Everything else is the contract above, unchanged: the rule before every candidate, one qr_pt_rays_async sample when taken,
+ *     Welford's update one fp32 operation per step, a column written back only when its count changed, samples = a + b the bits
+ *     of two calls.
+ *   - rgb_dev, if given, receives the means of the LISTED rays only; the rows of the others are not written.  open_dev, if given
+ *     (the caller zeroes it), receives the number of listed rays the rule still lets take on the final state.
+ *   - The list is any list, not only an open list: a region of interest, a permutation, a single ray.
+ *   - Refusals: every one of qr_pt_adapt_rays_async (the open list has no samples argument); and QR_ERR_ARG for a null index_dev,
+ *     count_dev or work_dev, any of them not 4-byte aligned, cap < 0, any flag.  A refused call launches nothing and changes
+ *     nothing.  n == 0 or cap == 0 returns QR_OK without a launch -- an open list of n == 0 rays does not write *count_dev.
+ */
+#define QR_PT_OPEN_BLOCK 1024            /* rays per workgroup of the list kernels: 16 waves */
+#define QR_PT_OPEN_CHUNK 1024            /* block counts one pass of the scan workgroup takes */
+int qr_pt_adapt_list_work_bytes(qr_device_scene *scn, int64_t n, uint64_t *bytes_out);
+int qr_pt_adapt_open_list_async(qr_device_scene *scn, const void *state_dev, int64_t n,
+                                int min_samples, int max_samples, float tol2,
+                                uint32_t *index_dev, uint32_t *count_dev, void *work_dev, uint32_t flags, void *stream);
+int qr_pt_adapt_list_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
+                                void *state_dev, const uint32_t *index_dev, const uint32_t *count_dev, int64_t cap,
+                                int samples, int min_samples, int max_samples, float tol2,
+                                float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream);
 
 /*
  * Hit records: the closest hit of a ray AND the surface point the renderer would shade there -- hit point, normal, texture

@@ -24,7 +24,8 @@ ABI_SYMBOLS = [
     "qr_shade_rays_async", "qr_render_views_async", "qr_render_views_mean_async",
     "qr_pt_views_state_bytes", "qr_pt_views_reset", "qr_pt_views_async",
     "qr_pt_rays_state_bytes", "qr_pt_rays_reset", "qr_pt_rays_async",
-    "qr_pt_adapt_state_bytes", "qr_pt_adapt_reset", "qr_pt_adapt_rays_async", "qr_hit_rays_async", "qr_hit_views_async",
+    "qr_pt_adapt_state_bytes", "qr_pt_adapt_reset", "qr_pt_adapt_rays_async",
+    "qr_pt_adapt_list_work_bytes", "qr_pt_adapt_open_list_async", "qr_pt_adapt_list_rays_async", "qr_hit_rays_async", "qr_hit_views_async",
     "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async", "qr_layer_rays_async", "qr_layer_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
@@ -45,6 +46,8 @@ PT_RAYS_MAX_SAMPLES = 512   # QR_PT_RAYS_MAX_SAMPLES: the most samples of one qr
 PT_RAYS_STATE_WORDS = 4     # QR_PT_RAYS_STATE_WORDS: 32-bit planes of a path-traced ray state
 PT_ADAPT_MAX_SAMPLES = 512  # QR_PT_ADAPT_MAX_SAMPLES: the most candidate samples of one qr_pt_adapt_rays_async launch
 PT_ADAPT_STATE_WORDS = 8    # QR_PT_ADAPT_STATE_WORDS: 32-bit planes of an adaptive path-traced ray state
+PT_OPEN_BLOCK = 1024        # QR_PT_OPEN_BLOCK: rays per workgroup of the open-list kernels
+PT_OPEN_CHUNK = 1024        # QR_PT_OPEN_CHUNK: block counts one pass of the open list's scan workgroup takes
 LAYER_MAX = 64              # QR_LAYER_MAX: the most layers of one qr_layer_*_async call
 
 
@@ -119,6 +122,10 @@ def lib():
     L.qr_pt_adapt_state_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
     L.qr_pt_adapt_reset.argtypes = [vp, ctypes.c_int64, vp]
     L.qr_pt_adapt_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ci, ci, ci, ctypes.c_float, vp, vp, ctypes.c_uint32, vp]
+    L.qr_pt_adapt_list_work_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
+    L.qr_pt_adapt_open_list_async.argtypes = [vp, vp, ctypes.c_int64, ci, ci, ctypes.c_float, vp, vp, vp, ctypes.c_uint32, vp]
+    L.qr_pt_adapt_list_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, ci, ci, ci, ctypes.c_float,
+                                              vp, vp, ctypes.c_uint32, vp]
     L.qr_hit_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.qr_hit_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_uint32, vp]
     cf = ctypes.c_float
@@ -866,8 +873,9 @@ class PtAdaptive:
     r, g, b (float32 bits in int32 slots).  counts: a view of plane 4.  The state is all there is: the host may read it, edit
     it, copy it and continue from it.  tol2: float32(tol) * float32(tol), the squared tolerance the stop rule uses
     (rays.pt_adapt_open states the rule, rays.pt_adapt_fold the update).  A wave of 64 consecutive rays runs as long as its
-    slowest ray: sort or compact rays and state columns by what is still open between steps where that matters -- a ray's
-    result depends on nothing but its own column, ray and spread."""
+    slowest ray; open_list() writes the indices of the rays still open, on the device, and step(..., index=, count=) serves 64
+    listed rays per wave instead -- a ray's result depends on nothing but its own column, ray and spread, so the state is bit
+    for bit the plain step's (rays.pt_adapt_open_list, rays.pt_adapt_fold_list)."""
 
     def __init__(self, scene, n, min_samples, max_samples, tol, state=None):
         import numpy as np
@@ -887,6 +895,7 @@ class PtAdaptive:
             raise QrError("tol must be a finite number, 0 or more, whose square is finite in float32")
         self.scene, self.n, self.min_samples, self.max_samples = scene, n, min_samples, max_samples
         self.tol, self.tol2 = float(t), tol2
+        self._list_work = self._list_index = self._list_count = None
         nbytes = ctypes.c_uint64()
         _check(lib().qr_pt_adapt_state_bytes(scene._h, n, ctypes.byref(nbytes)))
         shape = (PT_ADAPT_STATE_WORDS, n)
@@ -913,14 +922,67 @@ class PtAdaptive:
         """A checkpoint: an accumulator with a copy of the state (on the current stream) that continues independently."""
         return PtAdaptive(self.scene, self.n, self.min_samples, self.max_samples, self.tol, self.state.clone())
 
-    def step(self, rays, samples=1, spread=None, rgb=True, open=False, stream=None):
+    def _list_arg(self, t, shape, what):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
+                and tuple(t.shape) == shape and t.is_contiguous() and t.is_cuda and t.device.index == self.scene.device):
+            raise QrError(f"{what} must be a contiguous int32 or uint32 {list(shape)} tensor on cuda:{self.scene.device}")
+        return t
+
+    def open_list(self, index=None, count=None, stream=None):
+        """The open list of the state (qr_pt_adapt_open_list_async): index[:count] = the indices of the rays the stop rule would
+        still let take a sample, ascending; index[count:] is not written.  Returns (index int32 [n], count int32 [1]), the
+        accumulator's own tensors (allocated on first use, written again by every call) or the caller's.  Nothing is read back:
+        hand both to step(..., index=, count=).  The work buffer belongs to the accumulator.  Asynchronous on `stream`."""
+        import torch
+        n, dev = self.n, f"cuda:{self.scene.device}"
+        if index is None:
+            if self._list_index is None:
+                self._list_index = torch.empty((n,), dtype=torch.int32, device=dev)
+            index = self._list_index
+        if count is None:
+            if self._list_count is None:
+                self._list_count = torch.zeros((1,), dtype=torch.int32, device=dev)
+            count = self._list_count
+        index, count = self._list_arg(index, (n,), "index"), self._list_arg(count, (1,), "count")
+        if self._list_work is None:
+            nbytes = ctypes.c_uint64()
+            _check(lib().qr_pt_adapt_list_work_bytes(self.scene._h, n, ctypes.byref(nbytes)))
+            self._list_work = torch.empty((max(1, nbytes.value // 4),), dtype=torch.int32, device=dev)
+        _check(lib().qr_pt_adapt_open_list_async(self.scene._h, ctypes.c_void_p(self.state.data_ptr()), n, self.min_samples,
+                                                 self.max_samples, ctypes.c_float(float(self.tol2)),
+                                                 ctypes.c_void_p(index.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                                 ctypes.c_void_p(self._list_work.data_ptr()), 0, Scene._stream_ptr(stream)))
+        return index, count
+
+    def step(self, rays, samples=1, spread=None, rgb=True, open=False, stream=None, index=None, count=None, cap=None):
         """Offer every ray up to `samples` (1 .. PT_ADAPT_MAX_SAMPLES) candidate samples in ONE launch; a ray takes them while the
         stop rule on its own column lets it.  rays, spread and rgb as for PtRays.step; rgb holds the means of every ray, taken
         or not.  open: False, True (a new one-element int32 tensor) or a one-element int32 / uint32 tensor on the scene's
         device; step zeroes it on `stream` and the launch adds the number of rays that would still take a sample.  Returns rgb,
-        or (rgb, open) when open is wanted.  The scene's current depth applies.  Asynchronous on `stream`."""
+        or (rgb, open) when open is wanted.  The scene's current depth applies.  Asynchronous on `stream`.
+        index, count: step the LISTED rays only (qr_pt_adapt_list_rays_async), 64 list entries per wave -- index an int32 or
+        uint32 tensor of ray indices on the scene's device (open_list()'s, or any list of distinct indices; an entry >= n is
+        skipped), count a one-element tensor there holding the list's length, which is read on the device.  cap: the host's upper
+        bound on that length, at most len(index); it sizes the launch and defaults to n or len(index), whichever is less; the
+        `open` read back after a step is the next open list's length.  The first min(cap, count) entries are served.  rgb rows
+        of unlisted rays are NOT written; open counts listed rays only.  The state is bit for bit what the plain step gives on
+        the listed columns; the others are untouched."""
         import torch
         n, dev = self.n, self.scene.device
+        if index is None:
+            if count is not None or cap is not None:
+                raise QrError("count and cap belong to a list: pass index")
+        else:
+            if count is None:
+                raise QrError("index needs count: a one-element tensor holding the list's length (open_list() returns both)")
+            if not (isinstance(index, torch.Tensor) and index.dim() == 1):
+                raise QrError(f"index must be a contiguous int32 or uint32 [length] tensor on cuda:{dev}")
+            index, count = self._list_arg(index, (index.shape[0],), "index"), self._list_arg(count, (1,), "count")
+            if cap is None:
+                cap = min(n, index.shape[0])
+            if not (isinstance(cap, int) and 0 <= cap <= index.shape[0]):
+                raise QrError(f"cap must be an integer, 0..{index.shape[0]}: it bounds the entries of index that are read")
         rays = self.scene._rays_arg(rays)
         if rays.shape[0] != n:
             raise QrError(f"this accumulation holds {n} rays, got {rays.shape[0]}")
@@ -950,6 +1012,16 @@ class PtAdaptive:
         if opent is not None:
             with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
                 opent.zero_()
+        if index is not None:
+            _check(lib().qr_pt_adapt_list_rays_async(self.scene._h, ctypes.c_void_p(rays.data_ptr()),
+                                                     ctypes.c_void_p(spread.data_ptr() if spread is not None else None), n,
+                                                     ctypes.c_void_p(self.state.data_ptr()), ctypes.c_void_p(index.data_ptr()),
+                                                     ctypes.c_void_p(count.data_ptr()), cap, samples, self.min_samples,
+                                                     self.max_samples, ctypes.c_float(float(self.tol2)),
+                                                     ctypes.c_void_p(rgb.data_ptr() if rgb is not None else None),
+                                                     ctypes.c_void_p(opent.data_ptr() if opent is not None else None), 0,
+                                                     Scene._stream_ptr(stream)))
+            return (rgb, opent) if opent is not None else rgb
         _check(lib().qr_pt_adapt_rays_async(self.scene._h, ctypes.c_void_p(rays.data_ptr()),
                                             ctypes.c_void_p(spread.data_ptr() if spread is not None else None), n,
                                             ctypes.c_void_p(self.state.data_ptr()), samples, self.min_samples, self.max_samples,

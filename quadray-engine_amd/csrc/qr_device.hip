@@ -12,6 +12,7 @@
 #include "qr_hitrec.hpp"
 #include "qr_fan.hpp"
 #include "qr_layers.hpp"
+#include "qr_openlist.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -746,9 +747,9 @@ extern "C" int qr_pt_adapt_reset(qr_device_scene *s, int64_t n, void *state_dev)
     return QR_OK;
 }
 
-extern "C" int qr_pt_adapt_rays_async(qr_device_scene *s, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
-                                      void *state_dev, int samples, int min_samples, int max_samples, float tol2,
-                                      float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream)
+/* the checks the adaptive launches share, in the order their refusals are documented: scene and count, flags, samples (the open
+ * list has none: it passes 1), the rule's parameters, the ray-query list */
+static int pt_adapt_args(const qr_device_scene *s, int64_t n, int samples, int min_samples, int max_samples, float tol2, uint32_t flags)
 {
     const int rc = pt_rays_dims(s, n);
     if (rc != QR_OK) return rc;
@@ -759,6 +760,15 @@ extern "C" int qr_pt_adapt_rays_async(qr_device_scene *s, const qr_ray *rays_dev
         return qr_fail(QR_ERR_ARG, "min_samples and max_samples must be 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24 (the count is exact in fp32)");
     if (!(tol2 >= 0.0f) || tol2 > FLT_MAX) return qr_fail(QR_ERR_ARG, "tol2 must be a finite number, 0 or more");
     if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    return QR_OK;
+}
+
+extern "C" int qr_pt_adapt_rays_async(qr_device_scene *s, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
+                                      void *state_dev, int samples, int min_samples, int max_samples, float tol2,
+                                      float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream)
+{
+    const int rc = pt_adapt_args(s, n, samples, min_samples, max_samples, tol2, flags);
+    if (rc != QR_OK) return rc;
     if (n == 0) return QR_OK;
     if (rays_dev == nullptr || state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
     if ((((uintptr_t)rays_dev | (uintptr_t)spread_dev) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays and spread must be 16-byte aligned");
@@ -770,6 +780,67 @@ extern "C" int qr_pt_adapt_rays_async(qr_device_scene *s, const qr_ray *rays_dev
     pr.rays = (const f32x4 *)rays_dev; pr.spread = (const f32x4 *)spread_dev; pr.n = (int32_t)n; pr.pad = 0; pr.rgb = rgb_dev;
     hipLaunchKernelGGL(qr_pt_adapt_kernel, grid, block, 0, (hipStream_t)stream, s->lp, pr, (uint32_t *)state_dev, samples,
                        min_samples, max_samples, tol2, open_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+/* ---- open lists and indexed adaptive steps (qr_openlist.hpp, qr_kernel.hpp qr_pt_list_kernel): compaction on chip ---- */
+
+static inline int64_t pt_open_blocks(int64_t n) { return (n + QR_PT_OPEN_BLOCK - 1) / QR_PT_OPEN_BLOCK; }
+
+extern "C" int qr_pt_adapt_list_work_bytes(qr_device_scene *s, int64_t n, uint64_t *bytes_out)
+{
+    const int rc = pt_rays_dims(s, n);
+    if (rc != QR_OK) return rc;
+    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    /* one word per block; the scan works in place and needs none of its own */
+    *bytes_out = (uint64_t)pt_open_blocks(n) * sizeof(uint32_t);
+    return QR_OK;
+}
+
+extern "C" int qr_pt_adapt_open_list_async(qr_device_scene *s, const void *state_dev, int64_t n,
+                                           int min_samples, int max_samples, float tol2,
+                                           uint32_t *index_dev, uint32_t *count_dev, void *work_dev, uint32_t flags, void *stream)
+{
+    const int rc = pt_adapt_args(s, n, 1, min_samples, max_samples, tol2, flags);
+    if (rc != QR_OK) return rc;
+    if (n == 0) return QR_OK;
+    if (state_dev == nullptr || index_dev == nullptr || count_dev == nullptr || work_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if ((((uintptr_t)state_dev | (uintptr_t)index_dev | (uintptr_t)count_dev | (uintptr_t)work_dev) & 3u) != 0)
+        return qr_fail(QR_ERR_ARG, "state, index, count and work must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const unsigned nb = (unsigned)pt_open_blocks(n);
+    const uint32_t *st = (const uint32_t *)state_dev;
+    uint32_t *work = (uint32_t *)work_dev;
+    hipLaunchKernelGGL(qr_open_count_kernel, dim3(nb), dim3(QR_PT_OPEN_BLOCK), 0, (hipStream_t)stream, st, (uint32_t)n,
+                       (uint32_t)min_samples, (uint32_t)max_samples, tol2, work);
+    hipLaunchKernelGGL(qr_open_scan_kernel, dim3(1), dim3(QR_PT_OPEN_CHUNK), 0, (hipStream_t)stream, work, (uint32_t)nb, count_dev);
+    hipLaunchKernelGGL(qr_open_scatter_kernel, dim3(nb), dim3(QR_PT_OPEN_BLOCK), 0, (hipStream_t)stream, st, (uint32_t)n,
+                       (uint32_t)min_samples, (uint32_t)max_samples, tol2, (const uint32_t *)work, index_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+extern "C" int qr_pt_adapt_list_rays_async(qr_device_scene *s, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
+                                           void *state_dev, const uint32_t *index_dev, const uint32_t *count_dev, int64_t cap,
+                                           int samples, int min_samples, int max_samples, float tol2,
+                                           float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream)
+{
+    const int rc = pt_adapt_args(s, n, samples, min_samples, max_samples, tol2, flags);
+    if (rc != QR_OK) return rc;
+    if (cap < 0) return qr_fail(QR_ERR_ARG, "cap must be 0 or more: the caller's upper bound on the list's length");
+    if (n == 0 || cap == 0) return QR_OK;
+    if (rays_dev == nullptr || state_dev == nullptr || index_dev == nullptr || count_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if ((((uintptr_t)rays_dev | (uintptr_t)spread_dev) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays and spread must be 16-byte aligned");
+    if ((((uintptr_t)state_dev | (uintptr_t)rgb_dev | (uintptr_t)open_dev | (uintptr_t)index_dev | (uintptr_t)count_dev) & 3u) != 0)
+        return qr_fail(QR_ERR_ARG, "state, rgb, open, index and count must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const int64_t most = cap < n ? cap : n;             /* distinct entries below n: a list holds at most n that count */
+    const dim3 grid((unsigned)((most + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    PtRaysP pr;
+    pr.rays = (const f32x4 *)rays_dev; pr.spread = (const f32x4 *)spread_dev; pr.n = (int32_t)n; pr.pad = 0; pr.rgb = rgb_dev;
+    hipLaunchKernelGGL(qr_pt_list_kernel, grid, block, 0, (hipStream_t)stream, s->lp, pr, (uint32_t *)state_dev, index_dev, count_dev,
+                       (uint32_t)most, samples, min_samples, max_samples, tol2, open_dev);
     HIP_TRY(hipGetLastError());
     return QR_OK;
 }

@@ -320,19 +320,24 @@ __device__ __forceinline__ bool pixel_of_view(u32 ord, int fsaa, const ViewsP &v
  * RAYS = 7 (adaptive path-traced rays, qr_pt_adapt_kernel; PT = true): RAYS = 6 with one difference: a lane is inside only when
  * its ray also takes this sample (`take`, the stop rule of include/qrhip.h evaluated by the caller's loop).  A lane that does not
  * is a lane past n: it draws nothing, walks nothing and stays out of every ballot.
+ * RAYS = 8 (indexed adaptive path-traced rays, qr_pt_list_kernel; PT = true): RAYS = 7 with the lane's ray index supplied by the
+ * caller (`ray_i`, an entry of its list) instead of gw * 64 + lane.  `take` is all that makes a lane inside: the caller has folded
+ * "this list position is served and its entry is below n" into it.  The index is used for the ray's and the spread's rows and
+ * nothing else, before the first walk: it is not live through the recursion.
  */
 template <bool COUNT, bool DIVK, bool PT = false, int RAYS = 0>
 __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, const u32 sched_head, const int gw,
                                             uint32_t *__restrict__ frame, int32_t *__restrict__ ids,
                                             unsigned long long *__restrict__ counters, const PtParams *ptp = nullptr,
                                             const RaysP *rp = nullptr, const ViewsP *vp = nullptr, V3 *mean_out = nullptr,
-                                            u32 *rng_io = nullptr, const PtRaysP *pr = nullptr, const bool take = true)
+                                            u32 *rng_io = nullptr, const PtRaysP *pr = nullptr, const bool take = true,
+                                            const u32 ray_i = 0u)
 {
     constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3 || RAYS == 4 || RAYS == 5, MEAN = RAYS == 4;
-    constexpr bool PTV = RAYS == 5, PTR = RAYS == 6 || RAYS == 7, PTA = RAYS == 7;
+    constexpr bool PTV = RAYS == 5, PTR = RAYS == 6 || RAYS == 7 || RAYS == 8, PTA = RAYS == 7, PTL = RAYS == 8;
     static_assert(!PTV || PT, "the path-traced view instance is a path-tracer instance");
     static_assert(!PTR || PT, "the path-traced ray instance is a path-tracer instance");
-    (void)mean_out; (void)rng_io; (void)pr; (void)take;
+    (void)mean_out; (void)rng_io; (void)pr; (void)take; (void)ray_i;
 #ifdef QR_WAVETIME
     const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
     const unsigned long long wt_clk0 = __builtin_amdgcn_s_memtime();      /* shader cycles: with the 100 MHz stamps, the clock the wave ran at */
@@ -379,6 +384,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     if constexpr (VIEW) inside = x < frm_w && y < vp->height;      /* the grid is the frame's footprints: every wave holds a pixel */
     else if constexpr (CALLER_RAYS) inside = (u32)gw * 64u + (u32)lane < (u32)rp->n;      /* n > 0: every wave holds a ray */
     else if constexpr (PTA) inside = (u32)gw * 64u + (u32)lane < (u32)pr->n && take;
+    else if constexpr (PTL) inside = take;
     else if constexpr (PTR) inside = (u32)gw * 64u + (u32)lane < (u32)pr->n;
     else
     {
@@ -424,7 +430,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
         /* the caller's ray as below, then the sample's jitter along the ray's spread: two draws, horizontal first, through the
          * tent filter of the frame's samples (tracer.cpp:1218-1285) without the FSAA halving -- caller rays have none; every
          * step one fp32 operation (-ffp-contract=off).  Lanes past the end read ray 0 and spread 0, draw nothing and do not walk */
-        const u32 i = inside ? (u32)gw * 64u + (u32)lane : 0u;
+        const u32 i = inside ? (PTL ? ray_i : (u32)gw * 64u + (u32)lane) : 0u;
         const f32x4 a = pr->rays[2 * (size_t)i], b = pr->rays[2 * (size_t)i + 1];
         ray.org = {a.x, a.y, a.z}; ray.tmin = a.w;
         ray.dir = {b.x, b.y, b.z};
@@ -619,7 +625,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
                 if (prio_round < 3) { prio_round++; if (prio_round == 2) __builtin_amdgcn_s_setprio(2); else if (prio_round == 3) __builtin_amdgcn_s_setprio(3); }
 #endif
             /* coherent: every ray of this round is a primary ray (neighbouring pixels; caller rays only when vouched for) */
-            const bool coherent = (RAYS != 1 && RAYS != 6 && RAYS != 7) && !any_lane(tr && sp != 0);
+            const bool coherent = (RAYS != 1 && RAYS != 6 && RAYS != 7 && RAYS != 8) && !any_lane(tr && sp != 0);
             traverse<false, DIVK, RAYS != 0>(B, tr, coherent, ray, h, occ
 #ifdef QR_STATS
                             , cx.stats
@@ -1301,6 +1307,113 @@ void qr_pt_adapt_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, int sam
         if (pr.rgb != nullptr)
         {
             pr.rgb[3 * i_e] = u2f(lds_st[1][lane_e]); pr.rgb[3 * i_e + 1] = u2f(lds_st[2][lane_e]); pr.rgb[3 * i_e + 2] = u2f(lds_st[3][lane_e]);
+        }
+    }
+    if (open != nullptr)
+    {
+        const unsigned long long still = __ballot(rule(lane_e));
+        if (still != 0ull && lane_e == 0) atomicAdd(open, (u32)__popcll(still));
+    }
+}
+
+/*
+ * Indexed adaptive path-traced rays (qr_pt_adapt_list_rays_async): qr_pt_adapt_kernel with the wave's 64 rays taken from a list of
+ * ray indices instead of from 64 consecutive columns, so that the rays a stop rule has left open -- scattered among rays that have
+ * stopped -- fill whole waves (the list: qr_openlist.hpp, or any list of distinct indices the caller makes).  Wave w serves list
+ * positions 64 w .. 64 w + 63 below min(cap, *count); *count is one scalar load, and a wave at or past it leaves before it touches
+ * anything else.  Lane l reads its entry i once; the ray's and the spread's rows, the eight state words and the rgb row are all
+ * addressed by i.  An entry >= n, and a position past the end, is a lane outside: it holds the sentinel index and m = max_samples,
+ * so the rule never lets it take, and reads and writes nothing.  The index waits in LDS beside the state (2 KB + 256 B per wave)
+ * and is read again at the top of every sample, as lane_s is made again: it is not a register live through the recursion.
+ * Everything else is qr_pt_adapt_kernel's body: the rule at the top of the wave-uniform sample loop, any_lane(take) the exit,
+ * Welford's update, a column written back only when its count changed, rgb for the listed rays only, `open` one vector atomic add
+ * per wave.  A ray's result depends on nothing but its own column, ray and spread, so the state after the call is bit for bit the
+ * state qr_pt_adapt_kernel leaves on the listed columns.
+ */
+__global__ __launch_bounds__(QR_BLOCK, 3)
+void qr_pt_list_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, const u32 *__restrict__ index, const u32 *__restrict__ count,
+                       u32 cap, int samples, int min_samples, int max_samples, float tol2, u32 *__restrict__ open)
+{
+    const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    const u32 cnt = *count;                                 /* wave-uniform address: a scalar load */
+    const u32 lim = cnt < cap ? cnt : cap;
+    if ((u32)gw * 64u >= lim) return;
+    __shared__ u32 lds_st[QR_PT_ADAPT_STATE_WORDS][64];
+    __shared__ u32 lds_ix[64];
+    const u32 n = (u32)pr.n;
+    constexpr u32 NONE = 0xFFFFFFFFu;                       /* n <= INT32_MAX: never a ray */
+    const int lane = (int)(threadIdx.x & 63u);
+    {
+        const u32 p = (u32)gw * 64u + (u32)lane;
+        u32 ix = NONE;
+        if (p < lim) { ix = index[p]; if (ix >= n) ix = NONE; }
+        /* lanes outside hold m = max_samples: the rule never lets them take */
+        u32 w[QR_PT_ADAPT_STATE_WORDS] = {0u, 0u, 0u, 0u, (u32)max_samples, 0u, 0u, 0u};
+        if (ix != NONE)
+        {
+#pragma unroll
+            for (int q = 0; q < QR_PT_ADAPT_STATE_WORDS; q++) w[q] = state[(size_t)q * n + ix];
+        }
+        lds_ix[lane] = ix;
+#pragma unroll
+        for (int q = 0; q < QR_PT_ADAPT_STATE_WORDS; q++) lds_st[q][lane] = w[q];
+    }
+    auto rule = [&](int l) -> bool {
+        const u32 m = lds_st[4][l];
+        const float m2r = u2f(lds_st[5][l]), m2g = u2f(lds_st[6][l]), m2b = u2f(lds_st[7][l]);
+        float lim2 = (float)m * (float)(m - 1u);
+        lim2 = lim2 * tol2;
+        const bool conv = m2r <= lim2 && m2g <= lim2 && m2b <= lim2;
+        return m < (u32)max_samples && (m < (u32)min_samples || m < 2u || !conv);
+    };
+#pragma nounroll
+    for (int s = 0; s < samples; s++)
+    {
+        int lane_s = (int)(threadIdx.x & 63u);
+        asm volatile("" : "+v"(lane_s));            /* not an address register kept alive through the sample */
+        const bool take = rule(lane_s);
+        if (!any_lane(take)) break;
+        u32 rng = lds_st[0][lane_s];
+        const u32 ri = lds_ix[lane_s];              /* dead after the ray's rows are read */
+        V3 c;
+        render_wave<false, false, true, 8>(lp, 0u, 0u, gw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &c, &rng, &pr, take, ri);
+        asm volatile("" : "+v"(lane_s));
+        if (take)
+        {
+            const u32 m = lds_st[4][lane_s] + 1u;
+            const float o = 1.0f / (float)m, u = 1.0f - o;
+            lds_st[4][lane_s] = m;
+            lds_st[0][lane_s] = rng;
+            const float col[3] = {c.x, c.y, c.z};
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++)
+            {
+                const float mean = u2f(lds_st[1 + ch][lane_s]);
+                const float d1 = col[ch] - mean;
+                const float a = col[ch] * o, b = mean * u;
+                const float mn = a + b;
+                const float d2 = col[ch] - mn;
+                const float p = d1 * d2;
+                lds_st[1 + ch][lane_s] = f2u(mn);
+                lds_st[5 + ch][lane_s] = f2u(u2f(lds_st[5 + ch][lane_s]) + p);
+            }
+        }
+    }
+    int lane_e = (int)(threadIdx.x & 63u);
+    asm volatile("" : "+v"(lane_e));
+    const u32 i_e = lds_ix[lane_e];
+    if (i_e < n)
+    {
+        /* a ray that took a sample holds more than it came with: the count in memory says which columns to write */
+        if (lds_st[4][lane_e] != state[(size_t)4 * n + i_e])
+        {
+#pragma unroll
+            for (int q = 0; q < QR_PT_ADAPT_STATE_WORDS; q++) state[(size_t)q * n + i_e] = lds_st[q][lane_e];
+        }
+        if (pr.rgb != nullptr)
+        {
+            const size_t o3 = 3 * (size_t)i_e;
+            pr.rgb[o3] = u2f(lds_st[1][lane_e]); pr.rgb[o3 + 1] = u2f(lds_st[2][lane_e]); pr.rgb[o3 + 2] = u2f(lds_st[3][lane_e]);
         }
     }
     if (open != nullptr)

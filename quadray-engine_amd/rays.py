@@ -54,6 +54,16 @@ before every sample whether the ray takes it.  pt_adapt_open states the rule and
     while True:
         rgb, still = acc.step(rays, samples=8, spread=spread, open=True)    # up to 8 more samples where the rule asks for them
         if int(still) == 0: break                                            # acc.counts: samples per ray
+
+A wave of that step holds 64 consecutive rays and runs as long as its slowest.  PtAdaptive.open_list writes the indices of the open
+rays on the device and step(index=, count=) serves 64 LISTED rays per wave; the state is bit for bit the same (pt_adapt_open_list
+and pt_adapt_fold_list are the specification):
+
+    cap = n
+    while cap:
+        index, count = acc.open_list()                                       # on the device; nothing is read back
+        _, still = acc.step(rays, 8, spread=spread, rgb=False, open=True, index=index, count=count, cap=cap)
+        cap = int(still)                                                     # exactly the next list's length
 """
 import struct
 
@@ -497,6 +507,36 @@ def pt_adapt_fold(state, cols, rngs, min_samples, max_samples, tol2):
             st[0, t] = rngs[t, s]
     rgb = np.ascontiguousarray(mean.T).copy()
     return st, rgb, int(pt_adapt_open(st, min_samples, max_samples, tol2).sum())
+
+
+def pt_adapt_open_list(state, min_samples, max_samples, tol2):
+    """The specification of qr_pt_adapt_open_list_async: the indices of the open rays of a state [8, N], ascending, uint32 [count]"""
+    return np.flatnonzero(pt_adapt_open(state, min_samples, max_samples, tol2)).astype(np.uint32)
+
+
+def pt_adapt_fold_list(state, index, count, cols, rngs, min_samples, max_samples, tol2, cap=None):
+    """The specification of one qr_pt_adapt_list_rays_async call: pt_adapt_fold restricted to the listed columns.  index: ray
+    indices (distinct); the first min(cap, count) entries are served (cap=None: no bound), entries >= N are skipped.  cols
+    [N, S, 3] and rngs [N, S] are indexed by RAY, not by list position, as for pt_adapt_fold.
+    Returns (state' uint32 [8, N] -- unlisted columns as they were --, rgb float32 [N, 3] with NaN in the rows of unlisted rays,
+    which the call does not write, open = the number of LISTED rays the rule would still let take a sample on state')."""
+    st = _pt_adapt_state(state).copy()
+    n = st.shape[1]
+    cols = np.asarray(cols, dtype=np.float32)
+    rngs = np.asarray(rngs, dtype=np.uint32)
+    if cols.ndim != 3 or cols.shape[0] != n or cols.shape[2] != 3 or rngs.shape != cols.shape[:2]:
+        raise ValueError("pt_adapt_fold_list needs cols [N, S, 3] and rngs [N, S] for a state [8, N]")
+    ix = np.asarray(index).reshape(-1).astype(np.int64)
+    served = min(int(count), len(ix)) if cap is None else min(int(count), int(cap), len(ix))
+    ix = ix[:max(served, 0)]
+    ix = ix[(ix >= 0) & (ix < n)]
+    if len(np.unique(ix)) != len(ix):
+        raise ValueError("the entries of a list must be distinct")
+    sub, srgb, op = pt_adapt_fold(st[:, ix], cols[ix], rngs[ix], min_samples, max_samples, tol2)
+    st[:, ix] = sub
+    rgb = np.full((n, 3), np.nan, dtype=np.float32)
+    rgb[ix] = srgb
+    return st, rgb, op
 
 
 # ---- hit records (include/qrhip.h qr_hit; Scene.hits, Scene.view_hits): float32 [..., 12] = pos xyz, t, nrm xyz, id, alb xyz, mat ----

@@ -15,6 +15,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     register or has a larger private segment than the scene's own path-tracer kernel (2128 B);
   * the path-traced ray kernel qr_pt_rays_kernel exceeds that same budget;
   * the adaptive path-traced ray kernel qr_pt_adapt_kernel exceeds that same budget;
+  * the indexed adaptive kernel qr_pt_list_kernel exceeds that same budget, or one of the three open-list kernels
+    (qr_openlist.hpp) spills a vector register or has a private segment;
   * a hit-record instance qr_hit_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more than
     168 VGPRs (128: the view instance with packet walks only);
   * an occlusion-fan instance qr_fan_kernel<SRC, DIVK, COHERENT> spills a vector register, has a private segment, or uses more
@@ -57,6 +59,12 @@ LIMITS = {
     "17qr_pt_rays_kernel": (168, 0, 2128),
     # adaptive path-traced rays (qr_kernel.hpp qr_pt_adapt_kernel): that kernel with per-ray counts and a stop rule: the same budget
     "18qr_pt_adapt_kernel": (168, 0, 2128),
+    # indexed adaptive path-traced rays (qr_kernel.hpp qr_pt_list_kernel): that kernel with its rays taken from a list: the same budget
+    "17qr_pt_list_kernel": (168, 0, 2128),
+    # the open list (qr_openlist.hpp): a rule, a ballot and a scan: nothing spilled, no private segment
+    "20qr_open_count_kernel": (128, 0, 0),
+    "19qr_open_scan_kernel": (128, 0, 0),
+    "22qr_open_scatter_kernel": (128, 0, 0),
     # hit records (qr_hitrec.hpp qr_hit_kernel<VIEW, DIVK, COHERENT>): a walk and one surface point, no recursion: nothing spilled and
     # no private segment at all; caller rays and views of scenes with long lists at the closest-hit query's 168 registers, views of
     # the others at the packet instances' 128
