@@ -362,6 +362,37 @@ static int host_threads()
     return n < 1 ? 1 : n;
 }
 
+/*
+ * The image-only words of a material record (qr_program.h, QR_MATX_*): `m` is the IMAGE's record (`tex` a byte offset into
+ * `img`).  A one-texel texture's colour is finished here, with shade()'s operations: (float)(int32_t)((texel >> s) & cmask) /
+ * clamp, one fp32 conversion and one IEEE fp32 division per channel -- the bits the kernel's own division gives.
+ */
+static float channel_colour(uint32_t v, uint32_t cmask, float clamp)
+{
+    volatile float num = (float)(int32_t)(v & cmask);      /* volatile: fp32 operands, one fp32 division, whatever the flags */
+    volatile float den = clamp;
+    return num / den;
+}
+
+static void material_colour(qr_material &m, const uint8_t *img, uint32_t lut = 0)
+{
+    for (int k = 0; k < 8; k++) m.pad[k] = 0;
+    if (m.xmask != 0 || m.ymask != 0)
+    {
+        if (lut != 0) { m.pad[QR_MATX_FLAGS] = (int32_t)QR_MATF_LUT; m.pad[QR_MATX_LUT] = (int32_t)lut; }
+        return;
+    }
+    uint32_t texel;
+    memcpy(&texel, img + (uint32_t)m.tex, 4);
+    const int sh[3] = {16, 8, 0};
+    for (int c = 0; c < 3; c++)
+    {
+        const float q = channel_colour(texel >> sh[c], m.cmask, m.clamp);
+        memcpy(&m.pad[QR_MATX_COL + c], &q, 4);
+    }
+    m.pad[QR_MATX_FLAGS] = (int32_t)QR_MATF_COLOUR;
+}
+
 struct Builder
 {
     const qr_scene_view &v;
@@ -1112,6 +1143,20 @@ static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem>
         b.o_mat = b.alloc((size_t)(n_mat + 1) * sizeof(qr_material), 128);
         b.o_lgt = b.alloc((size_t)(n_lgt + 1) * sizeof(qr_light), 64);
         b.o_tex = b.alloc((size_t)(n_tex + 1) * 4, 16);
+        /* colour tables of the textured materials (qr_program.h QR_MATF_LUT): room for one per distinct (cmask, clamp) */
+        struct LutKey { uint32_t cmask, clamp_bits, off; };
+        std::vector<LutKey> luts;
+        uint32_t n_lut = 0;
+        for (int i = 0; i < n_mat; i++)
+        {
+            const qr_material &m = v.mat[i];
+            if ((m.xmask == 0 && m.ymask == 0) || m.cmask > 0xFFu) continue;
+            bool seen = false;
+            for (int j = 0; j < i && !seen; j++)
+                seen = (v.mat[j].xmask != 0 || v.mat[j].ymask != 0) && v.mat[j].cmask == m.cmask && memcmp(&v.mat[j].clamp, &m.clamp, 4) == 0;
+            if (!seen) n_lut++;
+        }
+        const uint32_t o_lut = n_lut ? b.alloc((size_t)n_lut * 1024, 64) : 0u;
         const uint32_t o_til = b.alloc((T.size() + 1) * 4, 16);
 
         /* wave schedule geometry */
@@ -1128,6 +1173,26 @@ static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem>
         b.at<qr_material>(b.o_mat)[n_mat].clamp = 1.0f;
         memcpy(b.at<qr_light>(b.o_lgt), v.lgt, (size_t)n_lgt * sizeof(qr_light));
         memcpy(b.at<uint32_t>(b.o_tex), v.texels, (size_t)n_tex * 4);
+        /* the image-only words of the material records (qr_program.h): written here, from the image's own `tex`, `cmask` and
+         * `clamp` and the image's texels, so that whatever sets those three is followed by this */
+        for (int i = 0; i <= n_mat; i++)
+        {
+            qr_material &m = b.at<qr_material>(b.o_mat)[i];
+            uint32_t lut = 0;
+            if ((m.xmask != 0 || m.ymask != 0) && m.cmask <= 0xFFu)
+            {
+                /* textured, channels of at most 8 bits: one table i -> (float)(i & cmask) / clamp per distinct (cmask, clamp) */
+                uint32_t cb; memcpy(&cb, &m.clamp, 4);
+                for (const LutKey &k : luts) if (k.cmask == m.cmask && k.clamp_bits == cb) lut = k.off;
+                if (lut == 0) { lut = o_lut + (uint32_t)luts.size() * 1024u; luts.push_back(LutKey{m.cmask, cb, lut}); }
+            }
+            material_colour(b.at<qr_material>(b.o_mat)[i], out.blob.data(), lut);
+        }
+        for (const LutKey &k : luts)
+        {
+            float cl; memcpy(&cl, &k.clamp_bits, 4);
+            for (uint32_t i = 0; i < 256; i++) b.at<float>(k.off)[i] = channel_colour(i, k.cmask, cl);
+        }
         tick("fixed");
 
         /* box cull cells (QR_OPF_BOX) for images whose lists are all short: no list of such an image can be flagged as a long
@@ -1395,6 +1460,7 @@ static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem>
         h.off_shade = b.o_shd; h.off_tiles = o_til; h.off_order = o_ord; h.n_blocks = (uint32_t)n_waves;
         h.off_query = q_off;
         h.reach = 2.0f * b.big;
+        h.off_mat = b.o_mat; h.n_mat = (uint32_t)n_mat;
         b.alloc(64, 64);                    /* tail padding: wide scalar loads of the last record stay inside */
         out.off_order = o_ord; out.n_sched = (uint32_t)n_waves;
         out.off_query = q_off;
@@ -1633,7 +1699,27 @@ int qr_program_verify(const QrProgram &p, std::string &err)
         const uint64_t n = (uint64_t)(m->xmask + 1) * (m->ymask + 1);
         if ((uint32_t)m->tex < p.off_tex || ((uint32_t)m->tex & 3) || (uint64_t)(uint32_t)m->tex + n * 4 > (uint64_t)p.off_tex + ((uint64_t)p.n_tex + 1) * 4)
             return bad("texture offset");
+        /* the finished colour (QR_MATF_COLOUR) exactly for one-texel textures, and equal to what the record's texel, mask and
+         * clamp give now */
+        qr_material want = *m;
+        const bool lut_ok = (m->xmask != 0 || m->ymask != 0) && m->cmask <= 0xFFu;
+        const uint32_t lut = (uint32_t)m->pad[QR_MATX_LUT];
+        if (lut_ok)
+        {
+            /* the table: inside the fixed sections, and every entry what the record's mask and clamp give */
+            if (lut == 0 || (lut & 63) || lut < p.off_tex || (uint64_t)lut + 1024 > p.off_lists) return bad("material colour table offset");
+            const float *t = (const float *)(b.data() + lut);
+            for (uint32_t k = 0; k < 256; k++)
+            {
+                const float w = channel_colour(k, m->cmask, m->clamp);
+                if (memcmp(&w, &t[k], 4) != 0) return bad("material colour table");
+            }
+        }
+        material_colour(want, b.data(), lut_ok ? lut : 0u);
+        if (memcmp(want.pad, m->pad, sizeof(want.pad)) != 0) return bad("material colour words");
     }
+    const DevHeader *dh = (const DevHeader *)b.data();
+    if (dh->off_mat != p.off_mat || dh->n_mat != p.n_mat) return bad("header material table");
     return QR_OK;
 }
 

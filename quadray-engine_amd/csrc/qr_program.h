@@ -206,6 +206,21 @@ struct DShade
     uint32_t pad;
 };
 
+/*
+ * Material records: the image holds the snapshot's qr_material records (`tex` turned into a byte offset), and in their `pad`
+ * words -- 0 in a snapshot, no part of its format -- what the upload pass works out once per material instead of the kernel
+ * once per shaded hit.  A texture of one texel (xmask = ymask = 0: a plain colour) has one colour whatever the texture
+ * coordinates: pad[QR_MATX_COL + c] holds channel c (r, g, b) = (float)(int32_t)((texel >> (16, 8, 0)) & cmask) / clamp, one
+ * fp32 conversion and one IEEE fp32 division each as in shade(), and QR_MATF_COLOUR says so.  Gamma is a property of the
+ * surface side (QR_PROP_GAMMA), not of the material: the squaring stays in the kernel.
+ */
+#define QR_MATX_FLAGS  0        /* index into qr_material::pad: QR_MATF_* */
+#define QR_MATX_COL    1        /* ... pad[1..3]: the finished colour, float bits */
+#define QR_MATF_COLOUR 1u       /* one-texel texture: pad[QR_MATX_COL ..] is its colour */
+#define QR_MATX_LUT    4        /* ... pad[4]: byte offset of the material's colour table */
+#define QR_MATF_LUT    2u       /* textured, cmask <= 0xFF: a channel byte i of a texel has the colour table[i] = (float)(int32_t)(i & cmask)
+                                 * / clamp -- 256 floats, 64-byte aligned, one table per distinct (cmask, clamp) of the image */
+
 /* blob layout: header at offset 0, the DSurf array right behind it */
 #define QR_OFF_SRF 256u
 /* blob header at offset 0 */
@@ -221,7 +236,9 @@ struct DevHeader
     uint32_t off_query;         /* the global list compiled for ray queries (QR_UPLOAD_RAY_QUERIES), with its QR_LISTF_* bits; 0 none */
     float    reach;             /* twice the scene's largest coordinate (camera origin, finite surface bounds): caller rays whose origin
                                  * lies beyond it in some coordinate take the walk without culls (qr_walk.hpp traverse, CALLER) */
-    uint32_t pad[7];
+    uint32_t off_mat;           /* material table: n_mat + 1 qr_material records (the last one the zero record of lanes without a hit) */
+    uint32_t n_mat;
+    uint32_t pad[5];
 };
 #define QR_IMG_BOXES 1u         /* some cull cell carries a box (QR_OPF_BOX): packet walks prepare the slab test */
 

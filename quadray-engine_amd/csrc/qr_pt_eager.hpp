@@ -131,8 +131,7 @@ __device__ __forceinline__ V3 pt_eager(const Ctx &cx, const Ray &primary, bool i
                         const u32x4 p0 = *(const QR_CONST u32x4 *)(B + srf_off);
                         V3 d;
                         d.x = cur.org.x - u2f(p0.x); d.y = cur.org.y - u2f(p0.y); d.z = cur.org.z - u2f(p0.z);
-                        w.txyz = xform(B, srf_off, (op & QR_OPF_FULLM) != 0, d);
-                        w.trijk = xform(B, srf_off, (op & QR_OPF_FULLM) != 0, cur.dir);
+                        xform2(B, srf_off, (op & QR_OPF_FULLM) != 0, d, cur.dir, w.txyz, w.trijk);
                     }
                     (void)a1;
                     pos = next;

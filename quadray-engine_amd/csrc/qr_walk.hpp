@@ -123,6 +123,40 @@ __device__ __forceinline__ V3 xform(BaseP B, u32 off, bool full, V3 in)
     return o;
 }
 
+#ifndef QR_CUT_ROOT2
+#define QR_CUT_ROOT2 0      /* solve_cell: a quadric's second root is divided only where a lane reads it (0: both roots always).  OFF: it
+                             * lost its A/B -- demo scene 1 at 1080p 1.8 % slower with it (profiles/r05_shade_solve_cuts.txt) */
+#endif
+#ifndef QR_CUT_XFORM2
+#define QR_CUT_XFORM2 1     /* diff and ray through one record's matrix: the coefficients loaded once, `full` decided once (0: two xform calls) */
+#endif
+/* xform of `a` and of `b` with the same record: each with xform's operations in xform's order */
+__device__ __forceinline__ void xform2(BaseP B, u32 off, bool full, V3 a, V3 b, V3 &oa, V3 &ob)
+{
+#if QR_CUT_XFORM2
+    const QR_CONST DSurf *p = (const QR_CONST DSurf *)(B + off);
+    const float m00 = p->tci[0], m11 = p->tcj[1], m22 = p->tck[2];
+    float a4 = m00 * a.x, b4 = m00 * b.x;
+    float a5 = m11 * a.y, b5 = m11 * b.y;
+    float a6 = m22 * a.z, b6 = m22 * b.z;
+    if (full)
+    {
+        const float m01 = p->tci[1], m02 = p->tci[2], m10 = p->tcj[0], m12 = p->tcj[2], m20 = p->tck[0], m21 = p->tck[1];
+        a4 = a4 + m01 * a.y; b4 = b4 + m01 * b.y;
+        a4 = a4 + m02 * a.z; b4 = b4 + m02 * b.z;
+        a5 = a5 + m10 * a.x; b5 = b5 + m10 * b.x;
+        a5 = a5 + m12 * a.z; b5 = b5 + m12 * b.z;
+        a6 = a6 + m20 * a.x; b6 = b6 + m20 * b.x;
+        a6 = a6 + m21 * a.y; b6 = b6 + m21 * b.y;
+    }
+    oa.x = a4; oa.y = a5; oa.z = a6;
+    ob.x = b4; ob.y = b5; ob.z = b6;
+#else
+    oa = xform(B, off, full, a);
+    ob = xform(B, off, full, b);
+#endif
+}
+
 __device__ __forceinline__ float sel3(float a, float b, float c, u32 i) { return i == 0 ? a : i == 1 ? b : c; }
 /* component by one-hot axis flags (x, y, else z): two v_cndmask on scalar conditions */
 __device__ __forceinline__ float axis3(const V3 &v, bool is_x, bool is_y) { return is_x ? v.x : (is_y ? v.y : v.z); }
@@ -439,8 +473,7 @@ __device__ __forceinline__ void cell_space(BaseP B, u32 op, u32 srf_off, float p
         ry = r.dir;
         if (op & QR_OPF_OWN)
         {
-            df = xform(B, srf_off, (op & QR_OPF_FULLM) != 0, df);
-            ry = xform(B, srf_off, (op & QR_OPF_FULLM) != 0, r.dir);
+            xform2(B, srf_off, (op & QR_OPF_FULLM) != 0, df, r.dir, df, ry);
         }
     }
 }
@@ -472,6 +505,12 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
     {
         /* up to two candidate roots per lane, in the lane's own order */
         float ct0 = 0.0f, ct1 = 0.0f;
+#if QR_CUT_ROOT2
+        /* quadric without near-zero discriminant lanes: the second candidate's root as numerator and denominator, divided
+         * only when some lane still asks for it after the first candidate went through clip() */
+        bool lazy1 = false;
+        float ct1n = 0.0f, ct1d = 1.0f;
+#endif
         int   cs0 = 0, cs1 = 0;
         mask_t cm0 = K::none(), cm1 = K::none();
         int   ncand = 0;
@@ -568,8 +607,24 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
                         if (ceq(t2n, 0.0f)) t2d = 1.0f;
                     }
                 }
-                float t1 = t1n / t1d;
-                float t2 = t2n / t2d;
+                const bool inner_first = cgt(0.0f, a);      /* only read where xmask holds */
+                float t1, t2;
+#if QR_CUT_ROOT2
+                /* the roots meet only in the lanes of dmask (t1 - t2 below); without such a lane each candidate slot is its
+                 * own division of the operands selected per lane: the same operands, the same quotient bits */
+                lazy1 = !K::any(dmask);
+                if (lazy1)
+                {
+                    t1 = (inner_first ? t2n : t1n) / (inner_first ? t2d : t1d);     /* the first candidate's root */
+                    t2 = 0.0f;
+                    ct1n = inner_first ? t1n : t2n; ct1d = inner_first ? t1d : t2d;
+                }
+                else
+#endif
+                {
+                    t1 = t1n / t1d;
+                    t2 = t2n / t2d;
+                }
                 const mask_t t1msk = K::of(cne(t1d, 0.0f));
                 const mask_t t2msk = K::of(cne(t2d, 0.0f));
                 if (K::any(dmask))
@@ -592,7 +647,6 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
                     }
                 }
 
-                const bool inner_first = cgt(0.0f, a);      /* only read where xmask holds */
                 mask_t mo = xmask & t1msk, mi2 = xmask & t2msk;
                 if (K::any(same))
                 {
@@ -604,7 +658,11 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
                     mi2 = mi2 & K::inv(same & K::inv(so));
                 }
                 ncand = 2;
-                ct0 = inner_first ? t2 : t1; ct1 = inner_first ? t1 : t2;
+#if QR_CUT_ROOT2
+                if (lazy1) ct0 = t1;
+                else
+#endif
+                { ct0 = inner_first ? t2 : t1; ct1 = inner_first ? t1 : t2; }
                 cs0 = inner_first ? 1 : 0;   cs1 = inner_first ? 0 : 1;
                 const mask_t inf = K::of(inner_first);
                 cm0 = (inf & mi2) | (K::inv(inf) & mo); cm1 = (inf & mo) | (K::inv(inf) & mi2);
@@ -618,10 +676,13 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
 #pragma nounroll
         for (int p = 0; p < np; p++)
         {
-            const float t = p == 0 ? ct0 : ct1;
             const int side = p == 0 ? cs0 : cs1;
             mask_t m = (p == 0 ? cm0 : cm1) & K::inv(done);
             if (!K::any(m)) continue;
+#if QR_CUT_ROOT2
+            if (p != 0 && lazy1) ct1 = ct1n / ct1d;
+#endif
+            const float t = p == 0 ? ct0 : ct1;
             V3 loc;
             m = clip<DIV, CLIPL>(B, s, op, r, w.tbuf, ci, t, side, m, loc);
             done = done | m;
@@ -957,8 +1018,7 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
                     const u32x4 p0 = *(const QR_CONST u32x4 *)(B + srf_off);
                     V3 d;
                     d.x = r.org.x - u2f(p0.x); d.y = r.org.y - u2f(p0.y); d.z = r.org.z - u2f(p0.z);
-                    w.txyz = xform(B, srf_off, (op & QR_OPF_FULLM) != 0, d);
-                    w.trijk = xform(B, srf_off, (op & QR_OPF_FULLM) != 0, r.dir);
+                    xform2(B, srf_off, (op & QR_OPF_FULLM) != 0, d, r.dir, w.txyz, w.trijk);
                 }
             }
             else if (op & QR_OPT_BV)
@@ -1131,8 +1191,7 @@ __device__ __forceinline__ void walk_div(BaseP B, bool active, const Ray &r, Hit
                     const u32x4 p0 = *(const QR_CONST u32x4 *)(B + srf_off);
                     V3 d;
                     d.x = r.org.x - u2f(p0.x); d.y = r.org.y - u2f(p0.y); d.z = r.org.z - u2f(p0.z);
-                    w.txyz = xform(B, srf_off, (op & QR_OPF_FULLM) != 0, d);
-                    w.trijk = xform(B, srf_off, (op & QR_OPF_FULLM) != 0, r.dir);
+                    xform2(B, srf_off, (op & QR_OPF_FULLM) != 0, d, r.dir, w.txyz, w.trijk);
                 }
                 pos = next;
             }
