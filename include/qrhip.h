@@ -544,6 +544,56 @@ int qr_pt_adapt_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, const q
                            float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream);
 
 /*
+ * Adaptive path-traced views: qr_pt_views_async with the state of qr_pt_adapt_rays_async PER PIXEL SAMPLE and its stop rule on
+ * chip -- a path-traced frame from a free camera, a stereo pair or a cube-map probe in which quiet pixel samples retire early,
+ * with the frame's own output step, footprint-shaped waves and the view's ray arithmetic.
+ *   - The state, QR_PT_ADAPT_STATE_WORDS planes of 32-bit words per view:
+ *         state[view][plane][slot],  slot = (y * width + x) * samples_per_pixel + k,  slots = width * height * samples_per_pixel
+ *     planes 0..3 are qr_pt_views_async's (generator state, running means of r, g, b); plane 4 the count m; planes 5..7 Welford's
+ *     M2 of r, g, b.  One view's block is, word for word, a qr_pt_adapt_rays_async state of n = slots columns.
+ *     qr_pt_adapt_views_state_bytes gives the size (n_views * 8 * slots * 4 bytes).  qr_pt_adapt_views_reset writes plane 0 of
+ *     every view as qr_pt_views_reset does and sets every other plane to 0; it is SYNCHRONOUS.  The state is all there is: there
+ *     is no `done` argument.  The host may read it, edit it, copy it and continue from it.
+ *   - The rule and the update are those of qr_pt_adapt_rays_async, word for word and operation for operation (its text above:
+ *     take, lim, conv; m, o, u, d1, a, b, mean, d2, p, M2).  The rule is evaluated PER SLOT -- per pixel sample, not per pixel:
+ *     with FSAA the samples of one pixel retire one by one.  A per-pixel rule would have to define a pixel's noise from its
+ *     samples' and would break consequence (d); a host that wants one edits plane 4.
+ *   - A taken sample is exactly one sample of qr_pt_views_async for that slot: the tent-filter jitter with the FSAA halving, the
+ *     view's ray arithmetic, a first walk over the ray-query list with the view's t_min / t_max, then the path tracer in the
+ *     kernel's order of draws at the scene's current depth (qr_scene_set_depth).
+ *   - Consequences the tests rest on:
+ *       (a) with min_samples == max_samples, planes 0..3, frames and mean after any sequence of calls are qr_pt_views_async's
+ *           bits for the same totals;
+ *       (b) samples = a + b gives the bits of two calls with a, then b, state included;
+ *       (c) a slot's result depends on nothing but its own column, its (x, y, k) and its view: not on its neighbours in the
+ *           footprint, not on which lanes take a sample, not on n_views or on other views.  A slot that takes nothing keeps all
+ *           eight words bit for bit;
+ *       (d) state[j] handed to qr_pt_adapt_open_list_async with n = slots lists view j's open slots.
+ *   - Every pixel of every view is written on every call, also the pixels of footprints in which nothing was open.
+ *     frames_dev: required, uint32 [n_views][height][width], the packed running mean: qr_pt_views_async's output step on the
+ *     means.  mean_dev (NULL = not wanted): float32 [n_views][height][width][3], as in qr_pt_views_async.  counts_dev (NULL =
+ *     not wanted): int32 [n_views][height][width], the sum of m over the pixel's samples_per_pixel slots, the sample heat map.
+ *   - open_dev: optional, ONE uint32 that the caller zeroes.  The call adds the number of slots the rule still lets take on
+ *     the final state: one vector atomic add per wave, from one lane; waves with a count of 0 skip it.
+ *   - Cost: a wave is one footprint and runs as long as its slowest slot; the others' lanes idle.  The remedy for scattered
+ *     open slots is the ray path's open lists (below), not this call.
+ *   - Refusals: those of qr_pt_views_async (sizes and counts, QR_VIEW_MAX_DIM, QR_VIEW_MAX_VIEWS, QR_VIEW_MAX_WAVES; a null or
+ *     misaligned pointer, views 16, the others 4 bytes; any flag, none is defined) and of qr_pt_adapt_rays_async (samples outside
+ *     1 .. QR_PT_ADAPT_VIEWS_MAX_SAMPLES; min_samples < 0, max_samples < 1, min_samples > max_samples or max_samples >= 2^24;
+ *     tol2 negative, NaN or infinite) give QR_ERR_ARG; n_views * slots above 2^29 too (the state's bytes are held to what
+ *     qr_pt_views_async allows).  A scene without ray-query list gives QR_ERR_UNSUP.  A refused call launches nothing and changes
+ *     nothing.  n_views == 0 returns QR_OK without a launch.
+ *   - Independent of the scene's own path-tracer mode.  Asynchronous on `stream`, on the scene's own device; no hidden copy.
+ */
+#define QR_PT_ADAPT_VIEWS_MAX_SAMPLES 512        /* candidate samples of one launch */
+int qr_pt_adapt_views_state_bytes(qr_device_scene *scn, int n_views, int width, int height, uint64_t *bytes_out);
+int qr_pt_adapt_views_reset(qr_device_scene *scn, int n_views, int width, int height, void *state_dev);
+int qr_pt_adapt_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
+                            void *state_dev, int samples, int min_samples, int max_samples, float tol2,
+                            uint32_t *frames_dev, float *mean_dev, int32_t *counts_dev, uint32_t *open_dev,
+                            uint32_t flags, void *stream);
+
+/*
  * Open lists and indexed adaptive steps: compaction on chip.  qr_pt_adapt_open_list_async writes the indices of the rays the stop
  * rule would still let take a sample; qr_pt_adapt_list_rays_async is qr_pt_adapt_rays_async on the rays of such a list, 64 LISTED
  * rays per wave instead of 64 consecutive ones, so that waves hold open rays only.  By consequence (c) above the state after

@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "qr_pt_views_state_bytes", "qr_pt_views_reset", "qr_pt_views_async",
     "qr_pt_rays_state_bytes", "qr_pt_rays_reset", "qr_pt_rays_async",
     "qr_pt_adapt_state_bytes", "qr_pt_adapt_reset", "qr_pt_adapt_rays_async",
+    "qr_pt_adapt_views_state_bytes", "qr_pt_adapt_views_reset", "qr_pt_adapt_views_async",
     "qr_pt_adapt_list_work_bytes", "qr_pt_adapt_open_list_async", "qr_pt_adapt_list_rays_async", "qr_hit_rays_async", "qr_hit_views_async",
     "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async", "qr_layer_rays_async", "qr_layer_views_async",
     "qr_frame_register", "qr_frame_unregister",
@@ -46,6 +47,7 @@ PT_RAYS_MAX_SAMPLES = 512   # QR_PT_RAYS_MAX_SAMPLES: the most samples of one qr
 PT_RAYS_STATE_WORDS = 4     # QR_PT_RAYS_STATE_WORDS: 32-bit planes of a path-traced ray state
 PT_ADAPT_MAX_SAMPLES = 512  # QR_PT_ADAPT_MAX_SAMPLES: the most candidate samples of one qr_pt_adapt_rays_async launch
 PT_ADAPT_STATE_WORDS = 8    # QR_PT_ADAPT_STATE_WORDS: 32-bit planes of an adaptive path-traced ray state
+PT_ADAPT_VIEWS_MAX_SAMPLES = 512    # QR_PT_ADAPT_VIEWS_MAX_SAMPLES: the most candidate samples of one qr_pt_adapt_views_async launch
 PT_OPEN_BLOCK = 1024        # QR_PT_OPEN_BLOCK: rays per workgroup of the open-list kernels
 PT_OPEN_CHUNK = 1024        # QR_PT_OPEN_CHUNK: block counts one pass of the open list's scan workgroup takes
 LAYER_MAX = 64              # QR_LAYER_MAX: the most layers of one qr_layer_*_async call
@@ -122,6 +124,9 @@ def lib():
     L.qr_pt_adapt_state_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
     L.qr_pt_adapt_reset.argtypes = [vp, ctypes.c_int64, vp]
     L.qr_pt_adapt_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ci, ci, ci, ctypes.c_float, vp, vp, ctypes.c_uint32, vp]
+    L.qr_pt_adapt_views_state_bytes.argtypes = [vp, ci, ci, ci, ctypes.POINTER(cu64)]
+    L.qr_pt_adapt_views_reset.argtypes = [vp, ci, ci, ci, vp]
+    L.qr_pt_adapt_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, ctypes.c_float, vp, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_pt_adapt_list_work_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
     L.qr_pt_adapt_open_list_async.argtypes = [vp, vp, ctypes.c_int64, ci, ci, ctypes.c_float, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_pt_adapt_list_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, ci, ci, ci, ctypes.c_float,
@@ -697,6 +702,14 @@ class Scene:
         state=None: a new state tensor, reset.  state=<tensor>: continue from an int32 [8, n] tensor on the scene's device."""
         return PtAdaptive(self, n, min_samples, max_samples, tol, state)
 
+    def pt_adaptive_views(self, views, width=None, height=None, min_samples=0, max_samples=64, tol=0.0, state=None):
+        """Adaptive path-traced frames from caller-supplied cameras (qr_pt_adapt_views_async): returns a PtAdaptiveViews
+        accumulator for `views` (as for render_views) at width x height that keeps a sample count and a noise estimate per pixel
+        sample and stops a pixel sample once the standard error of its mean is at most `tol` in every channel, between
+        `min_samples` and `max_samples` samples since the reset.  state=None: a new state tensor, reset.  state=<tensor>:
+        continue from an int32 [N, 8, H * W * samples_per_pixel] tensor on the scene's device."""
+        return PtAdaptiveViews(self, views, width, height, min_samples, max_samples, tol, state)
+
     def render_count(self, frame=None, stream=None):
         if frame is None:
             frame = self.new_frame()
@@ -1030,6 +1043,151 @@ class PtAdaptive:
                                             ctypes.c_void_p(opent.data_ptr() if opent is not None else None), 0,
                                             Scene._stream_ptr(stream)))
         return (rgb, opent) if opent is not None else rgb
+
+
+class PtAdaptiveViews:
+    """An adaptive path-traced accumulation over caller cameras (Scene.pt_adaptive_views; include/qrhip.h
+    qr_pt_adapt_views_async).
+
+    state: int32 [N, 8, H * W * samples_per_pixel] on the scene's device, slot (y * W + x) * samples_per_pixel + k -- per view
+    planes 0..3 as PtViews keeps them (generator states, float32 running means of r, g, b), plane 4 the number of samples the
+    slot holds, planes 5..7 Welford's M2 of r, g, b: state[j] is a PtAdaptive state of `slots` columns.  counts: a view of plane
+    4, [N, slots].  The state is all there is: the host may read it, edit it, copy it and continue from it.  tol2:
+    float32(tol) * float32(tol).  The rule is per slot (rays.pt_adapt_open on state[j]), the update rays.pt_adapt_fold's.  A
+    wave is one footprint and runs as long as its slowest slot."""
+
+    def __init__(self, scene, views, width=None, height=None, min_samples=0, max_samples=64, tol=0.0, state=None):
+        import numpy as np
+        import torch
+        w, h = scene._views_arg(views, width, height)
+        if not (isinstance(min_samples, int) and isinstance(max_samples, int)
+                and 0 <= min_samples <= max_samples and 1 <= max_samples < (1 << 24)):
+            raise QrError("min_samples and max_samples must be integers, 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24")
+        try:
+            t = np.float32(tol)
+        except (TypeError, ValueError):
+            raise QrError("tol must be a number") from None
+        with np.errstate(over="ignore", invalid="ignore"):
+            tol2 = t * t
+        if not (t >= 0 and np.isfinite(tol2)):
+            raise QrError("tol must be a finite number, 0 or more, whose square is finite in float32")
+        self.scene, self.views, self.width, self.height = scene, views, w, h
+        self.min_samples, self.max_samples, self.tol, self.tol2 = min_samples, max_samples, float(t), tol2
+        self._list_work = self._list_index = self._list_count = None
+        n = views.shape[0]
+        nbytes = ctypes.c_uint64()
+        _check(lib().qr_pt_adapt_views_state_bytes(scene._h, n, w, h, ctypes.byref(nbytes)))
+        self.slots = (w * h) << scene.info.fsaa
+        shape = (n, PT_ADAPT_STATE_WORDS, self.slots)
+        assert nbytes.value == 4 * n * PT_ADAPT_STATE_WORDS * self.slots
+        if state is None:
+            self.state = torch.empty(shape, dtype=torch.int32, device=views.device)
+            self.reset()
+        else:
+            if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == shape
+                    and state.is_contiguous() and state.is_cuda and state.device.index == scene.device):
+                raise QrError(f"state must be a contiguous int32 {list(shape)} tensor on cuda:{scene.device}")
+            self.state = state
+
+    @property
+    def counts(self):
+        """plane 4 of the state (a view), [N, slots]: the number of samples every pixel sample holds"""
+        return self.state[:, 4]
+
+    def reset(self):
+        """Restart the accumulation: seeds as rays.pt_seeds in every view, every other plane 0.  Synchronous
+        (qr_pt_adapt_views_reset)."""
+        _check(lib().qr_pt_adapt_views_reset(self.scene._h, self.views.shape[0], self.width, self.height,
+                                             ctypes.c_void_p(self.state.data_ptr())))
+
+    def clone(self):
+        """A checkpoint: an accumulator with a copy of the state (on the current stream) that continues independently."""
+        return PtAdaptiveViews(self.scene, self.views, self.width, self.height, self.min_samples, self.max_samples, self.tol,
+                               self.state.clone())
+
+    _list_arg = PtAdaptive._list_arg
+
+    def open_list(self, view, index=None, count=None, stream=None):
+        """The open list of one view's block (qr_pt_adapt_open_list_async on state[view] with n = slots): index[:count] = the
+        slots of that view the stop rule would still let take a sample, ascending; index[count:] is not written.  Returns
+        (index int32 [slots], count int32 [1]), the accumulator's own tensors (allocated on first use, written again by every
+        call) or the caller's.  Asynchronous on `stream`."""
+        import torch
+        n, dev = self.slots, f"cuda:{self.scene.device}"
+        if not (isinstance(view, int) and 0 <= view < self.views.shape[0]):
+            raise QrError(f"view must be an integer, 0..{self.views.shape[0] - 1}")
+        if index is None:
+            if self._list_index is None:
+                self._list_index = torch.empty((n,), dtype=torch.int32, device=dev)
+            index = self._list_index
+        if count is None:
+            if self._list_count is None:
+                self._list_count = torch.zeros((1,), dtype=torch.int32, device=dev)
+            count = self._list_count
+        index, count = self._list_arg(index, (n,), "index"), self._list_arg(count, (1,), "count")
+        if self._list_work is None:
+            nbytes = ctypes.c_uint64()
+            _check(lib().qr_pt_adapt_list_work_bytes(self.scene._h, n, ctypes.byref(nbytes)))
+            self._list_work = torch.empty((max(1, nbytes.value // 4),), dtype=torch.int32, device=dev)
+        _check(lib().qr_pt_adapt_open_list_async(self.scene._h, ctypes.c_void_p(self.state[view].data_ptr()), n, self.min_samples,
+                                                 self.max_samples, ctypes.c_float(float(self.tol2)),
+                                                 ctypes.c_void_p(index.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                                 ctypes.c_void_p(self._list_work.data_ptr()), 0, Scene._stream_ptr(stream)))
+        return index, count
+
+    def step(self, samples=1, frames=None, mean=False, counts=False, open=False, stream=None):
+        """Offer every pixel sample of every view up to `samples` (1 .. PT_ADAPT_VIEWS_MAX_SAMPLES) candidate samples in ONE
+        launch; a slot takes them while the stop rule on its own column lets it.  Returns the packed running-mean frames (int32
+        [N, H, W]; a new tensor unless given), every pixel written.  mean: as PtViews.step (float32 [N, H, W, 3]).  counts:
+        False, True or an int32 [N, H, W] tensor: the samples every pixel holds, summed over its slots.  open: False, True or a
+        one-element int32 / uint32 tensor on the scene's device; step zeroes it on `stream` and the launch adds the number of
+        slots that would still take a sample.  Returns frames alone, or the tuple (frames, mean, counts, open) without the ones
+        not wanted.  The scene's current depth (set_depth) applies.  Asynchronous on `stream`."""
+        import torch
+        n, h, w, dev = self.views.shape[0], self.height, self.width, self.scene.device
+        if frames is None:
+            frames = torch.empty((n, h, w), dtype=torch.int32, device=self.views.device)    # every pixel is written
+        elif not (isinstance(frames, torch.Tensor) and frames.dtype == torch.int32 and tuple(frames.shape) == (n, h, w)
+                  and frames.is_contiguous() and frames.is_cuda and frames.device.index == dev):
+            raise QrError(f"frames must be a contiguous int32 [{n}, {h}, {w}] tensor on cuda:{dev}")
+        if mean is True:
+            mean = torch.empty((n, h, w, 3), dtype=torch.float32, device=self.views.device)
+        elif mean is False or mean is None:
+            mean = None
+        elif not (isinstance(mean, torch.Tensor) and mean.dtype == torch.float32 and tuple(mean.shape) == (n, h, w, 3)
+                  and mean.is_contiguous() and mean.is_cuda and mean.device.index == dev):
+            raise QrError(f"mean must be True, False or a contiguous float32 [{n}, {h}, {w}, 3] tensor on cuda:{dev}")
+        if counts is True:
+            counts = torch.empty((n, h, w), dtype=torch.int32, device=self.views.device)
+        elif counts is False or counts is None:
+            counts = None
+        elif not (isinstance(counts, torch.Tensor) and counts.dtype == torch.int32 and tuple(counts.shape) == (n, h, w)
+                  and counts.is_contiguous() and counts.is_cuda and counts.device.index == dev):
+            raise QrError(f"counts must be True, False or a contiguous int32 [{n}, {h}, {w}] tensor on cuda:{dev}")
+        opent = None
+        if open is True:
+            opent = torch.empty((1,), dtype=torch.int32, device=self.views.device)
+        elif not (open is False or open is None):
+            if not (isinstance(open, torch.Tensor) and open.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
+                    and open.numel() == 1 and open.is_contiguous() and open.is_cuda and open.device.index == dev):
+                raise QrError(f"open must be True, False or a one-element int32 or uint32 tensor on cuda:{dev}")
+            opent = open
+        if not isinstance(samples, int):
+            raise QrError("samples must be an integer")
+        if not 1 <= samples <= PT_ADAPT_VIEWS_MAX_SAMPLES:
+            raise QrError(f"samples must be 1..{PT_ADAPT_VIEWS_MAX_SAMPLES}")
+        if opent is not None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                opent.zero_()
+        _check(lib().qr_pt_adapt_views_async(self.scene._h, ctypes.c_void_p(self.views.data_ptr()), n, w, h,
+                                             ctypes.c_void_p(self.state.data_ptr()), samples, self.min_samples, self.max_samples,
+                                             ctypes.c_float(float(self.tol2)), ctypes.c_void_p(frames.data_ptr()),
+                                             ctypes.c_void_p(mean.data_ptr() if mean is not None else None),
+                                             ctypes.c_void_p(counts.data_ptr() if counts is not None else None),
+                                             ctypes.c_void_p(opent.data_ptr() if opent is not None else None), 0,
+                                             Scene._stream_ptr(stream)))
+        out = (frames,) + tuple(t for t in (mean, counts, opent) if t is not None)
+        return out if len(out) > 1 else frames
 
 
 class MultiRender:

@@ -784,6 +784,90 @@ extern "C" int qr_pt_adapt_rays_async(qr_device_scene *s, const qr_ray *rays_dev
     return QR_OK;
 }
 
+/* ---- adaptive path-traced views (qr_kernel.hpp qr_pt_adapt_views_kernel): qr_pt_views_async with the adaptive rays' state per slot ---- */
+
+/* the checks every entry point of the feature shares: pt_views_dims, and the state's bytes held to what qr_pt_views_async allows */
+static int pt_adapt_views_dims(const qr_device_scene *s, int n_views, int width, int height, uint64_t *slots)
+{
+    const int rc = pt_views_dims(s, n_views, width, height, slots);
+    if (rc != QR_OK) return rc;
+    if ((uint64_t)n_views * *slots > ((uint64_t)1 << 29))
+        return qr_fail(QR_ERR_ARG, "more than 2^29 pixel samples of adaptive path-tracer state in one launch");
+    return QR_OK;
+}
+
+extern "C" int qr_pt_adapt_views_state_bytes(qr_device_scene *s, int n_views, int width, int height, uint64_t *bytes_out)
+{
+    uint64_t slots = 0;
+    const int rc = pt_adapt_views_dims(s, n_views, width, height, &slots);
+    if (rc != QR_OK) return rc;
+    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    *bytes_out = (uint64_t)n_views * QR_PT_ADAPT_STATE_WORDS * slots * sizeof(uint32_t);
+    return QR_OK;
+}
+
+/* plane 0 of every view as qr_pt_views_reset writes it, every other plane 0: synchronous */
+extern "C" int qr_pt_adapt_views_reset(qr_device_scene *s, int n_views, int width, int height, void *state_dev)
+{
+    uint64_t slots = 0;
+    const int rc = pt_adapt_views_dims(s, n_views, width, height, &slots);
+    if (rc != QR_OK) return rc;
+    if (n_views == 0) return QR_OK;
+    if (state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (((uintptr_t)state_dev & 3u) != 0) return qr_fail(QR_ERR_ARG, "state must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<uint32_t> seeds(slots);
+    unsigned long long seed = 1;
+    for (uint64_t k = 0; k < slots; k++)
+    {
+        seed = (seed * 25214903917ull + 11ull) & 0x0000FFFFFFFFFFFFull;
+        seeds[k] = (uint32_t)seed;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t *st = (uint32_t *)state_dev;
+    for (int v = 0; v < n_views; v++, st += QR_PT_ADAPT_STATE_WORDS * slots)
+    {
+        HIP_TRY(hipMemcpy(st, seeds.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(st + slots, 0, (QR_PT_ADAPT_STATE_WORDS - 1) * slots * sizeof(uint32_t)));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return QR_OK;
+}
+
+extern "C" int qr_pt_adapt_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                       void *state_dev, int samples, int min_samples, int max_samples, float tol2,
+                                       uint32_t *frames_dev, float *mean_dev, int32_t *counts_dev, uint32_t *open_dev,
+                                       uint32_t flags, void *stream)
+{
+    uint64_t slots = 0;
+    const int rc = pt_adapt_views_dims(s, n_views, width, height, &slots);
+    if (rc != QR_OK) return rc;
+    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown adaptive path-traced view flags");
+    if (samples < 1 || samples > QR_PT_ADAPT_VIEWS_MAX_SAMPLES)
+        return qr_fail(QR_ERR_ARG, "samples must be 1.." + std::to_string(QR_PT_ADAPT_VIEWS_MAX_SAMPLES));
+    if (min_samples < 0 || max_samples < 1 || min_samples > max_samples || max_samples >= (1 << 24))
+        return qr_fail(QR_ERR_ARG, "min_samples and max_samples must be 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24 (the count is exact in fp32)");
+    if (!(tol2 >= 0.0f) || tol2 > FLT_MAX) return qr_fail(QR_ERR_ARG, "tol2 must be a finite number, 0 or more");
+    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
+    if (n_views == 0) return QR_OK;
+    if (views_dev == nullptr || state_dev == nullptr || frames_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (((uintptr_t)views_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "views must be 16-byte aligned");
+    if ((((uintptr_t)state_dev | (uintptr_t)frames_dev | (uintptr_t)mean_dev | (uintptr_t)counts_dev | (uintptr_t)open_dev) & 3u) != 0)
+        return qr_fail(QR_ERR_ARG, "state, frames, mean, counts and open must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const int fsaa = s->fr.fsaa;
+    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+    const dim3 grid((unsigned)((width + fw - 1) / fw), (unsigned)((height + fh - 1) / fh), (unsigned)n_views), block(QR_BLOCK);
+    ViewsP vp;
+    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
+    PtAdaptViewsP pa;
+    pa.state = (uint32_t *)state_dev; pa.samples = samples; pa.min_samples = min_samples; pa.max_samples = max_samples; pa.tol2 = tol2;
+    pa.mean = mean_dev; pa.counts = counts_dev; pa.open = open_dev;
+    hipLaunchKernelGGL(qr_pt_adapt_views_kernel, grid, block, 0, (hipStream_t)stream, s->lp, vp, pa, frames_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
 /* ---- open lists and indexed adaptive steps (qr_openlist.hpp, qr_kernel.hpp qr_pt_list_kernel): compaction on chip ---- */
 
 static inline int64_t pt_open_blocks(int64_t n) { return (n + QR_PT_OPEN_BLOCK - 1) / QR_PT_OPEN_BLOCK; }

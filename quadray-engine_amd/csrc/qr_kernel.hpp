@@ -324,6 +324,12 @@ __device__ __forceinline__ bool pixel_of_view(u32 ord, int fsaa, const ViewsP &v
  * caller (`ray_i`, an entry of its list) instead of gw * 64 + lane.  `take` is all that makes a lane inside: the caller has folded
  * "this list position is served and its entry is below n" into it.  The index is used for the ray's and the spread's rows and
  * nothing else, before the first walk: it is not live through the recursion.
+ * RAYS = 9 (adaptive path-traced views, qr_pt_adapt_views_kernel; PT = true): RAYS = 5 with one difference: a lane is inside only
+ * when its slot also takes this sample (`take`, as for RAYS = 7).  A lane that does not is a lane past the frame's edge: it draws
+ * nothing, walks nothing and stays out of every ballot.  The first round stays RAYS = 5's (`coherent`): the slots that take are a
+ * subset of one footprint's primary rays, and the flag only chooses among walks that solve the same surfaces in the same order
+ * with the same arithmetic (traverse) -- nothing in that round reads a neighbour lane's ray or needs one alive, which the partial
+ * footprints at a frame's right and bottom edges already rest on.
  */
 template <bool COUNT, bool DIVK, bool PT = false, int RAYS = 0>
 __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, const u32 sched_head, const int gw,
@@ -333,8 +339,8 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
                                             u32 *rng_io = nullptr, const PtRaysP *pr = nullptr, const bool take = true,
                                             const u32 ray_i = 0u)
 {
-    constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3 || RAYS == 4 || RAYS == 5, MEAN = RAYS == 4;
-    constexpr bool PTV = RAYS == 5, PTR = RAYS == 6 || RAYS == 7 || RAYS == 8, PTA = RAYS == 7, PTL = RAYS == 8;
+    constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3 || RAYS == 4 || RAYS == 5 || RAYS == 9, MEAN = RAYS == 4;
+    constexpr bool PTV = RAYS == 5 || RAYS == 9, PTVA = RAYS == 9, PTR = RAYS == 6 || RAYS == 7 || RAYS == 8, PTA = RAYS == 7, PTL = RAYS == 8;
     static_assert(!PTV || PT, "the path-traced view instance is a path-tracer instance");
     static_assert(!PTR || PT, "the path-traced ray instance is a path-tracer instance");
     (void)mean_out; (void)rng_io; (void)pr; (void)take; (void)ray_i;
@@ -381,7 +387,8 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     const int frm_w = VIEW ? vp->width : fr->fr.frm_w;
 
     bool inside;
-    if constexpr (VIEW) inside = x < frm_w && y < vp->height;      /* the grid is the frame's footprints: every wave holds a pixel */
+    if constexpr (PTVA) inside = x < frm_w && y < vp->height && take;
+    else if constexpr (VIEW) inside = x < frm_w && y < vp->height;      /* the grid is the frame's footprints: every wave holds a pixel */
     else if constexpr (CALLER_RAYS) inside = (u32)gw * 64u + (u32)lane < (u32)rp->n;      /* n > 0: every wave holds a ray */
     else if constexpr (PTA) inside = (u32)gw * 64u + (u32)lane < (u32)pr->n && take;
     else if constexpr (PTL) inside = take;
@@ -1313,6 +1320,143 @@ void qr_pt_adapt_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, int sam
     {
         const unsigned long long still = __ballot(rule(lane_e));
         if (still != 0ull && lane_e == 0) atomicAdd(open, (u32)__popcll(still));
+    }
+}
+
+/*
+ * Adaptive path-traced views (qr_pt_adapt_views_async): qr_pt_views_kernel's grid -- (footprint columns, footprint rows, views),
+ * one wave per workgroup -- with qr_pt_adapt_kernel's sample loop.  state: per view eight planes of width * height *
+ * samples-per-pixel 32-bit words, the planes of qr_pt_adapt_kernel, slot (y * width + x) * samples-per-pixel + k as in
+ * qr_pt_views_kernel: one view's block is a qr_pt_adapt_kernel state of `slots` columns.  All eight words wait in LDS (2 KB per
+ * wave); nothing of them is live in registers through a sample but the generator's state.  The rule is evaluated PER SLOT, per
+ * pixel sample and not per pixel, at the top of the wave-uniform loop; a lane outside the frame holds m = max_samples and never
+ * takes; a lane that does not take is out of the sample like a lane past the frame's edge (render_wave RAYS = 9); the wave leaves
+ * when no lane is left, so it runs as long as its slowest slot.  The update is qr_pt_adapt_kernel's, operation for operation.
+ * After the loop a column is written back only when its count is no longer the one in memory; then EVERY lane runs
+ * qr_pt_views_kernel's output step on the means read back from LDS (the FSAA reduce needs all lanes of a pixel, taken or not), the
+ * counts are reduced the same way in integers, and `open` gets one vector atomic add per wave from its first lane, none when
+ * the number is 0.
+ */
+struct PtAdaptViewsP { u32 *state; int32_t samples, min_samples, max_samples; float tol2; float *mean; int32_t *counts; u32 *open; };
+
+__global__ __launch_bounds__(QR_BLOCK, 3)
+void qr_pt_adapt_views_kernel(LaunchP lp, ViewsP vp, PtAdaptViewsP pa, uint32_t *__restrict__ frames)
+{
+    const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
+    const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
+    __shared__ u32 lds_st[QR_PT_ADAPT_STATE_WORDS][64];
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    const FrmP fr = c_frm((BaseP)lp.B);
+#pragma clang diagnostic pop
+    const int fsaa = fr->fr.fsaa;
+    const size_t slots = (size_t)vp.width * (size_t)vp.height << fsaa;      /* of one view, of one plane */
+    u32 *const st = pa.state + (size_t)view * (size_t)QR_PT_ADAPT_STATE_WORDS * slots;
+    const int max_samples = pa.max_samples, min_samples = pa.min_samples;
+    const float tol2 = pa.tol2;
+    /* lanes outside the frame hold m = max_samples: the rule never lets them take */
+    {
+        const int lane = (int)(threadIdx.x & 63u);
+        u32 w[QR_PT_ADAPT_STATE_WORDS] = {0u, 0u, 0u, 0u, (u32)max_samples, 0u, 0u, 0u};
+        int x_r, y_r, k_r;
+        if (pixel_of_view(ord, fsaa, vp, x_r, y_r, k_r))
+        {
+            const size_t si = (((size_t)y_r * (size_t)vp.width + (size_t)x_r) << fsaa) + (size_t)k_r;
+#pragma unroll
+            for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) w[p] = st[(size_t)p * slots + si];
+        }
+#pragma unroll
+        for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) lds_st[p][lane] = w[p];
+    }
+    auto rule = [&](int l) -> bool {
+        /* qr_pt_adapt_kernel's: four LDS reads, then vector compares whose lane masks are combined as scalars */
+        const u32 m = lds_st[4][l];
+        const float m2r = u2f(lds_st[5][l]), m2g = u2f(lds_st[6][l]), m2b = u2f(lds_st[7][l]);
+        float lim = (float)m * (float)(m - 1u);
+        lim = lim * tol2;
+        const bool conv = m2r <= lim && m2g <= lim && m2b <= lim;
+        return m < (u32)max_samples && (m < (u32)min_samples || m < 2u || !conv);
+    };
+#pragma nounroll
+    for (int s = 0; s < pa.samples; s++)
+    {
+        int lane_s = (int)(threadIdx.x & 63u);
+        asm volatile("" : "+v"(lane_s));            /* not an address register kept alive through the sample */
+        const bool take = rule(lane_s);
+        if (!any_lane(take)) break;
+        u32 rng = lds_st[0][lane_s];
+        V3 c;
+        render_wave<false, false, true, 9>(lp, ord, 0u, view, nullptr, nullptr, nullptr, nullptr, nullptr, &vp, &c, &rng, nullptr, take);
+        asm volatile("" : "+v"(lane_s));
+        if (take)
+        {
+            const u32 m = lds_st[4][lane_s] + 1u;
+            const float o = 1.0f / (float)m, u = 1.0f - o;
+            lds_st[4][lane_s] = m;
+            lds_st[0][lane_s] = rng;
+            const float col[3] = {c.x, c.y, c.z};
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++)
+            {
+                const float mean = u2f(lds_st[1 + ch][lane_s]);
+                const float d1 = col[ch] - mean;
+                const float a = col[ch] * o, b = mean * u;
+                const float mn = a + b;
+                const float d2 = col[ch] - mn;
+                const float p = d1 * d2;
+                lds_st[1 + ch][lane_s] = f2u(mn);
+                lds_st[5 + ch][lane_s] = f2u(u2f(lds_st[5 + ch][lane_s]) + p);
+            }
+        }
+    }
+    int lane_e = (int)(threadIdx.x & 63u);
+    asm volatile("" : "+v"(lane_e));
+    int x_e, y_e, k_e;
+    const bool inside_e = pixel_of_view(ord, fsaa, vp, x_e, y_e, k_e);
+    if (inside_e)
+    {
+        /* a slot that took a sample holds more than it came with: the count in memory says which columns to write */
+        const size_t si = (((size_t)y_e * (size_t)vp.width + (size_t)x_e) << fsaa) + (size_t)k_e;
+        if (lds_st[4][lane_e] != st[4 * slots + si])
+        {
+#pragma unroll
+            for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) st[(size_t)p * slots + si] = lds_st[p][lane_e];
+        }
+    }
+    /* XX_end 5161-5343 on the means: clamp, FSAA reduce, gamma, pack (qr_pt_views_kernel's output step), by every lane: lanes
+     * outside the frame carry zeros.  The counts take the same reduce in integers */
+    float cr = clamp1(u2f(lds_st[1][lane_e])), cg = clamp1(u2f(lds_st[2][lane_e])), cb = clamp1(u2f(lds_st[3][lane_e]));
+    int cn = inside_e ? (int)lds_st[4][lane_e] : 0;
+    if (fsaa >= 1)
+    {
+        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
+        cr = cr + __shfl_down(cr, 1); cg = cg + __shfl_down(cg, 1); cb = cb + __shfl_down(cb, 1);
+        cn = cn + __shfl_down(cn, 1);
+    }
+    if (fsaa >= 2)
+    {
+        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
+        cr = cr + __shfl_down(cr, 2); cg = cg + __shfl_down(cg, 2); cb = cb + __shfl_down(cb, 2);
+        cn = cn + __shfl_down(cn, 2);
+    }
+    if (inside_e && k_e == 0)
+    {
+        const size_t px = ((size_t)view * (size_t)vp.height + (size_t)y_e) * (size_t)vp.width + (size_t)x_e;
+        if (pa.mean != nullptr) { pa.mean[3 * px] = cr; pa.mean[3 * px + 1] = cg; pa.mean[3 * px + 2] = cb; }
+        if (pa.counts != nullptr) pa.counts[px] = cn;
+        if (fr->fr.ctx_flags & QR_PROP_GAMMA)
+        {
+            asm volatile("" ::: "memory");
+            cr = __builtin_sqrtf(cr); cg = __builtin_sqrtf(cg); cb = __builtin_sqrtf(cb);
+        }
+        const float cl = fr->fr.clamp; const u32 cmask = fr->fr.cmask;
+        cr = cr * cl; cg = cg * cl; cb = cb * cl;
+        frames[px] = (((u32)cvt_near(cr) & cmask) << 16) | (((u32)cvt_near(cg) & cmask) << 8) | ((u32)cvt_near(cb) & cmask);
+    }
+    if (pa.open != nullptr)
+    {
+        const unsigned long long still = __ballot(rule(lane_e));
+        if (still != 0ull && lane_e == 0) atomicAdd(pa.open, (u32)__popcll(still));
     }
 }
 

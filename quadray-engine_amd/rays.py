@@ -539,6 +539,50 @@ def pt_adapt_fold_list(state, index, count, cols, rngs, min_samples, max_samples
     return st, rgb, op
 
 
+# ---- adaptive path-traced views (include/qrhip.h qr_pt_adapt_views_async; Scene.pt_adaptive_views): the outputs in numpy ----
+# The fold itself is pt_adapt_fold on every state[j]: one view's block is an adaptive ray state of `slots` columns.
+
+def _pt_adapt_view_state(state):
+    st = np.ascontiguousarray(state)
+    if st.ndim == 2:
+        st = st[None]
+    if st.ndim != 3 or st.shape[1] != 8 or st.dtype.itemsize != 4:
+        raise ValueError("an adaptive view state is [N, 8, slots] (or [8, slots]) of 32-bit words")
+    return st.view(np.uint32)
+
+
+def pt_adapt_view_counts(state, spp):
+    """The sample heat map of qr_pt_adapt_views_async (counts_dev) for a state [N, 8, slots] (or one view's [8, slots]): int32
+    [N, H * W], per pixel the sum of plane 4 over its `spp` slots (slot = pixel * spp + k)."""
+    st = _pt_adapt_view_state(state)
+    spp = int(spp)
+    if spp < 1 or st.shape[2] % spp != 0:
+        raise ValueError("the slots of a view are pixels * samples per pixel")
+    m = st[:, 4].astype(np.int64).reshape(st.shape[0], st.shape[2] // spp, spp)
+    return m.sum(axis=2).astype(np.int32)
+
+
+def pt_adapt_view_frames(state, blob, width, height):
+    """The frames and means of qr_pt_adapt_views_async for a state [N, 8, slots] (or one view's [8, slots]) of the snapshot
+    `blob` (its FSAA, gamma, clamp and mask): the output step on planes 1..3 -- clamp1 and the FSAA reduce (reduce_colors),
+    then gamma, scale, round, mask and pack (pack_linear).  Returns (frames uint32 [N, height, width], mean float32
+    [N, height, width, 3])."""
+    st = _pt_adapt_view_state(state)
+    _, i = frame_record(blob)
+    ns = 1 << int(i[_F_FSAA])
+    w, h = int(width), int(height)
+    if st.shape[2] != w * h * ns:
+        raise ValueError(f"the state holds {st.shape[2]} slots per view, the frame {w * h * ns}")
+    frames = np.empty((st.shape[0], h, w), dtype=np.uint32)
+    mean = np.empty((st.shape[0], h, w, 3), dtype=np.float32)
+    for j in range(st.shape[0]):
+        rgb = st[j, 1:4].view(np.float32).T.reshape(w * h, ns, 3).transpose(1, 0, 2)       # [ns, P, 3]: sample k in row k
+        lin = reduce_colors(np.ascontiguousarray(rgb), blob)
+        mean[j] = lin.reshape(h, w, 3)
+        frames[j] = pack_linear(lin, blob, w, h)
+    return frames, mean
+
+
 # ---- hit records (include/qrhip.h qr_hit; Scene.hits, Scene.view_hits): float32 [..., 12] = pos xyz, t, nrm xyz, id, alb xyz, mat ----
 
 def hit_fields(h):

@@ -15,6 +15,7 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     register or has a larger private segment than the scene's own path-tracer kernel (2128 B);
   * the path-traced ray kernel qr_pt_rays_kernel exceeds that same budget;
   * the adaptive path-traced ray kernel qr_pt_adapt_kernel exceeds that same budget;
+  * the adaptive path-traced view kernel qr_pt_adapt_views_kernel exceeds that same budget;
   * the indexed adaptive kernel qr_pt_list_kernel exceeds that same budget, or one of the three open-list kernels
     (qr_openlist.hpp) spills a vector register or has a private segment;
   * a hit-record instance qr_hit_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more than
@@ -61,6 +62,9 @@ LIMITS = {
     "18qr_pt_adapt_kernel": (168, 0, 2128),
     # indexed adaptive path-traced rays (qr_kernel.hpp qr_pt_list_kernel): that kernel with its rays taken from a list: the same budget
     "17qr_pt_list_kernel": (168, 0, 2128),
+    # adaptive path-traced views (qr_kernel.hpp qr_pt_adapt_views_kernel): qr_pt_views_kernel's grid and output step around the
+    # adaptive ray kernel's sample loop: the same budget
+    "24qr_pt_adapt_views_kernel": (168, 0, 2128),
     # the open list (qr_openlist.hpp): a rule, a ballot and a scan: nothing spilled, no private segment
     "20qr_open_count_kernel": (128, 0, 0),
     "19qr_open_scan_kernel": (128, 0, 0),
