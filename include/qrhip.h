@@ -731,6 +731,50 @@ int qr_fan_hits_async(qr_device_scene *scn, const qr_hit *hits_dev, int64_t n, c
                       float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream);
 
 /*
+ * Gather fans: from every surface point a fan of K SHADED rays along ONE direction table, answered as one weighted sum of the
+ * renderer's colours per point, in one launch -- final gather, one-bounce diffuse irradiance, lightmap and probe baking, sky light
+ * weighted by visibility, glossy pre-integration.  What a host would otherwise build from qr_hit_views_async, N x K qr_ray rows
+ * of its own, qr_shade_rays_async and a reduction; here no hit record, ray or per-direction colour reaches memory.
+ * The three entry points mirror the occlusion fans': sources, limits, alignment rules, eps and reach, k in 1..QR_FAN_MAX_DIRS
+ * and the n == 0 / n_views == 0 behaviour are exactly those of the matching qr_fan_*_async call.  The differences:
+ *   - dirs_dev: k qr_gather_dir records, the layout of qr_fan_dir with the fourth word read: the direction's weight.
+ *   - Per element, for j = 0 .. k-1 in table order: dot, the TRACED rule and the ray (pos, eps, +-d, reach) are exactly the
+ *     occlusion fan's for (element, j) (quadray-engine_amd/rays.py fan_rays): without QR_FAN_FLIP traced iff the element has
+ *     a surface point and 0 < dot; with it every direction of a surface point, as -d where dot < 0.  An untraced direction does
+ *     nothing (it adds no + 0).  For a traced one, col = the three floats qr_shade_rays_async returns for that qr_ray: the
+ *     ray-query list, then the renderer's shading and recursion at the scene's current depth, linear, before the output step.
+ *     wgt = weight; with QR_GATHER_COSINE wgt = weight * c, c = dot without QR_FAN_FLIP and (dot < 0 ? -dot : dot) with it:
+ *     one fp32 multiply.  Then acc.r = acc.r + col.r * wgt, likewise g and b (one fp32 multiply, then one fp32 add, never
+ *     fused), acc.w = acc.w + wgt, cnt += 1.
+ *   - Start: acc = (+0, +0, +0, +0), cnt = 0.  With QR_GATHER_RESUME acc and cnt start from the element's row of gather_dev and
+ *     its word of count_dev instead: a table cut into consecutive chunks and sent in resumed calls gives the bits of one call.
+ *   - gather_dev: float32 [elements][4] (acc; 16-byte aligned: one 16-byte store per element); count_dev: int32 [elements]
+ *     (4-byte aligned), the number of traced directions.  Both required.  An element without a surface point gets a zero row
+ *     and count -1, with or without QR_GATHER_RESUME.
+ *   - An element's result depends on nothing but its own ray, pixel or record, the table and the scene: not on neighbouring
+ *     elements, on which of them trace a direction, on other views or on QR_TRACE_COHERENT.
+ *   - A scene in its own path-tracer mode gives QR_ERR_UNSUP, as qr_shade_rays_async does; so does one uploaded without
+ *     QR_UPLOAD_RAY_QUERIES.  Unknown flags, null or misaligned pointers, k, n or sizes out of range, a NaN eps or reach give
+ *     QR_ERR_ARG.  A refused call launches nothing and writes nothing.
+ * qr_gather_rays_async: an element is the first hit of ray i; flags QR_TRACE_COHERENT | QR_FAN_FLIP | QR_GATHER_COSINE |
+ * QR_GATHER_RESUME.  qr_gather_views_async: an element is a pixel of a caller camera (sample 0's ray under FSAA), elements
+ * [n_views][height][width]; flags QR_FAN_FLIP | QR_GATHER_COSINE | QR_GATHER_RESUME.  qr_gather_hits_async: an element is a
+ * caller qr_hit record (pos, nrm, id are read); the same flags.  Asynchronous on `stream`, on the scene's own device.
+ */
+typedef struct qr_gather_dir { float dir[3]; float weight; } qr_gather_dir;     /* 16 bytes */
+
+#define QR_GATHER_COSINE 4u     /* the weight of a traced direction is weight * |nrm . d| (weight * (nrm . d) without QR_FAN_FLIP) */
+#define QR_GATHER_RESUME 8u     /* acc and cnt start from gather_dev and count_dev instead of zero */
+
+int qr_gather_rays_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+                         float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream);
+int qr_gather_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
+                          const qr_gather_dir *dirs_dev, int k, float eps, float reach, float *gather_dev, int32_t *count_dev,
+                          uint32_t flags, void *stream);
+int qr_gather_hits_async(qr_device_scene *scn, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+                         float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream);
+
+/*
  * Hit layers: the first k hits along a ray, in order, in one launch -- picking through glass and x-ray selection, thickness and
  * entry / exit pairs of a solid, order-independent transparency, CSG inspection, layered depth images for reprojection, "how many
  * surfaces lie between A and B".  What a host would otherwise loop over qr_trace_rays_async, reading the rays again for every

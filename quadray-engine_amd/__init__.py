@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "qr_pt_adapt_views_state_bytes", "qr_pt_adapt_views_reset", "qr_pt_adapt_views_async",
     "qr_pt_adapt_list_work_bytes", "qr_pt_adapt_open_list_async", "qr_pt_adapt_list_rays_async", "qr_hit_rays_async", "qr_hit_views_async",
     "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async", "qr_layer_rays_async", "qr_layer_views_async",
+    "qr_gather_rays_async", "qr_gather_views_async", "qr_gather_hits_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -41,6 +42,8 @@ TRACE_COHERENT = 1          # qr_trace_rays_async / qr_occluded_async flag: cons
 MEAN_RESUME = 1             # qr_render_views_mean_async flag: the sum starts from the `sum` buffer's contents
 FAN_FLIP = 2                # qr_fan_*_async flag: every direction is traced, mirrored into the normal's hemisphere
 FAN_MAX_DIRS = 1024         # QR_FAN_MAX_DIRS
+GATHER_COSINE = 4           # qr_gather_*_async flag: a direction's weight is weight * |nrm . d| (weight * (nrm . d) without FAN_FLIP)
+GATHER_RESUME = 8           # qr_gather_*_async flag: the sums and counts start from the output buffers' contents
 PT_VIEWS_MAX_SAMPLES = 512  # QR_PT_VIEWS_MAX_SAMPLES: the most samples of one qr_pt_views_async launch
 PT_VIEWS_STATE_WORDS = 4    # QR_PT_VIEWS_STATE_WORDS: 32-bit planes per view of a path-traced view state
 PT_RAYS_MAX_SAMPLES = 512   # QR_PT_RAYS_MAX_SAMPLES: the most samples of one qr_pt_rays_async launch
@@ -137,6 +140,9 @@ def lib():
     L.qr_fan_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
     L.qr_fan_hits_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
     L.qr_fan_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    L.qr_gather_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    L.qr_gather_hits_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    L.qr_gather_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
     L.qr_layer_rays_async.argtypes = [vp, vp, ctypes.c_int64, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_layer_views_async.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
@@ -564,6 +570,95 @@ class Scene:
                                        ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
                                        FAN_FLIP if flip else 0, self._stream_ptr(stream)))
         return (opn, msk) if mask else opn
+
+    def _gather_args(self, dirs, eps, reach, shape, out, count, resume):
+        """(dirs as a contiguous float32 [K, 4] tensor, K, eps, reach, gather, count) of a gather-fan call whose elements have
+        `shape`; [K, 3] tables get weight 1.0"""
+        import math
+        import torch
+        if resume and (out is None or count is None):
+            raise QrError("resume=True needs both buffers: out (the sums so far) and count")
+        shape = tuple(shape)
+        for name, buf, want, dt in (("out", out, shape + (4,), torch.float32), ("count", count, shape, torch.int32)):
+            if buf is not None and not (isinstance(buf, torch.Tensor) and buf.dtype == dt and tuple(buf.shape) == want
+                                        and buf.is_contiguous() and buf.is_cuda and buf.device.index == self.device):
+                raise QrError(f"{name} must be a contiguous {str(dt).replace('torch.', '')} {list(want)} tensor on cuda:{self.device}")
+        if not (isinstance(dirs, torch.Tensor) and dirs.dtype == torch.float32 and dirs.dim() == 2 and dirs.shape[1] in (3, 4)
+                and dirs.is_cuda and dirs.device.index == self.device):
+            raise QrError(f"dirs must be a float32 [K, 3] or [K, 4] tensor on cuda:{self.device}")
+        k = dirs.shape[0]
+        if not 1 <= k <= FAN_MAX_DIRS:
+            raise QrError(f"dirs must hold 1..{FAN_MAX_DIRS} directions, got {k}")
+        if eps is None or math.isnan(eps) or math.isnan(reach):
+            raise QrError("eps (the step off the surface, in units of |dir|) is required; eps and reach must not be NaN")
+        if dirs.shape[1] == 3:
+            d4 = torch.ones((k, 4), dtype=torch.float32, device=dirs.device)
+            d4[:, 0:3] = dirs
+        else:
+            d4 = dirs.contiguous()
+        if out is None:
+            out = torch.empty(shape + (4,), dtype=torch.float32, device=dirs.device)    # every element is written
+        if count is None:
+            count = torch.empty(shape, dtype=torch.int32, device=dirs.device)
+        return d4, k, float(eps), float(reach), out, count
+
+    @staticmethod
+    def _gather_flags(flip, cosine, resume, coherent=False):
+        return ((TRACE_COHERENT if coherent else 0) | (FAN_FLIP if flip else 0) | (GATHER_COSINE if cosine else 0)
+                | (GATHER_RESUME if resume else 0))
+
+    def gather(self, rays, dirs, eps, reach=float("inf"), flip=False, cosine=False, coherent=False, out=None, count=None,
+               resume=False, stream=None):
+        """Gather fans from the first hits of caller rays (qr_gather_rays_async): for every ray, the surface point hits() gives
+        and from it one SHADED ray per row of `dirs` (float32 [K, 4] on the scene's device: direction xyz, weight; [K, 3]: weight
+        1.0; K <= 1024, shared by all rays), folded into one weighted sum per ray in ONE launch: no hit record, fan ray or
+        per-direction colour reaches memory.  Direction k is traced as for occlusion() (rays.fan_rays: iff 0 < nrm . dirs[k];
+        flip=True: always, as -dirs[k] where the dot product is negative); its colour is what shade() returns for the ray
+        (pos, eps, +-dirs[k], reach), at the scene's current depth; its weight is dirs[k, 3], times the dot product (its
+        absolute value with flip) with cosine=True.  rays.gather_fold states the sum exactly.
+        Returns (gather float32 [N, 4]: sum of colour * weight in r, g, b and the sum of weights in w; count int32 [N]: traced
+        directions, -1 and a zero row where the ray hits nothing).  out, count: buffers to write into; resume=True (needs
+        both): the sums and counts start from their contents, so that a table sent in consecutive chunks gives the bits of
+        one call.  coherent: as for trace(); results do not depend on it.  Asynchronous on `stream`."""
+        rays = self._rays_arg(rays)
+        n = rays.shape[0]
+        d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, (n,), out, count, resume)
+        _check(lib().qr_gather_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
+                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                          self._gather_flags(flip, cosine, resume, coherent), self._stream_ptr(stream)))
+        return out, count
+
+    def view_gather(self, views, dirs, width=None, height=None, eps=None, reach=float("inf"), flip=False, cosine=False,
+                    out=None, count=None, resume=False, stream=None):
+        """Gather fans from every pixel of caller-supplied cameras (qr_gather_views_async): one-bounce irradiance or sky light
+        of whole frames in one launch.  views, width, height as for view_hits -- the surface point of a pixel is its record
+        there (sample 0's under FSAA) -- the rest as for gather(); eps is required.  Returns (gather float32 [N, H, W, 4],
+        count int32 [N, H, W]).  Asynchronous on `stream`."""
+        w, h = self._views_arg(views, width, height)
+        n = views.shape[0]
+        d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, (n, h, w), out, count, resume)
+        _check(lib().qr_gather_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k, eps,
+                                           reach, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                           self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))
+        return out, count
+
+    def hit_gather(self, hits, dirs, eps, reach=float("inf"), flip=False, cosine=False, out=None, count=None, resume=False,
+                   stream=None):
+        """Gather fans from caller-supplied hit records (qr_gather_hits_async): hits as for hit_occlusion() (float32 [..., 12]:
+        pos in columns 0:3, nrm in 4:7, the int32 bits of an id >= 0 in column 7) -- lightmap texels, probes, a second bounce.
+        No first walk.  The rest as for gather().  Returns (gather float32 [..., 4], count int32 [...]).  Asynchronous on
+        `stream`."""
+        import torch
+        if not (isinstance(hits, torch.Tensor) and hits.dtype == torch.float32 and hits.dim() >= 2 and hits.shape[-1] == 12
+                and hits.is_contiguous() and hits.is_cuda and hits.device.index == self.device):
+            raise QrError(f"hits must be a contiguous float32 [..., 12] tensor on cuda:{self.device} (qr_hit records)")
+        shape = tuple(hits.shape[:-1])
+        n = hits.numel() // 12
+        d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, shape, out, count, resume)
+        _check(lib().qr_gather_hits_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
+                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                          self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))
+        return out, count
 
     def _layer_args(self, k, shape, t, ids, hits, device):
         """(k, count, t or None, ids or None, hits or None) of a hit-layer call whose elements have `shape`"""

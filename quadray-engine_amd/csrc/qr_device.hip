@@ -11,6 +11,7 @@
 #include "qr_query.hpp"
 #include "qr_hitrec.hpp"
 #include "qr_fan.hpp"
+#include "qr_gather.hpp"
 #include "qr_layers.hpp"
 #include "qr_openlist.hpp"
 
@@ -1089,6 +1090,115 @@ extern "C" int qr_fan_views_async(qr_device_scene *s, const qr_view *views_dev, 
     else
         hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_VIEW, false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
                            vp, fp, s->lp.stats);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+/* ---- gather fans (qr_gather.hpp): per surface point, the weighted sum of the renderer's colours along a shared table ---- */
+
+/* what the three entry points check alike before the element count decides whether anything is launched: the fans' checks, then
+ * what qr_shade_rays_async refuses */
+static int gather_args(const qr_device_scene *s, int k, float eps, float reach, uint32_t flags, uint32_t allowed)
+{
+    { const int rc = fan_args(s, k, eps, reach, flags, allowed | QR_FAN_FLIP | QR_GATHER_COSINE | QR_GATHER_RESUME); if (rc != QR_OK) return rc; }
+    if (s->pt_on) return qr_fail(QR_ERR_UNSUP, "scene is in path-tracer mode: fan rays carry no sample seeds");
+    return QR_OK;
+}
+
+/* ... and once there are elements: src is the ray, view or record array */
+static int gather_ptrs(const void *src, const qr_gather_dir *dirs, const float *gather, const int32_t *count)
+{
+    if (src == nullptr || dirs == nullptr || gather == nullptr || count == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if ((((uintptr_t)src | (uintptr_t)dirs | (uintptr_t)gather) & 15u) != 0)
+        return qr_fail(QR_ERR_ARG, "rays, views, hits, dirs and gather must be 16-byte aligned");
+    if (((uintptr_t)count & 3u) != 0) return qr_fail(QR_ERR_ARG, "count must be 4-byte aligned");
+    return QR_OK;
+}
+
+static GatherP gather_params(const qr_gather_dir *dirs, int k, float eps, float reach, float *gather, int32_t *count, uint32_t flags)
+{
+    GatherP gp;
+    gp.dirs = dirs; gp.k = k;
+    gp.flip = flags & QR_FAN_FLIP; gp.cosine = flags & QR_GATHER_COSINE; gp.resume = flags & QR_GATHER_RESUME;
+    gp.eps = eps; gp.reach = reach > FLT_MAX ? FLT_MAX : reach;     /* +inf is taken as FLT_MAX, as in qr_shade_rays_async */
+    gp.gather = (f32x4 *)gather; gp.count = count;
+    return gp;
+}
+
+extern "C" int qr_gather_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+                                    float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
+    { const int rc = gather_args(s, k, eps, reach, flags, QR_TRACE_COHERENT); if (rc != QR_OK) return rc; }
+    if (n == 0) return QR_OK;
+    { const int rc = gather_ptrs(rays_dev, dirs_dev, gather_dev, count_dev); if (rc != QR_OK) return rc; }
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    const f32x4 *r = (const f32x4 *)rays_dev;
+    const ViewsP vp = {};
+    const GatherP gp = gather_params(dirs_dev, k, eps, reach, gather_dev, count_dev, flags);
+    /* the per-lane walk instance, as qr_shade_rays_async */
+    if (flags & QR_TRACE_COHERENT)
+        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_RAYS, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, r,
+                           (int32_t)n, vp, gp);
+    else
+        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_RAYS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, r,
+                           (int32_t)n, vp, gp);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+extern "C" int qr_gather_hits_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+                                    float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "record count must be 0..INT32_MAX");
+    { const int rc = gather_args(s, k, eps, reach, flags, 0u); if (rc != QR_OK) return rc; }
+    if (n == 0) return QR_OK;
+    { const int rc = gather_ptrs(hits_dev, dirs_dev, gather_dev, count_dev); if (rc != QR_OK) return rc; }
+    HIP_TRY(hipSetDevice(s->device));
+    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
+    const ViewsP vp = {};
+    const GatherP gp = gather_params(dirs_dev, k, eps, reach, gather_dev, count_dev, flags);
+    hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_HITS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp,
+                       (const f32x4 *)hits_dev, (int32_t)n, vp, gp);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+extern "C" int qr_gather_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                     const qr_gather_dir *dirs_dev, int k, float eps, float reach, float *gather_dev, int32_t *count_dev,
+                                     uint32_t flags, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
+    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
+        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
+    { const int rc = gather_args(s, k, eps, reach, flags, 0u); if (rc != QR_OK) return rc; }
+    {
+        /* the limit of qr_fan_views_async */
+        const int fsaa = s->fr.fsaa;
+        const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
+        if ((int64_t)n_views * ((width + fw - 1) / fw) * ((height + fh - 1) / fh) > (int64_t)QR_VIEW_MAX_WAVES)
+            return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
+    }
+    if (n_views == 0) return QR_OK;
+    { const int rc = gather_ptrs(views_dev, dirs_dev, gather_dev, count_dev); if (rc != QR_OK) return rc; }
+    HIP_TRY(hipSetDevice(s->device));
+    /* one lane per pixel: 8x8 footprints at every FSAA, as qr_fan_views_async */
+    const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
+    ViewsP vp;
+    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
+    const GatherP gp = gather_params(dirs_dev, k, eps, reach, gather_dev, count_dev, flags);
+    const f32x4 *none = nullptr;
+    /* the instance is chosen as qr_render_views_async chooses its own */
+    if (s->divk)
+        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_VIEW, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, none, 0,
+                           vp, gp);
+    else
+        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_VIEW, false, true, QR_MIN_WAVES_PER_SIMD>), grid, block, 0, (hipStream_t)stream, s->lp, none, 0,
+                           vp, gp);
     HIP_TRY(hipGetLastError());
     return QR_OK;
 }

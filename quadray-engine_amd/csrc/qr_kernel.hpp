@@ -330,6 +330,11 @@ __device__ __forceinline__ bool pixel_of_view(u32 ord, int fsaa, const ViewsP &v
  * subset of one footprint's primary rays, and the flag only chooses among walks that solve the same surfaces in the same order
  * with the same arithmetic (traverse) -- nothing in that round reads a neighbour lane's ray or needs one alive, which the partial
  * footprints at a frame's right and bottom edges already rest on.
+ * RAYS = 10 (gather fans, qr_gather_kernel in qr_gather.hpp): RAYS = 1's machine on ONE ray per lane that the caller supplies in
+ * registers (`ray_in`: origin, direction, tmin, tmax already taken as FLT_MAX for +inf; the list is set here).  A lane is inside
+ * only when it has such a ray (`take`); a lane that has none is a lane past n, as for RAYS = 7.  The first round is `coherent`
+ * where the caller says so (`coh_in`: the fan kernel's rule).  The linear colour comes back in `mean_out`; no id, no depth, no
+ * store, and nothing is read from global memory for the ray.
  */
 template <bool COUNT, bool DIVK, bool PT = false, int RAYS = 0>
 __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, const u32 sched_head, const int gw,
@@ -337,13 +342,15 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
                                             unsigned long long *__restrict__ counters, const PtParams *ptp = nullptr,
                                             const RaysP *rp = nullptr, const ViewsP *vp = nullptr, V3 *mean_out = nullptr,
                                             u32 *rng_io = nullptr, const PtRaysP *pr = nullptr, const bool take = true,
-                                            const u32 ray_i = 0u)
+                                            const u32 ray_i = 0u, const Ray *ray_in = nullptr, const bool coh_in = false)
 {
     constexpr bool CALLER_RAYS = RAYS == 1 || RAYS == 2, VIEW = RAYS == 3 || RAYS == 4 || RAYS == 5 || RAYS == 9, MEAN = RAYS == 4;
     constexpr bool PTV = RAYS == 5 || RAYS == 9, PTVA = RAYS == 9, PTR = RAYS == 6 || RAYS == 7 || RAYS == 8, PTA = RAYS == 7, PTL = RAYS == 8;
+    constexpr bool GATHER = RAYS == 10;
     static_assert(!PTV || PT, "the path-traced view instance is a path-tracer instance");
     static_assert(!PTR || PT, "the path-traced ray instance is a path-tracer instance");
-    (void)mean_out; (void)rng_io; (void)pr; (void)take; (void)ray_i;
+    static_assert(!GATHER || !PT, "the gather instance is a ray-tracer instance");
+    (void)mean_out; (void)rng_io; (void)pr; (void)take; (void)ray_i; (void)ray_in; (void)coh_in;
 #ifdef QR_WAVETIME
     const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
     const unsigned long long wt_clk0 = __builtin_amdgcn_s_memtime();      /* shader cycles: with the 100 MHz stamps, the clock the wave ran at */
@@ -393,6 +400,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     else if constexpr (PTA) inside = (u32)gw * 64u + (u32)lane < (u32)pr->n && take;
     else if constexpr (PTL) inside = take;
     else if constexpr (PTR) inside = (u32)gw * 64u + (u32)lane < (u32)pr->n;
+    else if constexpr (GATHER) inside = take;
     else
     {
         inside = x < frm_w && y < fr->fr.frm_h && y >= lp.row_begin && y < lp.row_end;
@@ -432,7 +440,16 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
 
     u32 rng = 0;                                /* PT: this sample's LCG state */
     Ray ray;
-    if constexpr (PTR)
+    if constexpr (GATHER)
+    {
+        /* the caller's ray, from its registers: a caller ray's fields (no originating surface), the ray-query list */
+        ray.org = ray_in->org; ray.tmin = ray_in->tmin;
+        ray.dir = ray_in->dir; ray.tmax = ray_in->tmax;
+        ray.list = inside ? fr->off_query : 0u;
+        ray.osrf = 0; ray.oflg = 0;
+        ray.ploc = {0, 0, 0};
+    }
+    else if constexpr (PTR)
     {
         /* the caller's ray as below, then the sample's jitter along the ray's spread: two draws, horizontal first, through the
          * tent filter of the frame's samples (tracer.cpp:1218-1285) without the FSAA halving -- caller rays have none; every
@@ -632,7 +649,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
                 if (prio_round < 3) { prio_round++; if (prio_round == 2) __builtin_amdgcn_s_setprio(2); else if (prio_round == 3) __builtin_amdgcn_s_setprio(3); }
 #endif
             /* coherent: every ray of this round is a primary ray (neighbouring pixels; caller rays only when vouched for) */
-            const bool coherent = (RAYS != 1 && RAYS != 6 && RAYS != 7 && RAYS != 8) && !any_lane(tr && sp != 0);
+            const bool coherent = (GATHER ? coh_in : (RAYS != 1 && RAYS != 6 && RAYS != 7 && RAYS != 8)) && !any_lane(tr && sp != 0);
             traverse<false, DIVK, RAYS != 0>(B, tr, coherent, ray, h, occ
 #ifdef QR_STATS
                             , cx.stats
@@ -870,6 +887,12 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
         /* the sample's colour and the generator's state go back to the caller's loop: the running mean is taken there */
         *mean_out = ret;
         *rng_io = rng;
+        return;
+    }
+    if constexpr (GATHER)
+    {
+        /* the ray's linear colour goes back to the caller's loop: the weighted sum is taken there */
+        *mean_out = ret;
         return;
     }
     if constexpr (PT && !PTV && !PTR)

@@ -15,7 +15,9 @@ only where the engine's tiles hold other surfaces than its global list):
 Scene.hits / Scene.view_hits return hit records (qr_hit: position, t, normal, id, albedo, material); hit_fields splits them into
 typed views, offset_rays and reflect_rays build a host's own secondary rays from them.  Fans of many visibility rays per hit
 (ambient occlusion, sky visibility) need no rays: Scene.occlusion / view_occlusion / hit_occlusion trace a shared direction table
-(sphere_dirs) from every hit in one launch; fan_rays states what they trace, fan_bits unpacks their masks.  Scene.trace_layers /
+(sphere_dirs) from every hit in one launch; fan_rays states what they trace, fan_bits unpacks their masks.  Scene.gather /
+view_gather / hit_gather SHADE the same fans and return one weighted sum of colours per hit (final gather, irradiance, lightmap
+and probe baking); gather_fold states the sum.  Scene.trace_layers /
 Scene.view_layers give the first k hits along a ray, in order, in one launch; layers_of states them as a composition of trace(),
 next_rays builds the rays that resume a layered ray where a call stopped.
 
@@ -712,6 +714,51 @@ def sphere_dirs(n):
     phi = i * np.pi * (3.0 - np.sqrt(5.0))
     s = np.sqrt(1.0 - z * z)
     return np.stack([s * np.cos(phi), s * np.sin(phi), z], axis=1).astype(np.float32)
+
+
+# ---- gather fans (include/qrhip.h qr_gather_*_async; Scene.gather, Scene.view_gather, Scene.hit_gather) ----
+
+def gather_fold(hits, dirs, colours, flip=False, cosine=False, start=None):
+    """The sum a gather fan takes, in float32 numpy: hits float32 [N, 12], dirs float32 [K, 4] (direction xyz, weight) or
+    [K, 3] (weight 1.0), colours float32 [N, K, 3]: entry (i, k) is what Scene.shade returns for fan_rays' ray (i, k); entries
+    of untraced rays are not read.  Returns (gather float32 [N, 4], count int32 [N]).
+
+    For hit i, k = 0 .. K-1 in table order, with fan_rays' dot = (nrm.x * d.x + nrm.y * d.y) + nrm.z * d.z and its traced rule
+    (flip=False: the record is a hit and 0 < dot; flip=True: the record is a hit): an untraced direction does nothing; a traced
+    one has wgt = weight, with cosine=True wgt = weight * c where c = dot without flip and (-dot if dot < 0 else dot) with it,
+    then acc.rgb = acc.rgb + colour * wgt (one float32 multiply, then one float32 add), acc.w = acc.w + wgt, count += 1.
+    acc and count start from zero, or from start = (gather, count) of an earlier call: a table cut into consecutive chunks and
+    folded one after the other gives the bits of one fold.  A record that is no hit (id < 0) gets a zero row and count -1,
+    whatever `start` holds."""
+    hits, dirs, colours = np.asarray(hits), np.asarray(dirs), np.asarray(colours)
+    _, traced = fan_rays(hits, dirs, np.float32(0.0), flip=flip)
+    n, k = traced.shape
+    if colours.dtype != np.float32 or colours.shape != (n, k, 3):
+        raise ValueError(f"colours must be float32 [{n}, {k}, 3], got {colours.dtype} {list(colours.shape)}")
+    _, _, nrm, hid, _, _ = hit_fields(hits)
+    weight = dirs[:, 3] if dirs.shape[1] == 4 else np.ones(k, dtype=np.float32)
+    if start is None:
+        acc, cnt = np.zeros((n, 4), dtype=np.float32), np.zeros(n, dtype=np.int32)
+    else:
+        acc, cnt = np.asarray(start[0]), np.asarray(start[1])
+        if acc.dtype != np.float32 or acc.shape != (n, 4) or cnt.dtype != np.int32 or cnt.shape != (n,):
+            raise ValueError(f"start must be (float32 [{n}, 4], int32 [{n}])")
+        acc, cnt = acc.copy(), cnt.copy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        for j in range(k):
+            t = traced[:, j]
+            wgt = np.full(n, weight[j], dtype=np.float32)
+            if cosine:
+                dot = (nrm[:, 0] * dirs[j, 0] + nrm[:, 1] * dirs[j, 1]) + nrm[:, 2] * dirs[j, 2]
+                wgt = wgt * (np.where(dot < 0, -dot, dot) if flip else dot)
+            prod = colours[:, j, :] * wgt[:, None]
+            acc[t, 0:3] = (acc[:, 0:3] + prod)[t]
+            acc[t, 3] = (acc[:, 3] + wgt)[t]
+            cnt[t] += 1
+    miss = hid < 0
+    acc[miss] = 0.0
+    cnt[miss] = -1
+    return acc, cnt
 
 
 # ---- hit layers (include/qrhip.h qr_layer_*_async; Scene.trace_layers, Scene.view_layers) ----

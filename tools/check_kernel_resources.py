@@ -22,6 +22,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     168 VGPRs (128: the view instance with packet walks only);
   * an occlusion-fan instance qr_fan_kernel<SRC, DIVK, COHERENT> spills a vector register, has a private segment, or uses more
     than 168 VGPRs (128: the view instance with packet walks only and the instance that reads caller records);
+  * a gather-fan instance qr_gather_kernel<SRC, DIVK, COHERENT, WAVES> exceeds the budget of the ray-shading or view-rendering
+    instance whose machine it runs (168 VGPRs, 128 for the view instance with packet walks only; QR_MAX_DIVK_SPILL; 640 B);
   * a hit-layer instance qr_layer_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more
     than 168 VGPRs (128: the view instance with packet walks only);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
@@ -85,6 +87,14 @@ LIMITS = {
     "13qr_fan_kernelILi1ELb1ELb1EE": (168, 0, 0),
     "13qr_fan_kernelILi1ELb0ELb1EE": (128, 0, 0),
     "13qr_fan_kernelILi2ELb1ELb0EE": (128, 0, 0),
+    # gather fans (qr_gather.hpp qr_gather_kernel<SRC, DIVK, COHERENT, WAVES>): a fan kernel's first walk and loop around the ray
+    # shading machine, with point, normal, sums and count parked in LDS across it: held to the budget of the shading instance each
+    # one runs (qr_shade_rays_kernel for caller rays and records, qr_render_views_kernel<DIVK, WAVES> for views)
+    "16qr_gather_kernelILi0ELb1ELb0ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "16qr_gather_kernelILi0ELb1ELb1ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "16qr_gather_kernelILi2ELb1ELb0ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "16qr_gather_kernelILi1ELb1ELb1ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "16qr_gather_kernelILi1ELb0ELb1ELi4EE": (128, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
     # hit layers (qr_layers.hpp qr_layer_kernel<VIEW, DIVK, COHERENT>): a hit-record instance's walk and surface point in a loop over
     # the layers, with the ray, the count and the alive flag live across it: nothing spilled, no private segment, and no more
     # registers than the hit-record instance each one mirrors
