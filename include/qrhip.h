@@ -775,6 +775,60 @@ int qr_gather_hits_async(qr_device_scene *scn, const qr_hit *hits_dev, int64_t n
                          float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream);
 
 /*
+ * Framed fans: the occlusion fans and the gather fans with the direction table given in every surface point's OWN frame --
+ * local +z is the element's normal -- and, if wanted, turned about the normal by a spin per element.  A cosine-distributed
+ * hemisphere about the normal (ambient occlusion and diffuse irradiance at half the directions, no QR_GATHER_COSINE needed), no
+ * direction wasted below the surface, and a per-pixel rotation of the kernel, which turns the banding of one shared table into
+ * noise that a denoiser or an accumulation over calls removes.  Six entry points, each the matching unframed call with one
+ * parameter more after k; flags, limits, alignment rules, the n == 0 / n_views == 0 behaviour, outputs and refusals are exactly
+ * those of the matching call.  The differences:
+ *   - spin_dev: float32 [elements][2] = (c, sn), DEVICE memory, 8-byte aligned (else QR_ERR_ARG), indexed exactly as open_dev /
+ *     count_dev; it need not be unit length (c = cos, sn = sin of the turn is the intended use).  NULL: every element has
+ *     (1.0f, 0.0f), through the same operations.
+ *   - The frame, once per element, from its normal n = (nx, ny, nz) -- the unframed call's nrm -- all in fp32, the division
+ *     correctly rounded, nothing fused (the branchless basis of Duff et al. 2017 in this operation order):
+ *         s  = nz < 0 ? -1 : 1                       (-0.0 and NaN give +1)
+ *         a  = -1 / (s + nz)
+ *         b  = (nx * ny) * a
+ *         t  = ( 1 + ((s * nx) * nx) * a,   s * b,   -(s * nx) )
+ *         bt = ( b,   s + (ny * ny) * a,   -ny )
+ *         u  = t * c + bt * sn        per component: two products, then one add
+ *         v  = bt * c - t * sn        per component: two products, then one subtract
+ *     The frame is VALID iff every word of n, u and v satisfies |w| <= FLT_MAX.
+ *   - For direction j the table row is (x, y, z, w).  dot = z: the cosine is the table's own, it is not recomputed from the
+ *     world vectors.  Without QR_FAN_FLIP the direction is TRACED iff the element has a surface point, its frame is valid and
+ *     0 < z.  With QR_FAN_FLIP it is traced iff the element has a surface point and a valid frame, as (x', y', z') =
+ *     (-x, -y, -z) where z < 0 and as the row otherwise.  A NaN z decides as these comparisons do.
+ *   - The world direction is d = (u * x' + v * y') + n * z': per component three products and two adds in that order.  The ray
+ *     is (pos, eps, d, reach); everything after it is the unframed call's: qr_occluded_async's answer for the occlusion fans,
+ *     qr_shade_rays_async's colour for the gather fans.
+ *   - The gather weight is wgt = w; with QR_GATHER_COSINE wgt = w * z, or w * (z < 0 ? -z : z) under QR_FAN_FLIP.  The fold,
+ *     count, QR_GATHER_RESUME, the mask planes and the values of a miss (-1, a zero row) are unchanged.
+ *   - An element with a surface point but an invalid frame traces nothing: open 0 / count 0, zero mask bits and a zero row,
+ *     with or without QR_GATHER_RESUME.  It is a hit: it does not get -1.
+ * Results do not depend on QR_TRACE_COHERENT.  quadray-engine_amd/rays.py fan_frame, fan_rays(frame=True) and
+ * gather_fold(frame=True) state all of this in numpy; cosine_dirs makes the cosine-distributed table, spins the spin planes.
+ */
+int qr_fan_rays_framed_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+                             const float *spin_dev, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
+                             uint32_t flags, void *stream);
+int qr_fan_views_framed_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
+                              const qr_fan_dir *dirs_dev, int k, const float *spin_dev, float eps, float reach,
+                              int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream);
+int qr_fan_hits_framed_async(qr_device_scene *scn, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+                             const float *spin_dev, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
+                             uint32_t flags, void *stream);
+int qr_gather_rays_framed_async(qr_device_scene *scn, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+                                const float *spin_dev, float eps, float reach, float *gather_dev, int32_t *count_dev,
+                                uint32_t flags, void *stream);
+int qr_gather_views_framed_async(qr_device_scene *scn, const qr_view *views_dev, int n_views, int width, int height,
+                                 const qr_gather_dir *dirs_dev, int k, const float *spin_dev, float eps, float reach,
+                                 float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream);
+int qr_gather_hits_framed_async(qr_device_scene *scn, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+                                const float *spin_dev, float eps, float reach, float *gather_dev, int32_t *count_dev,
+                                uint32_t flags, void *stream);
+
+/*
  * Hit layers: the first k hits along a ray, in order, in one launch -- picking through glass and x-ray selection, thickness and
  * entry / exit pairs of a solid, order-independent transparency, CSG inspection, layered depth images for reprojection, "how many
  * surfaces lie between A and B".  What a host would otherwise loop over qr_trace_rays_async, reading the rays again for every

@@ -29,6 +29,8 @@ ABI_SYMBOLS = [
     "qr_pt_adapt_list_work_bytes", "qr_pt_adapt_open_list_async", "qr_pt_adapt_list_rays_async", "qr_hit_rays_async", "qr_hit_views_async",
     "qr_fan_rays_async", "qr_fan_views_async", "qr_fan_hits_async", "qr_layer_rays_async", "qr_layer_views_async",
     "qr_gather_rays_async", "qr_gather_views_async", "qr_gather_hits_async",
+    "qr_fan_rays_framed_async", "qr_fan_views_framed_async", "qr_fan_hits_framed_async",
+    "qr_gather_rays_framed_async", "qr_gather_views_framed_async", "qr_gather_hits_framed_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -143,6 +145,11 @@ def lib():
     L.qr_gather_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
     L.qr_gather_hits_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
     L.qr_gather_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    # the framed fans: the matching call's list with the spin plane after k
+    for name in ("qr_fan_rays", "qr_fan_hits", "qr_gather_rays", "qr_gather_hits"):
+        getattr(L, name + "_framed_async").argtypes = [vp, vp, ctypes.c_int64, vp, ci, vp, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    for name in ("qr_fan_views", "qr_gather_views"):
+        getattr(L, name + "_framed_async").argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, cf, cf, vp, vp, ctypes.c_uint32, vp]
     L.qr_layer_rays_async.argtypes = [vp, vp, ctypes.c_int64, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_layer_views_async.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
@@ -522,7 +529,22 @@ class Scene:
         msk = torch.empty(((k + 31) // 32,) + tuple(shape), dtype=torch.int32, device=dirs.device) if mask else None
         return d4, k, float(eps), float(reach), opn, msk
 
-    def occlusion(self, rays, dirs, eps, reach=float("inf"), flip=False, mask=False, coherent=False, stream=None):
+    def _spin_arg(self, frame, spin, shape):
+        """the spin plane of a framed fan call whose elements have `shape`, as a pointer (None: no spin); ValueError when it
+        cannot be one"""
+        import torch
+        if spin is None:
+            return None
+        if not frame:
+            raise ValueError("spin needs frame=True: it turns the table about the normal of a framed fan")
+        want = tuple(shape) + (2,)
+        if not (isinstance(spin, torch.Tensor) and spin.dtype == torch.float32 and tuple(spin.shape) == want and spin.is_contiguous()
+                and spin.is_cuda and spin.device.index == self.device):
+            raise ValueError(f"spin must be a contiguous float32 {list(want)} tensor on cuda:{self.device}")
+        return ctypes.c_void_p(spin.data_ptr())
+
+    def occlusion(self, rays, dirs, eps, reach=float("inf"), flip=False, mask=False, coherent=False, stream=None, frame=False,
+                  spin=None):
         """Occlusion fans from the first hits of caller rays (qr_fan_rays_async): for every ray, the surface point hits() gives
         (pos, nrm, id) and from it one visibility ray per row of `dirs` (float32 [K, 3] or [K, 4] on the scene's device, K <=
         1024, shared by all rays; [K, 3] is padded), in ONE launch: no hit record and no fan ray reaches memory.  Direction k is
@@ -531,41 +553,71 @@ class Scene:
         Returns open (int32 [N]: the number of open directions, -1 where the ray hits nothing); with mask=True (open, mask):
         mask int32 [ceil(K / 32), N], bit k & 31 of plane k >> 5 set iff direction k is open (rays.fan_bits unpacks it).
         eps: the step off the surface in units of |dir| (there is no self-exclusion).  coherent: as for trace(); results do not
-        depend on it.  Nothing is lit: depth and path-tracer mode do not matter.  Asynchronous on `stream`."""
+        depend on it.  Nothing is lit: depth and path-tracer mode do not matter.  Asynchronous on `stream`.
+        frame=True (qr_fan_rays_framed_async): `dirs` is in every surface point's own frame, local +z its normal
+        (rays.fan_frame), so a hemisphere table such as rays.cosine_dirs wastes no direction; direction k is traced iff
+        0 < dirs[k, 2] (flip=True: always, mirrored where dirs[k, 2] < 0) and the point's frame is valid.  spin (needs frame):
+        float32 [N, 2] = (cos, sin) of a turn of the table about the normal per element (rays.spins), on the scene's device,
+        contiguous.  rays.fan_rays(frame=True) states the composition exactly."""
         rays = self._rays_arg(rays)
         n = rays.shape[0]
+        sp = self._spin_arg(frame, spin, (n,))
         d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, (n,), mask)
+        if frame:
+            _check(lib().qr_fan_rays_framed_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, sp,
+                                                  eps, reach, ctypes.c_void_p(opn.data_ptr()),
+                                                  ctypes.c_void_p(msk.data_ptr() if mask else None),
+                                                  (TRACE_COHERENT if coherent else 0) | (FAN_FLIP if flip else 0),
+                                                  self._stream_ptr(stream)))
+            return (opn, msk) if mask else opn
         _check(lib().qr_fan_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
                                        ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
                                        (TRACE_COHERENT if coherent else 0) | (FAN_FLIP if flip else 0), self._stream_ptr(stream)))
         return (opn, msk) if mask else opn
 
-    def view_occlusion(self, views, dirs, width=None, height=None, eps=None, reach=float("inf"), flip=False, mask=False, stream=None):
+    def view_occlusion(self, views, dirs, width=None, height=None, eps=None, reach=float("inf"), flip=False, mask=False, stream=None,
+                       frame=False, spin=None):
         """Occlusion fans from every pixel of caller-supplied cameras (qr_fan_views_async): ambient occlusion or sky visibility
         of whole frames in one launch.  views, width, height as for view_hits -- the surface point of a pixel is its record there
         (sample 0's under FSAA) -- dirs, eps (required), reach, flip, mask as for occlusion().  Returns open int32 [N, H, W]
-        (-1 where the pixel shows nothing), with mask=True (open, mask int32 [ceil(K / 32), N, H, W]).  Asynchronous on `stream`."""
+        (-1 where the pixel shows nothing), with mask=True (open, mask int32 [ceil(K / 32), N, H, W]).  Asynchronous on `stream`.
+        frame, spin (float32 [N, H, W, 2]) as for occlusion() (qr_fan_views_framed_async)."""
         w, h = self._views_arg(views, width, height)
         n = views.shape[0]
+        sp = self._spin_arg(frame, spin, (n, h, w))
         d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, (n, h, w), mask)
+        if frame:
+            _check(lib().qr_fan_views_framed_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k, sp,
+                                                   eps, reach, ctypes.c_void_p(opn.data_ptr()),
+                                                   ctypes.c_void_p(msk.data_ptr() if mask else None),
+                                                   FAN_FLIP if flip else 0, self._stream_ptr(stream)))
+            return (opn, msk) if mask else opn
         _check(lib().qr_fan_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
                                         ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
                                         FAN_FLIP if flip else 0, self._stream_ptr(stream)))
         return (opn, msk) if mask else opn
 
-    def hit_occlusion(self, hits, dirs, eps, reach=float("inf"), flip=False, mask=False, stream=None):
+    def hit_occlusion(self, hits, dirs, eps, reach=float("inf"), flip=False, mask=False, stream=None, frame=False, spin=None):
         """Occlusion fans from caller-supplied hit records (qr_fan_hits_async): hits float32 [..., 12] on the scene's device,
         contiguous (hits(), view_hits(), or a host's own points: pos in columns 0:3, nrm in 4:7, the int32 bits of an id >= 0 in
         column 7; the rest is not read) -- second-bounce AO, lightmap texels, probes.  No first walk.  dirs, eps, reach, flip,
         mask as for occlusion().  Returns open int32 [...] (-1 where id < 0), with mask=True (open, mask int32
-        [ceil(K / 32), ...]).  Asynchronous on `stream`."""
+        [ceil(K / 32), ...]).  Asynchronous on `stream`.  frame, spin (float32 [..., 2]) as for occlusion()
+        (qr_fan_hits_framed_async)."""
         import torch
         if not (isinstance(hits, torch.Tensor) and hits.dtype == torch.float32 and hits.dim() >= 2 and hits.shape[-1] == 12
                 and hits.is_contiguous() and hits.is_cuda and hits.device.index == self.device):
             raise QrError(f"hits must be a contiguous float32 [..., 12] tensor on cuda:{self.device} (qr_hit records)")
         shape = tuple(hits.shape[:-1])
         n = hits.numel() // 12
+        sp = self._spin_arg(frame, spin, shape)
         d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, shape, mask)
+        if frame:
+            _check(lib().qr_fan_hits_framed_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, sp,
+                                                  eps, reach, ctypes.c_void_p(opn.data_ptr()),
+                                                  ctypes.c_void_p(msk.data_ptr() if mask else None),
+                                                  FAN_FLIP if flip else 0, self._stream_ptr(stream)))
+            return (opn, msk) if mask else opn
         _check(lib().qr_fan_hits_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
                                        ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
                                        FAN_FLIP if flip else 0, self._stream_ptr(stream)))
@@ -608,7 +660,7 @@ class Scene:
                 | (GATHER_RESUME if resume else 0))
 
     def gather(self, rays, dirs, eps, reach=float("inf"), flip=False, cosine=False, coherent=False, out=None, count=None,
-               resume=False, stream=None):
+               resume=False, stream=None, frame=False, spin=None):
         """Gather fans from the first hits of caller rays (qr_gather_rays_async): for every ray, the surface point hits() gives
         and from it one SHADED ray per row of `dirs` (float32 [K, 4] on the scene's device: direction xyz, weight; [K, 3]: weight
         1.0; K <= 1024, shared by all rays), folded into one weighted sum per ray in ONE launch: no hit record, fan ray or
@@ -619,42 +671,65 @@ class Scene:
         Returns (gather float32 [N, 4]: sum of colour * weight in r, g, b and the sum of weights in w; count int32 [N]: traced
         directions, -1 and a zero row where the ray hits nothing).  out, count: buffers to write into; resume=True (needs
         both): the sums and counts start from their contents, so that a table sent in consecutive chunks gives the bits of
-        one call.  coherent: as for trace(); results do not depend on it.  Asynchronous on `stream`."""
+        one call.  coherent: as for trace(); results do not depend on it.  Asynchronous on `stream`.
+        frame=True (qr_gather_rays_framed_async): `dirs` is in every surface point's own frame, local +z its normal, as for
+        occlusion(); the dot product is dirs[k, 2], the table's own cosine.  With rays.cosine_dirs the plain sum
+        (cosine=False) is the irradiance estimate.  spin (needs frame): float32 [N, 2], as for occlusion().
+        rays.gather_fold(frame=True) states the sum exactly."""
         rays = self._rays_arg(rays)
         n = rays.shape[0]
+        sp = self._spin_arg(frame, spin, (n,))
         d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, (n,), out, count, resume)
+        if frame:
+            _check(lib().qr_gather_rays_framed_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, sp,
+                                                     eps, reach, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                                     self._gather_flags(flip, cosine, resume, coherent), self._stream_ptr(stream)))
+            return out, count
         _check(lib().qr_gather_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
                                           ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
                                           self._gather_flags(flip, cosine, resume, coherent), self._stream_ptr(stream)))
         return out, count
 
     def view_gather(self, views, dirs, width=None, height=None, eps=None, reach=float("inf"), flip=False, cosine=False,
-                    out=None, count=None, resume=False, stream=None):
+                    out=None, count=None, resume=False, stream=None, frame=False, spin=None):
         """Gather fans from every pixel of caller-supplied cameras (qr_gather_views_async): one-bounce irradiance or sky light
         of whole frames in one launch.  views, width, height as for view_hits -- the surface point of a pixel is its record
         there (sample 0's under FSAA) -- the rest as for gather(); eps is required.  Returns (gather float32 [N, H, W, 4],
-        count int32 [N, H, W]).  Asynchronous on `stream`."""
+        count int32 [N, H, W]).  Asynchronous on `stream`.  frame, spin (float32 [N, H, W, 2]) as for gather()
+        (qr_gather_views_framed_async)."""
         w, h = self._views_arg(views, width, height)
         n = views.shape[0]
+        sp = self._spin_arg(frame, spin, (n, h, w))
         d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, (n, h, w), out, count, resume)
+        if frame:
+            _check(lib().qr_gather_views_framed_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k,
+                                                      sp, eps, reach, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                                      self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))
+            return out, count
         _check(lib().qr_gather_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k, eps,
                                            reach, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
                                            self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))
         return out, count
 
     def hit_gather(self, hits, dirs, eps, reach=float("inf"), flip=False, cosine=False, out=None, count=None, resume=False,
-                   stream=None):
+                   stream=None, frame=False, spin=None):
         """Gather fans from caller-supplied hit records (qr_gather_hits_async): hits as for hit_occlusion() (float32 [..., 12]:
         pos in columns 0:3, nrm in 4:7, the int32 bits of an id >= 0 in column 7) -- lightmap texels, probes, a second bounce.
         No first walk.  The rest as for gather().  Returns (gather float32 [..., 4], count int32 [...]).  Asynchronous on
-        `stream`."""
+        `stream`.  frame, spin (float32 [..., 2]) as for gather() (qr_gather_hits_framed_async)."""
         import torch
         if not (isinstance(hits, torch.Tensor) and hits.dtype == torch.float32 and hits.dim() >= 2 and hits.shape[-1] == 12
                 and hits.is_contiguous() and hits.is_cuda and hits.device.index == self.device):
             raise QrError(f"hits must be a contiguous float32 [..., 12] tensor on cuda:{self.device} (qr_hit records)")
         shape = tuple(hits.shape[:-1])
         n = hits.numel() // 12
+        sp = self._spin_arg(frame, spin, shape)
         d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, shape, out, count, resume)
+        if frame:
+            _check(lib().qr_gather_hits_framed_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, sp,
+                                                     eps, reach, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                                     self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))
+            return out, count
         _check(lib().qr_gather_hits_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
                                           ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
                                           self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))

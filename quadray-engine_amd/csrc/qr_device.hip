@@ -12,6 +12,7 @@
 #include "qr_hitrec.hpp"
 #include "qr_fan.hpp"
 #include "qr_gather.hpp"
+#include "qr_fan_framed.hpp"
 #include "qr_layers.hpp"
 #include "qr_openlist.hpp"
 
@@ -1008,6 +1009,13 @@ static int fan_ptrs(const void *src, const qr_fan_dir *dirs, const int32_t *open
     return QR_OK;
 }
 
+/* the spin plane of a framed call: float [elements][2], may be null */
+static int spin_ptr(const float *spin)
+{
+    if (((uintptr_t)spin & 7u) != 0) return qr_fail(QR_ERR_ARG, "spin must be 8-byte aligned");
+    return QR_OK;
+}
+
 static FanP fan_params(const qr_fan_dir *dirs, int k, float eps, float reach, int32_t *open, uint32_t *mask, uint32_t flags, uint64_t elems)
 {
     FanP fp;
@@ -1017,20 +1025,32 @@ static FanP fan_params(const qr_fan_dir *dirs, int k, float eps, float reach, in
     return fp;
 }
 
-extern "C" int qr_fan_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
-                                 float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream)
+/* the three sources, unframed (qr_fan.hpp) or framed (qr_fan_framed.hpp: spin may be null) */
+static int fan_rays(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k, float eps, float reach,
+                    int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream, bool framed, const float *spin_dev)
 {
     if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
     if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
     { const int rc = fan_args(s, k, eps, reach, flags, QR_TRACE_COHERENT | QR_FAN_FLIP); if (rc != QR_OK) return rc; }
     if (n == 0) return QR_OK;
     { const int rc = fan_ptrs(rays_dev, dirs_dev, open_dev, mask_dev); if (rc != QR_OK) return rc; }
+    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
     HIP_TRY(hipSetDevice(s->device));
     const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
     const f32x4 *r = (const f32x4 *)rays_dev;
+    const float2 *sp = (const float2 *)spin_dev;
     const ViewsP vp = {};
     const FanP fp = fan_params(dirs_dev, k, eps, reach, open_dev, mask_dev, flags, (uint64_t)n);
-    if (flags & QR_TRACE_COHERENT)
+    if (framed)
+    {
+        if (flags & QR_TRACE_COHERENT)
+            hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_RAYS, true, true>), grid, block, 0, (hipStream_t)stream,
+                               (const char *)s->d_blob, r, (int32_t)n, vp, fp, sp, s->lp.stats);
+        else
+            hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_RAYS, true, false>), grid, block, 0, (hipStream_t)stream,
+                               (const char *)s->d_blob, r, (int32_t)n, vp, fp, sp, s->lp.stats);
+    }
+    else if (flags & QR_TRACE_COHERENT)
         hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_RAYS, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r,
                            (int32_t)n, vp, fp, s->lp.stats);
     else
@@ -1040,27 +1060,58 @@ extern "C" int qr_fan_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int
     return QR_OK;
 }
 
-extern "C" int qr_fan_hits_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+extern "C" int qr_fan_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
                                  float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream)
+{
+    return fan_rays(s, rays_dev, n, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, false, nullptr);
+}
+
+extern "C" int qr_fan_rays_framed_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+                                        const float *spin_dev, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
+                                        uint32_t flags, void *stream)
+{
+    return fan_rays(s, rays_dev, n, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, true, spin_dev);
+}
+
+static int fan_hits(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k, float eps, float reach,
+                    int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream, bool framed, const float *spin_dev)
 {
     if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
     if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "record count must be 0..INT32_MAX");
     { const int rc = fan_args(s, k, eps, reach, flags, QR_FAN_FLIP); if (rc != QR_OK) return rc; }
     if (n == 0) return QR_OK;
     { const int rc = fan_ptrs(hits_dev, dirs_dev, open_dev, mask_dev); if (rc != QR_OK) return rc; }
+    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
     HIP_TRY(hipSetDevice(s->device));
     const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
     const ViewsP vp = {};
     const FanP fp = fan_params(dirs_dev, k, eps, reach, open_dev, mask_dev, flags, (uint64_t)n);
-    hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_HITS, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob,
-                       (const f32x4 *)hits_dev, (int32_t)n, vp, fp, s->lp.stats);
+    if (framed)
+        hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_HITS, true, false>), grid, block, 0, (hipStream_t)stream,
+                           (const char *)s->d_blob, (const f32x4 *)hits_dev, (int32_t)n, vp, fp, (const float2 *)spin_dev, s->lp.stats);
+    else
+        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_HITS, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob,
+                           (const f32x4 *)hits_dev, (int32_t)n, vp, fp, s->lp.stats);
     HIP_TRY(hipGetLastError());
     return QR_OK;
 }
 
-extern "C" int qr_fan_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                  const qr_fan_dir *dirs_dev, int k, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
-                                  uint32_t flags, void *stream)
+extern "C" int qr_fan_hits_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+                                 float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream)
+{
+    return fan_hits(s, hits_dev, n, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, false, nullptr);
+}
+
+extern "C" int qr_fan_hits_framed_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
+                                        const float *spin_dev, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
+                                        uint32_t flags, void *stream)
+{
+    return fan_hits(s, hits_dev, n, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, true, spin_dev);
+}
+
+static int fan_views(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height, const qr_fan_dir *dirs_dev, int k,
+                     float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream, bool framed,
+                     const float *spin_dev)
 {
     if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
     if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
@@ -1076,6 +1127,7 @@ extern "C" int qr_fan_views_async(qr_device_scene *s, const qr_view *views_dev, 
     }
     if (n_views == 0) return QR_OK;
     { const int rc = fan_ptrs(views_dev, dirs_dev, open_dev, mask_dev); if (rc != QR_OK) return rc; }
+    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
     HIP_TRY(hipSetDevice(s->device));
     /* one lane per pixel: 8x8 footprints at every FSAA, as qr_hit_views_async */
     const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
@@ -1083,8 +1135,18 @@ extern "C" int qr_fan_views_async(qr_device_scene *s, const qr_view *views_dev, 
     vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
     const FanP fp = fan_params(dirs_dev, k, eps, reach, open_dev, mask_dev, flags, (uint64_t)n_views * (uint64_t)width * (uint64_t)height);
     const f32x4 *none = nullptr;
+    const float2 *sp = (const float2 *)spin_dev;
     /* the instance is chosen as qr_hit_views_async chooses its own */
-    if (s->divk)
+    if (framed)
+    {
+        if (s->divk)
+            hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_VIEW, true, true>), grid, block, 0, (hipStream_t)stream,
+                               (const char *)s->d_blob, none, 0, vp, fp, sp, s->lp.stats);
+        else
+            hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_VIEW, false, true>), grid, block, 0, (hipStream_t)stream,
+                               (const char *)s->d_blob, none, 0, vp, fp, sp, s->lp.stats);
+    }
+    else if (s->divk)
         hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_VIEW, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
                            vp, fp, s->lp.stats);
     else
@@ -1092,6 +1154,20 @@ extern "C" int qr_fan_views_async(qr_device_scene *s, const qr_view *views_dev, 
                            vp, fp, s->lp.stats);
     HIP_TRY(hipGetLastError());
     return QR_OK;
+}
+
+extern "C" int qr_fan_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                  const qr_fan_dir *dirs_dev, int k, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
+                                  uint32_t flags, void *stream)
+{
+    return fan_views(s, views_dev, n_views, width, height, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, false, nullptr);
+}
+
+extern "C" int qr_fan_views_framed_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                         const qr_fan_dir *dirs_dev, int k, const float *spin_dev, float eps, float reach,
+                                         int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream)
+{
+    return fan_views(s, views_dev, n_views, width, height, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, true, spin_dev);
 }
 
 /* ---- gather fans (qr_gather.hpp): per surface point, the weighted sum of the renderer's colours along a shared table ---- */
@@ -1125,21 +1201,33 @@ static GatherP gather_params(const qr_gather_dir *dirs, int k, float eps, float 
     return gp;
 }
 
-extern "C" int qr_gather_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
-                                    float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream)
+/* the three sources, unframed (qr_gather.hpp) or framed (qr_fan_framed.hpp: spin may be null) */
+static int gather_rays(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k, float eps, float reach,
+                       float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream, bool framed, const float *spin_dev)
 {
     if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
     if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
     { const int rc = gather_args(s, k, eps, reach, flags, QR_TRACE_COHERENT); if (rc != QR_OK) return rc; }
     if (n == 0) return QR_OK;
     { const int rc = gather_ptrs(rays_dev, dirs_dev, gather_dev, count_dev); if (rc != QR_OK) return rc; }
+    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
     HIP_TRY(hipSetDevice(s->device));
     const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
     const f32x4 *r = (const f32x4 *)rays_dev;
     const ViewsP vp = {};
     const GatherP gp = gather_params(dirs_dev, k, eps, reach, gather_dev, count_dev, flags);
+    const float2 *sp = (const float2 *)spin_dev;
     /* the per-lane walk instance, as qr_shade_rays_async */
-    if (flags & QR_TRACE_COHERENT)
+    if (framed)
+    {
+        if (flags & QR_TRACE_COHERENT)
+            hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_RAYS, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream,
+                               s->lp, r, (int32_t)n, vp, gp, sp);
+        else
+            hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_RAYS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream,
+                               s->lp, r, (int32_t)n, vp, gp, sp);
+    }
+    else if (flags & QR_TRACE_COHERENT)
         hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_RAYS, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, r,
                            (int32_t)n, vp, gp);
     else
@@ -1149,27 +1237,58 @@ extern "C" int qr_gather_rays_async(qr_device_scene *s, const qr_ray *rays_dev, 
     return QR_OK;
 }
 
-extern "C" int qr_gather_hits_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+extern "C" int qr_gather_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
                                     float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream)
+{
+    return gather_rays(s, rays_dev, n, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, false, nullptr);
+}
+
+extern "C" int qr_gather_rays_framed_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+                                           const float *spin_dev, float eps, float reach, float *gather_dev, int32_t *count_dev,
+                                           uint32_t flags, void *stream)
+{
+    return gather_rays(s, rays_dev, n, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, true, spin_dev);
+}
+
+static int gather_hits(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k, float eps, float reach,
+                       float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream, bool framed, const float *spin_dev)
 {
     if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
     if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "record count must be 0..INT32_MAX");
     { const int rc = gather_args(s, k, eps, reach, flags, 0u); if (rc != QR_OK) return rc; }
     if (n == 0) return QR_OK;
     { const int rc = gather_ptrs(hits_dev, dirs_dev, gather_dev, count_dev); if (rc != QR_OK) return rc; }
+    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
     HIP_TRY(hipSetDevice(s->device));
     const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
     const ViewsP vp = {};
     const GatherP gp = gather_params(dirs_dev, k, eps, reach, gather_dev, count_dev, flags);
-    hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_HITS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp,
-                       (const f32x4 *)hits_dev, (int32_t)n, vp, gp);
+    if (framed)
+        hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_HITS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream,
+                           s->lp, (const f32x4 *)hits_dev, (int32_t)n, vp, gp, (const float2 *)spin_dev);
+    else
+        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_HITS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp,
+                           (const f32x4 *)hits_dev, (int32_t)n, vp, gp);
     HIP_TRY(hipGetLastError());
     return QR_OK;
 }
 
-extern "C" int qr_gather_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                     const qr_gather_dir *dirs_dev, int k, float eps, float reach, float *gather_dev, int32_t *count_dev,
-                                     uint32_t flags, void *stream)
+extern "C" int qr_gather_hits_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+                                    float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream)
+{
+    return gather_hits(s, hits_dev, n, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, false, nullptr);
+}
+
+extern "C" int qr_gather_hits_framed_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
+                                           const float *spin_dev, float eps, float reach, float *gather_dev, int32_t *count_dev,
+                                           uint32_t flags, void *stream)
+{
+    return gather_hits(s, hits_dev, n, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, true, spin_dev);
+}
+
+static int gather_views(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height, const qr_gather_dir *dirs_dev,
+                        int k, float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream, bool framed,
+                        const float *spin_dev)
 {
     if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
     if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
@@ -1185,6 +1304,7 @@ extern "C" int qr_gather_views_async(qr_device_scene *s, const qr_view *views_de
     }
     if (n_views == 0) return QR_OK;
     { const int rc = gather_ptrs(views_dev, dirs_dev, gather_dev, count_dev); if (rc != QR_OK) return rc; }
+    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
     HIP_TRY(hipSetDevice(s->device));
     /* one lane per pixel: 8x8 footprints at every FSAA, as qr_fan_views_async */
     const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
@@ -1192,8 +1312,18 @@ extern "C" int qr_gather_views_async(qr_device_scene *s, const qr_view *views_de
     vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
     const GatherP gp = gather_params(dirs_dev, k, eps, reach, gather_dev, count_dev, flags);
     const f32x4 *none = nullptr;
+    const float2 *sp = (const float2 *)spin_dev;
     /* the instance is chosen as qr_render_views_async chooses its own */
-    if (s->divk)
+    if (framed)
+    {
+        if (s->divk)
+            hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_VIEW, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream,
+                               s->lp, none, 0, vp, gp, sp);
+        else
+            hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_VIEW, false, true, QR_MIN_WAVES_PER_SIMD>), grid, block, 0,
+                               (hipStream_t)stream, s->lp, none, 0, vp, gp, sp);
+    }
+    else if (s->divk)
         hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_VIEW, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, none, 0,
                            vp, gp);
     else
@@ -1201,6 +1331,20 @@ extern "C" int qr_gather_views_async(qr_device_scene *s, const qr_view *views_de
                            vp, gp);
     HIP_TRY(hipGetLastError());
     return QR_OK;
+}
+
+extern "C" int qr_gather_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                     const qr_gather_dir *dirs_dev, int k, float eps, float reach, float *gather_dev, int32_t *count_dev,
+                                     uint32_t flags, void *stream)
+{
+    return gather_views(s, views_dev, n_views, width, height, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, false, nullptr);
+}
+
+extern "C" int qr_gather_views_framed_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
+                                            const qr_gather_dir *dirs_dev, int k, const float *spin_dev, float eps, float reach,
+                                            float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream)
+{
+    return gather_views(s, views_dev, n_views, width, height, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, true, spin_dev);
 }
 
 /* ---- hit layers (qr_layers.hpp): the first k hits along a ray, in order ---- */

@@ -638,7 +638,51 @@ def reflect_rays(rays, hits, eps):
 
 # ---- occlusion fans (include/qrhip.h qr_fan_*_async; Scene.occlusion, Scene.view_occlusion, Scene.hit_occlusion) ----
 
-def fan_rays(hits, dirs, eps, reach=float("inf"), flip=False):
+def fan_frame(nrm, spin=None):
+    """The frame of a framed fan (include/qrhip.h "Framed fans"): nrm float32 [..., 3], spin float32 [..., 2] = (c, sn) or None
+    (which is (1, 0) through the same operations), numpy arrays or torch tensors on one device.  Returns (u [..., 3],
+    v [..., 3], valid bool [...]).  The branchless orthonormal basis of Duff et al. 2017, every operation float32, in this order:
+        s  = nz < 0 ? -1 : 1                       (-0.0 and NaN give +1)
+        a  = -1 / (s + nz)
+        b  = (nx * ny) * a
+        t  = (1 + ((s * nx) * nx) * a,  s * b,  -(s * nx))
+        bt = (b,  s + (ny * ny) * a,  -ny)
+        u  = t * c + bt * sn        per component: two products, then one add
+        v  = bt * c - t * sn        per component: two products, then one subtract
+    valid iff every word of nrm, u and v has |w| <= FLT_MAX.  For a unit normal and a unit spin (u, v, nrm) is orthonormal to
+    a few ulp and right-handed: u x v = nrm."""
+    if nrm.shape[-1] != 3 or "float32" not in str(nrm.dtype):
+        raise ValueError(f"nrm must be float32 [..., 3], got {nrm.dtype} {list(nrm.shape)}")
+    if spin is not None and (tuple(spin.shape) != tuple(nrm.shape[:-1]) + (2,) or "float32" not in str(spin.dtype)):
+        raise ValueError(f"spin must be float32 {list(nrm.shape[:-1]) + [2]}, got {spin.dtype} {list(spin.shape)}")
+    flt_max = float(np.finfo(np.float32).max)
+    nx, ny, nz = nrm[..., 0], nrm[..., 1], nrm[..., 2]
+    if isinstance(nrm, np.ndarray):
+        const = lambda x: np.full(nz.shape, x, dtype=np.float32)
+        where, stack, absf = np.where, (lambda c: np.stack(c, axis=-1)), np.abs
+        ctx = np.errstate(invalid="ignore", over="ignore", divide="ignore")
+    else:
+        import contextlib
+        import torch
+        const = lambda x: torch.full_like(nz, x)
+        where, stack, absf = torch.where, (lambda c: torch.stack(c, dim=-1)), torch.abs
+        ctx = contextlib.nullcontext()
+    with ctx:
+        one = const(1.0)
+        s = where(nz < 0, const(-1.0), one)
+        a = const(-1.0) / (s + nz)
+        b = (nx * ny) * a
+        sx = s * nx
+        t = (one + (sx * nx) * a, s * b, -sx)
+        bt = (b, s + (ny * ny) * a, -ny)
+        c, sn = (one, const(0.0)) if spin is None else (spin[..., 0], spin[..., 1])
+        u = stack([t[i] * c + bt[i] * sn for i in range(3)])
+        v = stack([bt[i] * c - t[i] * sn for i in range(3)])
+        valid = ((absf(nrm) <= flt_max) & (absf(u) <= flt_max) & (absf(v) <= flt_max)).all(-1)
+    return u, v, valid
+
+
+def fan_rays(hits, dirs, eps, reach=float("inf"), flip=False, frame=False, spin=None):
     """The rays an occlusion fan traces, as a composition of the ray API: hits float32 [N, 12] (Scene.hits, or view_hits
     reshaped), dirs float32 [K, 3] or [K, 4] (the fourth column is ignored), numpy arrays or torch tensors on one device.
     Returns (rays float32 [N, K, 8], traced bool [N, K]).
@@ -649,14 +693,24 @@ def fan_rays(hits, dirs, eps, reach=float("inf"), flip=False):
     flip=True: the ray is (pos, eps, -d, reach) where dot < 0 and (pos, eps, d, reach) otherwise, and every direction of a
     hit is traced.  A NaN dot decides as these comparisons do (closed without flip, traced as d with it).  Rows of misses are
     filled the same way and never traced.  Direction k of element i is OPEN iff it is traced and Scene.occluded answers False
-    for its ray; Scene.occlusion counts the open directions (-1 for a miss) and sets bit k & 31 of mask plane k >> 5."""
+    for its ray; Scene.occlusion counts the open directions (-1 for a miss) and sets bit k & 31 of mask plane k >> 5.
+
+    frame=True (framed fans): the table is in the hit's own frame, (u, v, valid) = fan_frame(nrm, spin) with spin float32 [N, 2]
+    or None.  dot = z = dirs[k, 2]: the table's own cosine.  (x', y', z') is the row, under flip mirrored to (-x, -y, -z) where
+    z < 0; the ray is (pos, eps, (u * x' + v * y') + n * z', reach) -- per component three float32 products and two adds in
+    that order -- and it is traced iff the record is a hit, its frame is valid and (flip or 0 < z).  A NaN z decides as these
+    comparisons do."""
     pos, _, nrm, hid, _, _ = hit_fields(hits)
     if hits.ndim != 2:
         raise ValueError(f"hits must be [N, 12], got {list(hits.shape)}")
     if dirs.ndim != 2 or dirs.shape[1] not in (3, 4) or "float32" not in str(dirs.dtype):
         raise ValueError(f"dirs must be float32 [K, 3] or [K, 4], got {dirs.dtype} {list(dirs.shape)}")
+    if spin is not None and not frame:
+        raise ValueError("spin needs frame=True")
     n, k = hits.shape[0], dirs.shape[0]
     d = dirs[:, 0:3]
+    if frame:
+        u, v, valid = fan_frame(nrm, spin)
     if isinstance(hits, np.ndarray):
         where, full = np.where, (lambda shape, dt: np.empty(shape, dtype=dt))
         f32, bool_ = np.float32, np.bool_
@@ -668,16 +722,26 @@ def fan_rays(hits, dirs, eps, reach=float("inf"), flip=False):
         f32, bool_ = torch.float32, torch.bool
         ctx = contextlib.nullcontext()
     with ctx:
-        p0 = nrm[:, 0:1] * d[:, 0][None, :]
-        p1 = nrm[:, 1:2] * d[:, 1][None, :]
-        p2 = nrm[:, 2:3] * d[:, 2][None, :]
-        dot = (p0 + p1) + p2                                    # [N, K]
         rays = full((n, k, 8), f32)
         traced = full((n, k), bool_)
         rays[:, :, 0:3] = pos[:, None, :]
         rays[:, :, 3] = eps
         rays[:, :, 7] = reach
         hit = (hid >= 0)[:, None]
+        if frame:
+            z = d[:, 2]
+            loc = where((z < 0)[:, None], -d, d) if flip else d                         # [K, 3]: the row as it is traced
+            for i in range(3):
+                p0 = u[:, i:i + 1] * loc[:, 0][None, :]
+                p1 = v[:, i:i + 1] * loc[:, 1][None, :]
+                p2 = nrm[:, i:i + 1] * loc[:, 2][None, :]
+                rays[:, :, 4 + i] = (p0 + p1) + p2
+            traced[:, :] = hit & valid[:, None] if flip else hit & valid[:, None] & (0 < z)[None, :]
+            return rays, traced
+        p0 = nrm[:, 0:1] * d[:, 0][None, :]
+        p1 = nrm[:, 1:2] * d[:, 1][None, :]
+        p2 = nrm[:, 2:3] * d[:, 2][None, :]
+        dot = (p0 + p1) + p2                                    # [N, K]
         if flip:
             neg = (dot < 0)[:, :, None]
             rays[:, :, 4:7] = where(neg, -d[None, :, :], d[None, :, :])
@@ -716,9 +780,33 @@ def sphere_dirs(n):
     return np.stack([s * np.cos(phi), s * np.sin(phi), z], axis=1).astype(np.float32)
 
 
+def cosine_dirs(n):
+    """n directions of a cosine-distributed hemisphere about local +z with their weights, float32 [n, 4]: with i = arange(n) +
+    0.5, r = sqrt(i / n), phi = i * pi * (3 - sqrt(5)), a row is (r cos phi, r sin phi, sqrt(1 - r^2), 1 / n).  Computed in
+    float64 and rounded to float32 once.  A table for the framed fans (frame=True): every direction lies above the surface, so
+    none is wasted, and the density is the cosine, so the plain sum (cosine=False) of Scene.gather is the irradiance estimate,
+    acc.w is 1 where nothing is refused, and open / n of Scene.occlusion is cosine-weighted ambient occlusion."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("cosine_dirs needs n >= 1")
+    i = np.arange(n, dtype=np.float64) + 0.5
+    r = np.sqrt(i / n)
+    phi = i * np.pi * (3.0 - np.sqrt(5.0))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r * r), np.full(n, 1.0 / n)], axis=1).astype(np.float32)
+
+
+def spins(shape, seed):
+    """Spin planes for the framed fans: float32 shape + [2] = (cos a, sin a) with the angles a drawn by
+    np.random.default_rng(seed).uniform(0, 2 pi, shape); cos and sin are taken in float64 and rounded to float32 once.  One
+    turn of the table about the normal per element: neighbouring elements no longer share their K directions."""
+    shape = (int(shape),) if np.isscalar(shape) else tuple(int(x) for x in shape)
+    a = np.random.default_rng(seed).uniform(0.0, 2.0 * np.pi, shape)
+    return np.stack([np.cos(a), np.sin(a)], axis=-1).astype(np.float32)
+
+
 # ---- gather fans (include/qrhip.h qr_gather_*_async; Scene.gather, Scene.view_gather, Scene.hit_gather) ----
 
-def gather_fold(hits, dirs, colours, flip=False, cosine=False, start=None):
+def gather_fold(hits, dirs, colours, flip=False, cosine=False, start=None, frame=False, spin=None):
     """The sum a gather fan takes, in float32 numpy: hits float32 [N, 12], dirs float32 [K, 4] (direction xyz, weight) or
     [K, 3] (weight 1.0), colours float32 [N, K, 3]: entry (i, k) is what Scene.shade returns for fan_rays' ray (i, k); entries
     of untraced rays are not read.  Returns (gather float32 [N, 4], count int32 [N]).
@@ -729,9 +817,14 @@ def gather_fold(hits, dirs, colours, flip=False, cosine=False, start=None):
     then acc.rgb = acc.rgb + colour * wgt (one float32 multiply, then one float32 add), acc.w = acc.w + wgt, count += 1.
     acc and count start from zero, or from start = (gather, count) of an earlier call: a table cut into consecutive chunks and
     folded one after the other gives the bits of one fold.  A record that is no hit (id < 0) gets a zero row and count -1,
-    whatever `start` holds."""
+    whatever `start` holds.
+
+    frame=True (framed fans; spin float32 [N, 2] or None): the traced rule is framed fan_rays' and dot = z = dirs[k, 2], so
+    with cosine=True wgt = weight * z, or weight * (-z if z < 0 else z) with flip.  A hit whose frame is invalid
+    (fan_frame) traces nothing and gets a zero row and count 0, whatever `start` holds."""
     hits, dirs, colours = np.asarray(hits), np.asarray(dirs), np.asarray(colours)
-    _, traced = fan_rays(hits, dirs, np.float32(0.0), flip=flip)
+    spin = None if spin is None else np.asarray(spin)
+    _, traced = fan_rays(hits, dirs, np.float32(0.0), flip=flip, frame=frame, spin=spin)
     n, k = traced.shape
     if colours.dtype != np.float32 or colours.shape != (n, k, 3):
         raise ValueError(f"colours must be float32 [{n}, {k}, 3], got {colours.dtype} {list(colours.shape)}")
@@ -749,12 +842,19 @@ def gather_fold(hits, dirs, colours, flip=False, cosine=False, start=None):
             t = traced[:, j]
             wgt = np.full(n, weight[j], dtype=np.float32)
             if cosine:
-                dot = (nrm[:, 0] * dirs[j, 0] + nrm[:, 1] * dirs[j, 1]) + nrm[:, 2] * dirs[j, 2]
+                if frame:
+                    dot = np.full(n, dirs[j, 2], dtype=np.float32)
+                else:
+                    dot = (nrm[:, 0] * dirs[j, 0] + nrm[:, 1] * dirs[j, 1]) + nrm[:, 2] * dirs[j, 2]
                 wgt = wgt * (np.where(dot < 0, -dot, dot) if flip else dot)
             prod = colours[:, j, :] * wgt[:, None]
             acc[t, 0:3] = (acc[:, 0:3] + prod)[t]
             acc[t, 3] = (acc[:, 3] + wgt)[t]
             cnt[t] += 1
+    if frame:
+        bad = ~fan_frame(nrm, spin)[2]
+        acc[bad] = 0.0
+        cnt[bad] = 0
     miss = hid < 0
     acc[miss] = 0.0
     cnt[miss] = -1

@@ -24,6 +24,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     than 168 VGPRs (128: the view instance with packet walks only and the instance that reads caller records);
   * a gather-fan instance qr_gather_kernel<SRC, DIVK, COHERENT, WAVES> exceeds the budget of the ray-shading or view-rendering
     instance whose machine it runs (168 VGPRs, 128 for the view instance with packet walks only; QR_MAX_DIVK_SPILL; 640 B);
+  * a framed-fan instance qr_fan_framed_kernel<SRC, DIVK, COHERENT> or qr_gather_framed_kernel<SRC, DIVK, COHERENT, WAVES>
+    exceeds the budget of the unframed instance it mirrors;
   * a hit-layer instance qr_layer_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more
     than 168 VGPRs (128: the view instance with packet walks only);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
@@ -95,6 +97,18 @@ LIMITS = {
     "16qr_gather_kernelILi2ELb1ELb0ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
     "16qr_gather_kernelILi1ELb1ELb1ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
     "16qr_gather_kernelILi1ELb0ELb1ELi4EE": (128, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    # framed fans (qr_fan_framed.hpp): the five occlusion-fan instances with the element's frame (u, v: six more registers across
+    # the loop) and the five gather-fan instances with the spin parked beside the rest; each held to its unframed twin's budget
+    "20qr_fan_framed_kernelILi0ELb1ELb0EE": (168, 0, 0),
+    "20qr_fan_framed_kernelILi0ELb1ELb1EE": (168, 0, 0),
+    "20qr_fan_framed_kernelILi1ELb1ELb1EE": (168, 0, 0),
+    "20qr_fan_framed_kernelILi1ELb0ELb1EE": (128, 0, 0),
+    "20qr_fan_framed_kernelILi2ELb1ELb0EE": (128, 0, 0),
+    "23qr_gather_framed_kernelILi0ELb1ELb0ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "23qr_gather_framed_kernelILi0ELb1ELb1ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "23qr_gather_framed_kernelILi2ELb1ELb0ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "23qr_gather_framed_kernelILi1ELb1ELb1ELi3EE": (168, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
+    "23qr_gather_framed_kernelILi1ELb0ELb1ELi4EE": (128, int(os.environ.get("QR_MAX_DIVK_SPILL", "24")), 640),
     # hit layers (qr_layers.hpp qr_layer_kernel<VIEW, DIVK, COHERENT>): a hit-record instance's walk and surface point in a loop over
     # the layers, with the ray, the count and the alive flag live across it: nothing spilled, no private segment, and no more
     # registers than the hit-record instance each one mirrors
