@@ -866,8 +866,81 @@ int qr_layer_views_async(qr_device_scene *scn, const qr_view *views_dev, int n_v
                          int32_t *count_dev, float *t_dev, int32_t *id_dev, qr_hit *hits_dev,
                          uint32_t flags, void *stream);
 
+/*
+ * Guided a-trous filter: one edge-avoiding 5x5 wavelet pass (Dammertz et al. 2010; the spatial half of SVGF) over view frames
+ * of Monte-Carlo colour -- what qr_pt_adapt_views_async (mean_dev), qr_render_views_mean_async or the gather fans with a spin
+ * return -- guided by the qr_hit records qr_hit_views_async writes for the same views and, where there is one, by a variance
+ * per pixel (qr_pt_adapt_views_variance_async).  A denoiser runs passes with step = 1, 2, 4, ... and feeds each pass the colour
+ * and variance of the one before.  It is a pure function of its inputs.
+ *   - colour_in, colour_out: float32 [n_views][height][width][channels], compact, channels 3 or 4.  var_in, var_out: float32
+ *     [n_views][height][width], both given or both NULL.  hits: qr_hit [n_views][height][width] as qr_hit_views_async writes them
+ *     (pos, nrm, id, alb are read).  All DEVICE memory; hits 16-byte, the floats 4-byte aligned.  Every pixel of every view is
+ *     written.  colour_out == colour_in or var_out == var_in is refused (a pass reads neighbours); any OTHER overlap between
+ *     an input and an output is undefined.
+ *   - The arithmetic is pinned: fp32, IEEE division, nothing fused, no exp, pow or sqrt; every parenthesis is an order.
+ *     For pixel p with record (pos_p, nrm_p, id_p, alb_p), colour c_p and v_p = var_in ? var_in[p] : 1.0f:
+ *       read     With QR_ATROUS_DEMODULATE every colour read, at the centre and at every tap, is first divided per channel
+ *                (the first three; a fourth is never divided) by a = alb > alb_floor ? alb : alb_floor of ITS OWN pixel's
+ *                record (a NaN albedo gives the floor); a pixel with id < 0 is not divided.
+ *                lum(c) = (c.r * 0.2126f + c.g * 0.7152f) + c.b * 0.0722f on the colour as read.
+ *       miss     id_p < 0: the output is the colour as read and the input variance; nothing is filtered or modulated.
+ *       taps     dy = -2..2 outer, dx = -2..2 inner, q = p + (dx, dy) * step, h = H[dy + 2] * H[dx + 2] with
+ *                H = {1/16, 1/4, 3/8, 1/4, 1/16} (every product exact).  The centre tap has w = h and is always taken.
+ *                Another tap is skipped when q is outside the frame or id_q < 0.  Otherwise w = h, then in this order
+ *                  QR_ATROUS_NORMAL  d = (nrm_p.x * nrm_q.x + nrm_p.y * nrm_q.y) + nrm_p.z * nrm_q.z;  d = 0 < d ? d : 0;
+ *                                    d = d * d, normal_sq times;  w = w * d
+ *                  QR_ATROUS_PLANE   e = pos_q - pos_p;  d = (nrm_p.x * e.x + nrm_p.y * e.y) + nrm_p.z * e.z;
+ *                                    x = fabsf(d) / sigma_z;  w = w * (1.0f / (1.0f + x * x))
+ *                  QR_ATROUS_LUMA    dl = lum_p - lum_q;  den = sigma_l2 * v_p + eps_l;
+ *                                    w = w * (1.0f / (1.0f + (dl * dl) / den))
+ *                and the tap is taken iff 0 < w: a NaN, zero or negative weight -- a NaN normal, an infinite position, a
+ *                negative variance -- closes the tap instead of poisoning the pixel.  For a taken tap, in tap order:
+ *                sum_c = sum_c + c_q * w per channel;  sum_w = sum_w + w;  sum_v = sum_v + var_q * (w * w).
+ *       output   c = sum_c / sum_w per channel;  var = sum_v / (sum_w * sum_w).  With QR_ATROUS_MODULATE c is then
+ *                multiplied per channel (the first three) by max(alb_p, alb_floor), the same comparison as above.
+ *     A non-finite input colour propagates by this arithmetic and is not special-cased.  rays.py atrous_pass is this text
+ *     in numpy, and the GPU reproduces it bit for bit.
+ *   - On a flat guide without stops one pass divides the variance by (70/256)^2.  The customary starting points (SVGF's):
+ *     normal_sq 7 (power 128), sigma_z about one pixel's footprint in world units, sigma_l2 = 4^2, eps_l 1e-6.
+ *   - QR_ERR_ARG: a null or misaligned pointer, var_out without var_in or var_in without var_out, colour_out == colour_in,
+ *     var_out == var_in, step outside 1..QR_ATROUS_MAX_STEP, channels other than 3 or 4, normal_sq outside 0..7, unknown
+ *     flag bits, sigma_z, sigma_l2, eps_l or alb_floor not above 0 (NaN included), n_views outside 0..QR_VIEW_MAX_VIEWS, a size
+ *     outside 1..QR_VIEW_MAX_DIM.  A refused call launches nothing.  n_views == 0 returns QR_OK without a launch.
+ *   - The call reads nothing of the scene but its device: any mode, no QR_UPLOAD_RAY_QUERIES needed.  Asynchronous on `stream`.
+ *
+ * qr_pt_adapt_views_variance_async: the variance plane for it, from an adaptive view state (only read).  Per slot, with m =
+ * plane 4 as uint32:  2 <= m:  s = (M2r + M2g) + M2b;  s = 0 < s ? s : 0;  v = s / ((float(m) * float(m - 1)) * 3.0f);
+ * otherwise v = unknown.  Per pixel var = (...(v_0 + v_1) + ...) * (1.0f / (spp * spp)) over its spp slots in slot order (spp
+ * is 1, 2 or 4: the reciprocal is exact): the channel-mean variance of the pixel's FSAA-reduced mean, its slots taken as
+ * independent.  var_dev: float32 [n_views][height][width].  Sizes and limits as qr_pt_adapt_views_state_bytes; flags: none
+ * defined, anything but 0 gives QR_ERR_ARG, as does a null or misaligned (4 bytes) pointer.  No QR_UPLOAD_RAY_QUERIES needed.
+ * n_views == 0 returns QR_OK without a launch.  Asynchronous on `stream`.
+ */
+#define QR_ATROUS_NORMAL      1u
+#define QR_ATROUS_PLANE       2u
+#define QR_ATROUS_LUMA        4u
+#define QR_ATROUS_DEMODULATE  8u
+#define QR_ATROUS_MODULATE    16u
+#define QR_ATROUS_MAX_STEP    64
+typedef struct qr_atrous_params {      /* 32 bytes */
+    int32_t  step;        /* tap spacing in pixels, 1..QR_ATROUS_MAX_STEP */
+    int32_t  channels;    /* 3 or 4 floats per pixel in colour_in / colour_out */
+    int32_t  normal_sq;   /* 0..7: the normal stop is max(0, n.n')^(2^normal_sq) */
+    uint32_t flags;       /* QR_ATROUS_NORMAL | _PLANE | _LUMA | _DEMODULATE | _MODULATE */
+    float    sigma_z;     /* plane stop: world units, > 0 */
+    float    sigma_l2;    /* luma stop: squared tolerance, in units of the variance, > 0 */
+    float    eps_l;       /* luma stop: added to the denominator, > 0 */
+    float    alb_floor;   /* de/modulation: the smallest albedo divided by, > 0 */
+} qr_atrous_params;
+
+int qr_atrous_views_async(qr_device_scene *scn, const float *colour_in, const float *var_in, const qr_hit *hits,
+                          int n_views, int width, int height, const qr_atrous_params *p,
+                          float *colour_out, float *var_out, void *stream);
+int qr_pt_adapt_views_variance_async(qr_device_scene *scn, const int32_t *state, int n_views, int width, int height,
+                                     float unknown, float *var_dev, uint32_t flags, void *stream);
+
 /* ------------------------------------------------------------------------ */
-/* 3. Misc                                                                   */
+/* 3. Misc                                                                  */
 /* ------------------------------------------------------------------------ */
 
 /*

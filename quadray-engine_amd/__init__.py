@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "qr_gather_rays_async", "qr_gather_views_async", "qr_gather_hits_async",
     "qr_fan_rays_framed_async", "qr_fan_views_framed_async", "qr_fan_hits_framed_async",
     "qr_gather_rays_framed_async", "qr_gather_views_framed_async", "qr_gather_hits_framed_async",
+    "qr_atrous_views_async", "qr_pt_adapt_views_variance_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -56,6 +57,12 @@ PT_ADAPT_VIEWS_MAX_SAMPLES = 512    # QR_PT_ADAPT_VIEWS_MAX_SAMPLES: the most ca
 PT_OPEN_BLOCK = 1024        # QR_PT_OPEN_BLOCK: rays per workgroup of the open-list kernels
 PT_OPEN_CHUNK = 1024        # QR_PT_OPEN_CHUNK: block counts one pass of the open list's scan workgroup takes
 LAYER_MAX = 64              # QR_LAYER_MAX: the most layers of one qr_layer_*_async call
+ATROUS_NORMAL = 1           # qr_atrous_views_async flags: the normal stop,
+ATROUS_PLANE = 2            # the plane-distance stop,
+ATROUS_LUMA = 4             # the luminance stop against the variance,
+ATROUS_DEMODULATE = 8       # every colour read is divided by its own pixel's albedo,
+ATROUS_MODULATE = 16        # the output is multiplied by the centre pixel's albedo
+ATROUS_MAX_STEP = 64        # QR_ATROUS_MAX_STEP: the widest tap spacing of one pass
 
 
 class QrError(RuntimeError):
@@ -74,6 +81,12 @@ class ProgramInfo(ctypes.Structure):
     _fields_ = [("bytes", ctypes.c_uint64), ("n_lists", ctypes.c_uint32), ("n_cells", ctypes.c_uint32),
                 ("n_dropped", ctypes.c_uint32), ("n_clip_cells", ctypes.c_uint32), ("n_sched", ctypes.c_uint32),
                 ("n_grids", ctypes.c_uint32), ("n_grid_lists", ctypes.c_uint32), ("n_dda", ctypes.c_uint32)]
+
+
+class AtrousParams(ctypes.Structure):
+    """qr_atrous_params (include/qrhip.h), 32 bytes"""
+    _fields_ = [("step", ctypes.c_int32), ("channels", ctypes.c_int32), ("normal_sq", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("sigma_z", ctypes.c_float), ("sigma_l2", ctypes.c_float), ("eps_l", ctypes.c_float), ("alb_floor", ctypes.c_float)]
 
 
 class RayCounts(ctypes.Structure):
@@ -150,6 +163,8 @@ def lib():
         getattr(L, name + "_framed_async").argtypes = [vp, vp, ctypes.c_int64, vp, ci, vp, cf, cf, vp, vp, ctypes.c_uint32, vp]
     for name in ("qr_fan_views", "qr_gather_views"):
         getattr(L, name + "_framed_async").argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    L.qr_atrous_views_async.argtypes = [vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(AtrousParams), vp, vp, vp]
+    L.qr_pt_adapt_views_variance_async.argtypes = [vp, vp, ci, ci, ci, cf, vp, ctypes.c_uint32, vp]
     L.qr_layer_rays_async.argtypes = [vp, vp, ctypes.c_int64, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_layer_views_async.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
@@ -506,6 +521,105 @@ class Scene:
         _check(lib().qr_hit_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(out.data_ptr()),
                                         0, self._stream_ptr(stream)))
         return out
+
+    def _atrous_args(self, colour, hits, variance, out, variance_out):
+        """the tensors of atrous() / denoise(): dtype and shape first, then contiguity and device.  Returns (n, h, w, channels)."""
+        import torch
+        dev = self.device
+
+        def resident(t):
+            return t.is_contiguous() and t.is_cuda and t.device.index == dev
+        if not (isinstance(colour, torch.Tensor) and colour.dtype == torch.float32 and colour.dim() == 4 and colour.shape[3] in (3, 4)
+                and min(colour.shape) >= 1):
+            raise QrError("colour must be a float32 [N, H, W, 3] or [N, H, W, 4] tensor")
+        n, h, w, ch = (int(x) for x in colour.shape)
+        if not (isinstance(hits, torch.Tensor) and hits.dtype == torch.float32 and tuple(hits.shape) == (n, h, w, 12)):
+            raise QrError(f"hits must be a float32 [{n}, {h}, {w}, 12] tensor of qr_hit records (view_hits)")
+        if variance is not None and not (isinstance(variance, torch.Tensor) and variance.dtype == torch.float32
+                                         and tuple(variance.shape) == (n, h, w)):
+            raise QrError(f"variance must be None or a float32 [{n}, {h}, {w}] tensor")
+        if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == (n, h, w, ch)):
+            raise QrError(f"out must be None or a float32 [{n}, {h}, {w}, {ch}] tensor")
+        if variance_out is not None:
+            if variance is None:
+                raise QrError("variance_out needs a variance")
+            if not (isinstance(variance_out, torch.Tensor) and variance_out.dtype == torch.float32
+                    and tuple(variance_out.shape) == (n, h, w)):
+                raise QrError(f"variance_out must be None or a float32 [{n}, {h}, {w}] tensor")
+        for t, what in ((colour, "colour"), (hits, "hits"), (variance, "variance"), (out, "out"), (variance_out, "variance_out")):
+            if t is not None and not resident(t):
+                raise QrError(f"{what} must be contiguous and on cuda:{dev}")
+        return n, h, w, ch
+
+    @staticmethod
+    def _atrous_stops(**stops):
+        from . import rays
+        try:
+            return rays.atrous_stops(**stops)
+        except (ValueError, TypeError) as e:
+            raise QrError(str(e)) from None
+
+    def _atrous_launch(self, colour, variance, hits, dims, step, stops, out, variance_out, stream):
+        n, h, w, ch = dims
+        flags, nsq, sz, sl2, el, af = stops
+        p = AtrousParams(step, ch, nsq, flags, float(sz), float(sl2), float(el), float(af))
+        _check(lib().qr_atrous_views_async(self._h, ctypes.c_void_p(colour.data_ptr()),
+                                           ctypes.c_void_p(variance.data_ptr() if variance is not None else None),
+                                           ctypes.c_void_p(hits.data_ptr()), n, w, h, ctypes.byref(p),
+                                           ctypes.c_void_p(out.data_ptr()),
+                                           ctypes.c_void_p(variance_out.data_ptr() if variance_out is not None else None),
+                                           self._stream_ptr(stream)))
+
+    def atrous(self, colour, hits, variance=None, step=1, normal_power=128, plane=None, luma=None, luma_eps=1e-6, demodulate=False,
+               modulate=False, albedo_floor=1 / 256, out=None, variance_out=None, stream=None):
+        """One pass of the guided a-trous filter (qr_atrous_views_async; rays.atrous_pass is its arithmetic): an edge-avoiding
+        5x5 average of colour (float32 [N, H, W, 3|4]: PtAdaptiveViews.step(mean=True), render_views_mean's sum, view_gather)
+        with taps `step` pixels apart (1..ATROUS_MAX_STEP), guided by hits (view_hits of the same views) and, with a variance
+        (float32 [N, H, W]: PtAdaptiveViews.variance), by the luminance against it.  normal_power: None or a power of two 1..128,
+        the exponent of max(0, n . n'); plane: sigma_z in world units, or None; luma: the tolerance in standard deviations, or
+        None (without a variance: in units of 1); demodulate / modulate: divide every colour read by its pixel's albedo / multiply
+        the output by it, albedo_floor the smallest albedo divided by.  The defaults are SVGF's customary starting points, not
+        tuned.  out / variance_out: tensors to write, neither the inputs.  Returns colour_out, or (colour_out, variance_out) with
+        a variance.  Asynchronous on `stream`."""
+        import numbers
+        import torch
+        stops = self._atrous_stops(normal_power=normal_power, plane=plane, luma=luma, luma_eps=luma_eps, demodulate=demodulate,
+                                   modulate=modulate, albedo_floor=albedo_floor)
+        if isinstance(step, bool) or not isinstance(step, numbers.Integral) or not 1 <= step <= ATROUS_MAX_STEP:
+            raise QrError(f"step must be an integer, 1..{ATROUS_MAX_STEP}")
+        dims = self._atrous_args(colour, hits, variance, out, variance_out)
+        if out is None:
+            out = torch.empty_like(colour)
+        if variance is not None and variance_out is None:
+            variance_out = torch.empty_like(variance)
+        self._atrous_launch(colour, variance, hits, dims, int(step), stops, out, variance_out, stream)
+        return out if variance is None else (out, variance_out)
+
+    def denoise(self, colour, hits, variance=None, passes=5, albedo=False, **stops):
+        """The whole filter (rays.denoise): `passes` (1..7) atrous passes with step = 1, 2, 4, ... on `stream` (stream=, default
+        torch's current stream), each fed the one before.  It ping-pongs between two scratch tensors of its own and never
+        writes colour or variance.  albedo=True divides by the albedo on the first pass and multiplies on the last.  stops:
+        normal_power, plane, luma, luma_eps, albedo_floor as atrous() takes them.  Returns (colour, variance or None), new
+        tensors."""
+        import numbers
+        import torch
+        stream = stops.pop("stream", None)
+        if isinstance(passes, bool) or not isinstance(passes, numbers.Integral) or not 1 <= passes <= 7:
+            raise QrError("passes must be an integer, 1..7")
+        if "demodulate" in stops or "modulate" in stops:
+            raise QrError("denoise sets demodulate and modulate itself (albedo=True)")
+        per_pass = [self._atrous_stops(demodulate=bool(albedo) and k == 0, modulate=bool(albedo) and k == passes - 1, **stops)
+                    for k in range(passes)]
+        dims = self._atrous_args(colour, hits, variance, None, None)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            cbuf = [torch.empty_like(colour) for _ in range(min(passes, 2))]
+            vbuf = [torch.empty_like(variance) for _ in range(min(passes, 2))] if variance is not None else [None, None]
+        c, v = colour, variance
+        for k in range(passes):
+            co, vo = cbuf[k & 1], vbuf[k & 1]
+            self._atrous_launch(c, v, hits, dims, 1 << k, per_pass[k], co, vo, stream)
+            c, v = co, vo
+        return c, v
 
     def _fan_args(self, dirs, eps, reach, shape, mask):
         """(dirs as a contiguous float32 [K, 4] tensor, K, eps, reach, open, mask or None) of an occlusion-fan call whose
@@ -1263,6 +1377,27 @@ class PtAdaptiveViews:
     def counts(self):
         """plane 4 of the state (a view), [N, slots]: the number of samples every pixel sample holds"""
         return self.state[:, 4]
+
+    def variance(self, out=None, unknown=1.0, stream=None):
+        """The variance per pixel of the running mean (qr_pt_adapt_views_variance_async; rays.pt_adapt_view_variance): per slot
+        Welford's M2 summed over r, g, b, divided by 3 m (m - 1), `unknown` where the slot holds fewer than 2 samples; per pixel
+        the sum over its slots divided by their number squared.  What Scene.atrous / Scene.denoise take as `variance`.
+        Returns float32 [N, H, W] (a new tensor unless given).  The state is only read.  Asynchronous on `stream`."""
+        import torch
+        n, h, w, dev = self.views.shape[0], self.height, self.width, self.scene.device
+        if out is None:
+            out = torch.empty((n, h, w), dtype=torch.float32, device=self.views.device)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == (n, h, w)
+                  and out.is_contiguous() and out.is_cuda and out.device.index == dev):
+            raise QrError(f"out must be a contiguous float32 [{n}, {h}, {w}] tensor on cuda:{dev}")
+        try:
+            unknown = float(unknown)
+        except (TypeError, ValueError):
+            raise QrError("unknown must be a number") from None
+        _check(lib().qr_pt_adapt_views_variance_async(self.scene._h, ctypes.c_void_p(self.state.data_ptr()), n, w, h,
+                                                      ctypes.c_float(unknown), ctypes.c_void_p(out.data_ptr()), 0,
+                                                      Scene._stream_ptr(stream)))
+        return out
 
     def reset(self):
         """Restart the accumulation: seeds as rays.pt_seeds in every view, every other plane 0.  Synchronous

@@ -15,6 +15,7 @@
 #include "qr_fan_framed.hpp"
 #include "qr_layers.hpp"
 #include "qr_openlist.hpp"
+#include "qr_atrous.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -866,6 +867,71 @@ extern "C" int qr_pt_adapt_views_async(qr_device_scene *s, const qr_view *views_
     pa.state = (uint32_t *)state_dev; pa.samples = samples; pa.min_samples = min_samples; pa.max_samples = max_samples; pa.tol2 = tol2;
     pa.mean = mean_dev; pa.counts = counts_dev; pa.open = open_dev;
     hipLaunchKernelGGL(qr_pt_adapt_views_kernel, grid, block, 0, (hipStream_t)stream, s->lp, vp, pa, frames_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+/* the per-pixel variance of an adaptive view state (qr_atrous.hpp qr_pt_adapt_var_kernel): the state is only read */
+extern "C" int qr_pt_adapt_views_variance_async(qr_device_scene *s, const int32_t *state, int n_views, int width, int height,
+                                                float unknown, float *var_dev, uint32_t flags, void *stream)
+{
+    uint64_t slots = 0;
+    const int rc = pt_adapt_views_dims(s, n_views, width, height, &slots);
+    if (rc != QR_OK) return rc;
+    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown adaptive view variance flags");
+    if (n_views == 0) return QR_OK;
+    if (state == nullptr || var_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if ((((uintptr_t)state | (uintptr_t)var_dev) & 3u) != 0) return qr_fail(QR_ERR_ARG, "state and var must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t pixels = (uint32_t)width * (uint32_t)height;
+    const dim3 grid((pixels + 255u) / 256u, (unsigned)n_views), block(256);
+    hipLaunchKernelGGL(qr_pt_adapt_var_kernel, grid, block, 0, (hipStream_t)stream, (const uint32_t *)state, pixels, s->fr.fsaa,
+                       unknown, var_dev);
+    HIP_TRY(hipGetLastError());
+    return QR_OK;
+}
+
+/* ---- guided a-trous filter (qr_atrous.hpp): one edge-avoiding pass over view frames, tiles in the decimated lattice ---- */
+
+extern "C" int qr_atrous_views_async(qr_device_scene *s, const float *colour_in, const float *var_in, const qr_hit *hits,
+                                     int n_views, int width, int height, const qr_atrous_params *p,
+                                     float *colour_out, float *var_out, void *stream)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    if (p == nullptr) return qr_fail(QR_ERR_ARG, "null filter parameters");
+    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
+    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
+        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
+    if (p->step < 1 || p->step > QR_ATROUS_MAX_STEP) return qr_fail(QR_ERR_ARG, "step must be 1.." + std::to_string(QR_ATROUS_MAX_STEP));
+    if (p->channels != 3 && p->channels != 4) return qr_fail(QR_ERR_ARG, "channels must be 3 or 4");
+    if (p->normal_sq < 0 || p->normal_sq > 7) return qr_fail(QR_ERR_ARG, "normal_sq must be 0..7");
+    if ((p->flags & ~(QR_ATROUS_NORMAL | QR_ATROUS_PLANE | QR_ATROUS_LUMA | QR_ATROUS_DEMODULATE | QR_ATROUS_MODULATE)) != 0u)
+        return qr_fail(QR_ERR_ARG, "unknown filter flags");
+    if (!(p->sigma_z > 0.0f) || !(p->sigma_l2 > 0.0f) || !(p->eps_l > 0.0f) || !(p->alb_floor > 0.0f))
+        return qr_fail(QR_ERR_ARG, "sigma_z, sigma_l2, eps_l and alb_floor must be above 0");
+    if ((var_in == nullptr) != (var_out == nullptr)) return qr_fail(QR_ERR_ARG, "var_in and var_out go together: both or neither");
+    if (n_views == 0) return QR_OK;
+    if (colour_in == nullptr || colour_out == nullptr || hits == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
+    if (((uintptr_t)hits & 15u) != 0) return qr_fail(QR_ERR_ARG, "hits must be 16-byte aligned");
+    if ((((uintptr_t)colour_in | (uintptr_t)colour_out | (uintptr_t)var_in | (uintptr_t)var_out) & 3u) != 0)
+        return qr_fail(QR_ERR_ARG, "colour and variance must be 4-byte aligned");
+    if (colour_in == colour_out || (var_in != nullptr && var_in == var_out))
+        return qr_fail(QR_ERR_ARG, "a pass reads neighbours: it cannot run in place");
+    HIP_TRY(hipSetDevice(s->device));
+    AtrousP ap;
+    ap.colour_in = colour_in; ap.var_in = var_in; ap.hits = (const f32x4 *)hits; ap.colour_out = colour_out; ap.var_out = var_out;
+    ap.width = width; ap.height = height; ap.step = p->step; ap.normal_sq = p->normal_sq; ap.flags = p->flags;
+    ap.sigma_z = p->sigma_z; ap.sigma_l2 = p->sigma_l2; ap.eps_l = p->eps_l; ap.alb_floor = p->alb_floor;
+    /* phases per axis (no more than there are pixels), and tiles over the longest phase: entry i of phase f is pixel f + i * step */
+    const int phx = std::min(p->step, width), phy = std::min(p->step, height);
+    ap.tiles_x = ((width + p->step - 1) / p->step + QR_ATROUS_TW - 1) / QR_ATROUS_TW;
+    ap.tiles_y = ((height + p->step - 1) / p->step + QR_ATROUS_TH - 1) / QR_ATROUS_TH;
+    /* grid.y = phy * tiles_y <= height / 8 + 2 * step: far below 65535 at QR_VIEW_MAX_DIM */
+    const dim3 grid((unsigned)(phx * ap.tiles_x), (unsigned)(phy * ap.tiles_y), (unsigned)n_views), block(QR_ATROUS_BLOCK);
+    if (p->channels == 3)
+        hipLaunchKernelGGL(qr_atrous_kernel<3>, grid, block, 0, (hipStream_t)stream, ap);
+    else
+        hipLaunchKernelGGL(qr_atrous_kernel<4>, grid, block, 0, (hipStream_t)stream, ap);
     HIP_TRY(hipGetLastError());
     return QR_OK;
 }

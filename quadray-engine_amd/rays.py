@@ -66,6 +66,14 @@ and pt_adapt_fold_list are the specification):
         index, count = acc.open_list()                                       # on the device; nothing is read back
         _, still = acc.step(rays, 8, spread=spread, rgb=False, open=True, index=index, count=count, cap=cap)
         cap = int(still)                                                     # exactly the next list's length
+
+Scene.denoise removes the noise of such frames on the GPU: passes of a guided a-trous filter (include/qrhip.h
+qr_atrous_views_async) stopped by the hit records of the same views and by the accumulator's own variance.  atrous_pass, denoise
+and pt_adapt_view_variance state them in float32 numpy, operation for operation; atrous_stops is the host side of the arguments:
+
+    views_acc = scn.pt_adaptive_views(views, w, h, min_samples=8, max_samples=8)
+    _, mean = views_acc.step(8, mean=True)
+    clean, var = scn.denoise(mean, scn.view_hits(views, w, h), views_acc.variance(), passes=5, plane=0.05, luma=4.0)
 """
 import struct
 
@@ -920,3 +928,188 @@ def layers_of(trace, rays, k):
         cur = next_rays(cur, tj, ij)[hit]
         alive = alive[hit]
     return (ids >= 0).sum(axis=0).astype(np.int32), t, ids
+
+
+# ---- guided a-trous filter (include/qrhip.h qr_atrous_views_async; Scene.atrous, Scene.denoise) ----
+
+ATROUS_NORMAL, ATROUS_PLANE, ATROUS_LUMA, ATROUS_DEMODULATE, ATROUS_MODULATE = 1, 2, 4, 8, 16      # QR_ATROUS_* flags
+ATROUS_MAX_STEP = 64                                                                               # QR_ATROUS_MAX_STEP
+ATROUS_H = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16], dtype=np.float32)                       # the 1-D kernel: binary fractions
+
+
+def atrous_stops(normal_power=128, plane=None, luma=None, luma_eps=1e-6, demodulate=False, modulate=False, albedo_floor=1 / 256):
+    """The host side of Scene.atrous' arguments: (flags, normal_sq, sigma_z, sigma_l2, eps_l, alb_floor) as qr_atrous_params
+    takes them.  normal_power: None (no normal stop) or a power of two 1..128, sent as its log2; plane: sigma_z or None; luma:
+    the tolerance in standard deviations or None, sigma_l2 = float32(luma) * float32(luma); a stop that is off sends 1.0.
+    Raises ValueError for anything else."""
+    flags, normal_sq = 0, 0
+    if normal_power is not None:
+        if isinstance(normal_power, bool) or not isinstance(normal_power, (int, np.integer)) or normal_power not in (1, 2, 4, 8, 16, 32, 64, 128):
+            raise ValueError("normal_power must be None or a power of two, 1..128")
+        flags |= ATROUS_NORMAL
+        normal_sq = int(normal_power).bit_length() - 1
+
+    def positive(x, what):
+        try:
+            v = np.float32(x)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a number") from None
+        if not (v > 0 and np.isfinite(v)):
+            raise ValueError(f"{what} must be a finite float32 above 0")
+        return v
+    sigma_z = sigma_l2 = np.float32(1.0)
+    if plane is not None:
+        sigma_z = positive(plane, "plane")
+        flags |= ATROUS_PLANE
+    if luma is not None:
+        t = positive(luma, "luma")
+        with np.errstate(over="ignore", under="ignore"):
+            sigma_l2 = positive(t * t, "luma squared")
+        flags |= ATROUS_LUMA
+    eps_l, alb_floor = positive(luma_eps, "luma_eps"), positive(albedo_floor, "albedo_floor")
+    if demodulate:
+        flags |= ATROUS_DEMODULATE
+    if modulate:
+        flags |= ATROUS_MODULATE
+    return flags, normal_sq, sigma_z, sigma_l2, eps_l, alb_floor
+
+
+def _atrous_args(colour, variance, hits):
+    colour, hits = np.asarray(colour), np.asarray(hits)
+    if colour.dtype != np.float32 or colour.ndim not in (3, 4) or colour.shape[-1] not in (3, 4):
+        raise ValueError(f"colour must be float32 [N, H, W, 3|4] or [H, W, 3|4], got {colour.dtype} {list(colour.shape)}")
+    lead = colour.shape[:-1]
+    if hits.dtype != np.float32 or hits.shape != lead + (12,):
+        raise ValueError(f"hits must be float32 {list(lead) + [12]}, got {hits.dtype} {list(hits.shape)}")
+    if variance is not None:
+        variance = np.asarray(variance)
+        if variance.dtype != np.float32 or variance.shape != lead:
+            raise ValueError(f"variance must be float32 {list(lead)}, got {variance.dtype} {list(variance.shape)}")
+    return colour, variance, hits
+
+
+def atrous_pass(colour, variance, hits, step, flags=0, normal_sq=0, sigma_z=1.0, sigma_l2=1.0, eps_l=1e-6, alb_floor=1 / 256,
+                weights=None):
+    """The specification of one qr_atrous_views_async pass in float32 numpy, every operation elementwise so that it rounds once:
+    colour float32 [N, H, W, C] (or [H, W, C]; C 3 or 4), variance float32 [N, H, W] or None, hits float32 [N, H, W, 12]
+    (qr_hit records), step 1..ATROUS_MAX_STEP, flags of ATROUS_*, the rest as qr_atrous_params.  Returns (colour', variance' or
+    None), new arrays.
+
+    Per pixel p (include/qrhip.h has the full text): with ATROUS_DEMODULATE every colour is first divided, channels 0..2, by
+    a = alb if alb > alb_floor else alb_floor of its own record (id < 0: not divided); lum = (r * 0.2126 + g * 0.7152) + b * 0.0722.
+    id_p < 0: colour as read and variance pass through.  Otherwise the taps dy = -2..2 outer, dx = -2..2 inner, q = p + (dx, dy) *
+    step, h = H[dy + 2] * H[dx + 2]: the centre is taken with w = h; another tap is skipped outside the frame or when id_q < 0;
+    else w = h, times the NORMAL stop max(0, n_p . n_q) squared normal_sq times, times the PLANE stop 1 / (1 + x * x) with
+    x = |n_p . (pos_q - pos_p)| / sigma_z, times the LUMA stop 1 / (1 + (dl * dl) / (sigma_l2 * v_p + eps_l)), v_p = 1 without
+    a variance; taken iff 0 < w.  sum_c += c_q * w, sum_w += w, sum_v += var_q * (w * w) in tap order; c = sum_c / sum_w,
+    var = sum_v / (sum_w * sum_w); with ATROUS_MODULATE c * a_p on channels 0..2.
+
+    weights: if a list is given, the 25 (taken bool [N, H, W], w float32 [N, H, W]) pairs are appended to it in tap order (w
+    is 0 where the tap is not taken): what a test needs to evaluate the same sums in another precision."""
+    f = np.float32
+    colour, variance, hits = _atrous_args(colour, variance, hits)
+    single = colour.ndim == 3
+    if single:
+        colour, hits = colour[None], hits[None]
+        variance = None if variance is None else variance[None]
+    step, flags, normal_sq = int(step), int(flags), int(normal_sq)
+    if not 1 <= step <= ATROUS_MAX_STEP or not 0 <= normal_sq <= 7 or flags & ~31:
+        raise ValueError("step must be 1..64, normal_sq 0..7, flags of ATROUS_*")
+    sigma_z, sigma_l2, eps_l, alb_floor = f(sigma_z), f(sigma_l2), f(eps_l), f(alb_floor)
+    if not (sigma_z > 0 and sigma_l2 > 0 and eps_l > 0 and alb_floor > 0):
+        raise ValueError("sigma_z, sigma_l2, eps_l and alb_floor must be above 0")
+    n, h, w, ch = colour.shape
+    pos, _, nrm, ids, alb, _ = hit_fields(hits)
+    hit = ids >= 0
+    with np.errstate(all="ignore"):
+        a = np.where(alb > alb_floor, alb, alb_floor)                       # a NaN albedo gives the floor
+        a = np.where(hit[..., None], a, f(1.0))
+        col = colour.copy()
+        if flags & ATROUS_DEMODULATE:
+            col[..., 0:3] = np.where(hit[..., None], col[..., 0:3] / a, col[..., 0:3])
+        lum = (col[..., 0] * f(0.2126) + col[..., 1] * f(0.7152)) + col[..., 2] * f(0.0722)
+        var = np.ones((n, h, w), dtype=f) if variance is None else variance
+        den = sigma_l2 * var + eps_l
+        ys, xs = np.mgrid[0:h, 0:w]
+        sc, sw, sv = np.zeros((n, h, w, ch), dtype=f), np.zeros((n, h, w), dtype=f), np.zeros((n, h, w), dtype=f)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                qy, qx = ys + dy * step, xs + dx * step
+                ok = (qy >= 0) & (qy < h) & (qx >= 0) & (qx < w)
+                qy, qx = np.clip(qy, 0, h - 1), np.clip(qx, 0, w - 1)
+                wt = np.full((n, h, w), ATROUS_H[dy + 2] * ATROUS_H[dx + 2], dtype=f)
+                if dx == 0 and dy == 0:
+                    take = np.ones((n, h, w), dtype=bool)
+                else:
+                    ok = ok[None] & (ids[:, qy, qx] >= 0)
+                    if flags & ATROUS_NORMAL:
+                        nq = nrm[:, qy, qx]
+                        d = (nrm[..., 0] * nq[..., 0] + nrm[..., 1] * nq[..., 1]) + nrm[..., 2] * nq[..., 2]
+                        d = np.where(0 < d, d, f(0.0))
+                        for _ in range(normal_sq):
+                            d = d * d
+                        wt = wt * d
+                    if flags & ATROUS_PLANE:
+                        e = pos[:, qy, qx] - pos
+                        d = (nrm[..., 0] * e[..., 0] + nrm[..., 1] * e[..., 1]) + nrm[..., 2] * e[..., 2]
+                        x = np.abs(d) / sigma_z
+                        wt = wt * (f(1.0) / (f(1.0) + x * x))
+                    if flags & ATROUS_LUMA:
+                        dl = lum - lum[:, qy, qx]
+                        wt = wt * (f(1.0) / (f(1.0) + (dl * dl) / den))
+                    take = ok & (0 < wt)
+                wt = np.where(take, wt, f(0.0))
+                if weights is not None:
+                    weights.append((take, wt))
+                sc = np.where(take[..., None], sc + col[:, qy, qx] * wt[..., None], sc)
+                sw = np.where(take, sw + wt, sw)
+                sv = np.where(take, sv + var[:, qy, qx] * (wt * wt), sv)
+        out = sc / sw[..., None]
+        vout = sv / (sw * sw)
+        if flags & ATROUS_MODULATE:
+            out[..., 0:3] = out[..., 0:3] * a
+        out = np.where(hit[..., None], out, col).astype(f)
+        vout = None if variance is None else np.where(hit, vout, variance).astype(f)
+    if single:
+        return out[0], None if vout is None else vout[0]
+    return out, vout
+
+
+def denoise(colour, variance, hits, passes=5, albedo=False, **stops):
+    """The specification of Scene.denoise: `passes` (1..7) atrous_pass calls with step = 1, 2, 4, ..., each fed the colour and
+    variance of the one before; with albedo=True ATROUS_DEMODULATE is set on the first pass and ATROUS_MODULATE on the last.
+    stops: normal_power, plane, luma, luma_eps, albedo_floor as atrous_stops takes them.  Returns (colour, variance or None)."""
+    passes = int(passes)
+    if not 1 <= passes <= 7:
+        raise ValueError("passes must be 1..7")
+    if "demodulate" in stops or "modulate" in stops:
+        raise ValueError("denoise sets demodulate and modulate itself (albedo=True)")
+    c, v = colour, variance
+    for k in range(passes):
+        flags, nsq, sz, sl2, el, af = atrous_stops(demodulate=albedo and k == 0, modulate=albedo and k == passes - 1, **stops)
+        c, v = atrous_pass(c, v, hits, 1 << k, flags, nsq, sz, sl2, el, af)
+    return c, v
+
+
+def pt_adapt_view_variance(state, spp, unknown=1.0):
+    """The specification of qr_pt_adapt_views_variance_async (PtAdaptiveViews.variance) for a state [N, 8, slots] (or one view's
+    [8, slots]): float32 [N, H * W].  Per slot, m = plane 4 (unsigned): where 2 <= m, s = (M2r + M2g) + M2b, s = s if 0 < s else
+    0, v = s / ((float32(m) * float32(m - 1)) * 3); elsewhere v = unknown.  Per pixel (v_0 + v_1 + ... in slot order) * (1 /
+    (spp * spp)): the channel-mean variance of the pixel's FSAA-reduced mean, its slots taken as independent."""
+    f = np.float32
+    st = _pt_adapt_view_state(state)
+    spp = int(spp)
+    if spp not in (1, 2, 4) or st.shape[2] % spp != 0:
+        raise ValueError("the slots of a view are pixels * samples per pixel, 1, 2 or 4")
+    m = st[:, 4]
+    m2 = st[:, 5:8].view(f)
+    with np.errstate(all="ignore"):
+        s = (m2[:, 0] + m2[:, 1]) + m2[:, 2]
+        s = np.where(0 < s, s, f(0.0))
+        v = s / ((m.astype(f) * (m - np.uint32(1)).astype(f)) * f(3.0))
+        v = np.where(m >= np.uint32(2), v, f(unknown)).astype(f)
+        v = v.reshape(st.shape[0], st.shape[2] // spp, spp)
+        acc = v[..., 0]
+        for k in range(1, spp):
+            acc = acc + v[..., k]
+        return (acc * (f(1.0) / f(spp * spp))).astype(f)

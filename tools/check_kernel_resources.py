@@ -28,6 +28,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     exceeds the budget of the unframed instance it mirrors;
   * a hit-layer instance qr_layer_kernel<VIEW, DIVK, COHERENT> spills a vector register, has a private segment, or uses more
     than 168 VGPRs (128: the view instance with packet walks only);
+  * a guided a-trous instance qr_atrous_kernel<CH> or qr_pt_adapt_var_kernel spills a vector register, has a private segment or
+    uses more than 64 VGPRs, or a filter instance more LDS than its 36 x 12 staged entries (20736 B / 22464 B);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
 usage: check_kernel_resources.py <file.s> [--print]
 """
@@ -116,7 +118,14 @@ LIMITS = {
     "15qr_layer_kernelILb0ELb1ELb1EE": (168, 0, 0),
     "15qr_layer_kernelILb1ELb1ELb1EE": (168, 0, 0),
     "15qr_layer_kernelILb1ELb0ELb1EE": (128, 0, 0),
+    # guided a-trous filter (qr_atrous.hpp qr_atrous_kernel<CH>): 25 taps out of LDS, bound by LDS and memory, not by registers:
+    # nothing spilled, no private segment, 64 VGPRs (8 waves per SIMD: seven workgroups of 4 waves per CU fit their LDS), and no
+    # more LDS than 36 x 12 entries of 13 planes; the variance kernel beside it likewise
+    "16qr_atrous_kernelILi3EE": (64, 0, 0),
+    "16qr_atrous_kernelILi4EE": (64, 0, 0),
+    "22qr_pt_adapt_var_kernel": (64, 0, 0),
 }
+LDS_LIMITS = {"16qr_atrous_kernelILi3EE": 20736, "16qr_atrous_kernelILi4EE": 22464}
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 
 
@@ -146,6 +155,9 @@ def main():
                 if k["vgpr_count"] > vg: bad.append(f"{k['name']}: {k['vgpr_count']} VGPRs > {vg} (a wave per SIMD lost)")
                 if k["vgpr_spill_count"] > sp: bad.append(f"{k['name']}: {k['vgpr_spill_count']} vector registers spilled > {sp}")
                 if k["private_segment_fixed_size"] > scr: bad.append(f"{k['name']}: private segment {k['private_segment_fixed_size']} B > {scr}")
+        for frag, lds in LDS_LIMITS.items():
+            if frag in k["name"] and k["group_segment_fixed_size"] > lds:
+                bad.append(f"{k['name']}: {k['group_segment_fixed_size']} B of LDS > {lds} (a workgroup per CU lost)")
     missing = [frag for frag in LIMITS if not any(frag in k["name"] for k in ks)]
     if missing:
         bad.append(f"kernel instances missing from {path}: {missing}")
