@@ -35,12 +35,21 @@
 #include <chrono>
 #include <utility>
 #include <string>
+#include <type_traits>
+#include <initializer_list>
 
 #define HIP_TRY(expr)                                                          \
     do {                                                                       \
         hipError_t e_ = (expr);                                                \
         if (e_ != hipSuccess)                                                  \
             return qr_fail(QR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+/* ... and for a check of our own: its refusal is the caller's */
+#define QR_TRY(expr)                                                           \
+    do {                                                                       \
+        const int rc_ = (expr);                                                \
+        if (rc_ != QR_OK) return rc_;                                          \
     } while (0)
 
 struct qr_device_scene
@@ -73,6 +82,26 @@ struct qr_device_scene
 };
 
 static void multi_forget(const qr_device_scene *s);
+
+static int need_scene(const qr_device_scene *s)
+{
+    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    return QR_OK;
+}
+
+/* The first n seeds of the engine's seed plane, as rt_Scene::reset_pseed fills it (engine.cpp:3651-3685: a 48-bit LCG walks
+ * over the slots, each slot keeps the low 32 bits): what every path-tracer state starts from. */
+static std::vector<uint32_t> pt_seed_plane(size_t n)
+{
+    std::vector<uint32_t> seeds(n);
+    unsigned long long seed = 1;
+    for (size_t k = 0; k < n; k++)
+    {
+        seed = (seed * 25214903917ull + 11ull) & 0x0000FFFFFFFFFFFFull;
+        seeds[k] = (uint32_t)seed;
+    }
+    return seeds;
+}
 
 extern "C" const char *qr_kernel_name(void) { return "qr_render_kernel"; }
 
@@ -261,19 +290,18 @@ extern "C" int qr_scene_get_info(const qr_device_scene *s, qr_scene_info *info)
 
 extern "C" int qr_scene_set_depth(qr_device_scene *s, int depth)
 {
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    QR_TRY(need_scene(s));
     if (depth < 0 || depth > QR_MAX_DEPTH) return qr_fail(QR_ERR_ARG, "depth must be 0..10 (RT_STACK_DEPTH)");
     s->lp.depth = depth;
     return QR_OK;
 }
 
 /*
- * Path-tracer mode on / off.  Turning it on (re)starts the accumulation: the seed plane as rt_Scene::reset_pseed
- * fills it (engine.cpp:3651-3685: a 48-bit LCG walks over the slots, each slot keeps the low 32 bits), colour planes 0.
+ * Path-tracer mode on / off.  Turning it on (re)starts the accumulation: the engine's seed plane (pt_seed_plane), colour planes 0.
  */
 extern "C" int qr_scene_set_pt(qr_device_scene *s, int on)
 {
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    QR_TRY(need_scene(s));
     HIP_TRY(hipSetDevice(s->device));
     if (!on) { s->pt_on = false; return QR_OK; }
     const size_t n = (size_t)s->fr.frm_row * s->fr.frm_h * ((size_t)1 << s->fr.fsaa);
@@ -288,13 +316,7 @@ extern "C" int qr_scene_set_pt(qr_device_scene *s, int on)
         (void)hipFree(s->d_seeds); (void)hipFree(s->d_acc);
         s->d_seeds = seeds_dev; s->d_acc = acc_dev;
     }
-    std::vector<uint32_t> seeds(n);
-    unsigned long long seed = 1;
-    for (size_t k = 0; k < n; k++)
-    {
-        seed = (seed * 25214903917ull + 11ull) & 0x0000FFFFFFFFFFFFull;
-        seeds[k] = (uint32_t)seed;
-    }
+    const std::vector<uint32_t> seeds = pt_seed_plane(n);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(s->d_seeds, seeds.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(s->d_acc, 0, 3 * n * sizeof(float)));
@@ -306,7 +328,7 @@ extern "C" int qr_scene_set_pt(qr_device_scene *s, int on)
 
 extern "C" int qr_scene_set_rows(qr_device_scene *s, int row_begin, int row_end, int index, int thnum)
 {
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    QR_TRY(need_scene(s));
     const int h = s->fr.frm_h;
     if (row_begin < 0 || row_end > h || row_begin > row_end) return qr_fail(QR_ERR_ARG, "bad row range");
     if (thnum <= 0 || index < 0 || index >= thnum) return qr_fail(QR_ERR_ARG, "bad index/thnum");
@@ -320,7 +342,7 @@ extern "C" int qr_scene_set_rows(qr_device_scene *s, int row_begin, int row_end,
 
 extern "C" int qr_scene_set_tile_rows(qr_device_scene *s, int first, int stride)
 {
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
+    QR_TRY(need_scene(s));
     const int total = (s->fr.frm_h + 7) / 8;
     if (stride <= 0 || first < 0) return qr_fail(QR_ERR_ARG, "bad tile-row selection");
     s->lp.row_begin = 0; s->lp.row_end = s->fr.frm_h;
@@ -429,1077 +451,8 @@ extern "C" int qr_render_async(qr_device_scene *s, void *frame_dev, void *stream
     return QR_OK;
 }
 
-/* ---- ray queries (qr_query.hpp) ---- */
-
-static int query_args(const qr_device_scene *s, const qr_ray *rays, int64_t n, const void *out0, const void *out1, uint32_t flags)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
-    if (flags & ~QR_TRACE_COHERENT) return qr_fail(QR_ERR_ARG, "unknown query flags");
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    if (n == 0) return QR_OK;
-    if (rays == nullptr || out0 == nullptr || out1 == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if (((uintptr_t)rays & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays must be 16-byte aligned");
-    return QR_OK;
-}
-
-extern "C" int qr_trace_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,
-                                   float *t_out_dev, int32_t *id_out_dev, uint32_t flags, void *stream)
-{
-    const int rc = query_args(s, rays_dev, n, t_out_dev, id_out_dev, flags);
-    if (rc != QR_OK || n == 0) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    const f32x4 *r = (const f32x4 *)rays_dev;
-    if (flags & QR_TRACE_COHERENT)
-        hipLaunchKernelGGL((qr_trace_kernel<false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
-                           t_out_dev, id_out_dev, (uint8_t *)nullptr, s->lp.stats);
-    else
-        hipLaunchKernelGGL((qr_trace_kernel<false, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
-                           t_out_dev, id_out_dev, (uint8_t *)nullptr, s->lp.stats);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_occluded_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,
-                                 uint8_t *occ_out_dev, uint32_t flags, void *stream)
-{
-    const int rc = query_args(s, rays_dev, n, occ_out_dev, occ_out_dev, flags);
-    if (rc != QR_OK || n == 0) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    const f32x4 *r = (const f32x4 *)rays_dev;
-    if (flags & QR_TRACE_COHERENT)
-        hipLaunchKernelGGL((qr_trace_kernel<true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
-                           (float *)nullptr, (int32_t *)nullptr, occ_out_dev, s->lp.stats);
-    else
-        hipLaunchKernelGGL((qr_trace_kernel<true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
-                           (float *)nullptr, (int32_t *)nullptr, occ_out_dev, s->lp.stats);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* ray shading (qr_kernel.hpp qr_shade_rays_kernel): the renderer's colour for caller rays, at the scene's current depth */
-extern "C" int qr_shade_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,
-                                   float *rgb_out_dev, int32_t *id_out_dev, uint32_t flags, void *stream)
-{
-    const int rc = query_args(s, rays_dev, n, rgb_out_dev, rgb_out_dev, flags);
-    if (rc != QR_OK) return rc;
-    if (s->pt_on) return qr_fail(QR_ERR_UNSUP, "scene is in path-tracer mode: caller rays carry no sample seeds");
-    if (n == 0) return QR_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    RaysP rp;
-    rp.rays = (const f32x4 *)rays_dev; rp.n = (int32_t)n; rp.pad = 0; rp.rgb = rgb_out_dev;
-    if (flags & QR_TRACE_COHERENT)
-        hipLaunchKernelGGL((qr_shade_rays_kernel<true>), grid, block, 0, (hipStream_t)stream, s->lp, rp, id_out_dev);
-    else
-        hipLaunchKernelGGL((qr_shade_rays_kernel<false>), grid, block, 0, (hipStream_t)stream, s->lp, rp, id_out_dev);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* view rendering (qr_kernel.hpp qr_render_views_kernel): whole frames from caller-supplied cameras, at the scene's current depth */
-extern "C" int qr_render_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                     uint32_t *frames_dev, int32_t *ids_dev, float *depth_dev, uint32_t flags, void *stream)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
-    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
-        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
-    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown view flags");
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    if (s->pt_on) return qr_fail(QR_ERR_UNSUP, "scene is in path-tracer mode: its seeds and colour planes belong to the snapshot's frame");
-    const int fsaa = s->fr.fsaa;
-    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
-    const int64_t fcols = (width + fw - 1) / fw, frows = (height + fh - 1) / fh;
-    if ((int64_t)n_views * fcols * frows > (int64_t)QR_VIEW_MAX_WAVES)
-        return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
-    if (n_views == 0) return QR_OK;
-    if (views_dev == nullptr || frames_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if (((uintptr_t)views_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "views must be 16-byte aligned");
-    if ((((uintptr_t)frames_dev | (uintptr_t)ids_dev | (uintptr_t)depth_dev) & 3u) != 0) return qr_fail(QR_ERR_ARG, "frames, ids and depth must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)fcols, (unsigned)frows, (unsigned)n_views), block(QR_BLOCK);
-    ViewsP vp;
-    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = depth_dev;
-    /* the instance is chosen as render() chooses its own: per-lane walks only where some list is a long hierarchy or carries a grid */
-    if (s->divk)
-        hipLaunchKernelGGL((qr_render_views_kernel<true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, vp, frames_dev, ids_dev);
-    else
-        hipLaunchKernelGGL((qr_render_views_kernel<false, QR_MIN_WAVES_PER_SIMD>), grid, block, 0, (hipStream_t)stream, s->lp, vp, frames_dev, ids_dev);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* view accumulation (qr_kernel.hpp qr_views_mean_kernel): the sum and the mean frame of many views of one frame, in one launch */
-extern "C" int qr_render_views_mean_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                          float *sum_dev, uint32_t *frame_dev, float scale, uint32_t flags, void *stream)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
-    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
-        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
-    if ((flags & ~QR_MEAN_RESUME) != 0u) return qr_fail(QR_ERR_ARG, "unknown view accumulation flags");
-    if (frame_dev != nullptr && !(std::isfinite(scale) && scale > 0.0f))
-        return qr_fail(QR_ERR_ARG, "scale must be finite and greater than 0 when a frame is wanted");
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    if (s->pt_on) return qr_fail(QR_ERR_UNSUP, "scene is in path-tracer mode: its seeds and colour planes belong to the snapshot's frame");
-    if (n_views == 0) return QR_OK;
-    if (views_dev == nullptr || sum_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if (((uintptr_t)views_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "views must be 16-byte aligned");
-    if ((((uintptr_t)sum_dev | (uintptr_t)frame_dev) & 3u) != 0) return qr_fail(QR_ERR_ARG, "sum and frame must be 4-byte aligned");
-    const int fsaa = s->fr.fsaa;
-    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
-    HIP_TRY(hipSetDevice(s->device));
-    /* one wave per footprint of the ONE frame, whatever n_views is (at most 4096 x 4096 workgroups: QR_VIEW_MAX_DIM) */
-    const dim3 grid((unsigned)((width + fw - 1) / fw), (unsigned)((height + fh - 1) / fh), 1u), block(QR_BLOCK);
-    ViewsP vp;
-    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
-    const uint32_t resume = flags & QR_MEAN_RESUME;
-    if (frame_dev == nullptr) scale = 1.0f;
-    /* the instance is chosen as qr_render_views_async chooses its own */
-    if (s->divk)
-        hipLaunchKernelGGL((qr_views_mean_kernel<true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, vp, n_views,
-                           sum_dev, frame_dev, scale, resume);
-    else
-        hipLaunchKernelGGL((qr_views_mean_kernel<false, QR_MIN_WAVES_PER_SIMD>), grid, block, 0, (hipStream_t)stream, s->lp, vp, n_views,
-                           sum_dev, frame_dev, scale, resume);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* ---- path-traced views (qr_kernel.hpp qr_pt_views_kernel): progressive frames from caller cameras, state in the caller's memory ---- */
-
-/* the checks every entry point of the feature shares: sizes and the view launch's limits; *slots: words of one plane of one view */
-static int pt_views_dims(const qr_device_scene *s, int n_views, int width, int height, uint64_t *slots)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
-    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
-        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
-    const int fsaa = s->fr.fsaa;
-    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
-    const int64_t fcols = (width + fw - 1) / fw, frows = (height + fh - 1) / fh;
-    if ((int64_t)n_views * fcols * frows > (int64_t)QR_VIEW_MAX_WAVES)
-        return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
-    *slots = ((uint64_t)width * (uint64_t)height) << fsaa;
-    if ((uint64_t)n_views * *slots > ((uint64_t)1 << 30))
-        return qr_fail(QR_ERR_ARG, "more than 2^30 pixel samples of path-tracer state in one launch");
-    return QR_OK;
-}
-
-extern "C" int qr_pt_views_state_bytes(qr_device_scene *s, int n_views, int width, int height, uint64_t *bytes_out)
-{
-    uint64_t slots = 0;
-    const int rc = pt_views_dims(s, n_views, width, height, &slots);
-    if (rc != QR_OK) return rc;
-    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    *bytes_out = (uint64_t)n_views * QR_PT_VIEWS_STATE_WORDS * slots * sizeof(uint32_t);
-    return QR_OK;
-}
-
-/* the seed plane of qr_scene_set_pt (rt_Scene::reset_pseed) for every view, running means 0: synchronous, as qr_scene_set_pt is */
-extern "C" int qr_pt_views_reset(qr_device_scene *s, int n_views, int width, int height, void *state_dev)
-{
-    uint64_t slots = 0;
-    const int rc = pt_views_dims(s, n_views, width, height, &slots);
-    if (rc != QR_OK) return rc;
-    if (n_views == 0) return QR_OK;
-    if (state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if (((uintptr_t)state_dev & 3u) != 0) return qr_fail(QR_ERR_ARG, "state must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    std::vector<uint32_t> seeds(slots);
-    unsigned long long seed = 1;
-    for (uint64_t k = 0; k < slots; k++)
-    {
-        seed = (seed * 25214903917ull + 11ull) & 0x0000FFFFFFFFFFFFull;
-        seeds[k] = (uint32_t)seed;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    uint32_t *st = (uint32_t *)state_dev;
-    for (int v = 0; v < n_views; v++, st += QR_PT_VIEWS_STATE_WORDS * slots)
-    {
-        HIP_TRY(hipMemcpy(st, seeds.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(st + slots, 0, 3 * slots * sizeof(uint32_t)));
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    return QR_OK;
-}
-
-extern "C" int qr_pt_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                 void *state_dev, int done, int samples, uint32_t *frames_dev, float *mean_dev,
-                                 uint32_t flags, void *stream)
-{
-    uint64_t slots = 0;
-    const int rc = pt_views_dims(s, n_views, width, height, &slots);
-    if (rc != QR_OK) return rc;
-    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown path-traced view flags");
-    if (samples < 1 || samples > QR_PT_VIEWS_MAX_SAMPLES)
-        return qr_fail(QR_ERR_ARG, "samples must be 1.." + std::to_string(QR_PT_VIEWS_MAX_SAMPLES));
-    if (done < 0 || (int64_t)done + (int64_t)samples >= ((int64_t)1 << 24))
-        return qr_fail(QR_ERR_ARG, "done must be 0 or more and done + samples below 2^24 (the sample number is exact in fp32)");
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    if (n_views == 0) return QR_OK;
-    if (views_dev == nullptr || state_dev == nullptr || frames_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if (((uintptr_t)views_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "views must be 16-byte aligned");
-    if ((((uintptr_t)state_dev | (uintptr_t)frames_dev | (uintptr_t)mean_dev) & 3u) != 0)
-        return qr_fail(QR_ERR_ARG, "state, frames and mean must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    const int fsaa = s->fr.fsaa;
-    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
-    const dim3 grid((unsigned)((width + fw - 1) / fw), (unsigned)((height + fh - 1) / fh), (unsigned)n_views), block(QR_BLOCK);
-    ViewsP vp;
-    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
-    PtViewsP pv;
-    pv.state = (uint32_t *)state_dev; pv.done = done; pv.samples = samples; pv.mean = mean_dev;
-    /* one instance, as the scene's own path tracer has one: the packet walks (shade<..., PT> exists for them alone) */
-    hipLaunchKernelGGL(qr_pt_views_kernel, grid, block, 0, (hipStream_t)stream, s->lp, vp, pv, frames_dev);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* ---- path-traced rays (qr_kernel.hpp qr_pt_rays_kernel): progressive samples for caller rays, state in the caller's memory ---- */
-
-/* the checks every entry point of the feature shares: the scene and the ray count of query_args */
-static int pt_rays_dims(const qr_device_scene *s, int64_t n)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
-    return QR_OK;
-}
-
-extern "C" int qr_pt_rays_state_bytes(qr_device_scene *s, int64_t n, uint64_t *bytes_out)
-{
-    const int rc = pt_rays_dims(s, n);
-    if (rc != QR_OK) return rc;
-    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    *bytes_out = (uint64_t)n * QR_PT_RAYS_STATE_WORDS * sizeof(uint32_t);
-    return QR_OK;
-}
-
-/* the seeds of slots 0 .. n - 1 of qr_scene_set_pt's plane (rt_Scene::reset_pseed), running means 0: synchronous, as qr_pt_views_reset is */
-extern "C" int qr_pt_rays_reset(qr_device_scene *s, int64_t n, void *state_dev)
-{
-    const int rc = pt_rays_dims(s, n);
-    if (rc != QR_OK) return rc;
-    if (n == 0) return QR_OK;
-    if (state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if (((uintptr_t)state_dev & 3u) != 0) return qr_fail(QR_ERR_ARG, "state must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    std::vector<uint32_t> seeds((size_t)n);
-    unsigned long long seed = 1;
-    for (int64_t k = 0; k < n; k++)
-    {
-        seed = (seed * 25214903917ull + 11ull) & 0x0000FFFFFFFFFFFFull;
-        seeds[(size_t)k] = (uint32_t)seed;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    uint32_t *st = (uint32_t *)state_dev;
-    HIP_TRY(hipMemcpy(st, seeds.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(st + n, 0, 3 * (size_t)n * sizeof(uint32_t)));
-    HIP_TRY(hipDeviceSynchronize());
-    return QR_OK;
-}
-
-extern "C" int qr_pt_rays_async(qr_device_scene *s, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
-                                void *state_dev, int done, int samples, float *rgb_dev, uint32_t flags, void *stream)
-{
-    const int rc = pt_rays_dims(s, n);
-    if (rc != QR_OK) return rc;
-    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown path-traced ray flags");
-    if (samples < 1 || samples > QR_PT_RAYS_MAX_SAMPLES)
-        return qr_fail(QR_ERR_ARG, "samples must be 1.." + std::to_string(QR_PT_RAYS_MAX_SAMPLES));
-    if (done < 0 || (int64_t)done + (int64_t)samples >= ((int64_t)1 << 24))
-        return qr_fail(QR_ERR_ARG, "done must be 0 or more and done + samples below 2^24 (the sample number is exact in fp32)");
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    if (n == 0) return QR_OK;
-    if (rays_dev == nullptr || state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if ((((uintptr_t)rays_dev | (uintptr_t)spread_dev) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays and spread must be 16-byte aligned");
-    if ((((uintptr_t)state_dev | (uintptr_t)rgb_dev) & 3u) != 0) return qr_fail(QR_ERR_ARG, "state and rgb must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    PtRaysP pr;
-    pr.rays = (const f32x4 *)rays_dev; pr.spread = (const f32x4 *)spread_dev; pr.n = (int32_t)n; pr.pad = 0; pr.rgb = rgb_dev;
-    /* one instance, as the scene's own path tracer has one: the packet walks (shade<..., PT> exists for them alone); rays are
-     * never taken as neighbours */
-    hipLaunchKernelGGL(qr_pt_rays_kernel, grid, block, 0, (hipStream_t)stream, s->lp, pr, (uint32_t *)state_dev, done, samples);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* ---- adaptive path-traced rays (qr_kernel.hpp qr_pt_adapt_kernel): per-ray counts, Welford's M2 and a stop rule on chip ---- */
-
-extern "C" int qr_pt_adapt_state_bytes(qr_device_scene *s, int64_t n, uint64_t *bytes_out)
-{
-    const int rc = pt_rays_dims(s, n);
-    if (rc != QR_OK) return rc;
-    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    *bytes_out = (uint64_t)n * QR_PT_ADAPT_STATE_WORDS * sizeof(uint32_t);
-    return QR_OK;
-}
-
-/* plane 0 as qr_pt_rays_reset writes it, every other plane 0: synchronous */
-extern "C" int qr_pt_adapt_reset(qr_device_scene *s, int64_t n, void *state_dev)
-{
-    const int rc = qr_pt_rays_reset(s, n, state_dev);
-    if (rc != QR_OK || n == 0) return rc;
-    HIP_TRY(hipMemset((uint32_t *)state_dev + QR_PT_RAYS_STATE_WORDS * (size_t)n, 0,
-                      (QR_PT_ADAPT_STATE_WORDS - QR_PT_RAYS_STATE_WORDS) * (size_t)n * sizeof(uint32_t)));
-    HIP_TRY(hipDeviceSynchronize());
-    return QR_OK;
-}
-
-/* the checks the adaptive launches share, in the order their refusals are documented: scene and count, flags, samples (the open
- * list has none: it passes 1), the rule's parameters, the ray-query list */
-static int pt_adapt_args(const qr_device_scene *s, int64_t n, int samples, int min_samples, int max_samples, float tol2, uint32_t flags)
-{
-    const int rc = pt_rays_dims(s, n);
-    if (rc != QR_OK) return rc;
-    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown adaptive path-traced ray flags");
-    if (samples < 1 || samples > QR_PT_ADAPT_MAX_SAMPLES)
-        return qr_fail(QR_ERR_ARG, "samples must be 1.." + std::to_string(QR_PT_ADAPT_MAX_SAMPLES));
-    if (min_samples < 0 || max_samples < 1 || min_samples > max_samples || max_samples >= (1 << 24))
-        return qr_fail(QR_ERR_ARG, "min_samples and max_samples must be 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24 (the count is exact in fp32)");
-    if (!(tol2 >= 0.0f) || tol2 > FLT_MAX) return qr_fail(QR_ERR_ARG, "tol2 must be a finite number, 0 or more");
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    return QR_OK;
-}
-
-extern "C" int qr_pt_adapt_rays_async(qr_device_scene *s, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
-                                      void *state_dev, int samples, int min_samples, int max_samples, float tol2,
-                                      float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream)
-{
-    const int rc = pt_adapt_args(s, n, samples, min_samples, max_samples, tol2, flags);
-    if (rc != QR_OK) return rc;
-    if (n == 0) return QR_OK;
-    if (rays_dev == nullptr || state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if ((((uintptr_t)rays_dev | (uintptr_t)spread_dev) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays and spread must be 16-byte aligned");
-    if ((((uintptr_t)state_dev | (uintptr_t)rgb_dev | (uintptr_t)open_dev) & 3u) != 0)
-        return qr_fail(QR_ERR_ARG, "state, rgb and open must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    PtRaysP pr;
-    pr.rays = (const f32x4 *)rays_dev; pr.spread = (const f32x4 *)spread_dev; pr.n = (int32_t)n; pr.pad = 0; pr.rgb = rgb_dev;
-    hipLaunchKernelGGL(qr_pt_adapt_kernel, grid, block, 0, (hipStream_t)stream, s->lp, pr, (uint32_t *)state_dev, samples,
-                       min_samples, max_samples, tol2, open_dev);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* ---- adaptive path-traced views (qr_kernel.hpp qr_pt_adapt_views_kernel): qr_pt_views_async with the adaptive rays' state per slot ---- */
-
-/* the checks every entry point of the feature shares: pt_views_dims, and the state's bytes held to what qr_pt_views_async allows */
-static int pt_adapt_views_dims(const qr_device_scene *s, int n_views, int width, int height, uint64_t *slots)
-{
-    const int rc = pt_views_dims(s, n_views, width, height, slots);
-    if (rc != QR_OK) return rc;
-    if ((uint64_t)n_views * *slots > ((uint64_t)1 << 29))
-        return qr_fail(QR_ERR_ARG, "more than 2^29 pixel samples of adaptive path-tracer state in one launch");
-    return QR_OK;
-}
-
-extern "C" int qr_pt_adapt_views_state_bytes(qr_device_scene *s, int n_views, int width, int height, uint64_t *bytes_out)
-{
-    uint64_t slots = 0;
-    const int rc = pt_adapt_views_dims(s, n_views, width, height, &slots);
-    if (rc != QR_OK) return rc;
-    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    *bytes_out = (uint64_t)n_views * QR_PT_ADAPT_STATE_WORDS * slots * sizeof(uint32_t);
-    return QR_OK;
-}
-
-/* plane 0 of every view as qr_pt_views_reset writes it, every other plane 0: synchronous */
-extern "C" int qr_pt_adapt_views_reset(qr_device_scene *s, int n_views, int width, int height, void *state_dev)
-{
-    uint64_t slots = 0;
-    const int rc = pt_adapt_views_dims(s, n_views, width, height, &slots);
-    if (rc != QR_OK) return rc;
-    if (n_views == 0) return QR_OK;
-    if (state_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if (((uintptr_t)state_dev & 3u) != 0) return qr_fail(QR_ERR_ARG, "state must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    std::vector<uint32_t> seeds(slots);
-    unsigned long long seed = 1;
-    for (uint64_t k = 0; k < slots; k++)
-    {
-        seed = (seed * 25214903917ull + 11ull) & 0x0000FFFFFFFFFFFFull;
-        seeds[k] = (uint32_t)seed;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    uint32_t *st = (uint32_t *)state_dev;
-    for (int v = 0; v < n_views; v++, st += QR_PT_ADAPT_STATE_WORDS * slots)
-    {
-        HIP_TRY(hipMemcpy(st, seeds.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(st + slots, 0, (QR_PT_ADAPT_STATE_WORDS - 1) * slots * sizeof(uint32_t)));
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    return QR_OK;
-}
-
-extern "C" int qr_pt_adapt_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                       void *state_dev, int samples, int min_samples, int max_samples, float tol2,
-                                       uint32_t *frames_dev, float *mean_dev, int32_t *counts_dev, uint32_t *open_dev,
-                                       uint32_t flags, void *stream)
-{
-    uint64_t slots = 0;
-    const int rc = pt_adapt_views_dims(s, n_views, width, height, &slots);
-    if (rc != QR_OK) return rc;
-    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown adaptive path-traced view flags");
-    if (samples < 1 || samples > QR_PT_ADAPT_VIEWS_MAX_SAMPLES)
-        return qr_fail(QR_ERR_ARG, "samples must be 1.." + std::to_string(QR_PT_ADAPT_VIEWS_MAX_SAMPLES));
-    if (min_samples < 0 || max_samples < 1 || min_samples > max_samples || max_samples >= (1 << 24))
-        return qr_fail(QR_ERR_ARG, "min_samples and max_samples must be 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24 (the count is exact in fp32)");
-    if (!(tol2 >= 0.0f) || tol2 > FLT_MAX) return qr_fail(QR_ERR_ARG, "tol2 must be a finite number, 0 or more");
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    if (n_views == 0) return QR_OK;
-    if (views_dev == nullptr || state_dev == nullptr || frames_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if (((uintptr_t)views_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "views must be 16-byte aligned");
-    if ((((uintptr_t)state_dev | (uintptr_t)frames_dev | (uintptr_t)mean_dev | (uintptr_t)counts_dev | (uintptr_t)open_dev) & 3u) != 0)
-        return qr_fail(QR_ERR_ARG, "state, frames, mean, counts and open must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    const int fsaa = s->fr.fsaa;
-    const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
-    const dim3 grid((unsigned)((width + fw - 1) / fw), (unsigned)((height + fh - 1) / fh), (unsigned)n_views), block(QR_BLOCK);
-    ViewsP vp;
-    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
-    PtAdaptViewsP pa;
-    pa.state = (uint32_t *)state_dev; pa.samples = samples; pa.min_samples = min_samples; pa.max_samples = max_samples; pa.tol2 = tol2;
-    pa.mean = mean_dev; pa.counts = counts_dev; pa.open = open_dev;
-    hipLaunchKernelGGL(qr_pt_adapt_views_kernel, grid, block, 0, (hipStream_t)stream, s->lp, vp, pa, frames_dev);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* the per-pixel variance of an adaptive view state (qr_atrous.hpp qr_pt_adapt_var_kernel): the state is only read */
-extern "C" int qr_pt_adapt_views_variance_async(qr_device_scene *s, const int32_t *state, int n_views, int width, int height,
-                                                float unknown, float *var_dev, uint32_t flags, void *stream)
-{
-    uint64_t slots = 0;
-    const int rc = pt_adapt_views_dims(s, n_views, width, height, &slots);
-    if (rc != QR_OK) return rc;
-    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown adaptive view variance flags");
-    if (n_views == 0) return QR_OK;
-    if (state == nullptr || var_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if ((((uintptr_t)state | (uintptr_t)var_dev) & 3u) != 0) return qr_fail(QR_ERR_ARG, "state and var must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    const uint32_t pixels = (uint32_t)width * (uint32_t)height;
-    const dim3 grid((pixels + 255u) / 256u, (unsigned)n_views), block(256);
-    hipLaunchKernelGGL(qr_pt_adapt_var_kernel, grid, block, 0, (hipStream_t)stream, (const uint32_t *)state, pixels, s->fr.fsaa,
-                       unknown, var_dev);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* ---- guided a-trous filter (qr_atrous.hpp): one edge-avoiding pass over view frames, tiles in the decimated lattice ---- */
-
-extern "C" int qr_atrous_views_async(qr_device_scene *s, const float *colour_in, const float *var_in, const qr_hit *hits,
-                                     int n_views, int width, int height, const qr_atrous_params *p,
-                                     float *colour_out, float *var_out, void *stream)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (p == nullptr) return qr_fail(QR_ERR_ARG, "null filter parameters");
-    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
-    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
-        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
-    if (p->step < 1 || p->step > QR_ATROUS_MAX_STEP) return qr_fail(QR_ERR_ARG, "step must be 1.." + std::to_string(QR_ATROUS_MAX_STEP));
-    if (p->channels != 3 && p->channels != 4) return qr_fail(QR_ERR_ARG, "channels must be 3 or 4");
-    if (p->normal_sq < 0 || p->normal_sq > 7) return qr_fail(QR_ERR_ARG, "normal_sq must be 0..7");
-    if ((p->flags & ~(QR_ATROUS_NORMAL | QR_ATROUS_PLANE | QR_ATROUS_LUMA | QR_ATROUS_DEMODULATE | QR_ATROUS_MODULATE)) != 0u)
-        return qr_fail(QR_ERR_ARG, "unknown filter flags");
-    if (!(p->sigma_z > 0.0f) || !(p->sigma_l2 > 0.0f) || !(p->eps_l > 0.0f) || !(p->alb_floor > 0.0f))
-        return qr_fail(QR_ERR_ARG, "sigma_z, sigma_l2, eps_l and alb_floor must be above 0");
-    if ((var_in == nullptr) != (var_out == nullptr)) return qr_fail(QR_ERR_ARG, "var_in and var_out go together: both or neither");
-    if (n_views == 0) return QR_OK;
-    if (colour_in == nullptr || colour_out == nullptr || hits == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if (((uintptr_t)hits & 15u) != 0) return qr_fail(QR_ERR_ARG, "hits must be 16-byte aligned");
-    if ((((uintptr_t)colour_in | (uintptr_t)colour_out | (uintptr_t)var_in | (uintptr_t)var_out) & 3u) != 0)
-        return qr_fail(QR_ERR_ARG, "colour and variance must be 4-byte aligned");
-    if (colour_in == colour_out || (var_in != nullptr && var_in == var_out))
-        return qr_fail(QR_ERR_ARG, "a pass reads neighbours: it cannot run in place");
-    HIP_TRY(hipSetDevice(s->device));
-    AtrousP ap;
-    ap.colour_in = colour_in; ap.var_in = var_in; ap.hits = (const f32x4 *)hits; ap.colour_out = colour_out; ap.var_out = var_out;
-    ap.width = width; ap.height = height; ap.step = p->step; ap.normal_sq = p->normal_sq; ap.flags = p->flags;
-    ap.sigma_z = p->sigma_z; ap.sigma_l2 = p->sigma_l2; ap.eps_l = p->eps_l; ap.alb_floor = p->alb_floor;
-    /* phases per axis (no more than there are pixels), and tiles over the longest phase: entry i of phase f is pixel f + i * step */
-    const int phx = std::min(p->step, width), phy = std::min(p->step, height);
-    ap.tiles_x = ((width + p->step - 1) / p->step + QR_ATROUS_TW - 1) / QR_ATROUS_TW;
-    ap.tiles_y = ((height + p->step - 1) / p->step + QR_ATROUS_TH - 1) / QR_ATROUS_TH;
-    /* grid.y = phy * tiles_y <= height / 8 + 2 * step: far below 65535 at QR_VIEW_MAX_DIM */
-    const dim3 grid((unsigned)(phx * ap.tiles_x), (unsigned)(phy * ap.tiles_y), (unsigned)n_views), block(QR_ATROUS_BLOCK);
-    if (p->channels == 3)
-        hipLaunchKernelGGL(qr_atrous_kernel<3>, grid, block, 0, (hipStream_t)stream, ap);
-    else
-        hipLaunchKernelGGL(qr_atrous_kernel<4>, grid, block, 0, (hipStream_t)stream, ap);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* ---- open lists and indexed adaptive steps (qr_openlist.hpp, qr_kernel.hpp qr_pt_list_kernel): compaction on chip ---- */
-
-static inline int64_t pt_open_blocks(int64_t n) { return (n + QR_PT_OPEN_BLOCK - 1) / QR_PT_OPEN_BLOCK; }
-
-extern "C" int qr_pt_adapt_list_work_bytes(qr_device_scene *s, int64_t n, uint64_t *bytes_out)
-{
-    const int rc = pt_rays_dims(s, n);
-    if (rc != QR_OK) return rc;
-    if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    /* one word per block; the scan works in place and needs none of its own */
-    *bytes_out = (uint64_t)pt_open_blocks(n) * sizeof(uint32_t);
-    return QR_OK;
-}
-
-extern "C" int qr_pt_adapt_open_list_async(qr_device_scene *s, const void *state_dev, int64_t n,
-                                           int min_samples, int max_samples, float tol2,
-                                           uint32_t *index_dev, uint32_t *count_dev, void *work_dev, uint32_t flags, void *stream)
-{
-    const int rc = pt_adapt_args(s, n, 1, min_samples, max_samples, tol2, flags);
-    if (rc != QR_OK) return rc;
-    if (n == 0) return QR_OK;
-    if (state_dev == nullptr || index_dev == nullptr || count_dev == nullptr || work_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if ((((uintptr_t)state_dev | (uintptr_t)index_dev | (uintptr_t)count_dev | (uintptr_t)work_dev) & 3u) != 0)
-        return qr_fail(QR_ERR_ARG, "state, index, count and work must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    const unsigned nb = (unsigned)pt_open_blocks(n);
-    const uint32_t *st = (const uint32_t *)state_dev;
-    uint32_t *work = (uint32_t *)work_dev;
-    hipLaunchKernelGGL(qr_open_count_kernel, dim3(nb), dim3(QR_PT_OPEN_BLOCK), 0, (hipStream_t)stream, st, (uint32_t)n,
-                       (uint32_t)min_samples, (uint32_t)max_samples, tol2, work);
-    hipLaunchKernelGGL(qr_open_scan_kernel, dim3(1), dim3(QR_PT_OPEN_CHUNK), 0, (hipStream_t)stream, work, (uint32_t)nb, count_dev);
-    hipLaunchKernelGGL(qr_open_scatter_kernel, dim3(nb), dim3(QR_PT_OPEN_BLOCK), 0, (hipStream_t)stream, st, (uint32_t)n,
-                       (uint32_t)min_samples, (uint32_t)max_samples, tol2, (const uint32_t *)work, index_dev);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_pt_adapt_list_rays_async(qr_device_scene *s, const qr_ray *rays_dev, const qr_ray_spread *spread_dev, int64_t n,
-                                           void *state_dev, const uint32_t *index_dev, const uint32_t *count_dev, int64_t cap,
-                                           int samples, int min_samples, int max_samples, float tol2,
-                                           float *rgb_dev, uint32_t *open_dev, uint32_t flags, void *stream)
-{
-    const int rc = pt_adapt_args(s, n, samples, min_samples, max_samples, tol2, flags);
-    if (rc != QR_OK) return rc;
-    if (cap < 0) return qr_fail(QR_ERR_ARG, "cap must be 0 or more: the caller's upper bound on the list's length");
-    if (n == 0 || cap == 0) return QR_OK;
-    if (rays_dev == nullptr || state_dev == nullptr || index_dev == nullptr || count_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if ((((uintptr_t)rays_dev | (uintptr_t)spread_dev) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays and spread must be 16-byte aligned");
-    if ((((uintptr_t)state_dev | (uintptr_t)rgb_dev | (uintptr_t)open_dev | (uintptr_t)index_dev | (uintptr_t)count_dev) & 3u) != 0)
-        return qr_fail(QR_ERR_ARG, "state, rgb, open, index and count must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    const int64_t most = cap < n ? cap : n;             /* distinct entries below n: a list holds at most n that count */
-    const dim3 grid((unsigned)((most + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    PtRaysP pr;
-    pr.rays = (const f32x4 *)rays_dev; pr.spread = (const f32x4 *)spread_dev; pr.n = (int32_t)n; pr.pad = 0; pr.rgb = rgb_dev;
-    hipLaunchKernelGGL(qr_pt_list_kernel, grid, block, 0, (hipStream_t)stream, s->lp, pr, (uint32_t *)state_dev, index_dev, count_dev,
-                       (uint32_t)most, samples, min_samples, max_samples, tol2, open_dev);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* ---- hit records (qr_hitrec.hpp): the closest hit of qr_trace_rays_async and the surface point shading would use there ---- */
-
-extern "C" int qr_hit_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n,
-                                 qr_hit *hits_dev, uint32_t flags, void *stream)
-{
-    const int rc = query_args(s, rays_dev, n, hits_dev, hits_dev, flags);
-    if (rc != QR_OK || n == 0) return rc;
-    if (((uintptr_t)hits_dev & 15u) != 0) return qr_fail(QR_ERR_ARG, "hits must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    const f32x4 *r = (const f32x4 *)rays_dev;
-    const ViewsP vp = {};
-    if (flags & QR_TRACE_COHERENT)
-        hipLaunchKernelGGL((qr_hit_kernel<false, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
-                           vp, s->off_mat, (f32x4 *)hits_dev, s->lp.stats);
-    else
-        hipLaunchKernelGGL((qr_hit_kernel<false, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
-                           vp, s->off_mat, (f32x4 *)hits_dev, s->lp.stats);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_hit_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                  qr_hit *hits_dev, uint32_t flags, void *stream)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
-    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
-        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
-    if (flags != 0u) return qr_fail(QR_ERR_ARG, "unknown view flags");
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    {
-        /* the limit of qr_render_views_async, in its footprints (the frame's FSAA), so that a size it takes is taken here too */
-        const int fsaa = s->fr.fsaa;
-        const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
-        if ((int64_t)n_views * ((width + fw - 1) / fw) * ((height + fh - 1) / fh) > (int64_t)QR_VIEW_MAX_WAVES)
-            return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
-    }
-    if (n_views == 0) return QR_OK;
-    if (views_dev == nullptr || hits_dev == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if ((((uintptr_t)views_dev | (uintptr_t)hits_dev) & 15u) != 0) return qr_fail(QR_ERR_ARG, "views and hits must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    /* one lane per pixel: 8x8 footprints at every FSAA (never more workgroups than the limit above allows) */
-    const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
-    ViewsP vp;
-    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
-    const f32x4 *none = nullptr;
-    if (s->divk)
-        hipLaunchKernelGGL((qr_hit_kernel<true, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
-                           vp, s->off_mat, (f32x4 *)hits_dev, s->lp.stats);
-    else
-        hipLaunchKernelGGL((qr_hit_kernel<true, false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
-                           vp, s->off_mat, (f32x4 *)hits_dev, s->lp.stats);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-/* ---- occlusion fans (qr_fan.hpp): per surface point, how many directions of a shared table are open ---- */
-
-/* what the three entry points check alike, before the element count decides whether anything is launched */
-static int fan_args(const qr_device_scene *s, int k, float eps, float reach, uint32_t flags, uint32_t allowed)
-{
-    if (flags & ~allowed) return qr_fail(QR_ERR_ARG, "unknown fan flags");
-    if (k < 1 || k > QR_FAN_MAX_DIRS) return qr_fail(QR_ERR_ARG, "direction count must be 1.." + std::to_string(QR_FAN_MAX_DIRS));
-    if (std::isnan(eps) || std::isnan(reach)) return qr_fail(QR_ERR_ARG, "eps and reach must not be NaN");
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    return QR_OK;
-}
-
-/* ... and once there are elements: src is the ray, view or record array */
-static int fan_ptrs(const void *src, const qr_fan_dir *dirs, const int32_t *open, const uint32_t *mask)
-{
-    if (src == nullptr || dirs == nullptr || open == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if ((((uintptr_t)src | (uintptr_t)dirs) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays, views, hits and dirs must be 16-byte aligned");
-    if ((((uintptr_t)open | (uintptr_t)mask) & 3u) != 0) return qr_fail(QR_ERR_ARG, "open and mask must be 4-byte aligned");
-    return QR_OK;
-}
-
-/* the spin plane of a framed call: float [elements][2], may be null */
-static int spin_ptr(const float *spin)
-{
-    if (((uintptr_t)spin & 7u) != 0) return qr_fail(QR_ERR_ARG, "spin must be 8-byte aligned");
-    return QR_OK;
-}
-
-static FanP fan_params(const qr_fan_dir *dirs, int k, float eps, float reach, int32_t *open, uint32_t *mask, uint32_t flags, uint64_t elems)
-{
-    FanP fp;
-    fp.dirs = dirs; fp.k = k; fp.flip = flags & QR_FAN_FLIP;
-    fp.eps = eps; fp.reach = reach > FLT_MAX ? FLT_MAX : reach;     /* +inf is taken as FLT_MAX, as in qr_trace_kernel */
-    fp.open = open; fp.mask = mask; fp.elems = elems;
-    return fp;
-}
-
-/* the three sources, unframed (qr_fan.hpp) or framed (qr_fan_framed.hpp: spin may be null) */
-static int fan_rays(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k, float eps, float reach,
-                    int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream, bool framed, const float *spin_dev)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
-    { const int rc = fan_args(s, k, eps, reach, flags, QR_TRACE_COHERENT | QR_FAN_FLIP); if (rc != QR_OK) return rc; }
-    if (n == 0) return QR_OK;
-    { const int rc = fan_ptrs(rays_dev, dirs_dev, open_dev, mask_dev); if (rc != QR_OK) return rc; }
-    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    const f32x4 *r = (const f32x4 *)rays_dev;
-    const float2 *sp = (const float2 *)spin_dev;
-    const ViewsP vp = {};
-    const FanP fp = fan_params(dirs_dev, k, eps, reach, open_dev, mask_dev, flags, (uint64_t)n);
-    if (framed)
-    {
-        if (flags & QR_TRACE_COHERENT)
-            hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_RAYS, true, true>), grid, block, 0, (hipStream_t)stream,
-                               (const char *)s->d_blob, r, (int32_t)n, vp, fp, sp, s->lp.stats);
-        else
-            hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_RAYS, true, false>), grid, block, 0, (hipStream_t)stream,
-                               (const char *)s->d_blob, r, (int32_t)n, vp, fp, sp, s->lp.stats);
-    }
-    else if (flags & QR_TRACE_COHERENT)
-        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_RAYS, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r,
-                           (int32_t)n, vp, fp, s->lp.stats);
-    else
-        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_RAYS, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r,
-                           (int32_t)n, vp, fp, s->lp.stats);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_fan_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
-                                 float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream)
-{
-    return fan_rays(s, rays_dev, n, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, false, nullptr);
-}
-
-extern "C" int qr_fan_rays_framed_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
-                                        const float *spin_dev, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
-                                        uint32_t flags, void *stream)
-{
-    return fan_rays(s, rays_dev, n, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, true, spin_dev);
-}
-
-static int fan_hits(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k, float eps, float reach,
-                    int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream, bool framed, const float *spin_dev)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "record count must be 0..INT32_MAX");
-    { const int rc = fan_args(s, k, eps, reach, flags, QR_FAN_FLIP); if (rc != QR_OK) return rc; }
-    if (n == 0) return QR_OK;
-    { const int rc = fan_ptrs(hits_dev, dirs_dev, open_dev, mask_dev); if (rc != QR_OK) return rc; }
-    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    const ViewsP vp = {};
-    const FanP fp = fan_params(dirs_dev, k, eps, reach, open_dev, mask_dev, flags, (uint64_t)n);
-    if (framed)
-        hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_HITS, true, false>), grid, block, 0, (hipStream_t)stream,
-                           (const char *)s->d_blob, (const f32x4 *)hits_dev, (int32_t)n, vp, fp, (const float2 *)spin_dev, s->lp.stats);
-    else
-        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_HITS, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob,
-                           (const f32x4 *)hits_dev, (int32_t)n, vp, fp, s->lp.stats);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_fan_hits_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
-                                 float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream)
-{
-    return fan_hits(s, hits_dev, n, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, false, nullptr);
-}
-
-extern "C" int qr_fan_hits_framed_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_fan_dir *dirs_dev, int k,
-                                        const float *spin_dev, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
-                                        uint32_t flags, void *stream)
-{
-    return fan_hits(s, hits_dev, n, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, true, spin_dev);
-}
-
-static int fan_views(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height, const qr_fan_dir *dirs_dev, int k,
-                     float eps, float reach, int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream, bool framed,
-                     const float *spin_dev)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
-    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
-        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
-    { const int rc = fan_args(s, k, eps, reach, flags, QR_FAN_FLIP); if (rc != QR_OK) return rc; }
-    {
-        /* the limit of qr_hit_views_async, in qr_render_views_async's footprints (the frame's FSAA) */
-        const int fsaa = s->fr.fsaa;
-        const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
-        if ((int64_t)n_views * ((width + fw - 1) / fw) * ((height + fh - 1) / fh) > (int64_t)QR_VIEW_MAX_WAVES)
-            return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
-    }
-    if (n_views == 0) return QR_OK;
-    { const int rc = fan_ptrs(views_dev, dirs_dev, open_dev, mask_dev); if (rc != QR_OK) return rc; }
-    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
-    HIP_TRY(hipSetDevice(s->device));
-    /* one lane per pixel: 8x8 footprints at every FSAA, as qr_hit_views_async */
-    const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
-    ViewsP vp;
-    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
-    const FanP fp = fan_params(dirs_dev, k, eps, reach, open_dev, mask_dev, flags, (uint64_t)n_views * (uint64_t)width * (uint64_t)height);
-    const f32x4 *none = nullptr;
-    const float2 *sp = (const float2 *)spin_dev;
-    /* the instance is chosen as qr_hit_views_async chooses its own */
-    if (framed)
-    {
-        if (s->divk)
-            hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_VIEW, true, true>), grid, block, 0, (hipStream_t)stream,
-                               (const char *)s->d_blob, none, 0, vp, fp, sp, s->lp.stats);
-        else
-            hipLaunchKernelGGL((qr_fan_framed_kernel<QR_FAN_SRC_VIEW, false, true>), grid, block, 0, (hipStream_t)stream,
-                               (const char *)s->d_blob, none, 0, vp, fp, sp, s->lp.stats);
-    }
-    else if (s->divk)
-        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_VIEW, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
-                           vp, fp, s->lp.stats);
-    else
-        hipLaunchKernelGGL((qr_fan_kernel<QR_FAN_SRC_VIEW, false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
-                           vp, fp, s->lp.stats);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_fan_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                  const qr_fan_dir *dirs_dev, int k, float eps, float reach, int32_t *open_dev, uint32_t *mask_dev,
-                                  uint32_t flags, void *stream)
-{
-    return fan_views(s, views_dev, n_views, width, height, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, false, nullptr);
-}
-
-extern "C" int qr_fan_views_framed_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                         const qr_fan_dir *dirs_dev, int k, const float *spin_dev, float eps, float reach,
-                                         int32_t *open_dev, uint32_t *mask_dev, uint32_t flags, void *stream)
-{
-    return fan_views(s, views_dev, n_views, width, height, dirs_dev, k, eps, reach, open_dev, mask_dev, flags, stream, true, spin_dev);
-}
-
-/* ---- gather fans (qr_gather.hpp): per surface point, the weighted sum of the renderer's colours along a shared table ---- */
-
-/* what the three entry points check alike before the element count decides whether anything is launched: the fans' checks, then
- * what qr_shade_rays_async refuses */
-static int gather_args(const qr_device_scene *s, int k, float eps, float reach, uint32_t flags, uint32_t allowed)
-{
-    { const int rc = fan_args(s, k, eps, reach, flags, allowed | QR_FAN_FLIP | QR_GATHER_COSINE | QR_GATHER_RESUME); if (rc != QR_OK) return rc; }
-    if (s->pt_on) return qr_fail(QR_ERR_UNSUP, "scene is in path-tracer mode: fan rays carry no sample seeds");
-    return QR_OK;
-}
-
-/* ... and once there are elements: src is the ray, view or record array */
-static int gather_ptrs(const void *src, const qr_gather_dir *dirs, const float *gather, const int32_t *count)
-{
-    if (src == nullptr || dirs == nullptr || gather == nullptr || count == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if ((((uintptr_t)src | (uintptr_t)dirs | (uintptr_t)gather) & 15u) != 0)
-        return qr_fail(QR_ERR_ARG, "rays, views, hits, dirs and gather must be 16-byte aligned");
-    if (((uintptr_t)count & 3u) != 0) return qr_fail(QR_ERR_ARG, "count must be 4-byte aligned");
-    return QR_OK;
-}
-
-static GatherP gather_params(const qr_gather_dir *dirs, int k, float eps, float reach, float *gather, int32_t *count, uint32_t flags)
-{
-    GatherP gp;
-    gp.dirs = dirs; gp.k = k;
-    gp.flip = flags & QR_FAN_FLIP; gp.cosine = flags & QR_GATHER_COSINE; gp.resume = flags & QR_GATHER_RESUME;
-    gp.eps = eps; gp.reach = reach > FLT_MAX ? FLT_MAX : reach;     /* +inf is taken as FLT_MAX, as in qr_shade_rays_async */
-    gp.gather = (f32x4 *)gather; gp.count = count;
-    return gp;
-}
-
-/* the three sources, unframed (qr_gather.hpp) or framed (qr_fan_framed.hpp: spin may be null) */
-static int gather_rays(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k, float eps, float reach,
-                       float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream, bool framed, const float *spin_dev)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
-    { const int rc = gather_args(s, k, eps, reach, flags, QR_TRACE_COHERENT); if (rc != QR_OK) return rc; }
-    if (n == 0) return QR_OK;
-    { const int rc = gather_ptrs(rays_dev, dirs_dev, gather_dev, count_dev); if (rc != QR_OK) return rc; }
-    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    const f32x4 *r = (const f32x4 *)rays_dev;
-    const ViewsP vp = {};
-    const GatherP gp = gather_params(dirs_dev, k, eps, reach, gather_dev, count_dev, flags);
-    const float2 *sp = (const float2 *)spin_dev;
-    /* the per-lane walk instance, as qr_shade_rays_async */
-    if (framed)
-    {
-        if (flags & QR_TRACE_COHERENT)
-            hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_RAYS, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream,
-                               s->lp, r, (int32_t)n, vp, gp, sp);
-        else
-            hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_RAYS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream,
-                               s->lp, r, (int32_t)n, vp, gp, sp);
-    }
-    else if (flags & QR_TRACE_COHERENT)
-        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_RAYS, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, r,
-                           (int32_t)n, vp, gp);
-    else
-        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_RAYS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, r,
-                           (int32_t)n, vp, gp);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_gather_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
-                                    float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream)
-{
-    return gather_rays(s, rays_dev, n, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, false, nullptr);
-}
-
-extern "C" int qr_gather_rays_framed_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
-                                           const float *spin_dev, float eps, float reach, float *gather_dev, int32_t *count_dev,
-                                           uint32_t flags, void *stream)
-{
-    return gather_rays(s, rays_dev, n, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, true, spin_dev);
-}
-
-static int gather_hits(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k, float eps, float reach,
-                       float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream, bool framed, const float *spin_dev)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "record count must be 0..INT32_MAX");
-    { const int rc = gather_args(s, k, eps, reach, flags, 0u); if (rc != QR_OK) return rc; }
-    if (n == 0) return QR_OK;
-    { const int rc = gather_ptrs(hits_dev, dirs_dev, gather_dev, count_dev); if (rc != QR_OK) return rc; }
-    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    const ViewsP vp = {};
-    const GatherP gp = gather_params(dirs_dev, k, eps, reach, gather_dev, count_dev, flags);
-    if (framed)
-        hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_HITS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream,
-                           s->lp, (const f32x4 *)hits_dev, (int32_t)n, vp, gp, (const float2 *)spin_dev);
-    else
-        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_HITS, true, false, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp,
-                           (const f32x4 *)hits_dev, (int32_t)n, vp, gp);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_gather_hits_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
-                                    float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream)
-{
-    return gather_hits(s, hits_dev, n, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, false, nullptr);
-}
-
-extern "C" int qr_gather_hits_framed_async(qr_device_scene *s, const qr_hit *hits_dev, int64_t n, const qr_gather_dir *dirs_dev, int k,
-                                           const float *spin_dev, float eps, float reach, float *gather_dev, int32_t *count_dev,
-                                           uint32_t flags, void *stream)
-{
-    return gather_hits(s, hits_dev, n, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, true, spin_dev);
-}
-
-static int gather_views(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height, const qr_gather_dir *dirs_dev,
-                        int k, float eps, float reach, float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream, bool framed,
-                        const float *spin_dev)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
-    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
-        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
-    { const int rc = gather_args(s, k, eps, reach, flags, 0u); if (rc != QR_OK) return rc; }
-    {
-        /* the limit of qr_fan_views_async */
-        const int fsaa = s->fr.fsaa;
-        const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
-        if ((int64_t)n_views * ((width + fw - 1) / fw) * ((height + fh - 1) / fh) > (int64_t)QR_VIEW_MAX_WAVES)
-            return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
-    }
-    if (n_views == 0) return QR_OK;
-    { const int rc = gather_ptrs(views_dev, dirs_dev, gather_dev, count_dev); if (rc != QR_OK) return rc; }
-    { const int rc = spin_ptr(spin_dev); if (rc != QR_OK) return rc; }
-    HIP_TRY(hipSetDevice(s->device));
-    /* one lane per pixel: 8x8 footprints at every FSAA, as qr_fan_views_async */
-    const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
-    ViewsP vp;
-    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
-    const GatherP gp = gather_params(dirs_dev, k, eps, reach, gather_dev, count_dev, flags);
-    const f32x4 *none = nullptr;
-    const float2 *sp = (const float2 *)spin_dev;
-    /* the instance is chosen as qr_render_views_async chooses its own */
-    if (framed)
-    {
-        if (s->divk)
-            hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_VIEW, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream,
-                               s->lp, none, 0, vp, gp, sp);
-        else
-            hipLaunchKernelGGL((qr_gather_framed_kernel<QR_FAN_SRC_VIEW, false, true, QR_MIN_WAVES_PER_SIMD>), grid, block, 0,
-                               (hipStream_t)stream, s->lp, none, 0, vp, gp, sp);
-    }
-    else if (s->divk)
-        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_VIEW, true, true, QR_DIVK_WAVES>), grid, block, 0, (hipStream_t)stream, s->lp, none, 0,
-                           vp, gp);
-    else
-        hipLaunchKernelGGL((qr_gather_kernel<QR_FAN_SRC_VIEW, false, true, QR_MIN_WAVES_PER_SIMD>), grid, block, 0, (hipStream_t)stream, s->lp, none, 0,
-                           vp, gp);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_gather_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                     const qr_gather_dir *dirs_dev, int k, float eps, float reach, float *gather_dev, int32_t *count_dev,
-                                     uint32_t flags, void *stream)
-{
-    return gather_views(s, views_dev, n_views, width, height, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, false, nullptr);
-}
-
-extern "C" int qr_gather_views_framed_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height,
-                                            const qr_gather_dir *dirs_dev, int k, const float *spin_dev, float eps, float reach,
-                                            float *gather_dev, int32_t *count_dev, uint32_t flags, void *stream)
-{
-    return gather_views(s, views_dev, n_views, width, height, dirs_dev, k, eps, reach, gather_dev, count_dev, flags, stream, true, spin_dev);
-}
-
-/* ---- hit layers (qr_layers.hpp): the first k hits along a ray, in order ---- */
-
-/* what the two entry points check alike, before the element count decides whether anything is launched */
-static int layer_args(const qr_device_scene *s, int k, uint32_t flags, uint32_t allowed)
-{
-    if (flags & ~allowed) return qr_fail(QR_ERR_ARG, "unknown layer flags");
-    if (k < 1 || k > QR_LAYER_MAX) return qr_fail(QR_ERR_ARG, "layer count must be 1.." + std::to_string(QR_LAYER_MAX));
-    if (s->off_query == 0) return qr_fail(QR_ERR_UNSUP, "scene was uploaded without QR_UPLOAD_RAY_QUERIES: it holds no ray-query list");
-    return QR_OK;
-}
-
-/* ... and once there are elements: src is the ray or view array; t, id and hits may be null */
-static int layer_ptrs(const void *src, const int32_t *count, const float *t, const int32_t *id, const qr_hit *hits)
-{
-    if (src == nullptr || count == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
-    if ((((uintptr_t)src | (uintptr_t)hits) & 15u) != 0) return qr_fail(QR_ERR_ARG, "rays, views and hits must be 16-byte aligned");
-    if ((((uintptr_t)count | (uintptr_t)t | (uintptr_t)id) & 3u) != 0) return qr_fail(QR_ERR_ARG, "count, t and id must be 4-byte aligned");
-    return QR_OK;
-}
-
-static LayerP layer_params(const qr_device_scene *s, int k, int32_t *count, float *t, int32_t *id, qr_hit *hits, uint64_t elems)
-{
-    LayerP lp;
-    lp.k = k; lp.off_mat = s->off_mat;
-    lp.count = count; lp.t = t; lp.id = id; lp.hits = (f32x4 *)hits; lp.elems = elems;
-    return lp;
-}
-
-extern "C" int qr_layer_rays_async(qr_device_scene *s, const qr_ray *rays_dev, int64_t n, int k,
-                                   int32_t *count_dev, float *t_dev, int32_t *id_dev, qr_hit *hits_dev,
-                                   uint32_t flags, void *stream)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n < 0 || n > (int64_t)INT32_MAX) return qr_fail(QR_ERR_ARG, "ray count must be 0..INT32_MAX");
-    { const int rc = layer_args(s, k, flags, QR_TRACE_COHERENT); if (rc != QR_OK) return rc; }
-    if (n == 0) return QR_OK;
-    { const int rc = layer_ptrs(rays_dev, count_dev, t_dev, id_dev, hits_dev); if (rc != QR_OK) return rc; }
-    HIP_TRY(hipSetDevice(s->device));
-    const dim3 grid((unsigned)((n + QR_BLOCK - 1) / QR_BLOCK)), block(QR_BLOCK);
-    const f32x4 *r = (const f32x4 *)rays_dev;
-    const ViewsP vp = {};
-    const LayerP lp = layer_params(s, k, count_dev, t_dev, id_dev, hits_dev, (uint64_t)n);
-    if (flags & QR_TRACE_COHERENT)
-        hipLaunchKernelGGL((qr_layer_kernel<false, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
-                           vp, lp, s->lp.stats);
-    else
-        hipLaunchKernelGGL((qr_layer_kernel<false, true, false>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, r, (int32_t)n,
-                           vp, lp, s->lp.stats);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
-
-extern "C" int qr_layer_views_async(qr_device_scene *s, const qr_view *views_dev, int n_views, int width, int height, int k,
-                                    int32_t *count_dev, float *t_dev, int32_t *id_dev, qr_hit *hits_dev,
-                                    uint32_t flags, void *stream)
-{
-    if (s == nullptr) return qr_fail(QR_ERR_ARG, "null scene");
-    if (n_views < 0 || n_views > QR_VIEW_MAX_VIEWS) return qr_fail(QR_ERR_ARG, "view count must be 0.." + std::to_string(QR_VIEW_MAX_VIEWS));
-    if (width < 1 || height < 1 || width > QR_VIEW_MAX_DIM || height > QR_VIEW_MAX_DIM)
-        return qr_fail(QR_ERR_ARG, "view frame size must be 1.." + std::to_string(QR_VIEW_MAX_DIM) + " in each dimension");
-    { const int rc = layer_args(s, k, flags, 0u); if (rc != QR_OK) return rc; }
-    {
-        /* the limit of qr_hit_views_async, in qr_render_views_async's footprints (the frame's FSAA) */
-        const int fsaa = s->fr.fsaa;
-        const int fw = fsaa == 2 ? 4 : 8, fh = fsaa == 0 ? 8 : 4;
-        if ((int64_t)n_views * ((width + fw - 1) / fw) * ((height + fh - 1) / fh) > (int64_t)QR_VIEW_MAX_WAVES)
-            return qr_fail(QR_ERR_ARG, "views x footprints exceed one grid (QR_VIEW_MAX_WAVES)");
-    }
-    if (n_views == 0) return QR_OK;
-    { const int rc = layer_ptrs(views_dev, count_dev, t_dev, id_dev, hits_dev); if (rc != QR_OK) return rc; }
-    HIP_TRY(hipSetDevice(s->device));
-    /* one lane per pixel: 8x8 footprints at every FSAA, as qr_hit_views_async */
-    const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8), (unsigned)n_views), block(QR_BLOCK);
-    ViewsP vp;
-    vp.views = views_dev; vp.width = width; vp.height = height; vp.depth = nullptr;
-    const LayerP lp = layer_params(s, k, count_dev, t_dev, id_dev, hits_dev, (uint64_t)n_views * (uint64_t)width * (uint64_t)height);
-    const f32x4 *none = nullptr;
-    /* the instance is chosen as qr_hit_views_async chooses its own */
-    if (s->divk)
-        hipLaunchKernelGGL((qr_layer_kernel<true, true, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
-                           vp, lp, s->lp.stats);
-    else
-        hipLaunchKernelGGL((qr_layer_kernel<true, false, true>), grid, block, 0, (hipStream_t)stream, (const char *)s->d_blob, none, 0,
-                           vp, lp, s->lp.stats);
-    HIP_TRY(hipGetLastError());
-    return QR_OK;
-}
+/* ---- the ray API: queries, shading, views, path-traced rays and views, filter, hit records, fans, layers ---- */
+#include "qr_rayapi.hpp"
 
 /* combined schedules of multi-target launches, keyed by (scene, row range) per target; only the schedule is
  * cached -- recursion depth and frame pointers travel in the kernel arguments of every launch */
