@@ -3,10 +3,11 @@
  * point a fan of K visibility rays along a direction table shared by all points, answered as the number of open directions per
  * point and, if wanted, one bit per direction.  Ambient occlusion, sky and sun visibility, openness of lightmap texels and probes.
  *
- * One kernel template, three sources of the surface point (pos, nrm, id):
- *   SRC = QR_FAN_SRC_RAYS   the first hit of the caller's qr_ray i, found as qr_hit_kernel<false, ...> finds it (qr_hitrec.hpp):
- *                           lane i of workgroup g is ray g * 64 + i, traverse<false, DIVK, true>, then surface_point.
- *   SRC = QR_FAN_SRC_VIEW   the first hit of a pixel of a caller-supplied camera, as qr_hit_kernel<true, ...> finds it: the grid is
+ * One kernel template, three sources of the surface point (pos, nrm, id): fan_element below, which the framed fan and the
+ * gather kernels call for all three and this kernel for caller rays and records (its view branch keeps the text):
+ *   SRC = QR_FAN_SRC_RAYS   the first hit of the caller's qr_ray i, the hit record's (qr_hitrec.hpp): lane i of workgroup g is
+ *                           ray g * 64 + i, traverse<false, DIVK, true>, then surface_point.
+ *   SRC = QR_FAN_SRC_VIEW   the first hit of a pixel of a caller-supplied camera, the hit record's again: the grid is
  *                           (footprint columns, footprint rows, views), a footprint is 8x8 pixels, sample 0's ray under FSAA.
  *   SRC = QR_FAN_SRC_HITS   the caller's qr_hit record i: pos, nrm and id are read (two of its three 16-byte pieces), no first walk.
  * The hit stays in registers: no record and no ray ever reaches memory.
@@ -48,6 +49,73 @@ struct FanP
     uint64_t elems;
 };
 
+/* This lane's element of a fan launch and its surface point: rec, pos, nrm, and has (a surface point: id >= 0); returns whether
+ * the lane is inside the launch.  RAYS and VIEW: launch_ray (qr_hitrec.hpp), the first walk -- traverse<false, DIVK, true> on
+ * DevHeader::off_query, coherent for a view or where the caller vouches for it -- and surface_point for the lanes that hit.
+ * HITS: two of record i's three 16-byte pieces, no walk; n > 0: a lane past the end reads record 0 and traces nothing. */
+template <int SRC, bool DIVK, bool COHERENT>
+__device__ __forceinline__ bool fan_element(BaseP B, const char *G, const f32x4 *__restrict__ src, int32_t n, const ViewsP &vp,
+                                            size_t &rec, V3 &pos, V3 &nrm, bool &has
+#ifdef QR_STATS
+                                            , unsigned long long *stats
+#endif
+                                            )
+{
+    bool active;
+    pos = {0.0f, 0.0f, 0.0f}; nrm = {0.0f, 0.0f, 0.0f};
+    if constexpr (SRC == QR_FAN_SRC_HITS)
+    {
+        const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
+        active = i < (int64_t)n;
+        const int64_t q = active ? i : 0;
+        const f32x4 a = src[3 * q], b = src[3 * q + 1];
+        pos = {a.x, a.y, a.z};
+        nrm = {b.x, b.y, b.z};
+        has = active && __float_as_int(b.w) >= 0;
+        rec = (size_t)q;
+    }
+    else
+    {
+        const FrmP fr = c_frm(B);
+        Ray r;
+        active = launch_ray<SRC == QR_FAN_SRC_VIEW>(fr, G, src, n, vp, r, rec);
+        r.list = active ? fr->off_query : 0u;
+
+        Hit h;
+        bool occ0 = false;
+        traverse<false, DIVK, true>(B, active, SRC == QR_FAN_SRC_VIEW || COHERENT, r, h, occ0
+#ifdef QR_STATS
+                                    , stats
+#endif
+                                    );
+        has = active && h.srf != 0;
+        if (has)
+        {
+            V3 tex; u32 mo;
+            surface_point(G, fr->off_shade, r, h, pos, nrm, tex, mo);
+        }
+    }
+    return active;
+}
+
+/* direction d4 of the table as an element with normal n traces it: dot = (n.x * d.x + n.y * d.y) + n.z * d.z; with `flip` the
+ * direction is mirrored where dot < 0 (a NaN dot is not) and every element with a surface point traces it; without, it is traced
+ * iff 0 < dot (LT_amb: a NaN dot is closed) */
+__device__ __forceinline__ bool fan_dir(const f32x4 d4, const V3 n, const bool has, const uint32_t flip, V3 &dir, float &dot)
+{
+    float x1 = n.x * d4.x, x2 = n.y * d4.y, x3 = n.z * d4.z;
+    x1 = x1 + x2;
+    dot = x1 + x3;
+    if (flip != 0u)
+    {
+        const bool neg = dot < 0.0f;
+        dir.x = neg ? -d4.x : d4.x; dir.y = neg ? -d4.y : d4.y; dir.z = neg ? -d4.z : d4.z;
+        return has;
+    }
+    dir = {d4.x, d4.y, d4.z};
+    return has && 0.0f < dot;
+}
+
 template <int SRC, bool DIVK, bool COHERENT>
 __global__ __launch_bounds__(QR_BLOCK, DIVK && SRC != QR_FAN_SRC_HITS ? QR_DIVK_WAVES : QR_MIN_WAVES_PER_SIMD)
 void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src, int32_t n, ViewsP vp, FanP fp,
@@ -64,24 +132,12 @@ void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src,
     size_t rec;                                 /* this lane's element */
     V3 pos = {0.0f, 0.0f, 0.0f}, nrm = {0.0f, 0.0f, 0.0f};
     bool has = false;                           /* a surface point: id >= 0 */
-
-    if constexpr (SRC == QR_FAN_SRC_HITS)
+    if constexpr (SRC == QR_FAN_SRC_VIEW)
     {
-        const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
-        active = i < (int64_t)n;
-        const int64_t q = active ? i : 0;           /* n > 0: lanes past the end read record 0 and trace nothing */
-        const f32x4 a = src[3 * q], b = src[3 * q + 1];
-        pos = {a.x, a.y, a.z};
-        nrm = {b.x, b.y, b.z};
-        has = active && __float_as_int(b.w) >= 0;
-        rec = (size_t)q;
-    }
-    else
-    {
+        /* fan_element's view branch -- launch_ray<true>, the first walk, surface_point -- kept here as text (DESIGN.md 4s:
+         * through the functions the view instances' assembly changed and one of them measured slower) */
         Ray r;
-        if constexpr (SRC == QR_FAN_SRC_VIEW)
         {
-            /* qr_hit_kernel's VIEW branch: one lane per pixel of an 8x8 footprint, sample 0's offsets at the frame's FSAA */
             const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
             const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
             int x, y, k;
@@ -96,19 +152,6 @@ void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src,
 #pragma clang diagnostic pop
             view_ray(vw, hs, vs, r);
             rec = ((size_t)view * (size_t)vp.height + (size_t)(active ? y : 0)) * (size_t)vp.width + (size_t)(active ? x : 0);
-        }
-        else
-        {
-            const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
-            active = i < (int64_t)n;
-            const int64_t q = active ? i : 0;       /* n > 0: lanes past the end read ray 0 and do not walk */
-            const f32x4 a = src[2 * q], b = src[2 * q + 1];
-            r.org = {a.x, a.y, a.z}; r.tmin = a.w;
-            r.dir = {b.x, b.y, b.z};
-            r.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;
-            r.osrf = 0; r.oflg = 0;
-            r.ploc = {0.0f, 0.0f, 0.0f};
-            rec = (size_t)q;
         }
         r.list = active ? fr->off_query : 0u;
 
@@ -126,6 +169,11 @@ void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src,
             surface_point(blob, fr->off_shade, r, h, pos, nrm, tex, mo);
         }
     }
+    else active = fan_element<SRC, DIVK, COHERENT>(B, blob, src, n, vp, rec, pos, nrm, has
+#ifdef QR_STATS
+                                                   , stats
+#endif
+                                                   );
 
     /* the fan: every lane of the wave stays in the loop (the walks are wave-wide), lanes without a surface point trace nothing */
     const bool coherent = (SRC == QR_FAN_SRC_VIEW || COHERENT) && fp.flip == 0u;
@@ -135,22 +183,9 @@ void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src,
     for (int k = 0; k < fp.k; k++)
     {
         const f32x4 d4 = dirs[k];                   /* wave-uniform: one scalar load */
-        float x1 = nrm.x * d4.x, x2 = nrm.y * d4.y, x3 = nrm.z * d4.z;
-        x1 = x1 + x2;
-        const float dot = x1 + x3;
         Ray f;
-        bool traced;
-        if (fp.flip != 0u)
-        {
-            const bool neg = dot < 0.0f;            /* a NaN dot is not flipped */
-            f.dir.x = neg ? -d4.x : d4.x; f.dir.y = neg ? -d4.y : d4.y; f.dir.z = neg ? -d4.z : d4.z;
-            traced = has;
-        }
-        else
-        {
-            f.dir = {d4.x, d4.y, d4.z};
-            traced = has && 0.0f < dot;             /* LT_amb: a NaN dot is closed */
-        }
+        float dot;
+        const bool traced = fan_dir(d4, nrm, has, fp.flip, f.dir, dot);
         bool open = false;
         if (LM(traced) != 0)
         {
@@ -167,6 +202,7 @@ void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src,
                                        );
             open = traced && !occ;
         }
+        /* the end of direction k: kept as text in both fan kernels (as a function it cost the view instances time) */
         count += open ? 1 : 0;
         word |= (open ? 1u : 0u) << (k & 31);
         if ((k & 31) == 31 || k == fp.k - 1)

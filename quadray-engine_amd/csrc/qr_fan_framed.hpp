@@ -14,7 +14,8 @@
  * Per direction (x, y, z, w) of the table (wave-uniform: scalar loads, as in the unframed kernels): dot = z, the table's own
  * cosine; the mirror under `flip` ((-x, -y, -z) where z < 0) and the rule without it (0 < z) are wave-uniform too, so a row that
  * points below the surface is skipped by the whole wave; d = (u * x' + v * y') + n * z' per component, three products and two
- * adds in that order: 9 multiplies and 6 adds per lane.  Everything after the ray (pos, eps, d, reach) is the unframed kernel's.
+ * adds in that order: 9 multiplies and 6 adds per lane.  Elements (fan_element), the fold and the final store
+ * (gather_fold, gather_store) are the unframed kernels' own functions (qr_fan.hpp, qr_gather.hpp).
  *
  * Two kernel templates with symbols of their own (the unframed kernels' assembly stays as it was), five instances each, chosen
  * as the unframed calls choose theirs.  The fan kernel keeps u and v in six more registers across the loop and has no LDS of its
@@ -79,7 +80,7 @@ __device__ __forceinline__ V3 framed_dir(const V3 u, const V3 v, const V3 n, con
     return d;
 }
 
-/* ---- the occlusion fan: qr_fan_kernel (qr_fan.hpp) with the frame; spin: float [elements][2] or null ---- */
+/* ---- the occlusion fan with the frame; spin: float [elements][2] or null ---- */
 
 template <int SRC, bool DIVK, bool COHERENT>
 __global__ __launch_bounds__(QR_BLOCK, DIVK && SRC != QR_FAN_SRC_HITS ? QR_DIVK_WAVES : QR_MIN_WAVES_PER_SIMD)
@@ -92,73 +93,14 @@ void qr_fan_framed_kernel(const char *__restrict__ blob, const f32x4 *__restrict
     const QR_CONST f32x4 *dirs = (const QR_CONST f32x4 *)fp.dirs;
 #pragma clang diagnostic pop
     (void)stats;
-    const FrmP fr = c_frm(B);
-    bool active;
     size_t rec;                                 /* this lane's element */
-    V3 pos = {0.0f, 0.0f, 0.0f}, nrm = {0.0f, 0.0f, 0.0f};
-    bool has = false;                           /* a surface point: id >= 0 */
-
-    if constexpr (SRC == QR_FAN_SRC_HITS)
-    {
-        const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
-        active = i < (int64_t)n;
-        const int64_t q = active ? i : 0;           /* n > 0: lanes past the end read record 0 and trace nothing */
-        const f32x4 a = src[3 * q], b = src[3 * q + 1];
-        pos = {a.x, a.y, a.z};
-        nrm = {b.x, b.y, b.z};
-        has = active && __float_as_int(b.w) >= 0;
-        rec = (size_t)q;
-    }
-    else
-    {
-        Ray r;
-        if constexpr (SRC == QR_FAN_SRC_VIEW)
-        {
-            /* qr_hit_kernel's VIEW branch: one lane per pixel of an 8x8 footprint, sample 0's offsets at the frame's FSAA */
-            const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
-            const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
-            int x, y, k;
-            active = pixel_of_view(ord, 0, vp, x, y, k);
-            float ha, va;
-            sample_offsets(fr, blob, fr->fr.fsaa, x, k, ha, va);
-            float hs = (float)x + ha; hs = hs + 0.0f;
-            float vs = (float)y + va; vs = vs + 0.0f;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-            const QR_CONST qr_view *vw = (const QR_CONST qr_view *)vp.views + view;
-#pragma clang diagnostic pop
-            view_ray(vw, hs, vs, r);
-            rec = ((size_t)view * (size_t)vp.height + (size_t)(active ? y : 0)) * (size_t)vp.width + (size_t)(active ? x : 0);
-        }
-        else
-        {
-            const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
-            active = i < (int64_t)n;
-            const int64_t q = active ? i : 0;       /* n > 0: lanes past the end read ray 0 and do not walk */
-            const f32x4 a = src[2 * q], b = src[2 * q + 1];
-            r.org = {a.x, a.y, a.z}; r.tmin = a.w;
-            r.dir = {b.x, b.y, b.z};
-            r.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;
-            r.osrf = 0; r.oflg = 0;
-            r.ploc = {0.0f, 0.0f, 0.0f};
-            rec = (size_t)q;
-        }
-        r.list = active ? fr->off_query : 0u;
-
-        Hit h;
-        bool occ0 = false;
-        traverse<false, DIVK, true>(B, active, SRC == QR_FAN_SRC_VIEW || COHERENT, r, h, occ0
+    V3 pos, nrm;
+    bool has = false;
+    const bool active = fan_element<SRC, DIVK, COHERENT>(B, blob, src, n, vp, rec, pos, nrm, has
 #ifdef QR_STATS
-                                    , stats
+                                                         , stats
 #endif
-                                    );
-        has = active && h.srf != 0;
-        if (has)
-        {
-            V3 tex; u32 mo;
-            surface_point(blob, fr->off_shade, r, h, pos, nrm, tex, mo);
-        }
-    }
+                                                         );
 
     /* the frame: rec is inside the launch for every lane (element 0 for the lanes past it) */
     float c = 1.0f, sn = 0.0f;
@@ -172,7 +114,7 @@ void qr_fan_framed_kernel(const char *__restrict__ blob, const f32x4 *__restrict
 
     /* the fan: every lane of the wave stays in the loop (the walks are wave-wide), lanes without a frame trace nothing */
     const bool coherent = (SRC == QR_FAN_SRC_VIEW || COHERENT) && fp.flip == 0u && spin == nullptr;
-    const u32 qlist = fr->off_query;
+    const u32 qlist = c_frm(B)->off_query;
     int count = 0;
     u32 word = 0;
     for (int k = 0; k < fp.k; k++)
@@ -198,6 +140,7 @@ void qr_fan_framed_kernel(const char *__restrict__ blob, const f32x4 *__restrict
                                        );
             open = traced && !occ;
         }
+        /* the end of direction k: kept as text in both fan kernels (as a function it cost the view instances time) */
         count += open ? 1 : 0;
         word |= (open ? 1u : 0u) << (k & 31);
         if ((k & 31) == 31 || k == fp.k - 1)
@@ -209,7 +152,7 @@ void qr_fan_framed_kernel(const char *__restrict__ blob, const f32x4 *__restrict
     if (active) fp.open[rec] = has ? count : -1;
 }
 
-/* ---- the gather fan: qr_gather_kernel (qr_gather.hpp) with the frame ---- */
+/* ---- the gather fan with the frame ---- */
 
 template <int SRC, bool DIVK, bool COHERENT, int WAVES>
 __global__ __launch_bounds__(QR_BLOCK, WAVES)
@@ -221,77 +164,18 @@ void qr_gather_framed_kernel(LaunchP lp, const f32x4 *__restrict__ src, int32_t 
     const BaseP B = (BaseP)lp.B;
     const QR_CONST f32x4 *dirs = (const QR_CONST f32x4 *)gp.dirs;
 #pragma clang diagnostic pop
-    const FrmP fr = c_frm(B);
     /* pos xyz, nrm xyz, acc rgbw, cnt (its bits), spin c sn: [word][lane] */
     __shared__ float lds_g[13][64];
     lm_t in_mask, has_mask, frm_mask;           /* lanes inside the launch; with a surface point; with a valid frame as well */
     {
-        bool active;
         size_t rec;                             /* this lane's element */
-        V3 pos = {0.0f, 0.0f, 0.0f}, nrm = {0.0f, 0.0f, 0.0f};
-        bool has = false;                       /* a surface point: id >= 0 */
-
-        if constexpr (SRC == QR_FAN_SRC_HITS)
-        {
-            const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
-            active = i < (int64_t)n;
-            const int64_t q = active ? i : 0;       /* n > 0: lanes past the end read record 0 and trace nothing */
-            const f32x4 a = src[3 * q], b = src[3 * q + 1];
-            pos = {a.x, a.y, a.z};
-            nrm = {b.x, b.y, b.z};
-            has = active && __float_as_int(b.w) >= 0;
-            rec = (size_t)q;
-        }
-        else
-        {
-            Ray r;
-            if constexpr (SRC == QR_FAN_SRC_VIEW)
-            {
-                /* qr_hit_kernel's VIEW branch: one lane per pixel of an 8x8 footprint, sample 0's offsets at the frame's FSAA */
-                const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
-                const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
-                int x, y, k;
-                active = pixel_of_view(ord, 0, vp, x, y, k);
-                float ha, va;
-                sample_offsets(fr, lp.B, fr->fr.fsaa, x, k, ha, va);
-                float hs = (float)x + ha; hs = hs + 0.0f;
-                float vs = (float)y + va; vs = vs + 0.0f;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-                const QR_CONST qr_view *vw = (const QR_CONST qr_view *)vp.views + view;
-#pragma clang diagnostic pop
-                view_ray(vw, hs, vs, r);
-                rec = ((size_t)view * (size_t)vp.height + (size_t)(active ? y : 0)) * (size_t)vp.width + (size_t)(active ? x : 0);
-            }
-            else
-            {
-                const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
-                active = i < (int64_t)n;
-                const int64_t q = active ? i : 0;   /* n > 0: lanes past the end read ray 0 and do not walk */
-                const f32x4 a = src[2 * q], b = src[2 * q + 1];
-                r.org = {a.x, a.y, a.z}; r.tmin = a.w;
-                r.dir = {b.x, b.y, b.z};
-                r.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;
-                r.osrf = 0; r.oflg = 0;
-                r.ploc = {0.0f, 0.0f, 0.0f};
-                rec = (size_t)q;
-            }
-            r.list = active ? fr->off_query : 0u;
-
-            Hit h;
-            bool occ0 = false;
-            traverse<false, DIVK, true>(B, active, SRC == QR_FAN_SRC_VIEW || COHERENT, r, h, occ0
+        V3 pos, nrm;
+        bool has = false;
+        const bool active = fan_element<SRC, DIVK, COHERENT>(B, lp.B, src, n, vp, rec, pos, nrm, has
 #ifdef QR_STATS
-                                        , lp.stats
+                                                             , lp.stats
 #endif
-                                        );
-            has = active && h.srf != 0;
-            if (has)
-            {
-                V3 tex; u32 mo;
-                surface_point(lp.B, fr->off_shade, r, h, pos, nrm, tex, mo);
-            }
-        }
+                                                             );
 
         /* the frame's validity is decided here, once; u and v are computed again where a direction is traced */
         float c = 1.0f, sn = 0.0f;
@@ -351,39 +235,9 @@ void qr_gather_framed_kernel(LaunchP lp, const f32x4 *__restrict__ src, int32_t 
         const f32x4 d4 = dirs[k];
         int lane_s = (int)(threadIdx.x & 63u);
         asm volatile("" : "+v"(lane_s));
-        if (((frm_mask >> lane_s) & 1ull) != 0ull)
-        {
-            float wgt = d4.w;
-            if (gp.cosine != 0u)
-            {
-                const float cz = (gp.flip != 0u && d4.z < 0.0f) ? -d4.z : d4.z;
-                wgt = wgt * cz;
-            }
-            const float pr = col.x * wgt, pg = col.y * wgt, pb = col.z * wgt;
-            lds_g[6][lane_s] = lds_g[6][lane_s] + pr;
-            lds_g[7][lane_s] = lds_g[7][lane_s] + pg;
-            lds_g[8][lane_s] = lds_g[8][lane_s] + pb;
-            lds_g[9][lane_s] = lds_g[9][lane_s] + wgt;
-            lds_g[10][lane_s] = __int_as_float(__float_as_int(lds_g[10][lane_s]) + 1);
-        }
+        if (((frm_mask >> lane_s) & 1ull) != 0ull) gather_fold(lds_g, lane_s, col, d4.w, d4.z, gp);
     }
-
-    int lane_e = (int)(threadIdx.x & 63u);
-    asm volatile("" : "+v"(lane_e));
-    if (((in_mask >> lane_e) & 1ull) != 0ull)
-    {
-        const size_t rec = gather_element<SRC>(vp);
-        const bool has = ((has_mask >> lane_e) & 1ull) != 0ull;
-        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-        int cnt = -1;
-        if (has)
-        {
-            acc = {lds_g[6][lane_e], lds_g[7][lane_e], lds_g[8][lane_e], lds_g[9][lane_e]};
-            cnt = __float_as_int(lds_g[10][lane_e]);
-        }
-        gp.gather[rec] = acc;                       /* one 16-byte store per lane */
-        gp.count[rec] = cnt;
-    }
+    gather_store<SRC>(lds_g, in_mask, has_mask, vp, gp);
 }
 
 #endif /* QR_FAN_FRAMED_HPP */

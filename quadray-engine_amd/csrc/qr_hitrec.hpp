@@ -3,9 +3,10 @@
  * of caller-supplied cameras, the closest hit qr_trace_rays_async finds and the surface point the renderer would shade there --
  * hit point, world normal, texture colour, material -- 48 bytes per ray.  Nothing is lit and no secondary ray is traced.
  *
- * One kernel template, two ray sources:
- *   VIEW = false  the caller's qr_ray array, read as qr_trace_kernel reads it (qr_query.hpp): lane i of workgroup g is ray
- *                 g * 64 + i.  Per-lane walks on long lists unless the caller vouches for coherence (QR_TRACE_COHERENT).
+ * One kernel template, two ray sources (launch_ray below, shared with the layer, fan and gather kernels; DESIGN.md 4s lists it
+ * and the kernels that keep its text, this one's ray branch among them):
+ *   VIEW = false  the caller's qr_ray array (caller_ray, qr_query.hpp): lane i of workgroup g is ray g * 64 + i.  Per-lane walks
+ *                 on long lists unless the caller vouches for coherence (QR_TRACE_COHERENT).
  *   VIEW = true   the grid is (footprint columns, footprint rows, views) as for qr_render_views_kernel, but a footprint is always
  *                 8x8 pixels, one lane per PIXEL: only sample 0 of a pixel is recorded (as ids and depth of a view render are), so
  *                 with FSAA the other samples' lanes would idle.  pixel_of_view (qr_kernel.hpp, at fsaa 0) gives the pixel;
@@ -56,6 +57,45 @@ __device__ __forceinline__ void view_ray(const QR_CONST qr_view *vw, float hs, f
     ray.tmax = vt > FLT_MAX ? FLT_MAX : vt;
     ray.osrf = 0; ray.oflg = 0;
     ray.ploc = {0, 0, 0};
+}
+
+/* This lane's element of a launch and its ray, everything but the list; returns whether the lane is inside the launch.
+ *   VIEW = false  lane i of workgroup g is ray g * 64 + i of the caller's array (caller_ray, qr_query.hpp); rec = i.  n > 0: a
+ *                 lane past the end reads ray 0, keeps rec = 0, and neither walks nor stores.
+ *   VIEW = true   one lane per pixel of an 8x8 footprint (pixel_of_view at fsaa 0: k = 0), sample 0's offsets at the frame's FSAA;
+ *                 rec = (view, y, x).  A lane outside the frame keeps pixel (0, 0) of its view and stores nothing.
+ * (render_wave keeps its own copy of the view ray's arithmetic: its assembly is what bench.py times.) */
+template <bool VIEW>
+__device__ __forceinline__ bool launch_ray(FrmP fr, const char *G, const f32x4 *__restrict__ rays, int32_t n, const ViewsP &vp,
+                                           Ray &r, size_t &rec)
+{
+    bool active;
+    if constexpr (VIEW)
+    {
+        const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
+        const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
+        int x, y, k;
+        active = pixel_of_view(ord, 0, vp, x, y, k);
+        float ha, va;
+        sample_offsets(fr, G, fr->fr.fsaa, x, k, ha, va);
+        float hs = (float)x + ha; hs = hs + 0.0f;       /* the zero jitter of a frame that is not path-traced */
+        float vs = (float)y + va; vs = vs + 0.0f;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+        const QR_CONST qr_view *vw = (const QR_CONST qr_view *)vp.views + view;
+#pragma clang diagnostic pop
+        view_ray(vw, hs, vs, r);
+        rec = ((size_t)view * (size_t)vp.height + (size_t)(active ? y : 0)) * (size_t)vp.width + (size_t)(active ? x : 0);
+    }
+    else
+    {
+        const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
+        active = i < (int64_t)n;
+        const int64_t q = active ? i : 0;
+        caller_ray(rays, q, r);
+        rec = (size_t)q;
+    }
+    return active;
 }
 
 /* hit point, world normal as shading uses it, texture colour and the byte offset of the hit side's material, for a lane WITH a hit */
@@ -174,34 +214,17 @@ void qr_hit_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ rays
     bool active;
     size_t rec;                                 /* this lane's record in `out` */
     Ray r;
-    if constexpr (VIEW)
-    {
-        /* one lane per pixel of an 8x8 footprint (pixel_of_view at fsaa 0: k = 0), sample 0's offsets at the frame's FSAA */
-        const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
-        const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
-        int x, y, k;
-        active = pixel_of_view(ord, 0, vp, x, y, k);
-        float ha, va;
-        sample_offsets(fr, blob, fr->fr.fsaa, x, k, ha, va);
-        float hs = (float)x + ha; hs = hs + 0.0f;       /* the zero jitter of a frame that is not path-traced */
-        float vs = (float)y + va; vs = vs + 0.0f;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-        const QR_CONST qr_view *vw = (const QR_CONST qr_view *)vp.views + view;
-#pragma clang diagnostic pop
-        view_ray(vw, hs, vs, r);
-        /* lanes outside the frame keep record 0 of their view and store nothing */
-        rec = ((size_t)view * (size_t)vp.height + (size_t)(active ? y : 0)) * (size_t)vp.width + (size_t)(active ? x : 0);
-    }
+    if constexpr (VIEW) active = launch_ray<true>(fr, blob, rays, n, vp, r, rec);
     else
     {
+        /* launch_ray<false>'s text, kept here (through the function this kernel's ray address took another form) */
         const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
         active = i < (int64_t)n;
         const int64_t q = active ? i : 0;           /* n > 0: lanes past the end read ray 0 and do not walk */
         const f32x4 a = rays[2 * q], b = rays[2 * q + 1];
         r.org = {a.x, a.y, a.z}; r.tmin = a.w;
         r.dir = {b.x, b.y, b.z};
-        r.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;     /* +inf is taken as FLT_MAX, as in qr_trace_kernel */
+        r.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;
         r.osrf = 0; r.oflg = 0;
         r.ploc = {0.0f, 0.0f, 0.0f};
         rec = (size_t)q;

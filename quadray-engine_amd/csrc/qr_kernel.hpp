@@ -1041,6 +1041,141 @@ void qr_render_views_kernel(LaunchP lp, ViewsP vp, uint32_t *__restrict__ frames
 }
 
 /*
+ * The pieces the kernels below are composed of.  Their operation order is the interface: rays.py states it in
+ * numpy and the tests compare bit for bit.  render_wave keeps its own copy of the output step: its assembly is what bench.py times.
+ */
+
+/* XX_end 5161-5343, first half: clamp and FSAA reduce, by EVERY lane of the wave (the reduce needs all samples of a pixel; sample
+ * 0's lane ends with the pixel's colour).  cn: an integer per sample that takes the same reduce, unscaled */
+__device__ __forceinline__ void fsaa_reduce(const int fsaa, float &cr, float &cg, float &cb, int *cn = nullptr)
+{
+    cr = clamp1(cr); cg = clamp1(cg); cb = clamp1(cb);
+    if (fsaa >= 1)
+    {
+        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
+        cr = cr + __shfl_down(cr, 1); cg = cg + __shfl_down(cg, 1); cb = cb + __shfl_down(cb, 1);
+        if (cn != nullptr) *cn = *cn + __shfl_down(*cn, 1);
+    }
+    if (fsaa >= 2)
+    {
+        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
+        cr = cr + __shfl_down(cr, 2); cg = cg + __shfl_down(cg, 2); cb = cb + __shfl_down(cb, 2);
+        if (cn != nullptr) *cn = *cn + __shfl_down(*cn, 2);
+    }
+}
+
+/* ... second half: gamma, scale, round, mask, pack */
+__device__ __forceinline__ u32 pack_pixel(FrmP fr, float cr, float cg, float cb)
+{
+    if (fr->fr.ctx_flags & QR_PROP_GAMMA)
+    {
+        asm volatile("" ::: "memory");      /* keep the branch: three IEEE square roots are not worth speculating */
+        cr = __builtin_sqrtf(cr); cg = __builtin_sqrtf(cg); cb = __builtin_sqrtf(cb);
+    }
+    const float cl = fr->fr.clamp; const u32 cmask = fr->fr.cmask;
+    cr = cr * cl; cg = cg * cl; cb = cb * cl;
+    return (((u32)cvt_near(cr) & cmask) << 16) | (((u32)cvt_near(cg) & cmask) << 8) | ((u32)cvt_near(cb) & cmask);
+}
+
+/* 5176-5219: the running mean after sample `number` (1-based, counted from the state's reset) of a lane whose means wait in
+ * column l of `acc`: weights 1.0f / (float)number and 1.0f - that, IEEE division, the bits of the host's (qr_device.hip
+ * launch<>).  The generator's state is parked beside it; the means only when another sample follows (`more`) */
+__device__ __forceinline__ V3 pt_mean_fold(u32 *rng_col, float (*acc)[64], const int l, const u32 rng, const V3 c, const int number,
+                                           const bool more)
+{
+    const float pts_o = 1.0f / (float)number, pts_u = 1.0f - pts_o;
+    V3 m;
+    m.x = c.x * pts_o + acc[0][l] * pts_u;
+    m.y = c.y * pts_o + acc[1][l] * pts_u;
+    m.z = c.z * pts_o + acc[2][l] * pts_u;
+    rng_col[l] = rng;
+    if (more) { acc[0][l] = m.x; acc[1][l] = m.y; acc[2][l] = m.z; }
+    return m;
+}
+
+/*
+ * The adaptive state (include/qrhip.h): eight planes of 32-bit words -- the LCG state, the running means of r, g, b, the count m,
+ * Welford's M2 of r, g, b -- a column per ray or per slot.  A wave keeps 64 columns in LDS (`st`, [word][lane], 2 KB); a lane finds
+ * its column in memory as state[p * stride + col].  The ray, list and view kernels differ only in stride and col.
+ */
+
+/* the stop rule on values: the only statement of the expression of include/qrhip.h.  Vector compares whose lane masks are
+ * combined as scalars: no branch */
+__device__ __forceinline__ bool pt_adapt_rule(const u32 m, const float m2r, const float m2g, const float m2b, const u32 min_samples,
+                                              const u32 max_samples, const float tol2)
+{
+    float lim = (float)m * (float)(m - 1u);
+    lim = lim * tol2;
+    const bool conv = m2r <= lim && m2g <= lim && m2b <= lim;
+    return m < max_samples && (m < min_samples || m < 2u || !conv);
+}
+
+/* ... on column l of the wave's state */
+__device__ __forceinline__ bool pt_adapt_take(const u32 (*st)[64], const int l, const int min_samples, const int max_samples, const float tol2)
+{
+    return pt_adapt_rule(st[4][l], u2f(st[5][l]), u2f(st[6][l]), u2f(st[7][l]), (u32)min_samples, (u32)max_samples, tol2);
+}
+
+/* the wave's state from memory.  A lane outside the launch holds m = max_samples: the rule never lets it take */
+__device__ __forceinline__ void pt_adapt_load(u32 (*st)[64], const int l, const u32 *state, const size_t stride, const size_t col,
+                                              const bool inside, const int max_samples)
+{
+    u32 w[QR_PT_ADAPT_STATE_WORDS] = {0u, 0u, 0u, 0u, (u32)max_samples, 0u, 0u, 0u};
+    if (inside)
+    {
+#pragma unroll
+        for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) w[p] = state[(size_t)p * stride + col];
+    }
+#pragma unroll
+    for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) st[p][l] = w[p];
+}
+
+/* one sample of colour c into column l: Welford's update, one fp32 operation per step, the division IEEE */
+__device__ __forceinline__ void pt_adapt_fold(u32 (*st)[64], const int l, const u32 rng, const V3 c)
+{
+    const u32 m = st[4][l] + 1u;
+    const float o = 1.0f / (float)m, u = 1.0f - o;
+    st[4][l] = m;
+    st[0][l] = rng;
+    const float col[3] = {c.x, c.y, c.z};
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++)
+    {
+        const float mean = u2f(st[1 + ch][l]);
+        const float d1 = col[ch] - mean;
+        const float a = col[ch] * o, b = mean * u;
+        const float mn = a + b;
+        const float d2 = col[ch] - mn;
+        const float p = d1 * d2;
+        st[1 + ch][l] = f2u(mn);
+        st[5 + ch][l] = f2u(u2f(st[5 + ch][l]) + p);
+    }
+}
+
+/* column l back to memory, by a lane inside the launch: a column that took a sample holds more than it came with, so the count in
+ * memory says which columns to write (no flag is carried through the samples) */
+__device__ __forceinline__ void pt_adapt_store(const u32 (*st)[64], const int l, u32 *state, const size_t stride, const size_t col)
+{
+    if (st[4][l] != state[4 * stride + col])
+    {
+#pragma unroll
+        for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) state[(size_t)p * stride + col] = st[p][l];
+    }
+}
+
+/* `open` (may be null): ONE vector atomic add per wave, from its first lane, of the number of lanes the rule on the final state
+ * still lets take, and none when that number is 0 */
+__device__ __forceinline__ void pt_adapt_open(u32 *open, const u32 (*st)[64], const int l, const int min_samples, const int max_samples,
+                                              const float tol2)
+{
+    if (open != nullptr)
+    {
+        const unsigned long long still = __ballot(pt_adapt_take(st, l, min_samples, max_samples, tol2));
+        if (still != 0ull && l == 0) atomicAdd(open, (u32)__popcll(still));
+    }
+}
+
+/*
  * View accumulation (qr_render_views_mean_async): the grid is the footprints of ONE frame, one wave per workgroup; the wave renders
  * its footprint from every view of the launch in array order (a wave-uniform loop: the view record comes through scalar loads,
  * as in a view launch) and keeps the running sum of the reduced linear colours -- one fp32 add per channel and view, in order,
@@ -1093,16 +1228,8 @@ void qr_views_mean_kernel(LaunchP lp, ViewsP vp, int n_views, float *__restrict_
         sum[3 * px] = s.x; sum[3 * px + 1] = s.y; sum[3 * px + 2] = s.z;
         if (frame != nullptr)
         {
-            /* the rest of XX_end on the scaled sum: gamma, scale, round, mask, pack */
-            float cr = s.x * scale, cg = s.y * scale, cb = s.z * scale;
-            if (fr->fr.ctx_flags & QR_PROP_GAMMA)
-            {
-                asm volatile("" ::: "memory");
-                cr = __builtin_sqrtf(cr); cg = __builtin_sqrtf(cg); cb = __builtin_sqrtf(cb);
-            }
-            const float cl = fr->fr.clamp; const u32 cmask = fr->fr.cmask;
-            cr = cr * cl; cg = cg * cl; cb = cb * cl;
-            frame[px] = (((u32)cvt_near(cr) & cmask) << 16) | (((u32)cvt_near(cg) & cmask) << 8) | ((u32)cvt_near(cb) & cmask);
+            /* the rest of the output step on the scaled sum */
+            frame[px] = pack_pixel(fr, s.x * scale, s.y * scale, s.z * scale);
         }
     }
 }
@@ -1112,9 +1239,9 @@ void qr_views_mean_kernel(LaunchP lp, ViewsP vp, int n_views, float *__restrict_
  * view launch; the wave adds pv.samples samples to its footprint in a wave-uniform loop.  What the engine keeps per pixel sample
  * (PtParams: one LCG state, three running means) is read from the caller's state once, waits in LDS while a sample is traced
  * (1 KB per wave: nothing of it is live in registers through the recursion but the generator's state, which the path tracer
- * carries anyway), and is written back once, after the last sample; then the frame's output step runs once on the means.  The
- * weights of sample n (1-based, counted from the state's reset) are 1.0f / (float)n and 1.0f - that: IEEE division, the bits of
- * the host's (qr_device.hip launch<>); wave-uniform.  The path-tracer instance's walks and launch bound.
+ * carries anyway), and is written back once, after the last sample; then the frame's output step (fsaa_reduce, pack_pixel) runs
+ * once on the means.  The running mean is pt_mean_fold's; its weights are wave-uniform.  The path-tracer instance's walks and
+ * launch bound.
  */
 __global__ __launch_bounds__(QR_BLOCK, 3)
 void qr_pt_views_kernel(LaunchP lp, ViewsP vp, PtViewsP pv, uint32_t *__restrict__ frames)
@@ -1150,13 +1277,8 @@ void qr_pt_views_kernel(LaunchP lp, ViewsP vp, PtViewsP pv, uint32_t *__restrict
         V3 c;
         render_wave<false, false, true, 5>(lp, ord, 0u, view, nullptr, nullptr, nullptr, nullptr, nullptr, &vp, &c, &rng);
         asm volatile("" : "+v"(lane_s));
-        /* 5176-5219: running mean of the samples; lanes outside the frame carry zeros and a state nobody reads */
-        const float pts_o = 1.0f / (float)(pv.done + s + 1), pts_u = 1.0f - pts_o;
-        m.x = c.x * pts_o + lds_acc[0][lane_s] * pts_u;
-        m.y = c.y * pts_o + lds_acc[1][lane_s] * pts_u;
-        m.z = c.z * pts_o + lds_acc[2][lane_s] * pts_u;
-        lds_rng[lane_s] = rng;
-        if (s + 1 < pv.samples) { lds_acc[0][lane_s] = m.x; lds_acc[1][lane_s] = m.y; lds_acc[2][lane_s] = m.z; }
+        /* lanes outside the frame carry zeros and a state nobody reads */
+        m = pt_mean_fold(lds_rng, lds_acc, lane_s, rng, c, pv.done + s + 1, s + 1 < pv.samples);
     }
     int x_e, y_e, k_e;
     const bool inside_e = pixel_of_view(ord, fsaa, vp, x_e, y_e, k_e);
@@ -1166,40 +1288,24 @@ void qr_pt_views_kernel(LaunchP lp, ViewsP vp, PtViewsP pv, uint32_t *__restrict
         st[si] = lds_rng[lane];
         st[slots + si] = f2u(m.x); st[2 * slots + si] = f2u(m.y); st[3 * slots + si] = f2u(m.z);
     }
-    /* XX_end 5161-5343 on the means: clamp, FSAA reduce, gamma, pack (render_wave's output step) */
-    float cr = clamp1(m.x), cg = clamp1(m.y), cb = clamp1(m.z);
-    if (fsaa >= 1)
-    {
-        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
-        cr = cr + __shfl_down(cr, 1); cg = cg + __shfl_down(cg, 1); cb = cb + __shfl_down(cb, 1);
-    }
-    if (fsaa >= 2)
-    {
-        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
-        cr = cr + __shfl_down(cr, 2); cg = cg + __shfl_down(cg, 2); cb = cb + __shfl_down(cb, 2);
-    }
+    /* the frame's output step on the means */
+    float cr = m.x, cg = m.y, cb = m.z;
+    fsaa_reduce(fsaa, cr, cg, cb);
     if (inside_e && k_e == 0)
     {
         const size_t px = ((size_t)view * (size_t)vp.height + (size_t)y_e) * (size_t)vp.width + (size_t)x_e;
         if (pv.mean != nullptr) { pv.mean[3 * px] = cr; pv.mean[3 * px + 1] = cg; pv.mean[3 * px + 2] = cb; }
-        if (fr->fr.ctx_flags & QR_PROP_GAMMA)
-        {
-            asm volatile("" ::: "memory");
-            cr = __builtin_sqrtf(cr); cg = __builtin_sqrtf(cg); cb = __builtin_sqrtf(cb);
-        }
-        const float cl = fr->fr.clamp; const u32 cmask = fr->fr.cmask;
-        cr = cr * cl; cg = cg * cl; cb = cb * cl;
-        frames[px] = (((u32)cvt_near(cr) & cmask) << 16) | (((u32)cvt_near(cg) & cmask) << 8) | ((u32)cvt_near(cb) & cmask);
+        frames[px] = pack_pixel(fr, cr, cg, cb);
     }
 }
 
 /*
  * Path-traced rays (qr_pt_rays_async): one lane per caller ray, 64 per wave, one wave per workgroup, as in ray shading; the wave
- * adds `samples` samples to its rays in the wave-uniform loop of qr_pt_views_kernel.  state: four planes of n 32-bit words --
+ * adds `samples` samples to its rays in a wave-uniform loop.  state: four planes of n 32-bit words --
  * the LCG states, then the running means of r, g, b -- ray i is column i (include/qrhip.h).  It is read once before the first
  * sample, waits in LDS while a sample is traced (1 KB per wave: nothing of it is live in registers through the recursion but the
  * generator's state, which the path tracer carries anyway) and is written once after the last, with the optional rgb; the ray
- * and its spread are read again by every sample.  The weights of sample number done + s + 1 are those of qr_pt_views_kernel.
+ * and its spread are read again by every sample.  The running mean of sample number done + s + 1 is pt_mean_fold's.
  * A lane past n reads and writes nothing.  The path-tracer instance's walks (packet walks only) and launch bound.
  */
 __global__ __launch_bounds__(QR_BLOCK, 3)
@@ -1228,13 +1334,8 @@ void qr_pt_rays_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, int done
         V3 c;
         render_wave<false, false, true, 6>(lp, 0u, 0u, gw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &c, &rng, &pr);
         asm volatile("" : "+v"(lane_s));
-        /* the running mean of qr_pt_views_kernel; lanes past n carry zeros and a state nobody reads */
-        const float pts_o = 1.0f / (float)(done + s + 1), pts_u = 1.0f - pts_o;
-        m.x = c.x * pts_o + lds_acc[0][lane_s] * pts_u;
-        m.y = c.y * pts_o + lds_acc[1][lane_s] * pts_u;
-        m.z = c.z * pts_o + lds_acc[2][lane_s] * pts_u;
-        lds_rng[lane_s] = rng;
-        if (s + 1 < samples) { lds_acc[0][lane_s] = m.x; lds_acc[1][lane_s] = m.y; lds_acc[2][lane_s] = m.z; }
+        /* lanes past n carry zeros and a state nobody reads */
+        m = pt_mean_fold(lds_rng, lds_acc, lane_s, rng, c, done + s + 1, s + 1 < samples);
     }
     int lane_e = (int)(threadIdx.x & 63u);
     asm volatile("" : "+v"(lane_e));
@@ -1251,16 +1352,14 @@ void qr_pt_rays_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, int done
  * Adaptive path-traced rays (qr_pt_adapt_rays_async): qr_pt_rays_kernel with a sample count and a noise estimate per ray and a
  * stop rule evaluated on chip.  state: eight planes of n 32-bit words -- the LCG states, the running means of r, g, b, the count
  * m of samples the ray holds, Welford's M2 (sum of squared deviations) of r, g, b -- ray i is column i (include/qrhip.h).  All
- * eight words are read once and wait in LDS (2 KB per wave); nothing of them is live in registers through a sample but the
- * generator's state.  Before every candidate sample each lane evaluates the rule on its own column:
+ * eight words are read once (pt_adapt_load) and wait in LDS (2 KB per wave); nothing of them is live in registers through a
+ * sample but the generator's state.  Before every candidate sample each lane evaluates the rule on its own column (pt_adapt_take):
  *     take = m < max && (m < min || m < 2 || !(M2r <= lim && M2g <= lim && M2b <= lim)),  lim = ((float)m * (float)(m - 1)) * tol2
  * (per-lane data, so vector compares; only the ballot is scalar).  A lane that does not take a candidate takes none later in the
  * launch -- its column did not change -- and is out of the sample like a lane past n (render_wave RAYS = 7); the wave leaves the
- * loop when no lane is left, so a wave runs as long as its slowest ray.  The update is Welford's, one fp32 operation per step
- * (-ffp-contract=off), the division IEEE.  The state is written back once, by the lanes that took a sample (their count is no
- * longer the one in memory: no flag is carried through the samples); rgb by every lane
- * below n; `open` gets ONE vector atomic add per wave, from its first lane, of the number of lanes the rule on the final
- * state still lets take, and none when that number is 0.
+ * loop when no lane is left, so a wave runs as long as its slowest ray.  The update is Welford's (pt_adapt_fold).  The state is
+ * written back once, by the lanes that took a sample (pt_adapt_store); rgb by every lane below n; `open` gets ONE vector atomic
+ * add per wave (pt_adapt_open).
  */
 __global__ __launch_bounds__(QR_BLOCK, 3)
 void qr_pt_adapt_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, int samples, int min_samples, int max_samples, float tol2,
@@ -1271,94 +1370,46 @@ void qr_pt_adapt_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, int sam
     const size_t n = (size_t)(u32)pr.n;
     const int lane = (int)(threadIdx.x & 63u);
     const size_t i = (size_t)(u32)gw * 64u + (size_t)lane;
-    /* lanes past n hold m = max_samples: the rule never lets them take */
-    {
-        u32 w[QR_PT_ADAPT_STATE_WORDS] = {0u, 0u, 0u, 0u, (u32)max_samples, 0u, 0u, 0u};
-        if (i < n)
-        {
-#pragma unroll
-            for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) w[p] = state[(size_t)p * n + i];
-        }
-#pragma unroll
-        for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) lds_st[p][lane] = w[p];
-    }
-    auto rule = [&](int l) -> bool {
-        /* four LDS reads, then vector compares whose lane masks are combined as scalars: no branch */
-        const u32 m = lds_st[4][l];
-        const float m2r = u2f(lds_st[5][l]), m2g = u2f(lds_st[6][l]), m2b = u2f(lds_st[7][l]);
-        float lim = (float)m * (float)(m - 1u);
-        lim = lim * tol2;
-        const bool conv = m2r <= lim && m2g <= lim && m2b <= lim;
-        return m < (u32)max_samples && (m < (u32)min_samples || m < 2u || !conv);
-    };
+    pt_adapt_load(lds_st, lane, state, n, i, i < n, max_samples);
 #pragma nounroll
     for (int s = 0; s < samples; s++)
     {
         int lane_s = (int)(threadIdx.x & 63u);
         asm volatile("" : "+v"(lane_s));            /* not an address register kept alive through the sample */
-        const bool take = rule(lane_s);
+        const bool take = pt_adapt_take(lds_st, lane_s, min_samples, max_samples, tol2);
         if (!any_lane(take)) break;
         u32 rng = lds_st[0][lane_s];
         V3 c;
         render_wave<false, false, true, 7>(lp, 0u, 0u, gw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &c, &rng, &pr, take);
         asm volatile("" : "+v"(lane_s));
-        if (take)
-        {
-            const u32 m = lds_st[4][lane_s] + 1u;
-            const float o = 1.0f / (float)m, u = 1.0f - o;
-            lds_st[4][lane_s] = m;
-            lds_st[0][lane_s] = rng;
-            const float col[3] = {c.x, c.y, c.z};
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++)
-            {
-                const float mean = u2f(lds_st[1 + ch][lane_s]);
-                const float d1 = col[ch] - mean;
-                const float a = col[ch] * o, b = mean * u;
-                const float mn = a + b;
-                const float d2 = col[ch] - mn;
-                const float p = d1 * d2;
-                lds_st[1 + ch][lane_s] = f2u(mn);
-                lds_st[5 + ch][lane_s] = f2u(u2f(lds_st[5 + ch][lane_s]) + p);
-            }
-        }
+        if (take) pt_adapt_fold(lds_st, lane_s, rng, c);
     }
     int lane_e = (int)(threadIdx.x & 63u);
     asm volatile("" : "+v"(lane_e));
     const size_t i_e = (size_t)(u32)gw * 64u + (size_t)lane_e;
     if (i_e < n)
     {
-        /* a ray that took a sample holds more than it came with: the count in memory says which columns to write */
-        if (lds_st[4][lane_e] != state[4 * n + i_e])
-        {
-#pragma unroll
-            for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) state[(size_t)p * n + i_e] = lds_st[p][lane_e];
-        }
+        pt_adapt_store(lds_st, lane_e, state, n, i_e);
         if (pr.rgb != nullptr)
         {
             pr.rgb[3 * i_e] = u2f(lds_st[1][lane_e]); pr.rgb[3 * i_e + 1] = u2f(lds_st[2][lane_e]); pr.rgb[3 * i_e + 2] = u2f(lds_st[3][lane_e]);
         }
     }
-    if (open != nullptr)
-    {
-        const unsigned long long still = __ballot(rule(lane_e));
-        if (still != 0ull && lane_e == 0) atomicAdd(open, (u32)__popcll(still));
-    }
+    pt_adapt_open(open, lds_st, lane_e, min_samples, max_samples, tol2);
 }
 
 /*
- * Adaptive path-traced views (qr_pt_adapt_views_async): qr_pt_views_kernel's grid -- (footprint columns, footprint rows, views),
- * one wave per workgroup -- with qr_pt_adapt_kernel's sample loop.  state: per view eight planes of width * height *
- * samples-per-pixel 32-bit words, the planes of qr_pt_adapt_kernel, slot (y * width + x) * samples-per-pixel + k as in
- * qr_pt_views_kernel: one view's block is a qr_pt_adapt_kernel state of `slots` columns.  All eight words wait in LDS (2 KB per
- * wave); nothing of them is live in registers through a sample but the generator's state.  The rule is evaluated PER SLOT, per
+ * Adaptive path-traced views (qr_pt_adapt_views_async): the grid of a view launch -- (footprint columns, footprint rows, views),
+ * one wave per workgroup -- around the adaptive sample loop.  state: per view eight planes of width * height *
+ * samples-per-pixel 32-bit words, the adaptive state's planes, slot (y * width + x) * samples-per-pixel + k: one view's block is
+ * an adaptive ray state of `slots` columns.  All eight words wait in LDS (2 KB per wave); nothing of them is live in registers
+ * through a sample but the generator's state.  The rule is evaluated PER SLOT, per
  * pixel sample and not per pixel, at the top of the wave-uniform loop; a lane outside the frame holds m = max_samples and never
  * takes; a lane that does not take is out of the sample like a lane past the frame's edge (render_wave RAYS = 9); the wave leaves
- * when no lane is left, so it runs as long as its slowest slot.  The update is qr_pt_adapt_kernel's, operation for operation.
- * After the loop a column is written back only when its count is no longer the one in memory; then EVERY lane runs
- * qr_pt_views_kernel's output step on the means read back from LDS (the FSAA reduce needs all lanes of a pixel, taken or not), the
- * counts are reduced the same way in integers, and `open` gets one vector atomic add per wave from its first lane, none when
- * the number is 0.
+ * when no lane is left, so it runs as long as its slowest slot.  Rule, update, write-back and `open` are the adaptive state's
+ * functions (pt_adapt_take, _fold, _store, _open) on stride `slots` and column `si`.  After the write-back EVERY lane runs the
+ * frame's output step on the means read back from LDS (the FSAA reduce needs all lanes of a pixel, taken or not); the counts
+ * are reduced the same way in integers.
  */
 struct PtAdaptViewsP { u32 *state; int32_t samples, min_samples, max_samples; float tol2; float *mean; int32_t *counts; u32 *open; };
 
@@ -1377,60 +1428,25 @@ void qr_pt_adapt_views_kernel(LaunchP lp, ViewsP vp, PtAdaptViewsP pa, uint32_t 
     u32 *const st = pa.state + (size_t)view * (size_t)QR_PT_ADAPT_STATE_WORDS * slots;
     const int max_samples = pa.max_samples, min_samples = pa.min_samples;
     const float tol2 = pa.tol2;
-    /* lanes outside the frame hold m = max_samples: the rule never lets them take */
     {
-        const int lane = (int)(threadIdx.x & 63u);
-        u32 w[QR_PT_ADAPT_STATE_WORDS] = {0u, 0u, 0u, 0u, (u32)max_samples, 0u, 0u, 0u};
         int x_r, y_r, k_r;
-        if (pixel_of_view(ord, fsaa, vp, x_r, y_r, k_r))
-        {
-            const size_t si = (((size_t)y_r * (size_t)vp.width + (size_t)x_r) << fsaa) + (size_t)k_r;
-#pragma unroll
-            for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) w[p] = st[(size_t)p * slots + si];
-        }
-#pragma unroll
-        for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) lds_st[p][lane] = w[p];
+        const bool inside_r = pixel_of_view(ord, fsaa, vp, x_r, y_r, k_r);
+        /* pixel_of_view always writes x, y and k, so si is a number for a lane outside the frame too; only `inside_r` lanes read */
+        const size_t si = (((size_t)y_r * (size_t)vp.width + (size_t)x_r) << fsaa) + (size_t)k_r;
+        pt_adapt_load(lds_st, (int)(threadIdx.x & 63u), st, slots, si, inside_r, max_samples);
     }
-    auto rule = [&](int l) -> bool {
-        /* qr_pt_adapt_kernel's: four LDS reads, then vector compares whose lane masks are combined as scalars */
-        const u32 m = lds_st[4][l];
-        const float m2r = u2f(lds_st[5][l]), m2g = u2f(lds_st[6][l]), m2b = u2f(lds_st[7][l]);
-        float lim = (float)m * (float)(m - 1u);
-        lim = lim * tol2;
-        const bool conv = m2r <= lim && m2g <= lim && m2b <= lim;
-        return m < (u32)max_samples && (m < (u32)min_samples || m < 2u || !conv);
-    };
 #pragma nounroll
     for (int s = 0; s < pa.samples; s++)
     {
         int lane_s = (int)(threadIdx.x & 63u);
         asm volatile("" : "+v"(lane_s));            /* not an address register kept alive through the sample */
-        const bool take = rule(lane_s);
+        const bool take = pt_adapt_take(lds_st, lane_s, min_samples, max_samples, tol2);
         if (!any_lane(take)) break;
         u32 rng = lds_st[0][lane_s];
         V3 c;
         render_wave<false, false, true, 9>(lp, ord, 0u, view, nullptr, nullptr, nullptr, nullptr, nullptr, &vp, &c, &rng, nullptr, take);
         asm volatile("" : "+v"(lane_s));
-        if (take)
-        {
-            const u32 m = lds_st[4][lane_s] + 1u;
-            const float o = 1.0f / (float)m, u = 1.0f - o;
-            lds_st[4][lane_s] = m;
-            lds_st[0][lane_s] = rng;
-            const float col[3] = {c.x, c.y, c.z};
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++)
-            {
-                const float mean = u2f(lds_st[1 + ch][lane_s]);
-                const float d1 = col[ch] - mean;
-                const float a = col[ch] * o, b = mean * u;
-                const float mn = a + b;
-                const float d2 = col[ch] - mn;
-                const float p = d1 * d2;
-                lds_st[1 + ch][lane_s] = f2u(mn);
-                lds_st[5 + ch][lane_s] = f2u(u2f(lds_st[5 + ch][lane_s]) + p);
-            }
-        }
+        if (take) pt_adapt_fold(lds_st, lane_s, rng, c);
     }
     int lane_e = (int)(threadIdx.x & 63u);
     asm volatile("" : "+v"(lane_e));
@@ -1438,64 +1454,37 @@ void qr_pt_adapt_views_kernel(LaunchP lp, ViewsP vp, PtAdaptViewsP pa, uint32_t 
     const bool inside_e = pixel_of_view(ord, fsaa, vp, x_e, y_e, k_e);
     if (inside_e)
     {
-        /* a slot that took a sample holds more than it came with: the count in memory says which columns to write */
         const size_t si = (((size_t)y_e * (size_t)vp.width + (size_t)x_e) << fsaa) + (size_t)k_e;
-        if (lds_st[4][lane_e] != st[4 * slots + si])
-        {
-#pragma unroll
-            for (int p = 0; p < QR_PT_ADAPT_STATE_WORDS; p++) st[(size_t)p * slots + si] = lds_st[p][lane_e];
-        }
+        pt_adapt_store(lds_st, lane_e, st, slots, si);
     }
-    /* XX_end 5161-5343 on the means: clamp, FSAA reduce, gamma, pack (qr_pt_views_kernel's output step), by every lane: lanes
-     * outside the frame carry zeros.  The counts take the same reduce in integers */
-    float cr = clamp1(u2f(lds_st[1][lane_e])), cg = clamp1(u2f(lds_st[2][lane_e])), cb = clamp1(u2f(lds_st[3][lane_e]));
+    /* the frame's output step on the means, by every lane: lanes outside the frame carry zeros.  The counts take the same
+     * reduce in integers */
+    float cr = u2f(lds_st[1][lane_e]), cg = u2f(lds_st[2][lane_e]), cb = u2f(lds_st[3][lane_e]);
     int cn = inside_e ? (int)lds_st[4][lane_e] : 0;
-    if (fsaa >= 1)
-    {
-        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
-        cr = cr + __shfl_down(cr, 1); cg = cg + __shfl_down(cg, 1); cb = cb + __shfl_down(cb, 1);
-        cn = cn + __shfl_down(cn, 1);
-    }
-    if (fsaa >= 2)
-    {
-        cr = cr * 0.5f; cg = cg * 0.5f; cb = cb * 0.5f;
-        cr = cr + __shfl_down(cr, 2); cg = cg + __shfl_down(cg, 2); cb = cb + __shfl_down(cb, 2);
-        cn = cn + __shfl_down(cn, 2);
-    }
+    fsaa_reduce(fsaa, cr, cg, cb, &cn);
     if (inside_e && k_e == 0)
     {
         const size_t px = ((size_t)view * (size_t)vp.height + (size_t)y_e) * (size_t)vp.width + (size_t)x_e;
         if (pa.mean != nullptr) { pa.mean[3 * px] = cr; pa.mean[3 * px + 1] = cg; pa.mean[3 * px + 2] = cb; }
         if (pa.counts != nullptr) pa.counts[px] = cn;
-        if (fr->fr.ctx_flags & QR_PROP_GAMMA)
-        {
-            asm volatile("" ::: "memory");
-            cr = __builtin_sqrtf(cr); cg = __builtin_sqrtf(cg); cb = __builtin_sqrtf(cb);
-        }
-        const float cl = fr->fr.clamp; const u32 cmask = fr->fr.cmask;
-        cr = cr * cl; cg = cg * cl; cb = cb * cl;
-        frames[px] = (((u32)cvt_near(cr) & cmask) << 16) | (((u32)cvt_near(cg) & cmask) << 8) | ((u32)cvt_near(cb) & cmask);
+        frames[px] = pack_pixel(fr, cr, cg, cb);
     }
-    if (pa.open != nullptr)
-    {
-        const unsigned long long still = __ballot(rule(lane_e));
-        if (still != 0ull && lane_e == 0) atomicAdd(pa.open, (u32)__popcll(still));
-    }
+    pt_adapt_open(pa.open, lds_st, lane_e, min_samples, max_samples, tol2);
 }
 
 /*
- * Indexed adaptive path-traced rays (qr_pt_adapt_list_rays_async): qr_pt_adapt_kernel with the wave's 64 rays taken from a list of
- * ray indices instead of from 64 consecutive columns, so that the rays a stop rule has left open -- scattered among rays that have
+ * Indexed adaptive path-traced rays (qr_pt_adapt_list_rays_async): adaptive path-traced rays with the wave's 64 rays taken from a
+ * list of ray indices instead of from 64 consecutive columns, so that the rays a stop rule has left open -- scattered among rays that have
  * stopped -- fill whole waves (the list: qr_openlist.hpp, or any list of distinct indices the caller makes).  Wave w serves list
  * positions 64 w .. 64 w + 63 below min(cap, *count); *count is one scalar load, and a wave at or past it leaves before it touches
  * anything else.  Lane l reads its entry i once; the ray's and the spread's rows, the eight state words and the rgb row are all
  * addressed by i.  An entry >= n, and a position past the end, is a lane outside: it holds the sentinel index and m = max_samples,
  * so the rule never lets it take, and reads and writes nothing.  The index waits in LDS beside the state (2 KB + 256 B per wave)
  * and is read again at the top of every sample, as lane_s is made again: it is not a register live through the recursion.
- * Everything else is qr_pt_adapt_kernel's body: the rule at the top of the wave-uniform sample loop, any_lane(take) the exit,
- * Welford's update, a column written back only when its count changed, rgb for the listed rays only, `open` one vector atomic add
- * per wave.  A ray's result depends on nothing but its own column, ray and spread, so the state after the call is bit for bit the
- * state qr_pt_adapt_kernel leaves on the listed columns.
+ * Everything else is the adaptive state's functions on stride n and column i: the rule at the top of the wave-uniform sample
+ * loop, any_lane(take) the exit, Welford's update, a column written back only when its count changed, rgb for the listed rays
+ * only, `open` one vector atomic add per wave.  A ray's result depends on nothing but its own column, ray and spread, so the
+ * state after the call is bit for bit the state qr_pt_adapt_kernel leaves on the listed columns.
  */
 __global__ __launch_bounds__(QR_BLOCK, 3)
 void qr_pt_list_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, const u32 *__restrict__ index, const u32 *__restrict__ count,
@@ -1514,80 +1503,36 @@ void qr_pt_list_kernel(LaunchP lp, PtRaysP pr, u32 *__restrict__ state, const u3
         const u32 p = (u32)gw * 64u + (u32)lane;
         u32 ix = NONE;
         if (p < lim) { ix = index[p]; if (ix >= n) ix = NONE; }
-        /* lanes outside hold m = max_samples: the rule never lets them take */
-        u32 w[QR_PT_ADAPT_STATE_WORDS] = {0u, 0u, 0u, 0u, (u32)max_samples, 0u, 0u, 0u};
-        if (ix != NONE)
-        {
-#pragma unroll
-            for (int q = 0; q < QR_PT_ADAPT_STATE_WORDS; q++) w[q] = state[(size_t)q * n + ix];
-        }
         lds_ix[lane] = ix;
-#pragma unroll
-        for (int q = 0; q < QR_PT_ADAPT_STATE_WORDS; q++) lds_st[q][lane] = w[q];
+        pt_adapt_load(lds_st, lane, state, n, ix, ix != NONE, max_samples);
     }
-    auto rule = [&](int l) -> bool {
-        const u32 m = lds_st[4][l];
-        const float m2r = u2f(lds_st[5][l]), m2g = u2f(lds_st[6][l]), m2b = u2f(lds_st[7][l]);
-        float lim2 = (float)m * (float)(m - 1u);
-        lim2 = lim2 * tol2;
-        const bool conv = m2r <= lim2 && m2g <= lim2 && m2b <= lim2;
-        return m < (u32)max_samples && (m < (u32)min_samples || m < 2u || !conv);
-    };
 #pragma nounroll
     for (int s = 0; s < samples; s++)
     {
         int lane_s = (int)(threadIdx.x & 63u);
         asm volatile("" : "+v"(lane_s));            /* not an address register kept alive through the sample */
-        const bool take = rule(lane_s);
+        const bool take = pt_adapt_take(lds_st, lane_s, min_samples, max_samples, tol2);
         if (!any_lane(take)) break;
         u32 rng = lds_st[0][lane_s];
         const u32 ri = lds_ix[lane_s];              /* dead after the ray's rows are read */
         V3 c;
         render_wave<false, false, true, 8>(lp, 0u, 0u, gw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &c, &rng, &pr, take, ri);
         asm volatile("" : "+v"(lane_s));
-        if (take)
-        {
-            const u32 m = lds_st[4][lane_s] + 1u;
-            const float o = 1.0f / (float)m, u = 1.0f - o;
-            lds_st[4][lane_s] = m;
-            lds_st[0][lane_s] = rng;
-            const float col[3] = {c.x, c.y, c.z};
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++)
-            {
-                const float mean = u2f(lds_st[1 + ch][lane_s]);
-                const float d1 = col[ch] - mean;
-                const float a = col[ch] * o, b = mean * u;
-                const float mn = a + b;
-                const float d2 = col[ch] - mn;
-                const float p = d1 * d2;
-                lds_st[1 + ch][lane_s] = f2u(mn);
-                lds_st[5 + ch][lane_s] = f2u(u2f(lds_st[5 + ch][lane_s]) + p);
-            }
-        }
+        if (take) pt_adapt_fold(lds_st, lane_s, rng, c);
     }
     int lane_e = (int)(threadIdx.x & 63u);
     asm volatile("" : "+v"(lane_e));
     const u32 i_e = lds_ix[lane_e];
     if (i_e < n)
     {
-        /* a ray that took a sample holds more than it came with: the count in memory says which columns to write */
-        if (lds_st[4][lane_e] != state[(size_t)4 * n + i_e])
-        {
-#pragma unroll
-            for (int q = 0; q < QR_PT_ADAPT_STATE_WORDS; q++) state[(size_t)q * n + i_e] = lds_st[q][lane_e];
-        }
+        pt_adapt_store(lds_st, lane_e, state, n, i_e);
         if (pr.rgb != nullptr)
         {
             const size_t o3 = 3 * (size_t)i_e;
             pr.rgb[o3] = u2f(lds_st[1][lane_e]); pr.rgb[o3 + 1] = u2f(lds_st[2][lane_e]); pr.rgb[o3 + 2] = u2f(lds_st[3][lane_e]);
         }
     }
-    if (open != nullptr)
-    {
-        const unsigned long long still = __ballot(rule(lane_e));
-        if (still != 0ull && lane_e == 0) atomicAdd(open, (u32)__popcll(still));
-    }
+    pt_adapt_open(open, lds_st, lane_e, min_samples, max_samples, tol2);
 }
 
 /*

@@ -9,10 +9,10 @@
  * reading the rays again for every layer and rewriting tmin in between; here the ray, the count and the alive flag stay in
  * registers and only the answers leave.
  *
- * One kernel template, two ray sources, set up as in qr_hit_kernel (qr_hitrec.hpp) and qr_fan_kernel (qr_fan.hpp):
+ * One kernel template, two ray sources (launch_ray, qr_hitrec.hpp):
  *   VIEW = false  the caller's qr_ray array: lane i of workgroup g is ray g * 64 + i.
  *   VIEW = true   the grid is (footprint columns, footprint rows, views), a footprint is 8x8 pixels, one lane per pixel, sample
- *                 0's ray under FSAA (pixel_of_view, sample_offsets, view_ray).
+ *                 0's ray under FSAA.
  * Then a wave-uniform loop over the layers.  Per layer: the ballot of the lanes that are still alive; when it is empty the walk
  * loop is left (traverse is never called without an active lane, as the fan kernel never calls it: its LM(traced) != 0).
  * Otherwise traverse<false, DIVK, true> on DevHeader::off_query with the ballot's lanes as `active` (r.list = 0 for the others),
@@ -59,41 +59,9 @@ void qr_layer_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ ra
 #pragma clang diagnostic pop
     (void)stats;
     const FrmP fr = c_frm(B);
-    bool active;
     size_t rec;                                 /* this lane's element */
     Ray r;
-    if constexpr (VIEW)
-    {
-        /* qr_hit_kernel's VIEW branch: one lane per pixel of an 8x8 footprint, sample 0's offsets at the frame's FSAA */
-        const u32 ord = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x | (blockIdx.y << 14)));
-        const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
-        int x, y, k;
-        active = pixel_of_view(ord, 0, vp, x, y, k);
-        float ha, va;
-        sample_offsets(fr, blob, fr->fr.fsaa, x, k, ha, va);
-        float hs = (float)x + ha; hs = hs + 0.0f;
-        float vs = (float)y + va; vs = vs + 0.0f;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-        const QR_CONST qr_view *vw = (const QR_CONST qr_view *)vp.views + view;
-#pragma clang diagnostic pop
-        view_ray(vw, hs, vs, r);
-        /* lanes outside the frame keep element 0 of their view and store nothing */
-        rec = ((size_t)view * (size_t)vp.height + (size_t)(active ? y : 0)) * (size_t)vp.width + (size_t)(active ? x : 0);
-    }
-    else
-    {
-        const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
-        active = i < (int64_t)n;
-        const int64_t q = active ? i : 0;           /* n > 0: lanes past the end read ray 0 and do not walk */
-        const f32x4 a = rays[2 * q], b = rays[2 * q + 1];
-        r.org = {a.x, a.y, a.z}; r.tmin = a.w;
-        r.dir = {b.x, b.y, b.z};
-        r.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;     /* +inf is taken as FLT_MAX, as in qr_trace_kernel */
-        r.osrf = 0; r.oflg = 0;
-        r.ploc = {0.0f, 0.0f, 0.0f};
-        rec = (size_t)q;
-    }
+    const bool active = launch_ray<VIEW>(fr, blob, rays, n, vp, r, rec);
 
     /* the layers: every lane of the wave stays in the loop (the walks are wave-wide), a lane that has missed walks no more */
     const u32 qlist = fr->off_query;

@@ -16,16 +16,13 @@
 static_assert(QR_PT_OPEN_BLOCK % 64 == 0 && QR_PT_OPEN_BLOCK >= 64 && QR_PT_OPEN_BLOCK <= 1024, "whole waves, one workgroup");
 static_assert(QR_PT_OPEN_CHUNK % 64 == 0 && QR_PT_OPEN_CHUNK >= 64 && QR_PT_OPEN_CHUNK <= 1024, "whole waves, one workgroup");
 
-/* the stop rule of qr_pt_adapt_rays_async on column i of the state (planes 4..7), the expression of include/qrhip.h */
+/* the stop rule of qr_pt_adapt_rays_async (pt_adapt_rule, qr_kernel.hpp) on column i of the state in memory (planes 4..7) */
 __device__ __forceinline__ bool qr_open_rule(const u32 *__restrict__ state, size_t n, size_t i, u32 min_samples, u32 max_samples,
                                              float tol2)
 {
     const u32 m = state[4 * n + i];
     const float m2r = u2f(state[5 * n + i]), m2g = u2f(state[6 * n + i]), m2b = u2f(state[7 * n + i]);
-    float lim = (float)m * (float)(m - 1u);
-    lim = lim * tol2;
-    const bool conv = m2r <= lim && m2g <= lim && m2b <= lim;
-    return m < max_samples && (m < min_samples || m < 2u || !conv);
+    return pt_adapt_rule(m, m2r, m2g, m2b, min_samples, max_samples, tol2);
 }
 
 __global__ __launch_bounds__(QR_PT_OPEN_BLOCK)

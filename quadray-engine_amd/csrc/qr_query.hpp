@@ -18,6 +18,19 @@
 
 #include <float.h>
 
+/* the caller's qr_ray q, everything but the list: two 16-byte loads (consecutive lanes, consecutive rays).  No originating
+ * surface.  +inf is taken as FLT_MAX (what the engine's cameras use): the walk scales the depth bound (w.tbuf * 1.000001,
+ * w.tbuf * dd), and with +inf a zero factor would give NaN.  (render_wave keeps its own copy: its assembly is what bench.py times.) */
+__device__ __forceinline__ void caller_ray(const f32x4 *__restrict__ rays, const int64_t q, Ray &r)
+{
+    const f32x4 a = rays[2 * q], b = rays[2 * q + 1];
+    r.org = {a.x, a.y, a.z}; r.tmin = a.w;
+    r.dir = {b.x, b.y, b.z};
+    r.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;
+    r.osrf = 0; r.oflg = 0;
+    r.ploc = {0.0f, 0.0f, 0.0f};
+}
+
 template <bool SHADOW, bool COHERENT>
 __global__ __launch_bounds__(QR_BLOCK, SHADOW ? QR_MIN_WAVES_PER_SIMD : QR_DIVK_WAVES)
 void qr_trace_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ rays, int32_t n,
@@ -33,12 +46,11 @@ void qr_trace_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ ra
     const bool active = i < (int64_t)n;
     Ray r;
     {
+        /* caller_ray's text, kept here (through the function this kernel's ray address took another form) */
         const int64_t k = active ? i : 0;           /* n > 0: lanes past the end read ray 0 and do not walk */
         const f32x4 a = rays[2 * k], b = rays[2 * k + 1];
         r.org = {a.x, a.y, a.z}; r.tmin = a.w;
         r.dir = {b.x, b.y, b.z};
-        /* +inf is taken as FLT_MAX (what the engine's cameras use): the walk scales the depth bound (w.tbuf * 1.000001,
-         * w.tbuf * dd), and with +inf a zero factor would give NaN */
         r.tmax = b.w > FLT_MAX ? FLT_MAX : b.w;
         r.list = active ? c_frm(B)->off_query : 0u;
         r.osrf = 0; r.oflg = 0;

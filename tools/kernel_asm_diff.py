@@ -6,7 +6,8 @@ descriptor block (registers, scratch, LDS), from the symbol's label to its .Lfun
 .LBB<f>_<n>, .Ltmp<n>, .Lfunc_end<n> and the numbered labels of inline assembly (qr_cull_*_<n>) -- are renumbered in order
 of first appearance, since they follow the position of the kernel in the file.  Kernels only the NEW file has are listed.
 A change to the device code that must leave the existing kernels as they were (a new instance, a new kernel) shows an
-empty diff.
+empty diff.  A kernel that DIFFERS also says whether its .amdhsa_ descriptor lines are identical and how many instruction lines
+it has in OLD and in NEW: what a refactor that moves code between functions is judged by.
 
 usage: kernel_asm_diff.py OLD.s NEW.s [--show N]      exit status 1 when some kernel of OLD differs or is missing
 """
@@ -48,6 +49,16 @@ def kernels(path):
     return out
 
 
+def _descriptor(body):
+    """the .amdhsa_ lines of a kernel: registers, spills' private segment, LDS, what the launch sets up"""
+    return [ln.strip() for ln in body if ln.strip().startswith(".amdhsa_")]
+
+
+def _instructions(body):
+    """number of instruction lines: neither labels nor assembler directives"""
+    return sum(1 for ln in body if not ln.strip().startswith(".") and not ln.rstrip().endswith(":"))
+
+
 def main():
     if len(sys.argv) < 3:
         print(__doc__, file=sys.stderr)
@@ -64,7 +75,8 @@ def main():
             print(f"same     {name}  ({len(old[name])} lines)")
             continue
         bad += 1
-        print(f"DIFFERS  {name}")
+        desc = "identical" if _descriptor(old[name]) == _descriptor(new[name]) else "DIFFERENT"
+        print(f"DIFFERS  {name}  (descriptor {desc}; instructions {_instructions(old[name])} -> {_instructions(new[name])})")
         d = list(difflib.unified_diff(old[name], new[name], "old", "new", lineterm="", n=1))
         print("\n".join(d[:show]))
     for name in sorted(set(new) - set(old)):
