@@ -1553,6 +1553,8 @@ int qr_program_verify(const QrProgram &p, std::string &err)
                 if (mid != 0 && (mid <= o + 64 || mid >= c->end || (mid & 31) || !(slot[mid / 32] & 2))) return "array hand-over boundary outside the array";
             }
             if ((c->op & QR_OPF_CACHED) && (c->op & QR_OPF_OWN)) return "bad transform mode";
+            /* the cull run tells an array with a sphere by QR_OPF_CULL | QR_OPT_BV under a mask that may hold the box bit (qr_walk.hpp) */
+            if ((c->op & QR_OPF_BOX) && !(t & QR_OPT_SOLVER)) return "box cull bit on a cell that is no solver cell";
             if (world && (t == QR_OPT_TRNODE || (c->op & QR_OPF_LOCAL))) return "transform in a list flagged world-space";
             if ((c->op & QR_OPF_CULL) && !(t & (QR_OPT_SOLVER | QR_OPT_BV))) return "cull flag on a cell without solver or volume";
             if (c->op & QR_OPF_BOX)

@@ -600,14 +600,31 @@ extern "C" int qr_render_count(qr_device_scene *s, void *frame_dev, void *stream
         fprintf(stderr, "\nQR_PROF frames pushed by level 0..7+ (lanes), one child:    ");
         for (int i = 0; i < 8; i++) fprintf(stderr, " %llu", pf[40 + i]);
         fprintf(stderr, "\n");
+#ifdef QR_PROF_BVSPH_DRY
+        /* the array cut of walk_list, evaluated and not acted on (QR_CUT_BVSPH, profiles/r22_array_cull.txt) */
+        static const char *an[6] = { "(a) array cells reached", "(b) left by `far` for every ray that is on", "(c) volume test run, no ray enters",
+            "(d) cull sphere: every ray that is on misses", "(e) rays ruled out while others go on", "    (d) within (c)" };
+        for (int k = 0; k < 2; k++)
+            for (int i = 0; i < 6; i++) fprintf(stderr, "QR_PROF arrays, %s walks: %-44s %llu\n", k ? "nearest-hit" : "shadow", an[i], pf[50 + 6 * k + i]);
+#endif
+        fprintf(stderr, "QR_PROF trnode cells reached %llu, ranges that end without a member handed out %llu\n", pf[62], pf[63]);
         unsigned long long z[64] = {0};
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(qr_prof), z, sizeof(z)));
     }
 #endif
 #ifdef QR_STATS
     {
-        unsigned long long st[32];
+        unsigned long long st[60];
         HIP_TRY(hipMemcpy(st, s->d_counters + 4, sizeof(st), hipMemcpyDeviceToHost));
+        /* arrays with a cull sphere in the packet walks (walk_list, QR_CUT_BVSPH) */
+        for (int k = 0; k < 3; k++)
+        {
+            static const char *kind[3] = { "shadow", "primary", "secondary" };
+            const unsigned long long *a = st + 32 + 9 * k;
+            fprintf(stderr, "QR_STATS arrays %s: handed out %llu jumped in the run %llu jumped past waiting rays %llu jumped onto END %llu "
+                            "left all inside %llu split %llu rays ruled out %llu with occluded rays %llu with waiting rays %llu\n",
+                    kind[k], a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]);
+        }
         if (st[27]) fprintf(stderr, "QR_GUARD %llu bad cell offsets; first: tag %llu offset 0x%llx context 0x%llx\n", st[27], st[24], st[25], st[26]);
         fprintf(stderr, "QR_STATS per-lane walks %llu: steps %llu (%.1f per walk, %.1f lanes stepping), solve rounds %llu (%.1f lanes solving)\n",
                 st[16], st[17], st[16] ? (double)st[17] / st[16] : 0.0, st[17] ? (double)st[18] / st[17] : 0.0,
@@ -1136,7 +1153,7 @@ static int slot_prepare(DropSlot &c, int dev, size_t image_bytes, size_t frame_b
     }
     else HIP_TRY(hipSetDevice(dev));
     {
-        /* counter block as qr_scene_upload_ex sizes it: 64 words (ray counts, QR_STATS slots 4..34), and per wave of the
+        /* counter block as qr_scene_upload_ex sizes it: 64 words (ray counts, QR_STATS slots 4..62), and per wave of the
          * schedule QR_WT_SLOTS more in QR_WAVETIME builds */
 #ifdef QR_WAVETIME
         const size_t need = 64 + QR_WT_SLOTS * n_sched;

@@ -130,6 +130,21 @@ __device__ __forceinline__ V3 xform(BaseP B, u32 off, bool full, V3 in)
 #ifndef QR_CUT_XFORM2
 #define QR_CUT_XFORM2 1     /* diff and ray through one record's matrix: the coefficients loaded once, `full` decided once (0: two xform calls) */
 #endif
+#ifndef QR_CUT_BVSPH
+#define QR_CUT_BVSPH 1      /* walk_list: a bounding-volume array whose cull sphere every ray that is on misses sideways is skipped inside the
+                             * cull run, and a ray that misses it stays out of the volume test (0: arrays always end the run and only the
+                             * behind / beyond test is made, profiles/r22_array_cull.txt) */
+#endif
+/* -DQR_PROF -DQR_PROF_BVSPH_DRY (the count of profiles/r22_array_cull.txt): the walk of QR_CUT_BVSPH=0, which besides counts what
+ * the cut would decide (qr_prof[50..61]) without acting on it.  The plain QR_PROF build walks as the product does. */
+#if defined(QR_PROF_BVSPH_DRY) && !defined(QR_PROF)
+#error "QR_PROF_BVSPH_DRY is a mode of the QR_PROF build"
+#endif
+#if QR_CUT_BVSPH && !defined(QR_PROF_BVSPH_DRY)
+#define QR_BVSPH_ACT 1
+#else
+#define QR_BVSPH_ACT 0
+#endif
 /* xform of `a` and of `b` with the same record: each with xform's operations in xform's order */
 __device__ __forceinline__ void xform2(BaseP B, u32 off, bool full, V3 a, V3 b, V3 &oa, V3 &ob)
 {
@@ -734,14 +749,122 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
  * Box test: miss <=> tn > tf | tf < 0 | tn > tb1 with tb1 = 1.00001 * depth bound >= 0, folded into ONE compare:
  * max(tn, 0) > min(tf, tb1)  (max / min drop a NaN operand exactly where the three compares were false).
  */
+/*
+ * Arrays in the run (QR_CUT_BVSPH).  A bounding-volume cell with a cull sphere (QR_OPF_CULL | QR_OPT_BV: s96 == 40 after the mask)
+ * takes the solver cells' sphere test with R2 = R * R and the "origin outside" threshold 1.01 * R2 computed here: slot 2 of such
+ * a cell is the array's end offset and slot 3 walk_pool's marker, never an R2.  When no ray that is on needs the array the cursor
+ * becomes that end offset and the run goes on; otherwise the cell is handed out with the verdict per ray.  When every ray that is
+ * on starts inside the sphere (the enclosing arrays of a hierarchy, which the swarm's walks mostly meet: profiles/r22_array_cull.txt) the cell leaves after the
+ * distance alone, nobody ruled out: a sphere around the origin is neither behind it nor beyond a depth bound.  The block sits off
+ * the solver cells' path: a cell that is no plain cull cell branches here, and what is no array either leaves as before.
+ * Frames keep every bit: the sphere is the union of the members' bounding spheres, inflated (qr_compile.cpp), so a ray that misses
+ * it cannot meet a member at t in (t_min, t_buf) with t_min >= 0, and rays with t_min < 0 never reach this walk with culls on
+ * (traverse).  The reference either skips the array for such a ray or walks members that all miss.  Static walk state does not
+ * depend on whether an array was walked or skipped (qr_compile.cpp refuses lists where it would), and arrays nest.  A ray that
+ * starts on a member's surface has its origin inside the sphere, where the threshold keeps it in -- the fact the behind / beyond
+ * rule of the hand-out path rests on too.  Lanes that are off are compared by resume <= pos, never by equality: a jump cannot
+ * strand one, and nesting puts their resume point at or behind the jump's target.
+ */
+#if QR_BVSPH_ACT
+#ifdef QR_STATS
+/* the guarded diagnostic build counts, with s[96:97] still the rays that are on: arrays jumped; of them with rays waiting at an enclosing
+ * array's end (off and not occluded); of them onto the list's END cell; arrays that leave by the all-inside exit with some ray on */
+#define QR_RUN_NJ_ASM \
+            "s_add_u32 %[nj], %[nj], 1\n" \
+            "v_cmp_ne_u32 vcc, -1, %[res]\n" \
+            "s_andn2_b64 vcc, vcc, s[96:97]\n" \
+            "s_cselect_b32 s98, 1, 0\n" \
+            "s_add_u32 %[nw], %[nw], s98\n" \
+            "s_load_dword s98, %[B], s90 offset:0x0\n" \
+            "s_waitcnt lgkmcnt(0)\n" \
+            "s_cmp_eq_u32 s98, 0\n" \
+            "s_cselect_b32 s98, 1, 0\n" \
+            "s_add_u32 %[ne], %[ne], s98\n"
+#define QR_RUN_INS "qr_cull_ins_%="
+#define QR_RUN_INS_ASM \
+            "qr_cull_ins_%=:\n" \
+            "s_cmp_lg_u64 s[96:97], 0\n" \
+            "s_cselect_b32 s98, 1, 0\n" \
+            "s_add_u32 %[ni], %[ni], s98\n" \
+            "s_branch qr_cull_out_%=\n"
+#define QR_RUN_NJ_OP , [am] "=&s"(am), [nj] "+s"(njl.jump), [nw] "+s"(njl.jwait), [ne] "+s"(njl.jend), [ni] "+s"(njl.ins)
+#else
+#define QR_RUN_NJ_ASM
+#define QR_RUN_INS "qr_cull_out_%="
+#define QR_RUN_INS_ASM
+#define QR_RUN_NJ_OP , [am] "=&s"(am)
+#endif
+#define QR_RUN_LEAVE "qr_cull_arr_%="
+#define QR_RUN_ARRAY \
+            "qr_cull_arr_%=:\n" \
+            "s_cmp_lg_u32 s96, 40\n" \
+            "s_cbranch_scc1 qr_cull_out_%=\n" \
+            "v_sub_f32 %[t0], s92, %[ox]\n" \
+            "v_sub_f32 %[t1], s93, %[oy]\n" \
+            "v_sub_f32 %[t2], s94, %[oz]\n" \
+            "v_mul_f32 %[t4], %[t0], %[t0]\n" \
+            "v_mul_f32_e64 %[t3], s95, s95\n"               /* R2 */ \
+            "v_fmac_f32 %[t4], %[t1], %[t1]\n" \
+            "v_mul_f32 %[t3], 0x3f8147ae, %[t3]\n"          /* 1.01f * R2 */ \
+            "v_fmac_f32 %[t4], %[t2], %[t2]\n" \
+            "v_cmp_ge_u32 s[96:97], %[pos], %[res]\n"       /* rays that are on */ \
+            "v_cmp_lt_f32 vcc, %[t3], %[t4]\n" \
+            "s_mov_b64 %[am], 0\n" \
+            "s_and_b64 s[98:99], vcc, s[96:97]\n" \
+            "s_cbranch_scc0 " QR_RUN_INS "\n"               /* every ray that is on starts inside the sphere: handed out, nobody ruled out */ \
+            "v_mul_f32 %[t3], %[t0], %[dx]\n" \
+            "v_fmac_f32 %[t3], %[t1], %[dy]\n" \
+            "v_fmac_f32 %[t3], %[t2], %[dz]\n" \
+            "v_mul_f32_e64 %[t1], s95, s95\n" \
+            "v_sub_f32 %[t0], %[t4], %[t1]\n" \
+            "v_mul_f32_e64 %[t1], %[t3], |%[t3]|\n" \
+            "v_fmac_f32 %[t1], %[t4], %[dde]\n" \
+            "v_mul_f32 %[t0], %[dd], %[t0]\n" \
+            "v_fma_f32 %[t2], -s95, %[dlen], %[t3]\n" \
+            "v_cmp_lt_f32 vcc, %[t1], %[t0]\n" \
+            "s_and_b64 s[98:99], s[98:99], vcc\n" \
+            "v_cmp_gt_f32 vcc, %[t2], %[tbd]\n" \
+            "s_or_b64 vcc, vcc, s[98:99]\n" \
+            "s_mov_b64 %[am], vcc\n"                         /* the verdict per ray travels with a cell that is handed out */ \
+            "v_cmp_ne_u32 s[98:99], s89, %[osrf]\n" \
+            "s_and_b64 vcc, vcc, s[98:99]\n" \
+            "s_andn2_b64 s[98:99], s[96:97], vcc\n"          /* rays that are on and not provably missed (or whose own surface it is) */ \
+            "s_cbranch_scc1 qr_cull_out_%=\n" \
+            QR_RUN_NJ_ASM \
+            "s_mov_b32 %[pos], s90\n"                       /* the array's end */ \
+            "s_branch qr_cull_top_%=\n" \
+            QR_RUN_INS_ASM
+#else
+#define QR_RUN_NJ_OP
+#define QR_RUN_LEAVE "qr_cull_out_%="
+#define QR_RUN_ARRAY
+#endif
+
+#ifdef QR_STATS
+struct ArrJumps { u32 jump, jwait, jend, ins; };    /* arrays jumped in the run; of them with rays waiting / onto the END cell; all-inside exits */
+#endif
+
 template <bool BOXC>
 __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray &r, const WalkState &w,
-                                         float idx, float idy, float idz, float nox, float noy, float noz, float dd, float dde, float dlen)
+                                         float idx, float idy, float idz, float nox, float noy, float noz, float dd, float dde, float dlen
+#if QR_BVSPH_ACT
+                                         , lm_t &amiss
+#endif
+#if QR_BVSPH_ACT && defined(QR_STATS)
+                                         , ArrJumps &nj
+#endif
+                                         )
 {
     unsigned long long c01, c23, c45, c67;
     float t0, t1, t2, t3, t4, t5, t6;
     const float tb1 = w.tbuf * 1.00001f;
     u32 cur = __builtin_amdgcn_readfirstlane(pos);           /* wave-uniform by construction; says so to the compiler */
+#if QR_BVSPH_ACT
+    unsigned long long am;                                   /* written on the array path only, read only for an array cell */
+#endif
+#if QR_BVSPH_ACT && defined(QR_STATS)
+    ArrJumps njl = {0, 0, 0, 0};                             /* this run's counts, in SGPRs of their own */
+#endif
     if constexpr (BOXC)
     {
         asm volatile(
@@ -750,7 +873,7 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
             "s_waitcnt lgkmcnt(0)\n"
             "s_and_b32 s96, s88, 40\n"                      /* QR_OPF_CULL | QR_OPT_BV */
             "s_cmp_lg_u32 s96, 32\n"
-            "s_cbranch_scc1 qr_cull_out_%=\n"
+            "s_cbranch_scc1 " QR_RUN_LEAVE "\n"
             "s_bitcmp0_b32 s88, 19\n"                       /* QR_OPF_BOX */
             "s_cbranch_scc1 qr_cull_sph_%=\n"
             "v_fma_f32 %[t0], s90, %[idx], %[nox]\n"
@@ -799,13 +922,14 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
             "s_and_b64 vcc, vcc, s[96:97]\n"
             "s_or_b64 vcc, vcc, s[98:99]\n"
             "s_branch qr_cull_tst_%=\n"
+            QR_RUN_ARRAY
             "qr_cull_out_%=:\n"
             "s_mov_b64 %[c01], s[88:89]\n"
             "s_mov_b64 %[c23], s[90:91]\n"
             "s_mov_b64 %[c45], s[92:93]\n"
             "s_mov_b64 %[c67], s[94:95]\n"
             : [c01] "=&s"(c01), [c23] "=&s"(c23), [c45] "=&s"(c45), [c67] "=&s"(c67), [pos] "+s"(cur),
-              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6)
+              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6) QR_RUN_NJ_OP
             : [B] "s"(B), [idx] "v"(idx), [idy] "v"(idy), [idz] "v"(idz), [nox] "v"(nox), [noy] "v"(noy), [noz] "v"(noz), [tb1] "v"(tb1),
               [ox] "v"(r.org.x), [oy] "v"(r.org.y), [oz] "v"(r.org.z), [dx] "v"(r.dir.x), [dy] "v"(r.dir.y), [dz] "v"(r.dir.z),
               [dd] "v"(dd), [dde] "v"(dde), [dlen] "v"(dlen), [tbd] "v"(w.tbd), [res] "v"(w.resume), [osrf] "v"(r.osrf)
@@ -820,7 +944,7 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
             "s_waitcnt lgkmcnt(0)\n"
             "s_and_b32 s96, s88, 0x80028\n"                 /* QR_OPF_CULL | QR_OPT_BV | QR_OPF_BOX: a box cell is not culled here */
             "s_cmp_lg_u32 s96, 32\n"
-            "s_cbranch_scc1 qr_cull_out_%=\n"
+            "s_cbranch_scc1 " QR_RUN_LEAVE "\n"
             "v_sub_f32 %[t0], s92, %[ox]\n"
             "v_sub_f32 %[t1], s93, %[oy]\n"
             "v_sub_f32 %[t2], s94, %[oz]\n"
@@ -847,19 +971,26 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
             "s_cbranch_scc1 qr_cull_out_%=\n"
             "s_add_u32 %[pos], %[pos], 32\n"
             "s_branch qr_cull_top_%=\n"
+            QR_RUN_ARRAY
             "qr_cull_out_%=:\n"
             "s_mov_b64 %[c01], s[88:89]\n"
             "s_mov_b64 %[c23], s[90:91]\n"
             "s_mov_b64 %[c45], s[92:93]\n"
             "s_mov_b64 %[c67], s[94:95]\n"
             : [c01] "=&s"(c01), [c23] "=&s"(c23), [c45] "=&s"(c45), [c67] "=&s"(c67), [pos] "+s"(cur),
-              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4)
+              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4) QR_RUN_NJ_OP
             : [B] "s"(B),
               [ox] "v"(r.org.x), [oy] "v"(r.org.y), [oz] "v"(r.org.z), [dx] "v"(r.dir.x), [dy] "v"(r.dir.y), [dz] "v"(r.dir.z),
               [dd] "v"(dd), [dde] "v"(dde), [dlen] "v"(dlen), [tbd] "v"(w.tbd), [res] "v"(w.resume), [osrf] "v"(r.osrf)
             : "vcc", "scc", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99");
     }
     pos = cur;
+#if QR_BVSPH_ACT
+    amiss = am;
+#endif
+#if QR_BVSPH_ACT && defined(QR_STATS)
+    nj.jump += njl.jump; nj.jwait += njl.jwait; nj.jend += njl.jend; nj.ins += njl.ins;
+#endif
     c.s0 = (u32)c01; c.s1 = (u32)(c01 >> 32); c.s2 = (u32)c23; c.s3 = (u32)(c23 >> 32);
     c.s4 = (u32)c45; c.s5 = (u32)(c45 >> 32); c.s6 = (u32)c67; c.s7 = (u32)(c67 >> 32);
 }
@@ -903,6 +1034,17 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
     QR_CULL_FLOPS((BOXC && (c_frm(B)->img_flags & QR_IMG_BOXES)) ? 15 : 9);
 #ifdef QR_STATS
     unsigned long long st_iter = 0, st_lanes = 0, st_skip = 0;
+    /* arrays with a cull sphere: handed out, of them with rays already occluded / waiting at an enclosing array's end / out of reach
+     * for every ray that is on; handed out with some rays ruled out sideways while others go on, and those rays; jumped in the run */
+    u32 st_arr = 0, st_aocc = 0, st_await = 0, st_part = 0, st_plan = 0;
+    ArrJumps st_jump = {0, 0, 0, 0};
+#endif
+#ifdef QR_PROF
+    bool tn_open = false;               /* profiles/r22_array_cull.txt: trnode ranges that end without a member handed out */
+#endif
+#ifdef QR_PROF_BVSPH_DRY
+    constexpr int PA = SHADOW ? 50 : 56;    /* ... and what the array cut would decide, per walk kind */
+    lm_t qr_arr_side = 0;
 #endif
     for (;;)
     {
@@ -918,6 +1060,9 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
          * the walk's only cell load.
          */
         u32x8 c;
+#if QR_BVSPH_ACT
+        lm_t arr_miss = 0;                      /* an array handed out by the run: the rays its cull sphere rules out */
+#endif
         if constexpr (NOCULL)
         {
             QR_GUARD_POS(1, pos, head, return);
@@ -930,7 +1075,14 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
          * instructions -- and the cursor is checked before the run loads its first cell and when it hands a cell out (the
          * statistics of culled cells are not kept in that build) */
         QR_GUARD_POS(1, pos, head, return);
-        cull_run<BOXC>(B, pos, c, r, w, idx, idy, idz, nox, noy, noz, dd, dde, dlen);
+        cull_run<BOXC>(B, pos, c, r, w, idx, idy, idz, nox, noy, noz, dd, dde, dlen
+#if QR_BVSPH_ACT
+                       , arr_miss
+#endif
+#if QR_BVSPH_ACT && defined(QR_STATS)
+                       , st_jump
+#endif
+                       );
         QR_GUARD_POS(4, pos, head, return);
 #else
         for (;;)
@@ -944,8 +1096,21 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
 #endif
             c = *(const QR_CONST u32x8 *)(B + pos);
             QR_PROF_HIT(16);            /* cells loaded by packet walks */
+#ifdef QR_PROF
+            /* a solver cell outside the node's space ends the range of the trnode cell before it */
+            if (tn_open && (c.s0 & QR_OPT_SOLVER) && !(c.s0 & QR_OPF_CACHED)) { QR_PROF_HIT(63); tn_open = false; }
+#endif
+#if QR_BVSPH_ACT
+            /* an array with a cull sphere stays in the run (see QR_RUN_ARRAY): the sphere test with R2 and 1.01 R2 made here, and a
+             * step to the array's end */
+            const bool is_arr = (c.s0 & (QR_OPF_CULL | QR_OPT_BV)) == (QR_OPF_CULL | QR_OPT_BV);
+            if (!is_arr && (c.s0 & (QR_OPF_CULL | QR_OPT_BV | (BOXC ? 0u : QR_OPF_BOX))) != QR_OPF_CULL) break;
+#else
+            const bool is_arr = false;
             if ((c.s0 & (QR_OPF_CULL | QR_OPT_BV | (BOXC ? 0u : QR_OPF_BOX))) != QR_OPF_CULL) break;
+#endif
             lm_t miss;
+            bool inside_all = false;            /* an array, and every ray that is on starts inside its sphere */
             if (BOXC && (c.s0 & QR_OPF_BOX))
             {
                 /* axis-aligned box {lo, hi} of the surface's visible part (inflated at upload, far above the rounding here):
@@ -963,19 +1128,42 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
             else
             {
                 QR_CULL_FLOPS(20);
-                const float R = u2f(c.s7), R2 = u2f(c.s2), R2x = u2f(c.s3);
+                const float R = u2f(c.s7), R2 = is_arr ? R * R : u2f(c.s2), R2x = is_arr ? 1.01f * R2 : u2f(c.s3);
                 const float ocx = u2f(c.s4) - r.org.x, ocy = u2f(c.s5) - r.org.y, ocz = u2f(c.s6) - r.org.z;
                 const float b = __builtin_fmaf(ocz, r.dir.z, __builtin_fmaf(ocy, r.dir.y, ocx * r.dir.x));
                 const float oc2 = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, ocx * ocx));
                 const float q = oc2 - R2;
                 miss = (LM(oc2 > R2x) & LM(__builtin_fmaf(oc2, dde, b * __builtin_fabsf(b)) < dd * q))
                      | LM(__builtin_fmaf(-R, dlen, b) > w.tbd);
+                inside_all = is_arr && (LM(w.resume <= pos) & LM(oc2 > R2x)) == 0;
             }
             const lm_t need = LM(w.resume <= pos) & ~(miss & LM(c.s1 != r.osrf));
 #ifdef QR_STATS
-            st_iter++; st_lanes += __popcll(LM(w.resume <= pos));
+            if (!is_arr) { st_iter++; st_lanes += __popcll(LM(w.resume <= pos)); }     /* an array is counted where it is handed out or jumped */
+#endif
+#if QR_BVSPH_ACT
+            /* as the written-out run: handed out with nobody ruled out when every ray that is on starts inside (or none is on: the
+             * hand-out path then steps to the array's end) */
+            if (is_arr) arr_miss = inside_all ? 0 : miss;
+            if (inside_all)
+            {
+#ifdef QR_STATS
+                if (LM(w.resume <= pos) != 0) st_jump.ins++;
+#endif
+                break;
+            }
 #endif
             if (need != 0) break;
+            if (is_arr)
+            {
+#ifdef QR_STATS
+                st_iter++; st_lanes += __popcll(LM(w.resume <= pos)); st_jump.jump++;
+                if (LM(w.resume > pos && w.resume != 0xFFFFFFFFu) != 0) st_jump.jwait++;
+                if (*(const QR_CONST u32 *)(B + c.s2) == 0) st_jump.jend++;
+#endif
+                pos = __builtin_amdgcn_readfirstlane(c.s2);
+                continue;
+            }
             QR_PROF_HIT(17);            /* culled without looking at the surface */
 #ifdef QR_STATS
             st_skip++;
@@ -985,6 +1173,12 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
 #endif
         }
         const u32 op = c.s0;
+#ifdef QR_PROF
+        if (tn_open && (op == 0 || (op & QR_OPT_TRNODE))) { QR_PROF_HIT(63); tn_open = false; }     /* the list or the next node ends the range */
+#endif
+#ifdef QR_PROF_BVSPH_DRY
+        qr_arr_side = 0;
+#endif
         if (op == 0) break;
         const u32 srf_off = c.s1;
         const lm_t on = LM(w.resume <= pos);
@@ -994,6 +1188,26 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
         if (!((op & (QR_OPF_CULL | QR_OPT_BV)) == QR_OPF_CULL)) { st_iter++; st_lanes += __popcll(on); }
 #endif
         lm_t far = 0;                           /* bounding volume: lanes for which the whole array is out of reach */
+#if QR_BVSPH_ACT
+        if ((op & (QR_OPF_CULL | QR_OPT_BV)) == (QR_OPF_CULL | QR_OPT_BV) && !NOCULL)
+        {
+            /* the run has tested the array's own conservative sphere (qr_compile.cpp) for every ray and hands its verdict out with
+             * the cell: passed sideways or behind the origin, or entirely beyond the current depth bound -> nothing inside can be
+             * hit by this ray: treated as a miss of the volume.  Such a ray stays out of the volume's space and test and waits at
+             * the array's end.  (Testing it here again cost the swarm 3 % of its frame time, profiles/r22_array_cull.txt.) */
+            far = on & arr_miss;
+#ifdef QR_STATS
+            st_arr++;
+            if (far != 0 && (on & ~far) != 0) { st_part++; st_plan += __popcll(far); }
+            if (LM(w.resume == 0xFFFFFFFFu) != 0) st_aocc++;                    /* ... reached with rays already occluded */
+            if (LM(w.resume > pos && w.resume != 0xFFFFFFFFu) != 0) st_await++;  /* ... with rays waiting at an enclosing array's end */
+#endif
+            if (far != 0) { if (lane_of(far)) w.resume = c.s2; }
+            full = (on & ~far) != 0;
+        }
+        /* the walk without culls: as before the cut, an array with a sphere is entered when some ray is on */
+        else if ((op & (QR_OPF_CULL | QR_OPT_BV)) == (QR_OPF_CULL | QR_OPT_BV)) full = on != 0;
+#else
         if ((op & (QR_OPF_CULL | QR_OPT_BV)) == (QR_OPF_CULL | QR_OPT_BV))
         {
             /* the array's own conservative sphere (qr_compile.cpp): entirely behind the origin, or entirely beyond
@@ -1002,15 +1216,34 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
             const float ocx = u2f(c.s4) - r.org.x, ocy = u2f(c.s5) - r.org.y, ocz = u2f(c.s6) - r.org.z;
             const float b = __builtin_fmaf(ocz, r.dir.z, __builtin_fmaf(ocy, r.dir.y, ocx * r.dir.x));
             if constexpr (!NOCULL) far = on & (LM(__builtin_fmaf(R, dlen, b) < 0.0f) | LM(__builtin_fmaf(-R, dlen, b) > w.tbd));
+#ifdef QR_PROF_BVSPH_DRY
+            if constexpr (!NOCULL)
+            {
+                /* the rays that the solver cells' sphere test would rule out besides: counted below, not acted on */
+                const float R2 = R * R, R2x = 1.01f * R2;
+                const float oc2 = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, ocx * ocx));
+                qr_arr_side = on & ~far & LM(oc2 > R2x) & LM(__builtin_fmaf(oc2, dde, b * __builtin_fabsf(b)) < dd * (oc2 - R2));
+            }
+#endif
+#ifdef QR_STATS
+            st_arr++;
+#endif
             if (far != 0) { if (lane_of(far)) w.resume = c.s2; }
             full = (on & ~far) != 0;
         }
+#endif
+#ifdef QR_PROF_BVSPH_DRY
+        if (op & QR_OPT_BV) { QR_PROF_HIT(PA + 0); if (!full) QR_PROF_HIT(PA + 1); }      /* (a) array cells reached, (b) left by `far` */
+#endif
 
         if (full)
         {
             if (op & QR_OPT_TRNODE)
             {
                 QR_PROF_HIT(20);
+#ifdef QR_PROF
+                QR_PROF_HIT(62); tn_open = true;
+#endif
                 QR_FLOPS_M(3 + ((op & QR_OPF_FULLM) ? 30 : 6), __popcll(on));
                 /* array element with a transform: diff and ray in its space, cached for the surfaces behind it */
                 if (lane_of(on))
@@ -1038,6 +1271,14 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
                  * (tracer.cpp:4040-4054); rays that were off already wait for the end of an enclosing array,
                  * which lies at or behind this array's end (arrays nest, qr_compile.cpp) */
                 if (LM(w.resume <= pos) == 0) next = c.s2;
+#ifdef QR_PROF_BVSPH_DRY
+                {
+                    const bool nobody = LM(w.resume <= pos) == 0, sph_all = (on & ~far & ~qr_arr_side) == 0;
+                    if (nobody) QR_PROF_HIT(PA + 2);                                /* (c) the volume test run, no lane enters */
+                    if (sph_all) { QR_PROF_HIT(PA + 3); if (nobody) QR_PROF_HIT(PA + 5); }     /* (d) the sphere alone decides for the wave; of them in (c) */
+                    else if (qr_arr_side != 0) QR_PROF_ADD(PA + 4, __popcll(qr_arr_side));     /* (e) lanes ruled out while others go on */
+                }
+#endif
             }
             else
             {
@@ -1045,6 +1286,9 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
                 ld_surf(B, srf_off, s);
 #ifdef QR_WAVETIME
                 if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) qr_wt_cells[SHADOW ? 3 : 2]++;
+#endif
+#ifdef QR_PROF
+                if (op & QR_OPF_CACHED) tn_open = false;              /* a member of the node's range is handed out */
 #endif
                 if (lane_of(on)) solve_cell<SHADOW, false>(B, op, srf_off, s, r, dd, w, h);
                 if (SHADOW)
@@ -1065,6 +1309,15 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
         atomicAdd(&stats[b + 1], st_iter);
         atomicAdd(&stats[b + 2], st_lanes);
         atomicAdd(&stats[12 + b / 3], st_skip);
+        if (st_arr | st_jump.jump)
+        {
+            const int a = 32 + 3 * b;           /* nine counters per kind of walk: shadow, primary, secondary (rays that start on a surface) */
+            atomicAdd(&stats[a + 0], (unsigned long long)st_arr);        atomicAdd(&stats[a + 1], (unsigned long long)st_jump.jump);
+            atomicAdd(&stats[a + 2], (unsigned long long)st_jump.jwait); atomicAdd(&stats[a + 3], (unsigned long long)st_jump.jend);
+            atomicAdd(&stats[a + 4], (unsigned long long)st_jump.ins);   atomicAdd(&stats[a + 5], (unsigned long long)st_part);
+            atomicAdd(&stats[a + 6], (unsigned long long)st_plan);       atomicAdd(&stats[a + 7], (unsigned long long)st_aocc);
+            atomicAdd(&stats[a + 8], (unsigned long long)st_await);
+        }
     }
 #endif
 }
