@@ -10,6 +10,8 @@ no CPU fallback: without the shared library or without a GPU these calls raise.
 """
 import ctypes
 import gzip
+import math
+import numbers
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -128,45 +130,34 @@ def lib():
     L.qr_scene_destroy.argtypes = [vp]
     L.qr_program_stats.argtypes = [vp, cu64, ctypes.POINTER(ProgramInfo)]
     L.qr_program_stats_ex.argtypes = [vp, cu64, ctypes.c_uint32, ctypes.POINTER(ProgramInfo)]
-    L.qr_trace_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
-    L.qr_occluded_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
-    L.qr_shade_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
-    L.qr_render_views_async.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, ctypes.c_uint32, vp]
-    L.qr_render_views_mean_async.argtypes = [vp, vp, ci, ci, ci, vp, vp, ctypes.c_float, ctypes.c_uint32, vp]
-    L.qr_pt_views_state_bytes.argtypes = [vp, ci, ci, ci, ctypes.POINTER(cu64)]
-    L.qr_pt_views_reset.argtypes = [vp, ci, ci, ci, vp]
-    L.qr_pt_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.c_uint32, vp]
-    L.qr_pt_rays_state_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
-    L.qr_pt_rays_reset.argtypes = [vp, ctypes.c_int64, vp]
-    L.qr_pt_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ci, ci, vp, ctypes.c_uint32, vp]
-    L.qr_pt_adapt_state_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
-    L.qr_pt_adapt_reset.argtypes = [vp, ctypes.c_int64, vp]
-    L.qr_pt_adapt_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ci, ci, ci, ctypes.c_float, vp, vp, ctypes.c_uint32, vp]
-    L.qr_pt_adapt_views_state_bytes.argtypes = [vp, ci, ci, ci, ctypes.POINTER(cu64)]
-    L.qr_pt_adapt_views_reset.argtypes = [vp, ci, ci, ci, vp]
-    L.qr_pt_adapt_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, ctypes.c_float, vp, vp, vp, vp, ctypes.c_uint32, vp]
-    L.qr_pt_adapt_list_work_bytes.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(cu64)]
-    L.qr_pt_adapt_open_list_async.argtypes = [vp, vp, ctypes.c_int64, ci, ci, ctypes.c_float, vp, vp, vp, ctypes.c_uint32, vp]
-    L.qr_pt_adapt_list_rays_async.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, ci, ci, ci, ctypes.c_float,
-                                              vp, vp, ctypes.c_uint32, vp]
-    L.qr_hit_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
-    L.qr_hit_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_uint32, vp]
-    cf = ctypes.c_float
-    L.qr_fan_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
-    L.qr_fan_hits_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
-    L.qr_fan_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
-    L.qr_gather_rays_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
-    L.qr_gather_hits_async.argtypes = [vp, vp, ctypes.c_int64, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
-    L.qr_gather_views_async.argtypes = [vp, vp, ci, ci, ci, vp, ci, cf, cf, vp, vp, ctypes.c_uint32, vp]
-    # the framed fans: the matching call's list with the spin plane after k
-    for name in ("qr_fan_rays", "qr_fan_hits", "qr_gather_rays", "qr_gather_hits"):
-        getattr(L, name + "_framed_async").argtypes = [vp, vp, ctypes.c_int64, vp, ci, vp, cf, cf, vp, vp, ctypes.c_uint32, vp]
-    for name in ("qr_fan_views", "qr_gather_views"):
-        getattr(L, name + "_framed_async").argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, cf, cf, vp, vp, ctypes.c_uint32, vp]
+    # the ray API: a call's list is a head -- (scene, rays or records, n) or (scene, views, n_views, width, height) --, what is
+    # its own, and the tail (flags, stream)
+    i64, u32, cf = ctypes.c_int64, ctypes.c_uint32, ctypes.c_float
+    rays, views = [vp, vp, i64], [vp, vp, ci, ci, ci]
+    ray_api = {
+        "qr_trace_rays": rays + [vp, vp], "qr_occluded": rays + [vp], "qr_shade_rays": rays + [vp, vp],
+        "qr_render_views": views + [vp, vp, vp], "qr_render_views_mean": views + [vp, vp, cf],
+        "qr_pt_views": views + [vp, ci, ci, vp, vp],
+        "qr_pt_adapt_views": views + [vp, ci, ci, ci, cf, vp, vp, vp, vp], "qr_pt_adapt_views_variance": views + [cf, vp],
+        "qr_pt_adapt_open_list": rays + [ci, ci, cf, vp, vp, vp],
+        "qr_hit_rays": rays + [vp], "qr_hit_views": views + [vp],
+        "qr_layer_rays": rays + [ci, vp, vp, vp, vp], "qr_layer_views": views + [ci, vp, vp, vp, vp],
+    }
+    for src, head in (("rays", rays), ("hits", rays), ("views", views)):
+        for kind in ("fan", "gather"):
+            ray_api[f"qr_{kind}_{src}"] = head + [vp, ci, cf, cf, vp, vp]
+            ray_api[f"qr_{kind}_{src}_framed"] = head + [vp, ci, vp, cf, cf, vp, vp]       # the spin plane after k
+    for name, args in ray_api.items():
+        getattr(L, name + "_async").argtypes = args + [u32, vp]
+    # rays and spread in front of n; the state queries and resets have neither flags nor a stream
+    L.qr_pt_rays_async.argtypes = [vp, vp, vp, i64, vp, ci, ci, vp, u32, vp]
+    L.qr_pt_adapt_rays_async.argtypes = [vp, vp, vp, i64, vp, ci, ci, ci, cf, vp, vp, u32, vp]
+    L.qr_pt_adapt_list_rays_async.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, ci, ci, ci, cf, vp, vp, u32, vp]
+    for name, head in (("qr_pt_views", views[2:]), ("qr_pt_adapt_views", views[2:]), ("qr_pt_rays", [i64]), ("qr_pt_adapt", [i64])):
+        getattr(L, name + "_state_bytes").argtypes = [vp] + head + [ctypes.POINTER(cu64)]
+        getattr(L, name + "_reset").argtypes = [vp] + head + [vp]
+    L.qr_pt_adapt_list_work_bytes.argtypes = [vp, i64, ctypes.POINTER(cu64)]
     L.qr_atrous_views_async.argtypes = [vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(AtrousParams), vp, vp, vp]
-    L.qr_pt_adapt_views_variance_async.argtypes = [vp, vp, ci, ci, ci, cf, vp, ctypes.c_uint32, vp]
-    L.qr_layer_rays_async.argtypes = [vp, vp, ctypes.c_int64, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
-    L.qr_layer_views_async.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_uint32, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
     L.qr_frame_hash.argtypes = [vp, cu64]
@@ -195,6 +186,111 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise QrError(f"qrhip error {rc}: {lib().qr_last_error().decode()}")
+
+
+# ---- the binding's glue: every tensor check, output rule and argument rule is stated once ----
+
+# what the helpers need of torch, by dtype name and by device index, looked up once: torch is imported lazily
+_DTYPES, _DEVICES = {}, {}
+
+
+def _dtypes(name):
+    """(torch.Tensor, the torch dtypes a name such as "float32" or "int32 or uint32" stands for); a torch without uint32 takes
+    int32 for it"""
+    import torch
+    found = tuple(getattr(torch, d, torch.int32) if d == "uint32" else getattr(torch, d) for d in name.split(" or "))
+    dt = _DTYPES[name] = (torch.Tensor, found)
+    return dt
+
+
+def _ptr(t):
+    """what a c_void_p slot takes for a tensor: its address, None for None"""
+    return None if t is None else t.data_ptr()
+
+
+def _fits(t, dtype, shape, dev=None, contiguous=True):
+    """The residency predicate: is t a tensor of `dtype` (see _dtypes) and `shape`, contiguous, on cuda:dev?  In a shape None
+    stands for any size and a leading ... for any number of dimensions, at least one; no shape at all: any.  dev=None asks
+    for dtype and shape alone, dtype=None (of a tensor known to be one) for contiguity and device alone.  One function and
+    the exact shape first: it runs several times in every call of the ray API."""
+    if dtype is not None:
+        tensor, dtypes = _DTYPES.get(dtype) or _dtypes(dtype)
+        if not (isinstance(t, tensor) and t.dtype in dtypes):
+            return False
+        got = t.shape
+        if not (got == shape or shape is None):
+            if shape[0] is ...:
+                if not (len(got) >= len(shape) and got[1 - len(shape):] == shape[1:]):
+                    return False
+            elif len(got) != len(shape):
+                return False
+            else:
+                for want, have in zip(shape, got):
+                    if want is not None and want != have:
+                        return False
+    return dev is None or ((t.is_contiguous() or not contiguous) and t.is_cuda and t.device.index == dev)
+
+
+def _need(name, t, dtype, shape, dev, lead="a", suffix="", error=QrError):
+    """t when it fits, else the refusal, built from the same parts"""
+    if _fits(t, dtype, shape, dev):
+        return t
+    label = "[" + ", ".join("N" if s is None else "..." if s is ... else str(s) for s in shape) + "]"
+    raise error(f"{name} must be {lead} contiguous {dtype} {label} tensor on cuda:{dev}{suffix}")
+
+
+def _device(dev):
+    """(torch.empty, the device cuda:dev)"""
+    import torch
+    made = _DEVICES[dev] = (torch.empty, torch.device("cuda", dev))
+    return made
+
+
+def _new(dtype, shape, dev):
+    empty, device = _DEVICES.get(dev) or _device(dev)
+    return empty(shape, dtype=(_DTYPES.get(dtype) or _dtypes(dtype))[1][0], device=device)
+
+
+def _fill(name, t, dtype, shape, dev):
+    """an output that is None (a new tensor: every element is written) or a tensor to fill"""
+    return _new(dtype, shape, dev) if t is None else _need(name, t, dtype, shape, dev)
+
+
+def _wanted(name, t, dtype, shape, dev):
+    """an output that is True (a new tensor), False or None (not wanted: None) or a tensor to fill"""
+    if t is True:
+        return _new(dtype, shape, dev)
+    if t is False or t is None:
+        return None
+    return _need(name, t, dtype, shape, dev, lead="True, False or a")
+
+
+_FAN_FNS = {}       # (fan | gather, rays | hits | views, plain) -> the library's entry point, looked up once
+
+
+def _fan_fn(what, kind, plain):
+    """qr_{fan|gather}_{rays|hits|views}{_framed}_async"""
+    fn = _FAN_FNS[what, kind, plain] = getattr(lib(), f"qr_{what}_{kind}{'' if plain else '_framed'}_async")
+    return fn
+
+
+def _dirs_arg(dirs, eps, reach, pad, dev):
+    """(dirs as a contiguous float32 [K, 4] tensor, K, eps, reach) of a fan call; a [K, 3] table gets `pad` in column 3.
+    dirs need not be contiguous: they are made so"""
+    if not (_fits(dirs, "float32", (None, None), dev, contiguous=False) and dirs.shape[1] in (3, 4)):
+        raise QrError(f"dirs must be a float32 [K, 3] or [K, 4] tensor on cuda:{dev}")
+    k = dirs.shape[0]
+    if not 1 <= k <= FAN_MAX_DIRS:
+        raise QrError(f"dirs must hold 1..{FAN_MAX_DIRS} directions, got {k}")
+    if eps is None or math.isnan(eps) or math.isnan(reach):
+        raise QrError("eps (the step off the surface, in units of |dir|) is required; eps and reach must not be NaN")
+    if dirs.shape[1] == 3:
+        import torch
+        d4 = torch.full((k, 4), pad, dtype=torch.float32, device=dirs.device)
+        d4[:, 0:3] = dirs
+    else:
+        d4 = dirs.contiguous()
+    return d4, k, float(eps), float(reach)
 
 
 def read_snapshot(path):
@@ -426,43 +522,61 @@ class Scene:
             frame = self.new_frame()
         sp = self._stream_ptr(stream)
         if ids is None:
-            _check(lib().qr_render_async(self._h, ctypes.c_void_p(frame.data_ptr()), sp))
+            _check(lib().qr_render_async(self._h, frame.data_ptr(), sp))
         else:
-            _check(lib().qr_render_ids_async(self._h, ctypes.c_void_p(frame.data_ptr()),
-                                             ctypes.c_void_p(ids.data_ptr()), sp))
+            _check(lib().qr_render_ids_async(self._h, frame.data_ptr(), ids.data_ptr(), sp))
         return frame
 
+    # The three sources of the ray API: caller rays, caller views, caller hit records.  Each gives (kind, the head of the C
+    # argument list after the scene, the shape of the elements).
+
     def _rays_arg(self, rays):
-        import torch
-        if not (isinstance(rays, torch.Tensor) and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8
-                and rays.is_contiguous() and rays.is_cuda and rays.device.index == self.device):
-            raise QrError(f"rays must be a contiguous float32 [N, 8] tensor on cuda:{self.device} "
-                          "(org xyz, tmin, dir xyz, tmax per row)")
-        return rays
+        return _need("rays", rays, "float32", (None, 8), self.device, suffix=" (org xyz, tmin, dir xyz, tmax per row)")
+
+    def _rays_src(self, rays):
+        n = self._rays_arg(rays).shape[0]
+        return "rays", (rays.data_ptr(), n), (n,)
+
+    def _views_src(self, views, width, height):
+        _need("views", views, "float32", (None, 16), self.device,
+              suffix=" (org xyz, t_min, dir xyz, t_max, hor xyz, 0, ver xyz, 0 per row)")
+        w = self.width if width is None else width
+        h = self.height if height is None else height
+        if not ((type(w) is int or isinstance(w, numbers.Integral)) and (type(h) is int or isinstance(h, numbers.Integral))
+                and w >= 1 and h >= 1):                                     # a plain int first: the ABC test is the slow one
+            raise QrError("width and height must be positive integers")
+        n, w, h = views.shape[0], int(w), int(h)
+        return "views", (views.data_ptr(), n, w, h), (n, h, w)
+
+    def _hits_src(self, hits):
+        _need("hits", hits, "float32", (..., 12), self.device, suffix=" (qr_hit records)")
+        return "hits", (hits.data_ptr(), hits.numel() // 12), tuple(hits.shape[:-1])
+
+    def _rays_call(self, fn, rays, coherent, stream, *outs):
+        """one of the plain ray queries: `outs` are (dtype, the shape after [N]) or None for an output that is not wanted"""
+        _, head, shape = self._rays_src(rays)
+        outs = [o and _new(o[0], shape + o[1], self.device) for o in outs]
+        _check(fn(self._h, *head, *map(_ptr, outs), TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
+        return outs
+
+    def _hit_records(self, src, flags, stream):
+        kind, head, shape = src
+        out = _new("float32", shape + (12,), self.device)
+        _check(getattr(lib(), f"qr_hit_{kind}_async")(self._h, *head, out.data_ptr(), flags, self._stream_ptr(stream)))
+        return out
 
     def trace(self, rays, stream=None, coherent=False):
         """Closest hit of every ray (qr_trace_rays_async): rays float32 [N, 8] = (org xyz, tmin, dir xyz, tmax) on the scene's
         device.  Returns new tensors (t float32 [N]: t of the hit, tmax when none; ids int32 [N]: surface << 1 | side, -1 none).
         coherent: consecutive rays are neighbours (packet walks on long lists too).  Asynchronous on `stream`."""
-        import torch
-        rays = self._rays_arg(rays)
-        n = rays.shape[0]
-        t = torch.empty(n, dtype=torch.float32, device=rays.device)
-        ids = torch.empty(n, dtype=torch.int32, device=rays.device)
-        _check(lib().qr_trace_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(t.data_ptr()),
-                                         ctypes.c_void_p(ids.data_ptr()), TRACE_COHERENT if coherent else 0,
-                                         self._stream_ptr(stream)))
+        t, ids = self._rays_call(lib().qr_trace_rays_async, rays, coherent, stream, ("float32", ()), ("int32", ()))
         return t, ids
 
     def occluded(self, rays, stream=None, coherent=False):
         """Does a surface that casts a shadow (the renderer's rule) lie at tmin < t < tmax on each ray (qr_occluded_async)?
         Returns a new bool tensor [N].  Asynchronous on `stream`."""
         import torch
-        rays = self._rays_arg(rays)
-        n = rays.shape[0]
-        occ = torch.empty(n, dtype=torch.uint8, device=rays.device)
-        _check(lib().qr_occluded_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(occ.data_ptr()),
-                                       TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
+        occ, = self._rays_call(lib().qr_occluded_async, rays, coherent, stream, ("uint8", ()))
         return occ.view(torch.bool)
 
     def shade(self, rays, stream=None, coherent=False, ids=False):
@@ -470,14 +584,8 @@ class Scene:
         list, everything after it -- shadows, reflection and refraction to the scene's current depth (set_depth) -- is the
         renderer's.  Returns a new float32 [N, 3] tensor of linear colour, before the frame's output step (rays.pack_colors);
         with ids=True also the first hit's id (int32 [N], surface << 1 | side, -1 none).  Asynchronous on `stream`."""
-        import torch
-        rays = self._rays_arg(rays)
-        n = rays.shape[0]
-        rgb = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
-        hid = torch.empty(n, dtype=torch.int32, device=rays.device) if ids else None
-        _check(lib().qr_shade_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(rgb.data_ptr()),
-                                         ctypes.c_void_p(hid.data_ptr() if ids else None),
-                                         TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
+        rgb, hid = self._rays_call(lib().qr_shade_rays_async, rays, coherent, stream, ("float32", (3,)),
+                                   ("int32", ()) if ids else None)
         return (rgb, hid) if ids else rgb
 
     def hits(self, rays, stream=None, coherent=False):
@@ -487,26 +595,7 @@ class Scene:
         rays.hit_fields splits a record into typed views.  nrm: the world-space unit normal shading uses, facing the incoming
         ray; alb: the texture colour shading multiplies light by.  A miss has t = tmax, id = mat = -1 and zeros elsewhere.
         Nothing is lit: depth and path-tracer mode do not matter.  Asynchronous on `stream`."""
-        import torch
-        rays = self._rays_arg(rays)
-        n = rays.shape[0]
-        out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
-        _check(lib().qr_hit_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
-                                       TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
-        return out
-
-    def _views_arg(self, views, width, height):
-        import numbers
-        import torch
-        if not (isinstance(views, torch.Tensor) and views.dtype == torch.float32 and views.dim() == 2 and views.shape[1] == 16
-                and views.is_contiguous() and views.is_cuda and views.device.index == self.device):
-            raise QrError(f"views must be a contiguous float32 [N, 16] tensor on cuda:{self.device} "
-                          "(org xyz, t_min, dir xyz, t_max, hor xyz, 0, ver xyz, 0 per row)")
-        w = self.width if width is None else width
-        h = self.height if height is None else height
-        if not (isinstance(w, numbers.Integral) and isinstance(h, numbers.Integral) and w >= 1 and h >= 1):
-            raise QrError("width and height must be positive integers")
-        return int(w), int(h)
+        return self._hit_records(self._rays_src(rays), TRACE_COHERENT if coherent else 0, stream)
 
     def view_hits(self, views, width=None, height=None, stream=None):
         """Hit records of whole frames (qr_hit_views_async): a G-buffer -- position, normal, albedo, ids, materials, depth --
@@ -514,41 +603,27 @@ class Scene:
         it traces (rays.view_rays(view, width, height, blob, sample=0): with FSAA the record is sample 0's, as its ids and
         depth are).  Returns a new float32 [N, H, W, 12] tensor of qr_hit records (see hits(), rays.hit_fields); every pixel
         of every view is written.  Asynchronous on `stream`."""
-        import torch
-        w, h = self._views_arg(views, width, height)
-        n = views.shape[0]
-        out = torch.empty((n, h, w, 12), dtype=torch.float32, device=views.device)
-        _check(lib().qr_hit_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(out.data_ptr()),
-                                        0, self._stream_ptr(stream)))
-        return out
+        return self._hit_records(self._views_src(views, width, height), 0, stream)
 
     def _atrous_args(self, colour, hits, variance, out, variance_out):
         """the tensors of atrous() / denoise(): dtype and shape first, then contiguity and device.  Returns (n, h, w, channels)."""
-        import torch
-        dev = self.device
-
-        def resident(t):
-            return t.is_contiguous() and t.is_cuda and t.device.index == dev
-        if not (isinstance(colour, torch.Tensor) and colour.dtype == torch.float32 and colour.dim() == 4 and colour.shape[3] in (3, 4)
-                and min(colour.shape) >= 1):
+        if not (_fits(colour, "float32", (None, None, None, None)) and colour.shape[3] in (3, 4) and min(colour.shape) >= 1):
             raise QrError("colour must be a float32 [N, H, W, 3] or [N, H, W, 4] tensor")
         n, h, w, ch = (int(x) for x in colour.shape)
-        if not (isinstance(hits, torch.Tensor) and hits.dtype == torch.float32 and tuple(hits.shape) == (n, h, w, 12)):
+        if not _fits(hits, "float32", (n, h, w, 12)):
             raise QrError(f"hits must be a float32 [{n}, {h}, {w}, 12] tensor of qr_hit records (view_hits)")
-        if variance is not None and not (isinstance(variance, torch.Tensor) and variance.dtype == torch.float32
-                                         and tuple(variance.shape) == (n, h, w)):
+        if variance is not None and not _fits(variance, "float32", (n, h, w)):
             raise QrError(f"variance must be None or a float32 [{n}, {h}, {w}] tensor")
-        if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == (n, h, w, ch)):
+        if out is not None and not _fits(out, "float32", (n, h, w, ch)):
             raise QrError(f"out must be None or a float32 [{n}, {h}, {w}, {ch}] tensor")
         if variance_out is not None:
             if variance is None:
                 raise QrError("variance_out needs a variance")
-            if not (isinstance(variance_out, torch.Tensor) and variance_out.dtype == torch.float32
-                    and tuple(variance_out.shape) == (n, h, w)):
+            if not _fits(variance_out, "float32", (n, h, w)):
                 raise QrError(f"variance_out must be None or a float32 [{n}, {h}, {w}] tensor")
         for t, what in ((colour, "colour"), (hits, "hits"), (variance, "variance"), (out, "out"), (variance_out, "variance_out")):
-            if t is not None and not resident(t):
-                raise QrError(f"{what} must be contiguous and on cuda:{dev}")
+            if t is not None and not _fits(t, None, None, self.device):
+                raise QrError(f"{what} must be contiguous and on cuda:{self.device}")
         return n, h, w, ch
 
     @staticmethod
@@ -563,12 +638,8 @@ class Scene:
         n, h, w, ch = dims
         flags, nsq, sz, sl2, el, af = stops
         p = AtrousParams(step, ch, nsq, flags, float(sz), float(sl2), float(el), float(af))
-        _check(lib().qr_atrous_views_async(self._h, ctypes.c_void_p(colour.data_ptr()),
-                                           ctypes.c_void_p(variance.data_ptr() if variance is not None else None),
-                                           ctypes.c_void_p(hits.data_ptr()), n, w, h, ctypes.byref(p),
-                                           ctypes.c_void_p(out.data_ptr()),
-                                           ctypes.c_void_p(variance_out.data_ptr() if variance_out is not None else None),
-                                           self._stream_ptr(stream)))
+        _check(lib().qr_atrous_views_async(self._h, _ptr(colour), _ptr(variance), _ptr(hits), n, w, h, ctypes.byref(p),
+                                           _ptr(out), _ptr(variance_out), self._stream_ptr(stream)))
 
     def atrous(self, colour, hits, variance=None, step=1, normal_power=128, plane=None, luma=None, luma_eps=1e-6, demodulate=False,
                modulate=False, albedo_floor=1 / 256, out=None, variance_out=None, stream=None):
@@ -581,7 +652,6 @@ class Scene:
         the output by it, albedo_floor the smallest albedo divided by.  The defaults are SVGF's customary starting points, not
         tuned.  out / variance_out: tensors to write, neither the inputs.  Returns colour_out, or (colour_out, variance_out) with
         a variance.  Asynchronous on `stream`."""
-        import numbers
         import torch
         stops = self._atrous_stops(normal_power=normal_power, plane=plane, luma=luma, luma_eps=luma_eps, demodulate=demodulate,
                                    modulate=modulate, albedo_floor=albedo_floor)
@@ -601,7 +671,6 @@ class Scene:
         writes colour or variance.  albedo=True divides by the albedo on the first pass and multiplies on the last.  stops:
         normal_power, plane, luma, luma_eps, albedo_floor as atrous() takes them.  Returns (colour, variance or None), new
         tensors."""
-        import numbers
         import torch
         stream = stops.pop("stream", None)
         if isinstance(passes, bool) or not isinstance(passes, numbers.Integral) or not 1 <= passes <= 7:
@@ -624,38 +693,41 @@ class Scene:
     def _fan_args(self, dirs, eps, reach, shape, mask):
         """(dirs as a contiguous float32 [K, 4] tensor, K, eps, reach, open, mask or None) of an occlusion-fan call whose
         elements have `shape`"""
-        import math
-        import torch
-        if not (isinstance(dirs, torch.Tensor) and dirs.dtype == torch.float32 and dirs.dim() == 2 and dirs.shape[1] in (3, 4)
-                and dirs.is_cuda and dirs.device.index == self.device):
-            raise QrError(f"dirs must be a float32 [K, 3] or [K, 4] tensor on cuda:{self.device}")
-        k = dirs.shape[0]
-        if not 1 <= k <= FAN_MAX_DIRS:
-            raise QrError(f"dirs must hold 1..{FAN_MAX_DIRS} directions, got {k}")
-        if eps is None or math.isnan(eps) or math.isnan(reach):
-            raise QrError("eps (the step off the surface, in units of |dir|) is required; eps and reach must not be NaN")
-        if dirs.shape[1] == 3:
-            d4 = torch.zeros((k, 4), dtype=torch.float32, device=dirs.device)
-            d4[:, 0:3] = dirs
-        else:
-            d4 = dirs.contiguous()
-        opn = torch.empty(shape, dtype=torch.int32, device=dirs.device)                 # every element is written
-        msk = torch.empty(((k + 31) // 32,) + tuple(shape), dtype=torch.int32, device=dirs.device) if mask else None
-        return d4, k, float(eps), float(reach), opn, msk
+        d4, k, eps, reach = _dirs_arg(dirs, eps, reach, 0.0, self.device)
+        opn = _new("int32", shape, self.device)                                         # every element is written
+        msk = _new("int32", ((k + 31) // 32,) + tuple(shape), self.device) if mask else None
+        return d4, k, eps, reach, opn, msk
 
     def _spin_arg(self, frame, spin, shape):
         """the spin plane of a framed fan call whose elements have `shape`, as a pointer (None: no spin); ValueError when it
         cannot be one"""
-        import torch
         if spin is None:
             return None
         if not frame:
             raise ValueError("spin needs frame=True: it turns the table about the normal of a framed fan")
-        want = tuple(shape) + (2,)
-        if not (isinstance(spin, torch.Tensor) and spin.dtype == torch.float32 and tuple(spin.shape) == want and spin.is_contiguous()
-                and spin.is_cuda and spin.device.index == self.device):
-            raise ValueError(f"spin must be a contiguous float32 {list(want)} tensor on cuda:{self.device}")
-        return ctypes.c_void_p(spin.data_ptr())
+        return _need("spin", spin, "float32", tuple(shape) + (2,), self.device, error=ValueError).data_ptr()
+
+    def _occlusion(self, src, dirs, eps, reach, flags, mask, stream, frame, spin):
+        """the occlusion fans of any source: its spin, dirs, K and eps checks in that order, then the launch (the spin plane
+        after k when framed)"""
+        kind, head, shape = src
+        sp = None if spin is None else self._spin_arg(frame, spin, shape)
+        d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, shape, mask)
+        fn = _FAN_FNS.get(("fan", kind, not frame)) or _fan_fn("fan", kind, not frame)
+        _check(fn(self._h, *head, d4.data_ptr(), k, *((sp,) if frame else ()), eps, reach, opn.data_ptr(), _ptr(msk), flags,
+                  self._stream_ptr(stream)))
+        return (opn, msk) if mask else opn
+
+    def _gather(self, src, dirs, eps, reach, flags, out, count, resume, stream, frame, spin):
+        """the gather fans of any source: its spin, resume, out, count, dirs, K and eps checks in that order, then the launch
+        (the spin plane after k when framed)"""
+        kind, head, shape = src
+        sp = None if spin is None else self._spin_arg(frame, spin, shape)
+        d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, shape, out, count, resume)
+        fn = _FAN_FNS.get(("gather", kind, not frame)) or _fan_fn("gather", kind, not frame)
+        _check(fn(self._h, *head, d4.data_ptr(), k, *((sp,) if frame else ()), eps, reach, out.data_ptr(), count.data_ptr(),
+                  flags, self._stream_ptr(stream)))
+        return out, count
 
     def occlusion(self, rays, dirs, eps, reach=float("inf"), flip=False, mask=False, coherent=False, stream=None, frame=False,
                   spin=None):
@@ -673,21 +745,8 @@ class Scene:
         0 < dirs[k, 2] (flip=True: always, mirrored where dirs[k, 2] < 0) and the point's frame is valid.  spin (needs frame):
         float32 [N, 2] = (cos, sin) of a turn of the table about the normal per element (rays.spins), on the scene's device,
         contiguous.  rays.fan_rays(frame=True) states the composition exactly."""
-        rays = self._rays_arg(rays)
-        n = rays.shape[0]
-        sp = self._spin_arg(frame, spin, (n,))
-        d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, (n,), mask)
-        if frame:
-            _check(lib().qr_fan_rays_framed_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, sp,
-                                                  eps, reach, ctypes.c_void_p(opn.data_ptr()),
-                                                  ctypes.c_void_p(msk.data_ptr() if mask else None),
-                                                  (TRACE_COHERENT if coherent else 0) | (FAN_FLIP if flip else 0),
-                                                  self._stream_ptr(stream)))
-            return (opn, msk) if mask else opn
-        _check(lib().qr_fan_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
-                                       ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
-                                       (TRACE_COHERENT if coherent else 0) | (FAN_FLIP if flip else 0), self._stream_ptr(stream)))
-        return (opn, msk) if mask else opn
+        flags = (TRACE_COHERENT if coherent else 0) | (FAN_FLIP if flip else 0)
+        return self._occlusion(self._rays_src(rays), dirs, eps, reach, flags, mask, stream, frame, spin)
 
     def view_occlusion(self, views, dirs, width=None, height=None, eps=None, reach=float("inf"), flip=False, mask=False, stream=None,
                        frame=False, spin=None):
@@ -696,20 +755,8 @@ class Scene:
         (sample 0's under FSAA) -- dirs, eps (required), reach, flip, mask as for occlusion().  Returns open int32 [N, H, W]
         (-1 where the pixel shows nothing), with mask=True (open, mask int32 [ceil(K / 32), N, H, W]).  Asynchronous on `stream`.
         frame, spin (float32 [N, H, W, 2]) as for occlusion() (qr_fan_views_framed_async)."""
-        w, h = self._views_arg(views, width, height)
-        n = views.shape[0]
-        sp = self._spin_arg(frame, spin, (n, h, w))
-        d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, (n, h, w), mask)
-        if frame:
-            _check(lib().qr_fan_views_framed_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k, sp,
-                                                   eps, reach, ctypes.c_void_p(opn.data_ptr()),
-                                                   ctypes.c_void_p(msk.data_ptr() if mask else None),
-                                                   FAN_FLIP if flip else 0, self._stream_ptr(stream)))
-            return (opn, msk) if mask else opn
-        _check(lib().qr_fan_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
-                                        ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
-                                        FAN_FLIP if flip else 0, self._stream_ptr(stream)))
-        return (opn, msk) if mask else opn
+        return self._occlusion(self._views_src(views, width, height), dirs, eps, reach, FAN_FLIP if flip else 0, mask, stream,
+                               frame, spin)
 
     def hit_occlusion(self, hits, dirs, eps, reach=float("inf"), flip=False, mask=False, stream=None, frame=False, spin=None):
         """Occlusion fans from caller-supplied hit records (qr_fan_hits_async): hits float32 [..., 12] on the scene's device,
@@ -718,55 +765,25 @@ class Scene:
         mask as for occlusion().  Returns open int32 [...] (-1 where id < 0), with mask=True (open, mask int32
         [ceil(K / 32), ...]).  Asynchronous on `stream`.  frame, spin (float32 [..., 2]) as for occlusion()
         (qr_fan_hits_framed_async)."""
-        import torch
-        if not (isinstance(hits, torch.Tensor) and hits.dtype == torch.float32 and hits.dim() >= 2 and hits.shape[-1] == 12
-                and hits.is_contiguous() and hits.is_cuda and hits.device.index == self.device):
-            raise QrError(f"hits must be a contiguous float32 [..., 12] tensor on cuda:{self.device} (qr_hit records)")
-        shape = tuple(hits.shape[:-1])
-        n = hits.numel() // 12
-        sp = self._spin_arg(frame, spin, shape)
-        d4, k, eps, reach, opn, msk = self._fan_args(dirs, eps, reach, shape, mask)
-        if frame:
-            _check(lib().qr_fan_hits_framed_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, sp,
-                                                  eps, reach, ctypes.c_void_p(opn.data_ptr()),
-                                                  ctypes.c_void_p(msk.data_ptr() if mask else None),
-                                                  FAN_FLIP if flip else 0, self._stream_ptr(stream)))
-            return (opn, msk) if mask else opn
-        _check(lib().qr_fan_hits_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
-                                       ctypes.c_void_p(opn.data_ptr()), ctypes.c_void_p(msk.data_ptr() if mask else None),
-                                       FAN_FLIP if flip else 0, self._stream_ptr(stream)))
-        return (opn, msk) if mask else opn
+        return self._occlusion(self._hits_src(hits), dirs, eps, reach, FAN_FLIP if flip else 0, mask, stream, frame, spin)
 
     def _gather_args(self, dirs, eps, reach, shape, out, count, resume):
         """(dirs as a contiguous float32 [K, 4] tensor, K, eps, reach, gather, count) of a gather-fan call whose elements have
         `shape`; [K, 3] tables get weight 1.0"""
-        import math
-        import torch
         if resume and (out is None or count is None):
             raise QrError("resume=True needs both buffers: out (the sums so far) and count")
         shape = tuple(shape)
-        for name, buf, want, dt in (("out", out, shape + (4,), torch.float32), ("count", count, shape, torch.int32)):
-            if buf is not None and not (isinstance(buf, torch.Tensor) and buf.dtype == dt and tuple(buf.shape) == want
-                                        and buf.is_contiguous() and buf.is_cuda and buf.device.index == self.device):
-                raise QrError(f"{name} must be a contiguous {str(dt).replace('torch.', '')} {list(want)} tensor on cuda:{self.device}")
-        if not (isinstance(dirs, torch.Tensor) and dirs.dtype == torch.float32 and dirs.dim() == 2 and dirs.shape[1] in (3, 4)
-                and dirs.is_cuda and dirs.device.index == self.device):
-            raise QrError(f"dirs must be a float32 [K, 3] or [K, 4] tensor on cuda:{self.device}")
-        k = dirs.shape[0]
-        if not 1 <= k <= FAN_MAX_DIRS:
-            raise QrError(f"dirs must hold 1..{FAN_MAX_DIRS} directions, got {k}")
-        if eps is None or math.isnan(eps) or math.isnan(reach):
-            raise QrError("eps (the step off the surface, in units of |dir|) is required; eps and reach must not be NaN")
-        if dirs.shape[1] == 3:
-            d4 = torch.ones((k, 4), dtype=torch.float32, device=dirs.device)
-            d4[:, 0:3] = dirs
-        else:
-            d4 = dirs.contiguous()
+        # _fill in two halves: the buffers are checked before dirs and made after, so that a refused table allocates nothing
+        if out is not None:
+            _need("out", out, "float32", shape + (4,), self.device)
+        if count is not None:
+            _need("count", count, "int32", shape, self.device)
+        d4, k, eps, reach = _dirs_arg(dirs, eps, reach, 1.0, self.device)
         if out is None:
-            out = torch.empty(shape + (4,), dtype=torch.float32, device=dirs.device)    # every element is written
+            out = _new("float32", shape + (4,), self.device)
         if count is None:
-            count = torch.empty(shape, dtype=torch.int32, device=dirs.device)
-        return d4, k, float(eps), float(reach), out, count
+            count = _new("int32", shape, self.device)
+        return d4, k, eps, reach, out, count
 
     @staticmethod
     def _gather_flags(flip, cosine, resume, coherent=False):
@@ -790,19 +807,8 @@ class Scene:
         occlusion(); the dot product is dirs[k, 2], the table's own cosine.  With rays.cosine_dirs the plain sum
         (cosine=False) is the irradiance estimate.  spin (needs frame): float32 [N, 2], as for occlusion().
         rays.gather_fold(frame=True) states the sum exactly."""
-        rays = self._rays_arg(rays)
-        n = rays.shape[0]
-        sp = self._spin_arg(frame, spin, (n,))
-        d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, (n,), out, count, resume)
-        if frame:
-            _check(lib().qr_gather_rays_framed_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, sp,
-                                                     eps, reach, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                                                     self._gather_flags(flip, cosine, resume, coherent), self._stream_ptr(stream)))
-            return out, count
-        _check(lib().qr_gather_rays_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
-                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                                          self._gather_flags(flip, cosine, resume, coherent), self._stream_ptr(stream)))
-        return out, count
+        return self._gather(self._rays_src(rays), dirs, eps, reach, self._gather_flags(flip, cosine, resume, coherent), out, count,
+                            resume, stream, frame, spin)
 
     def view_gather(self, views, dirs, width=None, height=None, eps=None, reach=float("inf"), flip=False, cosine=False,
                     out=None, count=None, resume=False, stream=None, frame=False, spin=None):
@@ -811,19 +817,8 @@ class Scene:
         there (sample 0's under FSAA) -- the rest as for gather(); eps is required.  Returns (gather float32 [N, H, W, 4],
         count int32 [N, H, W]).  Asynchronous on `stream`.  frame, spin (float32 [N, H, W, 2]) as for gather()
         (qr_gather_views_framed_async)."""
-        w, h = self._views_arg(views, width, height)
-        n = views.shape[0]
-        sp = self._spin_arg(frame, spin, (n, h, w))
-        d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, (n, h, w), out, count, resume)
-        if frame:
-            _check(lib().qr_gather_views_framed_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k,
-                                                      sp, eps, reach, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                                                      self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))
-            return out, count
-        _check(lib().qr_gather_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(d4.data_ptr()), k, eps,
-                                           reach, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                                           self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))
-        return out, count
+        return self._gather(self._views_src(views, width, height), dirs, eps, reach, self._gather_flags(flip, cosine, resume), out,
+                            count, resume, stream, frame, spin)
 
     def hit_gather(self, hits, dirs, eps, reach=float("inf"), flip=False, cosine=False, out=None, count=None, resume=False,
                    stream=None, frame=False, spin=None):
@@ -831,40 +826,21 @@ class Scene:
         pos in columns 0:3, nrm in 4:7, the int32 bits of an id >= 0 in column 7) -- lightmap texels, probes, a second bounce.
         No first walk.  The rest as for gather().  Returns (gather float32 [..., 4], count int32 [...]).  Asynchronous on
         `stream`.  frame, spin (float32 [..., 2]) as for gather() (qr_gather_hits_framed_async)."""
-        import torch
-        if not (isinstance(hits, torch.Tensor) and hits.dtype == torch.float32 and hits.dim() >= 2 and hits.shape[-1] == 12
-                and hits.is_contiguous() and hits.is_cuda and hits.device.index == self.device):
-            raise QrError(f"hits must be a contiguous float32 [..., 12] tensor on cuda:{self.device} (qr_hit records)")
-        shape = tuple(hits.shape[:-1])
-        n = hits.numel() // 12
-        sp = self._spin_arg(frame, spin, shape)
-        d4, k, eps, reach, out, count = self._gather_args(dirs, eps, reach, shape, out, count, resume)
-        if frame:
-            _check(lib().qr_gather_hits_framed_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, sp,
-                                                     eps, reach, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                                                     self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))
-            return out, count
-        _check(lib().qr_gather_hits_async(self._h, ctypes.c_void_p(hits.data_ptr()), n, ctypes.c_void_p(d4.data_ptr()), k, eps, reach,
-                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                                          self._gather_flags(flip, cosine, resume), self._stream_ptr(stream)))
-        return out, count
+        return self._gather(self._hits_src(hits), dirs, eps, reach, self._gather_flags(flip, cosine, resume), out, count, resume,
+                            stream, frame, spin)
 
-    def _layer_args(self, k, shape, t, ids, hits, device):
-        """(k, count, t or None, ids or None, hits or None) of a hit-layer call whose elements have `shape`"""
-        import numbers
-        import torch
+    def _layers(self, src, k, t, ids, hits, flags, stream):
+        """the hit layers of either source: (count, t or None, ids or None) and, with hits, the records"""
+        kind, head, shape = src
         if not (isinstance(k, numbers.Integral) and 1 <= k <= LAYER_MAX):
             raise QrError(f"k must be an integer 1..{LAYER_MAX} (layers), got {k!r}")
         k = int(k)
-        shape = tuple(shape)
-        cnt = torch.empty(shape, dtype=torch.int32, device=device)                      # every element of every plane is written
-        tt = torch.empty((k,) + shape, dtype=torch.float32, device=device) if t else None
-        ii = torch.empty((k,) + shape, dtype=torch.int32, device=device) if ids else None
-        hh = torch.empty((k,) + shape + (12,), dtype=torch.float32, device=device) if hits else None
-        return k, cnt, tt, ii, hh
-
-    @staticmethod
-    def _layer_out(cnt, tt, ii, hh, hits):
+        cnt = _new("int32", shape, self.device)                                         # every element of every plane is written
+        tt = _new("float32", (k,) + shape, self.device) if t else None
+        ii = _new("int32", (k,) + shape, self.device) if ids else None
+        hh = _new("float32", (k,) + shape + (12,), self.device) if hits else None
+        _check(getattr(lib(), f"qr_layer_{kind}_async")(self._h, *head, k, cnt.data_ptr(), _ptr(tt), _ptr(ii), _ptr(hh), flags,
+                                                        self._stream_ptr(stream)))
         return (cnt, tt, ii, hh) if hits else (cnt, tt, ii)
 
     def trace_layers(self, rays, k, t=True, ids=True, hits=False, coherent=False, stream=None):
@@ -880,13 +856,7 @@ class Scene:
         ids[-1]) gives the rays that resume where this call stopped: k1 layers, then k2 on them, equal one call with k1 + k2.
         coherent: as for trace(); results do not depend on it.  Nothing is lit: depth and path-tracer mode do not matter.
         Asynchronous on `stream`."""
-        rays = self._rays_arg(rays)
-        n = rays.shape[0]
-        k, cnt, tt, ii, hh = self._layer_args(k, (n,), t, ids, hits, rays.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else None)
-        _check(lib().qr_layer_rays_async(self._h, ptr(rays), n, k, ptr(cnt), ptr(tt), ptr(ii), ptr(hh),
-                                         TRACE_COHERENT if coherent else 0, self._stream_ptr(stream)))
-        return self._layer_out(cnt, tt, ii, hh, hits)
+        return self._layers(self._rays_src(rays), k, t, ids, hits, TRACE_COHERENT if coherent else 0, stream)
 
     def view_layers(self, views, k, width=None, height=None, t=True, ids=True, hits=False, stream=None):
         """The first k hits behind every pixel of caller-supplied cameras (qr_layer_views_async): layered depth images, x-ray
@@ -894,13 +864,7 @@ class Scene:
         -- k, t, ids, hits as for trace_layers().  Returns (count int32 [N, H, W], t float32 [k, N, H, W], ids int32
         [k, N, H, W]) and, with hits=True, hits float32 [k, N, H, W, 12].  Layer 0 is view_hits' answer.  Asynchronous on
         `stream`."""
-        w, h = self._views_arg(views, width, height)
-        n = views.shape[0]
-        k, cnt, tt, ii, hh = self._layer_args(k, (n, h, w), t, ids, hits, views.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else None)
-        _check(lib().qr_layer_views_async(self._h, ptr(views), n, w, h, k, ptr(cnt), ptr(tt), ptr(ii), ptr(hh),
-                                          0, self._stream_ptr(stream)))
-        return self._layer_out(cnt, tt, ii, hh, hits)
+        return self._layers(self._views_src(views, width, height), k, t, ids, hits, 0, stream)
 
     def render_views(self, views, width=None, height=None, frames=None, ids=False, depth=False, stream=None):
         """Whole frames of the resident scene from caller-supplied cameras (qr_render_views_async): views float32 [N, 16] on the
@@ -909,19 +873,11 @@ class Scene:
         and with the snapshot's FSAA, gamma and output step.  Returns `frames` (int32 [N, H, W] like new_frame; a new tensor
         unless given), followed by the first hit's ids (int32 [N, H, W], surface << 1 | side, -1 none) with ids=True and the
         first hit's t (float32 [N, H, W], the view's t_max where none) with depth=True.  Asynchronous on `stream`."""
-        import torch
-        w, h = self._views_arg(views, width, height)
-        n = views.shape[0]
-        if frames is None:
-            frames = torch.empty((n, h, w), dtype=torch.int32, device=views.device)     # every pixel is written
-        elif not (isinstance(frames, torch.Tensor) and frames.dtype == torch.int32 and tuple(frames.shape) == (n, h, w)
-                  and frames.is_contiguous() and frames.is_cuda and frames.device.index == self.device):
-            raise QrError(f"frames must be a contiguous int32 [{n}, {h}, {w}] tensor on cuda:{self.device}")
-        hid = torch.empty((n, h, w), dtype=torch.int32, device=views.device) if ids else None
-        dep = torch.empty((n, h, w), dtype=torch.float32, device=views.device) if depth else None
-        _check(lib().qr_render_views_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h,
-                                           ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(hid.data_ptr() if ids else None),
-                                           ctypes.c_void_p(dep.data_ptr() if depth else None), 0, self._stream_ptr(stream)))
+        _, head, shape = self._views_src(views, width, height)
+        frames = _fill("frames", frames, "int32", shape, self.device)
+        hid = _new("int32", shape, self.device) if ids else None
+        dep = _new("float32", shape, self.device) if depth else None
+        _check(lib().qr_render_views_async(self._h, *head, frames.data_ptr(), _ptr(hid), _ptr(dep), 0, self._stream_ptr(stream)))
         out = (frames,) + ((hid,) if ids else ()) + ((dep,) if depth else ())
         return out if len(out) > 1 else frames
 
@@ -935,23 +891,11 @@ class Scene:
         of one call.  Returns (frame or None, sum).  One wave renders a footprint of all views: meant for full-size frames.
         Asynchronous on `stream`."""
         import numpy as np
-        import torch
-        w, h = self._views_arg(views, width, height)
-        n = views.shape[0]
+        _, head, (n, h, w) = self._views_src(views, width, height)
         if resume and sum is None:
             raise QrError("resume=True needs the `sum` tensor of the earlier calls")
-        if sum is None:
-            sum = torch.empty((h, w, 3), dtype=torch.float32, device=views.device)      # every pixel is written
-        elif not (isinstance(sum, torch.Tensor) and sum.dtype == torch.float32 and tuple(sum.shape) == (h, w, 3)
-                  and sum.is_contiguous() and sum.is_cuda and sum.device.index == self.device):
-            raise QrError(f"sum must be a contiguous float32 [{h}, {w}, 3] tensor on cuda:{self.device}")
-        if frame is True:
-            frame = torch.empty((h, w), dtype=torch.int32, device=views.device)
-        elif frame is False or frame is None:
-            frame = None
-        elif not (isinstance(frame, torch.Tensor) and frame.dtype == torch.int32 and tuple(frame.shape) == (h, w)
-                  and frame.is_contiguous() and frame.is_cuda and frame.device.index == self.device):
-            raise QrError(f"frame must be True, False or a contiguous int32 [{h}, {w}] tensor on cuda:{self.device}")
+        sum = _fill("sum", sum, "float32", (h, w, 3), self.device)
+        frame = _wanted("frame", frame, "int32", (h, w), self.device)
         if frame is not None:
             if scale is None:
                 if resume:
@@ -960,10 +904,8 @@ class Scene:
             scale = float(np.float32(scale))
             if not (np.isfinite(scale) and scale > 0.0):
                 raise QrError("scale must be finite and greater than 0")
-        _check(lib().qr_render_views_mean_async(self._h, ctypes.c_void_p(views.data_ptr()), n, w, h, ctypes.c_void_p(sum.data_ptr()),
-                                                ctypes.c_void_p(frame.data_ptr() if frame is not None else None),
-                                                scale if frame is not None else 1.0, MEAN_RESUME if resume else 0,
-                                                self._stream_ptr(stream)))
+        _check(lib().qr_render_views_mean_async(self._h, *head, sum.data_ptr(), _ptr(frame), scale if frame is not None else 1.0,
+                                                MEAN_RESUME if resume else 0, self._stream_ptr(stream)))
         return frame, sum
 
     def pt_views(self, views, width=None, height=None, state=None, samples=0):
@@ -998,13 +940,13 @@ class Scene:
         if frame is None:
             frame = self.new_frame()
         c = RayCounts()
-        _check(lib().qr_render_count(self._h, ctypes.c_void_p(frame.data_ptr()), self._stream_ptr(stream), ctypes.byref(c)))
+        _check(lib().qr_render_count(self._h, frame.data_ptr(), self._stream_ptr(stream), ctypes.byref(c)))
         return frame, c
 
     def render_timed(self, frame, iters, stream=None):
         avg, mn = ctypes.c_float(), ctypes.c_float()
-        _check(lib().qr_render_timed(self._h, ctypes.c_void_p(frame.data_ptr()), self._stream_ptr(stream),
-                                     iters, ctypes.byref(avg), ctypes.byref(mn)))
+        _check(lib().qr_render_timed(self._h, frame.data_ptr(), self._stream_ptr(stream), iters, ctypes.byref(avg),
+                                     ctypes.byref(mn)))
         return avg.value, mn.value
 
     def render_host(self, out=None, row_pixels=None):
@@ -1016,7 +958,106 @@ class Scene:
         return out
 
 
-class PtViews:
+_UNCOUNTED = object()      # _adopt's `samples` of the adaptive accumulators, whose state holds the counts itself
+_LIST = "int32 or uint32"   # what an open list's index and count, and an open counter, may be
+
+
+class _Accumulator:
+    """What the four accumulators share: how a state is adopted, and the caller rays of a step."""
+
+    def _adopt(self, query, head, shape, state, samples=_UNCOUNTED):
+        """Ask the library for the state's size (`query` with `head`), hold it against the layout, and take the state: a new
+        one, reset, or the caller's, checked.  samples (the two plain accumulators): how many the caller's state holds"""
+        nbytes = ctypes.c_uint64()
+        _check(query(self.scene._h, *head, ctypes.byref(nbytes)))
+        assert nbytes.value == 4 * math.prod(shape)
+        if state is None:
+            if samples is not _UNCOUNTED and samples != 0:
+                raise QrError("a new state holds no samples: pass the state tensor that holds them")
+            self.state = _new("int32", shape, self.scene.device)
+            self.reset()
+        else:
+            self.state = _need("state", state, "int32", shape, self.scene.device)
+            if samples is not _UNCOUNTED:
+                if not (isinstance(samples, int) and samples >= 0):
+                    raise QrError("samples must be the non-negative number of samples the state holds")
+                self.samples = samples
+
+    def _ray_args(self, rays, spread, rgb):
+        """(rays, spread or None, rgb or None) of a step over caller rays"""
+        n, dev = self.n, self.scene.device
+        rays = self.scene._rays_arg(rays)
+        if rays.shape[0] != n:
+            raise QrError(f"this accumulation holds {n} rays, got {rays.shape[0]}")
+        if spread is not None:
+            _need("spread", spread, "float32", (n, 8), dev, lead="None or a", suffix=" (du xyz, pad, dv xyz, pad per row)")
+        return rays, spread, _wanted("rgb", rgb, "float32", (n, 3), dev)
+
+
+class _Adaptive(_Accumulator):
+    """What the two adaptive accumulators share: the stop rule, the open list of a state block, the open counter."""
+
+    def _rule(self, min_samples, max_samples, tol):
+        import numpy as np
+        if not (isinstance(min_samples, int) and isinstance(max_samples, int)
+                and 0 <= min_samples <= max_samples and 1 <= max_samples < (1 << 24)):
+            raise QrError("min_samples and max_samples must be integers, 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24")
+        try:
+            t = np.float32(tol)
+        except (TypeError, ValueError):
+            raise QrError("tol must be a number") from None
+        with np.errstate(over="ignore", invalid="ignore"):
+            tol2 = t * t
+        if not (t >= 0 and np.isfinite(tol2)):
+            raise QrError("tol must be a finite number, 0 or more, whose square is finite in float32")
+        self.min_samples, self.max_samples, self.tol, self.tol2 = min_samples, max_samples, float(t), tol2
+        self._list_work = self._list_index = self._list_count = None
+
+    def _open_list(self, block, n, index, count, stream):
+        """qr_pt_adapt_open_list_async on `block`, a state of n columns; index, count: the caller's, or the accumulator's own"""
+        import torch
+        scene = self.scene
+        if index is None:
+            if self._list_index is None:
+                self._list_index = _new("int32", (n,), scene.device)
+            index = self._list_index
+        if count is None:
+            if self._list_count is None:
+                self._list_count = torch.zeros((1,), dtype=torch.int32, device=f"cuda:{scene.device}")
+            count = self._list_count
+        index, count = _need("index", index, _LIST, (n,), scene.device), _need("count", count, _LIST, (1,), scene.device)
+        if self._list_work is None:
+            nbytes = ctypes.c_uint64()
+            _check(lib().qr_pt_adapt_list_work_bytes(scene._h, n, ctypes.byref(nbytes)))
+            self._list_work = _new("int32", (max(1, nbytes.value // 4),), scene.device)
+        _check(lib().qr_pt_adapt_open_list_async(scene._h, block.data_ptr(), n, self.min_samples, self.max_samples,
+                                                 float(self.tol2), index.data_ptr(), count.data_ptr(),
+                                                 self._list_work.data_ptr(), 0, Scene._stream_ptr(stream)))
+        return index, count
+
+    def _open_counter(self, open, samples, most, stream):
+        """the open counter of a step: None, a new one-element tensor or the caller's, zeroed on `stream` once `samples`
+        (1..most), the last thing a step checks, has passed"""
+        dev = self.scene.device
+        opent = None
+        if open is True:
+            opent = _new("int32", (1,), dev)
+        elif not (open is False or open is None):
+            if not (_fits(open, _LIST, None, dev) and open.numel() == 1):
+                raise QrError(f"open must be True, False or a one-element int32 or uint32 tensor on cuda:{dev}")
+            opent = open
+        if not isinstance(samples, int):
+            raise QrError("samples must be an integer")
+        if not 1 <= samples <= most:
+            raise QrError(f"samples must be 1..{most}")
+        if opent is not None:
+            import torch
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                opent.zero_()
+        return opent
+
+
+class PtViews(_Accumulator):
     """A path-traced accumulation over caller cameras (Scene.pt_views; include/qrhip.h qr_pt_views_async).
 
     state: int32 [N, 4, H * W * samples_per_pixel] on the scene's device -- per view the generator states (plane 0) and the
@@ -1025,33 +1066,14 @@ class PtViews:
     The scene's own path-tracer mode (set_pt) neither matters nor is touched."""
 
     def __init__(self, scene, views, width=None, height=None, state=None, samples=0):
-        import torch
-        w, h = scene._views_arg(views, width, height)
+        _, (_, n, w, h), _ = scene._views_src(views, width, height)
         self.scene, self.views, self.width, self.height = scene, views, w, h
-        n = views.shape[0]
-        nbytes = ctypes.c_uint64()
-        _check(lib().qr_pt_views_state_bytes(scene._h, n, w, h, ctypes.byref(nbytes)))
         self.slots = (w * h) << scene.info.fsaa
-        shape = (n, PT_VIEWS_STATE_WORDS, self.slots)
-        assert nbytes.value == 4 * n * PT_VIEWS_STATE_WORDS * self.slots
-        if state is None:
-            if samples != 0:
-                raise QrError("a new state holds no samples: pass the state tensor that holds them")
-            self.state = torch.empty(shape, dtype=torch.int32, device=views.device)
-            self.samples = 0
-            self.reset()
-        else:
-            if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == shape
-                    and state.is_contiguous() and state.is_cuda and state.device.index == scene.device):
-                raise QrError(f"state must be a contiguous int32 {list(shape)} tensor on cuda:{scene.device}")
-            if not (isinstance(samples, int) and samples >= 0):
-                raise QrError("samples must be the non-negative number of samples the state holds")
-            self.state, self.samples = state, samples
+        self._adopt(lib().qr_pt_views_state_bytes, (n, w, h), (n, PT_VIEWS_STATE_WORDS, self.slots), state, samples)
 
     def reset(self):
         """Restart the accumulation: seeds as rays.pt_seeds in every view, means 0, samples 0.  Synchronous (qr_pt_views_reset)."""
-        _check(lib().qr_pt_views_reset(self.scene._h, self.views.shape[0], self.width, self.height,
-                                       ctypes.c_void_p(self.state.data_ptr())))
+        _check(lib().qr_pt_views_reset(self.scene._h, self.views.shape[0], self.width, self.height, self.state.data_ptr()))
         self.samples = 0
 
     def clone(self):
@@ -1063,32 +1085,19 @@ class PtViews:
         packed running-mean frames (int32 [N, H, W]; a new tensor unless given); with mean=True (or a float32 [N, H, W, 3]
         tensor to fill) also the pixels' linear colours after the FSAA reduce, before gamma and packing: (frames, mean).
         The scene's current depth (set_depth) applies.  Asynchronous on `stream`."""
-        import torch
         n, h, w, dev = self.views.shape[0], self.height, self.width, self.scene.device
-        if frames is None:
-            frames = torch.empty((n, h, w), dtype=torch.int32, device=self.views.device)    # every pixel is written
-        elif not (isinstance(frames, torch.Tensor) and frames.dtype == torch.int32 and tuple(frames.shape) == (n, h, w)
-                  and frames.is_contiguous() and frames.is_cuda and frames.device.index == dev):
-            raise QrError(f"frames must be a contiguous int32 [{n}, {h}, {w}] tensor on cuda:{dev}")
-        if mean is True:
-            mean = torch.empty((n, h, w, 3), dtype=torch.float32, device=self.views.device)
-        elif mean is False or mean is None:
-            mean = None
-        elif not (isinstance(mean, torch.Tensor) and mean.dtype == torch.float32 and tuple(mean.shape) == (n, h, w, 3)
-                  and mean.is_contiguous() and mean.is_cuda and mean.device.index == dev):
-            raise QrError(f"mean must be True, False or a contiguous float32 [{n}, {h}, {w}, 3] tensor on cuda:{dev}")
+        frames = _fill("frames", frames, "int32", (n, h, w), dev)
+        mean = _wanted("mean", mean, "float32", (n, h, w, 3), dev)
         if not isinstance(samples, int):
             raise QrError("samples must be an integer")
-        _check(lib().qr_pt_views_async(self.scene._h, ctypes.c_void_p(self.views.data_ptr()), n, w, h,
-                                       ctypes.c_void_p(self.state.data_ptr()), self.samples, samples,
-                                       ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(mean.data_ptr() if mean is not None else None),
-                                       0, Scene._stream_ptr(stream)))
+        _check(lib().qr_pt_views_async(self.scene._h, self.views.data_ptr(), n, w, h, self.state.data_ptr(), self.samples, samples,
+                                       frames.data_ptr(), _ptr(mean), 0, Scene._stream_ptr(stream)))
         if n > 0:
             self.samples += samples
         return (frames, mean) if mean is not None else frames
 
 
-class PtRays:
+class PtRays(_Accumulator):
     """A path-traced accumulation over caller rays (Scene.pt_rays; include/qrhip.h qr_pt_rays_async).
 
     state: int32 [4, N] on the scene's device -- the generator states (plane 0) and the float32 running means of r, g, b
@@ -1098,31 +1107,14 @@ class PtRays:
     touched."""
 
     def __init__(self, scene, n, state=None, samples=0):
-        import torch
         if not (isinstance(n, int) and n >= 0):
             raise QrError("n must be the non-negative number of rays")
         self.scene, self.n = scene, n
-        nbytes = ctypes.c_uint64()
-        _check(lib().qr_pt_rays_state_bytes(scene._h, n, ctypes.byref(nbytes)))
-        shape = (PT_RAYS_STATE_WORDS, n)
-        assert nbytes.value == 4 * PT_RAYS_STATE_WORDS * n
-        if state is None:
-            if samples != 0:
-                raise QrError("a new state holds no samples: pass the state tensor that holds them")
-            self.state = torch.empty(shape, dtype=torch.int32, device=f"cuda:{scene.device}")
-            self.samples = 0
-            self.reset()
-        else:
-            if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == shape
-                    and state.is_contiguous() and state.is_cuda and state.device.index == scene.device):
-                raise QrError(f"state must be a contiguous int32 {list(shape)} tensor on cuda:{scene.device}")
-            if not (isinstance(samples, int) and samples >= 0):
-                raise QrError("samples must be the non-negative number of samples the state holds")
-            self.state, self.samples = state, samples
+        self._adopt(lib().qr_pt_rays_state_bytes, (n,), (PT_RAYS_STATE_WORDS, n), state, samples)
 
     def reset(self):
         """Restart the accumulation: seeds as rays.pt_seeds(n, 1, 1), means 0, samples 0.  Synchronous (qr_pt_rays_reset)."""
-        _check(lib().qr_pt_rays_reset(self.scene._h, self.n, ctypes.c_void_p(self.state.data_ptr())))
+        _check(lib().qr_pt_rays_reset(self.scene._h, self.n, self.state.data_ptr()))
         self.samples = 0
 
     def clone(self):
@@ -1135,34 +1127,17 @@ class PtRays:
         jittered (rays.pt_jitter, rays.spread_rays).  Returns the running means after the call, float32 [N, 3] linear colour
         before any clamp (a new tensor with rgb=True, or the given tensor filled), or None with rgb=False.  The scene's
         current depth (set_depth) applies.  Asynchronous on `stream`."""
-        import torch
-        n, dev = self.n, self.scene.device
-        rays = self.scene._rays_arg(rays)
-        if rays.shape[0] != n:
-            raise QrError(f"this accumulation holds {n} rays, got {rays.shape[0]}")
-        if spread is not None and not (isinstance(spread, torch.Tensor) and spread.dtype == torch.float32
-                                       and tuple(spread.shape) == (n, 8) and spread.is_contiguous() and spread.is_cuda
-                                       and spread.device.index == dev):
-            raise QrError(f"spread must be None or a contiguous float32 [{n}, 8] tensor on cuda:{dev} (du xyz, pad, dv xyz, pad per row)")
-        if rgb is True:
-            rgb = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
-        elif rgb is False or rgb is None:
-            rgb = None
-        elif not (isinstance(rgb, torch.Tensor) and rgb.dtype == torch.float32 and tuple(rgb.shape) == (n, 3)
-                  and rgb.is_contiguous() and rgb.is_cuda and rgb.device.index == dev):
-            raise QrError(f"rgb must be True, False or a contiguous float32 [{n}, 3] tensor on cuda:{dev}")
+        rays, spread, rgb = self._ray_args(rays, spread, rgb)
         if not isinstance(samples, int):
             raise QrError("samples must be an integer")
-        _check(lib().qr_pt_rays_async(self.scene._h, ctypes.c_void_p(rays.data_ptr()),
-                                      ctypes.c_void_p(spread.data_ptr() if spread is not None else None), n,
-                                      ctypes.c_void_p(self.state.data_ptr()), self.samples, samples,
-                                      ctypes.c_void_p(rgb.data_ptr() if rgb is not None else None), 0, Scene._stream_ptr(stream)))
-        if n > 0:
+        _check(lib().qr_pt_rays_async(self.scene._h, rays.data_ptr(), _ptr(spread), self.n, self.state.data_ptr(), self.samples,
+                                      samples, _ptr(rgb), 0, Scene._stream_ptr(stream)))
+        if self.n > 0:
             self.samples += samples
         return rgb
 
 
-class PtAdaptive:
+class PtAdaptive(_Adaptive):
     """An adaptive path-traced accumulation over caller rays (Scene.pt_adaptive; include/qrhip.h qr_pt_adapt_rays_async).
 
     state: int32 [8, N] on the scene's device, ray i in column i -- plane 0 the generator states, planes 1..3 the float32
@@ -1175,36 +1150,11 @@ class PtAdaptive:
     for bit the plain step's (rays.pt_adapt_open_list, rays.pt_adapt_fold_list)."""
 
     def __init__(self, scene, n, min_samples, max_samples, tol, state=None):
-        import numpy as np
-        import torch
         if not (isinstance(n, int) and n >= 0):
             raise QrError("n must be the non-negative number of rays")
-        if not (isinstance(min_samples, int) and isinstance(max_samples, int)
-                and 0 <= min_samples <= max_samples and 1 <= max_samples < (1 << 24)):
-            raise QrError("min_samples and max_samples must be integers, 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24")
-        try:
-            t = np.float32(tol)
-        except (TypeError, ValueError):
-            raise QrError("tol must be a number") from None
-        with np.errstate(over="ignore", invalid="ignore"):
-            tol2 = t * t
-        if not (t >= 0 and np.isfinite(tol2)):
-            raise QrError("tol must be a finite number, 0 or more, whose square is finite in float32")
-        self.scene, self.n, self.min_samples, self.max_samples = scene, n, min_samples, max_samples
-        self.tol, self.tol2 = float(t), tol2
-        self._list_work = self._list_index = self._list_count = None
-        nbytes = ctypes.c_uint64()
-        _check(lib().qr_pt_adapt_state_bytes(scene._h, n, ctypes.byref(nbytes)))
-        shape = (PT_ADAPT_STATE_WORDS, n)
-        assert nbytes.value == 4 * PT_ADAPT_STATE_WORDS * n
-        if state is None:
-            self.state = torch.empty(shape, dtype=torch.int32, device=f"cuda:{scene.device}")
-            self.reset()
-        else:
-            if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == shape
-                    and state.is_contiguous() and state.is_cuda and state.device.index == scene.device):
-                raise QrError(f"state must be a contiguous int32 {list(shape)} tensor on cuda:{scene.device}")
-            self.state = state
+        self._rule(min_samples, max_samples, tol)
+        self.scene, self.n = scene, n
+        self._adopt(lib().qr_pt_adapt_state_bytes, (n,), (PT_ADAPT_STATE_WORDS, n), state)
 
     @property
     def counts(self):
@@ -1213,44 +1163,18 @@ class PtAdaptive:
 
     def reset(self):
         """Restart the accumulation: seeds as rays.pt_seeds(n, 1, 1), every other plane 0.  Synchronous (qr_pt_adapt_reset)."""
-        _check(lib().qr_pt_adapt_reset(self.scene._h, self.n, ctypes.c_void_p(self.state.data_ptr())))
+        _check(lib().qr_pt_adapt_reset(self.scene._h, self.n, self.state.data_ptr()))
 
     def clone(self):
         """A checkpoint: an accumulator with a copy of the state (on the current stream) that continues independently."""
         return PtAdaptive(self.scene, self.n, self.min_samples, self.max_samples, self.tol, self.state.clone())
-
-    def _list_arg(self, t, shape, what):
-        import torch
-        if not (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
-                and tuple(t.shape) == shape and t.is_contiguous() and t.is_cuda and t.device.index == self.scene.device):
-            raise QrError(f"{what} must be a contiguous int32 or uint32 {list(shape)} tensor on cuda:{self.scene.device}")
-        return t
 
     def open_list(self, index=None, count=None, stream=None):
         """The open list of the state (qr_pt_adapt_open_list_async): index[:count] = the indices of the rays the stop rule would
         still let take a sample, ascending; index[count:] is not written.  Returns (index int32 [n], count int32 [1]), the
         accumulator's own tensors (allocated on first use, written again by every call) or the caller's.  Nothing is read back:
         hand both to step(..., index=, count=).  The work buffer belongs to the accumulator.  Asynchronous on `stream`."""
-        import torch
-        n, dev = self.n, f"cuda:{self.scene.device}"
-        if index is None:
-            if self._list_index is None:
-                self._list_index = torch.empty((n,), dtype=torch.int32, device=dev)
-            index = self._list_index
-        if count is None:
-            if self._list_count is None:
-                self._list_count = torch.zeros((1,), dtype=torch.int32, device=dev)
-            count = self._list_count
-        index, count = self._list_arg(index, (n,), "index"), self._list_arg(count, (1,), "count")
-        if self._list_work is None:
-            nbytes = ctypes.c_uint64()
-            _check(lib().qr_pt_adapt_list_work_bytes(self.scene._h, n, ctypes.byref(nbytes)))
-            self._list_work = torch.empty((max(1, nbytes.value // 4),), dtype=torch.int32, device=dev)
-        _check(lib().qr_pt_adapt_open_list_async(self.scene._h, ctypes.c_void_p(self.state.data_ptr()), n, self.min_samples,
-                                                 self.max_samples, ctypes.c_float(float(self.tol2)),
-                                                 ctypes.c_void_p(index.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                                                 ctypes.c_void_p(self._list_work.data_ptr()), 0, Scene._stream_ptr(stream)))
-        return index, count
+        return self._open_list(self.state, self.n, index, count, stream)
 
     def step(self, rays, samples=1, spread=None, rgb=True, open=False, stream=None, index=None, count=None, cap=None):
         """Offer every ray up to `samples` (1 .. PT_ADAPT_MAX_SAMPLES) candidate samples in ONE launch; a ray takes them while the
@@ -1273,63 +1197,24 @@ class PtAdaptive:
         else:
             if count is None:
                 raise QrError("index needs count: a one-element tensor holding the list's length (open_list() returns both)")
-            if not (isinstance(index, torch.Tensor) and index.dim() == 1):
-                raise QrError(f"index must be a contiguous int32 or uint32 [length] tensor on cuda:{dev}")
-            index, count = self._list_arg(index, (index.shape[0],), "index"), self._list_arg(count, (1,), "count")
+            if not (isinstance(index, torch.Tensor) and index.dim() == 1):      # any length: only then is there a shape to ask for
+                raise QrError(f"index must be a contiguous {_LIST} [length] tensor on cuda:{dev}")
+            index, count = _need("index", index, _LIST, (index.shape[0],), dev), _need("count", count, _LIST, (1,), dev)
             if cap is None:
                 cap = min(n, index.shape[0])
             if not (isinstance(cap, int) and 0 <= cap <= index.shape[0]):
                 raise QrError(f"cap must be an integer, 0..{index.shape[0]}: it bounds the entries of index that are read")
-        rays = self.scene._rays_arg(rays)
-        if rays.shape[0] != n:
-            raise QrError(f"this accumulation holds {n} rays, got {rays.shape[0]}")
-        if spread is not None and not (isinstance(spread, torch.Tensor) and spread.dtype == torch.float32
-                                       and tuple(spread.shape) == (n, 8) and spread.is_contiguous() and spread.is_cuda
-                                       and spread.device.index == dev):
-            raise QrError(f"spread must be None or a contiguous float32 [{n}, 8] tensor on cuda:{dev} (du xyz, pad, dv xyz, pad per row)")
-        if rgb is True:
-            rgb = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
-        elif rgb is False or rgb is None:
-            rgb = None
-        elif not (isinstance(rgb, torch.Tensor) and rgb.dtype == torch.float32 and tuple(rgb.shape) == (n, 3)
-                  and rgb.is_contiguous() and rgb.is_cuda and rgb.device.index == dev):
-            raise QrError(f"rgb must be True, False or a contiguous float32 [{n}, 3] tensor on cuda:{dev}")
-        opent = None
-        if open is True:
-            opent = torch.empty((1,), dtype=torch.int32, device=rays.device)
-        elif not (open is False or open is None):
-            if not (isinstance(open, torch.Tensor) and open.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
-                    and open.numel() == 1 and open.is_contiguous() and open.is_cuda and open.device.index == dev):
-                raise QrError(f"open must be True, False or a one-element int32 or uint32 tensor on cuda:{dev}")
-            opent = open
-        if not isinstance(samples, int):
-            raise QrError("samples must be an integer")
-        if not 1 <= samples <= PT_ADAPT_MAX_SAMPLES:
-            raise QrError(f"samples must be 1..{PT_ADAPT_MAX_SAMPLES}")
-        if opent is not None:
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-                opent.zero_()
-        if index is not None:
-            _check(lib().qr_pt_adapt_list_rays_async(self.scene._h, ctypes.c_void_p(rays.data_ptr()),
-                                                     ctypes.c_void_p(spread.data_ptr() if spread is not None else None), n,
-                                                     ctypes.c_void_p(self.state.data_ptr()), ctypes.c_void_p(index.data_ptr()),
-                                                     ctypes.c_void_p(count.data_ptr()), cap, samples, self.min_samples,
-                                                     self.max_samples, ctypes.c_float(float(self.tol2)),
-                                                     ctypes.c_void_p(rgb.data_ptr() if rgb is not None else None),
-                                                     ctypes.c_void_p(opent.data_ptr() if opent is not None else None), 0,
-                                                     Scene._stream_ptr(stream)))
-            return (rgb, opent) if opent is not None else rgb
-        _check(lib().qr_pt_adapt_rays_async(self.scene._h, ctypes.c_void_p(rays.data_ptr()),
-                                            ctypes.c_void_p(spread.data_ptr() if spread is not None else None), n,
-                                            ctypes.c_void_p(self.state.data_ptr()), samples, self.min_samples, self.max_samples,
-                                            ctypes.c_float(float(self.tol2)),
-                                            ctypes.c_void_p(rgb.data_ptr() if rgb is not None else None),
-                                            ctypes.c_void_p(opent.data_ptr() if opent is not None else None), 0,
-                                            Scene._stream_ptr(stream)))
+        rays, spread, rgb = self._ray_args(rays, spread, rgb)
+        opent = self._open_counter(open, samples, PT_ADAPT_MAX_SAMPLES, stream)
+        # the list entry point takes (index, count, cap) after the state; everything else is the plain step's
+        fn, listed = (lib().qr_pt_adapt_rays_async, ()) if index is None else \
+                     (lib().qr_pt_adapt_list_rays_async, (index.data_ptr(), count.data_ptr(), cap))
+        _check(fn(self.scene._h, rays.data_ptr(), _ptr(spread), n, self.state.data_ptr(), *listed, samples, self.min_samples,
+                  self.max_samples, float(self.tol2), _ptr(rgb), _ptr(opent), 0, Scene._stream_ptr(stream)))
         return (rgb, opent) if opent is not None else rgb
 
 
-class PtAdaptiveViews:
+class PtAdaptiveViews(_Adaptive):
     """An adaptive path-traced accumulation over caller cameras (Scene.pt_adaptive_views; include/qrhip.h
     qr_pt_adapt_views_async).
 
@@ -1341,37 +1226,11 @@ class PtAdaptiveViews:
     wave is one footprint and runs as long as its slowest slot."""
 
     def __init__(self, scene, views, width=None, height=None, min_samples=0, max_samples=64, tol=0.0, state=None):
-        import numpy as np
-        import torch
-        w, h = scene._views_arg(views, width, height)
-        if not (isinstance(min_samples, int) and isinstance(max_samples, int)
-                and 0 <= min_samples <= max_samples and 1 <= max_samples < (1 << 24)):
-            raise QrError("min_samples and max_samples must be integers, 0 <= min_samples <= max_samples, 1 <= max_samples < 2^24")
-        try:
-            t = np.float32(tol)
-        except (TypeError, ValueError):
-            raise QrError("tol must be a number") from None
-        with np.errstate(over="ignore", invalid="ignore"):
-            tol2 = t * t
-        if not (t >= 0 and np.isfinite(tol2)):
-            raise QrError("tol must be a finite number, 0 or more, whose square is finite in float32")
+        _, (_, n, w, h), _ = scene._views_src(views, width, height)
+        self._rule(min_samples, max_samples, tol)
         self.scene, self.views, self.width, self.height = scene, views, w, h
-        self.min_samples, self.max_samples, self.tol, self.tol2 = min_samples, max_samples, float(t), tol2
-        self._list_work = self._list_index = self._list_count = None
-        n = views.shape[0]
-        nbytes = ctypes.c_uint64()
-        _check(lib().qr_pt_adapt_views_state_bytes(scene._h, n, w, h, ctypes.byref(nbytes)))
         self.slots = (w * h) << scene.info.fsaa
-        shape = (n, PT_ADAPT_STATE_WORDS, self.slots)
-        assert nbytes.value == 4 * n * PT_ADAPT_STATE_WORDS * self.slots
-        if state is None:
-            self.state = torch.empty(shape, dtype=torch.int32, device=views.device)
-            self.reset()
-        else:
-            if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == shape
-                    and state.is_contiguous() and state.is_cuda and state.device.index == scene.device):
-                raise QrError(f"state must be a contiguous int32 {list(shape)} tensor on cuda:{scene.device}")
-            self.state = state
+        self._adopt(lib().qr_pt_adapt_views_state_bytes, (n, w, h), (n, PT_ADAPT_STATE_WORDS, self.slots), state)
 
     @property
     def counts(self):
@@ -1383,62 +1242,34 @@ class PtAdaptiveViews:
         Welford's M2 summed over r, g, b, divided by 3 m (m - 1), `unknown` where the slot holds fewer than 2 samples; per pixel
         the sum over its slots divided by their number squared.  What Scene.atrous / Scene.denoise take as `variance`.
         Returns float32 [N, H, W] (a new tensor unless given).  The state is only read.  Asynchronous on `stream`."""
-        import torch
-        n, h, w, dev = self.views.shape[0], self.height, self.width, self.scene.device
-        if out is None:
-            out = torch.empty((n, h, w), dtype=torch.float32, device=self.views.device)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == (n, h, w)
-                  and out.is_contiguous() and out.is_cuda and out.device.index == dev):
-            raise QrError(f"out must be a contiguous float32 [{n}, {h}, {w}] tensor on cuda:{dev}")
+        n, h, w = self.views.shape[0], self.height, self.width
+        out = _fill("out", out, "float32", (n, h, w), self.scene.device)
         try:
             unknown = float(unknown)
         except (TypeError, ValueError):
             raise QrError("unknown must be a number") from None
-        _check(lib().qr_pt_adapt_views_variance_async(self.scene._h, ctypes.c_void_p(self.state.data_ptr()), n, w, h,
-                                                      ctypes.c_float(unknown), ctypes.c_void_p(out.data_ptr()), 0,
+        _check(lib().qr_pt_adapt_views_variance_async(self.scene._h, self.state.data_ptr(), n, w, h, unknown, out.data_ptr(), 0,
                                                       Scene._stream_ptr(stream)))
         return out
 
     def reset(self):
         """Restart the accumulation: seeds as rays.pt_seeds in every view, every other plane 0.  Synchronous
         (qr_pt_adapt_views_reset)."""
-        _check(lib().qr_pt_adapt_views_reset(self.scene._h, self.views.shape[0], self.width, self.height,
-                                             ctypes.c_void_p(self.state.data_ptr())))
+        _check(lib().qr_pt_adapt_views_reset(self.scene._h, self.views.shape[0], self.width, self.height, self.state.data_ptr()))
 
     def clone(self):
         """A checkpoint: an accumulator with a copy of the state (on the current stream) that continues independently."""
         return PtAdaptiveViews(self.scene, self.views, self.width, self.height, self.min_samples, self.max_samples, self.tol,
                                self.state.clone())
 
-    _list_arg = PtAdaptive._list_arg
-
     def open_list(self, view, index=None, count=None, stream=None):
         """The open list of one view's block (qr_pt_adapt_open_list_async on state[view] with n = slots): index[:count] = the
         slots of that view the stop rule would still let take a sample, ascending; index[count:] is not written.  Returns
         (index int32 [slots], count int32 [1]), the accumulator's own tensors (allocated on first use, written again by every
         call) or the caller's.  Asynchronous on `stream`."""
-        import torch
-        n, dev = self.slots, f"cuda:{self.scene.device}"
         if not (isinstance(view, int) and 0 <= view < self.views.shape[0]):
             raise QrError(f"view must be an integer, 0..{self.views.shape[0] - 1}")
-        if index is None:
-            if self._list_index is None:
-                self._list_index = torch.empty((n,), dtype=torch.int32, device=dev)
-            index = self._list_index
-        if count is None:
-            if self._list_count is None:
-                self._list_count = torch.zeros((1,), dtype=torch.int32, device=dev)
-            count = self._list_count
-        index, count = self._list_arg(index, (n,), "index"), self._list_arg(count, (1,), "count")
-        if self._list_work is None:
-            nbytes = ctypes.c_uint64()
-            _check(lib().qr_pt_adapt_list_work_bytes(self.scene._h, n, ctypes.byref(nbytes)))
-            self._list_work = torch.empty((max(1, nbytes.value // 4),), dtype=torch.int32, device=dev)
-        _check(lib().qr_pt_adapt_open_list_async(self.scene._h, ctypes.c_void_p(self.state[view].data_ptr()), n, self.min_samples,
-                                                 self.max_samples, ctypes.c_float(float(self.tol2)),
-                                                 ctypes.c_void_p(index.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                                                 ctypes.c_void_p(self._list_work.data_ptr()), 0, Scene._stream_ptr(stream)))
-        return index, count
+        return self._open_list(self.state[view], self.slots, index, count, stream)
 
     def step(self, samples=1, frames=None, mean=False, counts=False, open=False, stream=None):
         """Offer every pixel sample of every view up to `samples` (1 .. PT_ADAPT_VIEWS_MAX_SAMPLES) candidate samples in ONE
@@ -1448,49 +1279,14 @@ class PtAdaptiveViews:
         one-element int32 / uint32 tensor on the scene's device; step zeroes it on `stream` and the launch adds the number of
         slots that would still take a sample.  Returns frames alone, or the tuple (frames, mean, counts, open) without the ones
         not wanted.  The scene's current depth (set_depth) applies.  Asynchronous on `stream`."""
-        import torch
         n, h, w, dev = self.views.shape[0], self.height, self.width, self.scene.device
-        if frames is None:
-            frames = torch.empty((n, h, w), dtype=torch.int32, device=self.views.device)    # every pixel is written
-        elif not (isinstance(frames, torch.Tensor) and frames.dtype == torch.int32 and tuple(frames.shape) == (n, h, w)
-                  and frames.is_contiguous() and frames.is_cuda and frames.device.index == dev):
-            raise QrError(f"frames must be a contiguous int32 [{n}, {h}, {w}] tensor on cuda:{dev}")
-        if mean is True:
-            mean = torch.empty((n, h, w, 3), dtype=torch.float32, device=self.views.device)
-        elif mean is False or mean is None:
-            mean = None
-        elif not (isinstance(mean, torch.Tensor) and mean.dtype == torch.float32 and tuple(mean.shape) == (n, h, w, 3)
-                  and mean.is_contiguous() and mean.is_cuda and mean.device.index == dev):
-            raise QrError(f"mean must be True, False or a contiguous float32 [{n}, {h}, {w}, 3] tensor on cuda:{dev}")
-        if counts is True:
-            counts = torch.empty((n, h, w), dtype=torch.int32, device=self.views.device)
-        elif counts is False or counts is None:
-            counts = None
-        elif not (isinstance(counts, torch.Tensor) and counts.dtype == torch.int32 and tuple(counts.shape) == (n, h, w)
-                  and counts.is_contiguous() and counts.is_cuda and counts.device.index == dev):
-            raise QrError(f"counts must be True, False or a contiguous int32 [{n}, {h}, {w}] tensor on cuda:{dev}")
-        opent = None
-        if open is True:
-            opent = torch.empty((1,), dtype=torch.int32, device=self.views.device)
-        elif not (open is False or open is None):
-            if not (isinstance(open, torch.Tensor) and open.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
-                    and open.numel() == 1 and open.is_contiguous() and open.is_cuda and open.device.index == dev):
-                raise QrError(f"open must be True, False or a one-element int32 or uint32 tensor on cuda:{dev}")
-            opent = open
-        if not isinstance(samples, int):
-            raise QrError("samples must be an integer")
-        if not 1 <= samples <= PT_ADAPT_VIEWS_MAX_SAMPLES:
-            raise QrError(f"samples must be 1..{PT_ADAPT_VIEWS_MAX_SAMPLES}")
-        if opent is not None:
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-                opent.zero_()
-        _check(lib().qr_pt_adapt_views_async(self.scene._h, ctypes.c_void_p(self.views.data_ptr()), n, w, h,
-                                             ctypes.c_void_p(self.state.data_ptr()), samples, self.min_samples, self.max_samples,
-                                             ctypes.c_float(float(self.tol2)), ctypes.c_void_p(frames.data_ptr()),
-                                             ctypes.c_void_p(mean.data_ptr() if mean is not None else None),
-                                             ctypes.c_void_p(counts.data_ptr() if counts is not None else None),
-                                             ctypes.c_void_p(opent.data_ptr() if opent is not None else None), 0,
-                                             Scene._stream_ptr(stream)))
+        frames = _fill("frames", frames, "int32", (n, h, w), dev)
+        mean = _wanted("mean", mean, "float32", (n, h, w, 3), dev)
+        counts = _wanted("counts", counts, "int32", (n, h, w), dev)
+        opent = self._open_counter(open, samples, PT_ADAPT_VIEWS_MAX_SAMPLES, stream)
+        _check(lib().qr_pt_adapt_views_async(self.scene._h, self.views.data_ptr(), n, w, h, self.state.data_ptr(), samples,
+                                             self.min_samples, self.max_samples, float(self.tol2), frames.data_ptr(), _ptr(mean),
+                                             _ptr(counts), _ptr(opent), 0, Scene._stream_ptr(stream)))
         out = (frames,) + tuple(t for t in (mean, counts, opent) if t is not None)
         return out if len(out) > 1 else frames
 
