@@ -600,13 +600,6 @@ extern "C" int qr_render_count(qr_device_scene *s, void *frame_dev, void *stream
         fprintf(stderr, "\nQR_PROF frames pushed by level 0..7+ (lanes), one child:    ");
         for (int i = 0; i < 8; i++) fprintf(stderr, " %llu", pf[40 + i]);
         fprintf(stderr, "\n");
-#ifdef QR_PROF_BVSPH_DRY
-        /* the array cut of walk_list, evaluated and not acted on (QR_CUT_BVSPH, profiles/r22_array_cull.txt) */
-        static const char *an[6] = { "(a) array cells reached", "(b) left by `far` for every ray that is on", "(c) volume test run, no ray enters",
-            "(d) cull sphere: every ray that is on misses", "(e) rays ruled out while others go on", "    (d) within (c)" };
-        for (int k = 0; k < 2; k++)
-            for (int i = 0; i < 6; i++) fprintf(stderr, "QR_PROF arrays, %s walks: %-44s %llu\n", k ? "nearest-hit" : "shadow", an[i], pf[50 + 6 * k + i]);
-#endif
         fprintf(stderr, "QR_PROF trnode cells reached %llu, ranges that end without a member handed out %llu\n", pf[62], pf[63]);
         unsigned long long z[64] = {0};
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(qr_prof), z, sizeof(z)));
@@ -616,7 +609,7 @@ extern "C" int qr_render_count(qr_device_scene *s, void *frame_dev, void *stream
     {
         unsigned long long st[60];
         HIP_TRY(hipMemcpy(st, s->d_counters + 4, sizeof(st), hipMemcpyDeviceToHost));
-        /* arrays with a cull sphere in the packet walks (walk_list, QR_CUT_BVSPH) */
+        /* arrays with a cull sphere in the packet walks (walk_list, profiles/r22_array_cull.txt) */
         for (int k = 0; k < 3; k++)
         {
             static const char *kind[3] = { "shadow", "primary", "secondary" };

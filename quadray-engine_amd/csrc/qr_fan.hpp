@@ -55,11 +55,7 @@ struct FanP
  * HITS: two of record i's three 16-byte pieces, no walk; n > 0: a lane past the end reads record 0 and traces nothing. */
 template <int SRC, bool DIVK, bool COHERENT>
 __device__ __forceinline__ bool fan_element(BaseP B, const char *G, const f32x4 *__restrict__ src, int32_t n, const ViewsP &vp,
-                                            size_t &rec, V3 &pos, V3 &nrm, bool &has
-#ifdef QR_STATS
-                                            , unsigned long long *stats
-#endif
-                                            )
+                                            size_t &rec, V3 &pos, V3 &nrm, bool &has, WalkStats stats)
 {
     bool active;
     pos = {0.0f, 0.0f, 0.0f}; nrm = {0.0f, 0.0f, 0.0f};
@@ -83,11 +79,7 @@ __device__ __forceinline__ bool fan_element(BaseP B, const char *G, const f32x4 
 
         Hit h;
         bool occ0 = false;
-        traverse<false, DIVK, true>(B, active, SRC == QR_FAN_SRC_VIEW || COHERENT, r, h, occ0
-#ifdef QR_STATS
-                                    , stats
-#endif
-                                    );
+        traverse<false, DIVK, true>(B, active, SRC == QR_FAN_SRC_VIEW || COHERENT, r, h, occ0, stats);
         has = active && h.srf != 0;
         if (has)
         {
@@ -126,7 +118,6 @@ void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src,
     const BaseP B = (BaseP)blob;
     const QR_CONST f32x4 *dirs = (const QR_CONST f32x4 *)fp.dirs;
 #pragma clang diagnostic pop
-    (void)stats;
     const FrmP fr = c_frm(B);
     bool active;
     size_t rec;                                 /* this lane's element */
@@ -157,11 +148,7 @@ void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src,
 
         Hit h;
         bool occ0 = false;
-        traverse<false, DIVK, true>(B, active, SRC == QR_FAN_SRC_VIEW || COHERENT, r, h, occ0
-#ifdef QR_STATS
-                                    , stats
-#endif
-                                    );
+        traverse<false, DIVK, true>(B, active, SRC == QR_FAN_SRC_VIEW || COHERENT, r, h, occ0, stats);
         has = active && h.srf != 0;
         if (has)
         {
@@ -169,11 +156,7 @@ void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src,
             surface_point(blob, fr->off_shade, r, h, pos, nrm, tex, mo);
         }
     }
-    else active = fan_element<SRC, DIVK, COHERENT>(B, blob, src, n, vp, rec, pos, nrm, has
-#ifdef QR_STATS
-                                                   , stats
-#endif
-                                                   );
+    else active = fan_element<SRC, DIVK, COHERENT>(B, blob, src, n, vp, rec, pos, nrm, has, stats);
 
     /* the fan: every lane of the wave stays in the loop (the walks are wave-wide), lanes without a surface point trace nothing */
     const bool coherent = (SRC == QR_FAN_SRC_VIEW || COHERENT) && fp.flip == 0u;
@@ -195,11 +178,7 @@ void qr_fan_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ src,
             f.ploc = {0.0f, 0.0f, 0.0f};
             Hit fh;
             bool occ = false;
-            traverse<true, DIVK, true>(B, traced, coherent, f, fh, occ
-#ifdef QR_STATS
-                                       , stats
-#endif
-                                       );
+            traverse<true, DIVK, true>(B, traced, coherent, f, fh, occ, stats);
             open = traced && !occ;
         }
         /* the end of direction k: kept as text in both fan kernels (as a function it cost the view instances time) */

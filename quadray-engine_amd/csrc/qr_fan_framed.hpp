@@ -92,15 +92,10 @@ void qr_fan_framed_kernel(const char *__restrict__ blob, const f32x4 *__restrict
     const BaseP B = (BaseP)blob;
     const QR_CONST f32x4 *dirs = (const QR_CONST f32x4 *)fp.dirs;
 #pragma clang diagnostic pop
-    (void)stats;
     size_t rec;                                 /* this lane's element */
     V3 pos, nrm;
     bool has = false;
-    const bool active = fan_element<SRC, DIVK, COHERENT>(B, blob, src, n, vp, rec, pos, nrm, has
-#ifdef QR_STATS
-                                                         , stats
-#endif
-                                                         );
+    const bool active = fan_element<SRC, DIVK, COHERENT>(B, blob, src, n, vp, rec, pos, nrm, has, stats);
 
     /* the frame: rec is inside the launch for every lane (element 0 for the lanes past it) */
     float c = 1.0f, sn = 0.0f;
@@ -133,11 +128,7 @@ void qr_fan_framed_kernel(const char *__restrict__ blob, const f32x4 *__restrict
             f.ploc = {0.0f, 0.0f, 0.0f};
             Hit fh;
             bool occ = false;
-            traverse<true, DIVK, true>(B, traced, coherent, f, fh, occ
-#ifdef QR_STATS
-                                       , stats
-#endif
-                                       );
+            traverse<true, DIVK, true>(B, traced, coherent, f, fh, occ, stats);
             open = traced && !occ;
         }
         /* the end of direction k: kept as text in both fan kernels (as a function it cost the view instances time) */
@@ -171,11 +162,7 @@ void qr_gather_framed_kernel(LaunchP lp, const f32x4 *__restrict__ src, int32_t 
         size_t rec;                             /* this lane's element */
         V3 pos, nrm;
         bool has = false;
-        const bool active = fan_element<SRC, DIVK, COHERENT>(B, lp.B, src, n, vp, rec, pos, nrm, has
-#ifdef QR_STATS
-                                                             , lp.stats
-#endif
-                                                             );
+        const bool active = fan_element<SRC, DIVK, COHERENT>(B, lp.B, src, n, vp, rec, pos, nrm, has, lp.stats);
 
         /* the frame's validity is decided here, once; u and v are computed again where a direction is traced */
         float c = 1.0f, sn = 0.0f;

@@ -117,11 +117,7 @@ void qr_gather_kernel(LaunchP lp, const f32x4 *__restrict__ src, int32_t n, View
         size_t rec;                             /* this lane's element */
         V3 pos, nrm;
         bool has = false;
-        const bool active = fan_element<SRC, DIVK, COHERENT>(B, lp.B, src, n, vp, rec, pos, nrm, has
-#ifdef QR_STATS
-                                                             , lp.stats
-#endif
-                                                             );
+        const bool active = fan_element<SRC, DIVK, COHERENT>(B, lp.B, src, n, vp, rec, pos, nrm, has, lp.stats);
 
         /* the start: zeros, or with QR_GATHER_RESUME the element's row and count (an element without a surface point reads none) */
         f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};

@@ -209,7 +209,6 @@ void qr_hit_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ rays
 #pragma clang diagnostic ignored "-Wold-style-cast"
     const BaseP B = (BaseP)blob;
 #pragma clang diagnostic pop
-    (void)stats;
     const FrmP fr = c_frm(B);
     bool active;
     size_t rec;                                 /* this lane's record in `out` */
@@ -233,11 +232,7 @@ void qr_hit_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ rays
 
     Hit h;
     bool occ = false;
-    traverse<false, DIVK, true>(B, active, VIEW || COHERENT, r, h, occ
-#ifdef QR_STATS
-                                , stats
-#endif
-                                );
+    traverse<false, DIVK, true>(B, active, VIEW || COHERENT, r, h, occ, stats);
     if (!active) return;
 
     V3 hit = {0.0f, 0.0f, 0.0f}, nrm = {0.0f, 0.0f, 0.0f}, tex = {0.0f, 0.0f, 0.0f};

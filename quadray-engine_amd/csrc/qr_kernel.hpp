@@ -104,6 +104,34 @@ __device__ unsigned long long qr_prof[64];
 #define QR_CULL_FLOPS(n) do { } while (0)
 #endif
 
+/* The diagnostic builds enter the walks, shade() and render_wave through these hooks alone: QR_ST(...) holds statements
+ * and declarations of the -DQR_STATS build, QR_PF(...) of -DQR_PROF, QR_WT(...) of -DQR_WAVETIME (tools/gpu_wavetime.py), QR_GD(...)
+ * of the guarded statistics build (-DQR_STATS -DQR_GUARD); each expands to nothing in every other build, the product's among them.
+ * WalkStats is the counter block as the walks take it, always: the pointer itself in the statistics build, and an empty object made
+ * from that pointer -- no register, no argument -- elsewhere (Ctx::stats and LaunchP::stats stay pointers). */
+#ifdef QR_STATS
+typedef unsigned long long *WalkStats;
+#define QR_ST(...) __VA_ARGS__
+#else
+struct WalkStats { __device__ __forceinline__ WalkStats(unsigned long long *) {} };
+#define QR_ST(...)
+#endif
+#ifdef QR_PROF
+#define QR_PF(...) __VA_ARGS__
+#else
+#define QR_PF(...)
+#endif
+#ifdef QR_WAVETIME
+#define QR_WT(...) __VA_ARGS__
+#else
+#define QR_WT(...)
+#endif
+#if defined(QR_STATS) && defined(QR_GUARD)
+#define QR_GD(...) __VA_ARGS__
+#else
+#define QR_GD(...)
+#endif
+
 /* what a launch needs besides the scene image: kernel arguments */
 struct LaunchP
 {
@@ -351,12 +379,10 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
     static_assert(!PTR || PT, "the path-traced ray instance is a path-tracer instance");
     static_assert(!GATHER || !PT, "the gather instance is a ray-tracer instance");
     (void)mean_out; (void)rng_io; (void)pr; (void)take; (void)ray_i; (void)ray_in; (void)coh_in;
-#ifdef QR_WAVETIME
-    const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long wt_clk0 = __builtin_amdgcn_s_memtime();      /* shader cycles: with the 100 MHz stamps, the clock the wave ran at */
-    qr_wt_groups[0] = 0; qr_wt_groups[1] = 0; qr_wt_shadow = 0; qr_wt_cells[0] = qr_wt_cells[1] = qr_wt_cells[2] = qr_wt_cells[3] = 0;
-    unsigned long long wt_mid = 0, wt_trav = 0, wt_shade = 0, wt_t0 = 0; u32 wt_push = 0;
-#endif
+    QR_WT(const unsigned long long wt_start = __builtin_amdgcn_s_memrealtime();)
+    QR_WT(const unsigned long long wt_clk0 = __builtin_amdgcn_s_memtime();)      /* shader cycles: with the 100 MHz stamps, the clock the wave ran at */
+    QR_WT(qr_wt_groups[0] = 0; qr_wt_groups[1] = 0; qr_wt_shadow = 0; qr_wt_cells[0] = qr_wt_cells[1] = qr_wt_cells[2] = qr_wt_cells[3] = 0;)
+    QR_WT(unsigned long long wt_mid = 0, wt_trav = 0, wt_shade = 0, wt_t0 = 0; u32 wt_push = 0;)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wold-style-cast"
     Ctx cx;
@@ -641,26 +667,18 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
         if (any_lane(tr))
         {
             Hit h; bool occ;
-#ifdef QR_WAVETIME
-            wt_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
+            QR_WT(wt_t0 = __builtin_amdgcn_s_memrealtime();)
 #if QR_DYN_PRIO
             if constexpr (!RAYS)
                 if (prio_round < 3) { prio_round++; if (prio_round == 2) __builtin_amdgcn_s_setprio(2); else if (prio_round == 3) __builtin_amdgcn_s_setprio(3); }
 #endif
             /* coherent: every ray of this round is a primary ray (neighbouring pixels; caller rays only when vouched for) */
             const bool coherent = (GATHER ? coh_in : (RAYS != 1 && RAYS != 6 && RAYS != 7 && RAYS != 8)) && !any_lane(tr && sp != 0);
-            traverse<false, DIVK, RAYS != 0>(B, tr, coherent, ray, h, occ
-#ifdef QR_STATS
-                            , cx.stats
-#endif
-                            );
-#ifdef QR_WAVETIME
-            if (wt_mid == 0) wt_mid = __builtin_amdgcn_s_memrealtime();
-            wt_push++;
-            wt_trav += __builtin_amdgcn_s_memrealtime() - wt_t0;
-            wt_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
+            traverse<false, DIVK, RAYS != 0>(B, tr, coherent, ray, h, occ, cx.stats);
+            QR_WT(if (wt_mid == 0) wt_mid = __builtin_amdgcn_s_memrealtime();)
+            QR_WT(wt_push++;)
+            QR_WT(wt_trav += __builtin_amdgcn_s_memrealtime() - wt_t0;)
+            QR_WT(wt_t0 = __builtin_amdgcn_s_memrealtime();)
             if constexpr (VIEW && !PTV)
             {
                 /* the first hit's t (the view's t_max where there is none), sample 0's: stored here, in the only round whose
@@ -685,9 +703,7 @@ __device__ __forceinline__ void render_wave(const LaunchP &lp, const u32 ord, co
 
             Shaded o;
             shade<COUNT, DIVK, PT>(cx, got, coherent, ray, h, o, cnt, &rng, depth - sp);
-#ifdef QR_WAVETIME
-            wt_shade += __builtin_amdgcn_s_memrealtime() - wt_t0;
-#endif
+            QR_WT(wt_shade += __builtin_amdgcn_s_memrealtime() - wt_t0;)
 
             if (got)
             {

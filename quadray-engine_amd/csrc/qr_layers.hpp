@@ -57,7 +57,6 @@ void qr_layer_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ ra
 #pragma clang diagnostic ignored "-Wold-style-cast"
     const BaseP B = (BaseP)blob;
 #pragma clang diagnostic pop
-    (void)stats;
     const FrmP fr = c_frm(B);
     size_t rec;                                 /* this lane's element */
     Ray r;
@@ -75,11 +74,7 @@ void qr_layer_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ ra
         r.list = alive ? qlist : 0u;
         Hit h;
         bool occ = false;
-        traverse<false, DIVK, true>(B, alive, VIEW || COHERENT, r, h, occ
-#ifdef QR_STATS
-                                    , stats
-#endif
-                                    );
+        traverse<false, DIVK, true>(B, alive, VIEW || COHERENT, r, h, occ, stats);
         /* a lane that did not walk or did not hit holds traverse's defaults: h.t = r.tmax, h.srf = 0 */
         const bool hit = alive && h.srf != 0;
         const size_t e = (size_t)j * elems + rec;

@@ -41,7 +41,6 @@ void qr_trace_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ ra
 #pragma clang diagnostic ignored "-Wold-style-cast"
     const BaseP B = (BaseP)blob;
 #pragma clang diagnostic pop
-    (void)stats;
     const int64_t i = (int64_t)blockIdx.x * QR_BLOCK + (int64_t)threadIdx.x;
     const bool active = i < (int64_t)n;
     Ray r;
@@ -58,11 +57,7 @@ void qr_trace_kernel(const char *__restrict__ blob, const f32x4 *__restrict__ ra
     }
     Hit h;
     bool occ = false;
-    traverse<SHADOW, true, true>(B, active, COHERENT, r, h, occ
-#ifdef QR_STATS
-                           , stats
-#endif
-                           );
+    traverse<SHADOW, true, true>(B, active, COHERENT, r, h, occ, stats);
     if (!active) return;
     if constexpr (SHADOW) occ_out[i] = occ ? 1 : 0;
     else

@@ -29,23 +29,15 @@ struct Frame
 #endif
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-/* Work a hit used to repeat, each cut bit-exact by construction and switchable for A/B builds
- * (make variant NAME=x EXTRA=-DQR_CUT_...=0): */
-#ifndef QR_CUT_TEXEL
-#define QR_CUT_TEXEL 1      /* a one-texel material's colour comes finished from the image's material record (QR_MATF_COLOUR, written
-                             * by qr_compile.cpp): no texel load, no conversions, no divisions by `clamp` */
-#endif
-#ifndef QR_CUT_TEXLUT
-#define QR_CUT_TEXLUT 1     /* a textured material with channels of at most 8 bits: each channel's colour from the image's 256-entry
-                             * table (QR_MATF_LUT) instead of a conversion and an IEEE division */
-#endif
-#ifndef QR_CUT_RSQ
-#define QR_CUT_RSQ 1        /* light_terms: the specular block reads the diffuse block's rsq(|L|^2) */
-#endif
-#ifndef QR_CUT_NDIR
-#define QR_CUT_NDIR 1       /* a hit that takes the refraction / Fresnel block and the reflection block normalises the ray and takes
-                             * its dot product with the normal once */
-#endif
+/* Work a hit used to repeat is done once, each cut bit-exact by construction (tests/test_shade_solve_cuts.py) and measured alone on
+ * demo scene 1 at 1080p (profiles/r05_shade_solve_cuts.txt; the figure is what a frame cost more without the cut):
+ *   a one-texel material's colour comes finished from the image's material record (QR_MATF_COLOUR, written by qr_compile.cpp):
+ *     no texel load, no conversions, no divisions by `clamp` (+0.7 %);
+ *   a textured material with channels of at most 8 bits takes each channel's colour from the image's 256-entry table
+ *     (QR_MATF_LUT) instead of a conversion and an IEEE division (+1.5 %);
+ *   light_terms: the specular block reads the diffuse block's rsq(|L|^2) (+1.0 %);
+ *   a hit that takes the refraction / Fresnel block and the reflection block normalises the ray and takes its dot product with
+ *     the normal once (+0.3 %, the size of the noise there: few surfaces take both blocks; kept for the Fresnel workloads). */
 
 /* the colour of material `mt` at texel index `toff` of its texture, before gamma (MT_tex 2293-2327, PAINT_COLX 653-673) */
 __device__ __forceinline__ V3 texel_colour(const char *__restrict__ G, const qr_material *__restrict__ mt, u32 toff)
@@ -125,9 +117,7 @@ __device__ __forceinline__ void light_terms(const char *__restrict__ G, u32 mo, 
     x3 = L.z; x6 = x3 * x3;
     x4 = x4 + x5; x4 = x4 + x6;
     const float r2 = x4;
-#if QR_CUT_RSQ
     float ir = 0.0f;            /* rsq(r2) of the diffuse block, read again by the specular block */
-#endif
     x0 = dot;
     QR_FLOPS(10);
     if (props & QR_PROP_DIFFUSE)
@@ -135,9 +125,7 @@ __device__ __forceinline__ void light_terms(const char *__restrict__ G, u32 mo, 
         QR_FLOPS(17);
         x6 = x4;
         x5 = rsq(x4);
-#if QR_CUT_RSQ
         ir = x5;
-#endif
         x4 = x5 * x6;
         x6 = x6 * lg->a_qdr;
         x4 = x4 * lg->a_lnr;
@@ -172,12 +160,8 @@ __device__ __forceinline__ void light_terms(const char *__restrict__ G, u32 mo, 
             QR_FLOPS(32);
             x4 = r2;
             x5 = rsq(x6); x1 = x1 * x5;
-#if QR_CUT_RSQ
             /* the same input bits as the diffuse block's: one IEEE expansion where the material is diffuse */
             x5 = (props & QR_PROP_DIFFUSE) ? ir : rsq(x4); x1 = x1 * x5;
-#else
-            x5 = rsq(x4); x1 = x1 * x5;
-#endif
             /* fixed-point 28.4 power, 2981-3039 */
             const u32 lpow = mt->l_pow;
             u32 pw = lpow & 0xF;
@@ -334,10 +318,7 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
 
         /* MT_tex 2293-2327, PAINT_FRAG / PAINT_COLX 653-673 */
         const qr_material *__restrict__ mt = (const qr_material *)(G + mo);
-#if QR_CUT_TEXEL || QR_CUT_TEXLUT
         const u32 mfl = (u32)mt->pad[QR_MATX_FLAGS];
-#endif
-#if QR_CUT_TEXEL
         /* a one-texel texture has one colour, whatever the coordinates (both index masks are 0): converted at upload */
         if (mfl & QR_MATF_COLOUR)
         {
@@ -346,7 +327,6 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
             tex.z = u2f((u32)mt->pad[QR_MATX_COL + 2]);
         }
         else
-#endif
         {
             u32 toff = 0;
             if (props & QR_PROP_TEXTURE)
@@ -359,7 +339,6 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
                 const int32_t iv = cvt_floor(x5) & (int32_t)mt->ymask;
                 toff = (u32)iu + ((u32)iv << (mt->yshft & 31));
             }
-#if QR_CUT_TEXLUT
             if (mfl & QR_MATF_LUT)
             {
                 /* channels of at most 8 bits: a table load each instead of a conversion and an IEEE division */
@@ -369,9 +348,7 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
                 tex.y = *(const float *)(lut + ((texel >> 6) & 0x3FCu));
                 tex.z = *(const float *)(lut + ((texel << 2) & 0x3FCu));
             }
-            else
-#endif
-            tex = texel_colour(G, mt, toff);
+            else tex = texel_colour(G, mt, toff);
         }
         if (props & QR_PROP_GAMMA) { tex.x = tex.x * tex.x; tex.y = tex.y * tex.y; tex.z = tex.z * tex.z; }
 
@@ -535,17 +512,9 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
                         }
                         sr.list = sl;
                         Hit sh; bool occ;
-#ifdef QR_WAVETIME
-                        const unsigned long long wt_s0 = __builtin_amdgcn_s_memrealtime();
-#endif
-                        traverse<true, DIVK>(B, ta, false, sr, sh, occ
-#ifdef QR_STATS
-                                             , cx.stats
-#endif
-                                             );
-#ifdef QR_WAVETIME
-                        if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) qr_wt_shadow += __builtin_amdgcn_s_memrealtime() - wt_s0;
-#endif
+                        QR_WT(const unsigned long long wt_s0 = __builtin_amdgcn_s_memrealtime();)
+                        traverse<true, DIVK>(B, ta, false, sr, sh, occ, cx.stats);
+                        QR_WT(if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) qr_wt_shadow += __builtin_amdgcn_s_memrealtime() - wt_s0;)
                         if (ta && occ) atomicOr(&locc[own], 1u << jj);
                     }
                 }
@@ -626,17 +595,9 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
         if (QR_KNOB(2)) lm = false;
         if (QR_KNOB(1)) occ = false; else
         {
-#ifdef QR_WAVETIME
-            const unsigned long long wt_s0 = __builtin_amdgcn_s_memrealtime();
-#endif
-            traverse<true, DIVK>(B, lm, coherent, sr, sh, occ
-#ifdef QR_STATS
-                                  , cx.stats
-#endif
-                                  );
-#ifdef QR_WAVETIME
-            if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) qr_wt_shadow += __builtin_amdgcn_s_memrealtime() - wt_s0;
-#endif
+            QR_WT(const unsigned long long wt_s0 = __builtin_amdgcn_s_memrealtime();)
+            traverse<true, DIVK>(B, lm, coherent, sr, sh, occ, cx.stats);
+            QR_WT(if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) qr_wt_shadow += __builtin_amdgcn_s_memrealtime() - wt_s0;)
         }
         if (lm && !occ) light_terms(G, mo, props, lg, L, dot, r, nrm, tex, col);
         le = (has && !(cl.lgt & QR_CLIGHT_LAST)) ? le + (u32)sizeof(CLight) : 0u;
@@ -664,12 +625,10 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
         float x0 = 0.0f, x1, x2, x3, x4 = 0.0f, x5, x6 = 0.0f, x7 = 0.0f;
         bool m_trn = true;
         bool total_refl = false;
-#if QR_CUT_NDIR
         /* the refraction / Fresnel block's normalised ray and its dot product with the normal, for the reflection block
          * right behind it (same operations in the same order there) */
         bool have_nd = false;
         float nd1 = 0.0f, nd2 = 0.0f, nd3 = 0.0f, ndn = 0.0f;
-#endif
 
         /* transparency 3185-3552 */
         if (!(props & QR_PROP_OPAQUE))
@@ -689,9 +648,7 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
                 x7 = x2 * nrm.y; x0 = x0 + x7;
                 x7 = x3 * nrm.z; x0 = x0 + x7;
                 x4 = x0;
-#if QR_CUT_NDIR
                 have_nd = true; nd1 = x1; nd2 = x2; nd3 = x3; ndn = x0;
-#endif
                 x6 = mt->c_rfr;
                 x0 = x0 * x6;
                 x7 = x0 * x0;
@@ -772,14 +729,12 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
             (!(props & QR_PROP_OPAQUE) && (props & QR_PROP_FRESNEL)))
         {
             QR_FLOPS(24);
-#if QR_CUT_NDIR
             if (have_nd)
             {
                 x1 = nd1; x2 = nd2; x3 = nd3; x0 = ndn;
                 x4 = nrm.x; x5 = nrm.y; x6 = nrm.z;
             }
             else
-#endif
             {
                 x1 = r.dir.x; x4 = nrm.x; x7 = x1 * x1; x0 = x7;
                 x2 = r.dir.y; x5 = nrm.y; x7 = x2 * x2; x0 = x0 + x7;

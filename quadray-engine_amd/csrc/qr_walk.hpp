@@ -32,11 +32,6 @@ typedef unsigned long long lm_t;
 #define QR_GUARD_POS(tag, p, prev, onbad) do { } while (0)
 #endif
 #define LM(cond) __builtin_amdgcn_ballot_w64(cond)
-#ifndef QR_CLIP_PREFETCH
-#define QR_CLIP_PREFETCH 0  /* 1: clip() loads the next cell of a clipper program while the current one is evaluated.  Measured: no
-                             * change for a band of the slowest footprints rendered alone (92.3 / 92.6 us), 1.6 % slower frames (two
-                             * more spilled scalar registers): the cells of a program share cache lines, the waits are elsewhere */
-#endif
 __device__ __forceinline__ bool lane_of(lm_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 __device__ __forceinline__ bool any_lane(bool b) { return LM(b) != 0ull; }
 
@@ -65,10 +60,8 @@ template <> struct MK<true>
     static __device__ __forceinline__ T none() { return false; }
 };
 
-#ifdef QR_PROF
-__device__ __forceinline__ unsigned long long qr_lanes(lm_t m) { return (unsigned long long)__popcll(m); }
-__device__ __forceinline__ unsigned long long qr_lanes(bool m) { return (unsigned long long)__popcll(__ballot(m)); }
-#endif
+QR_PF(__device__ __forceinline__ unsigned long long qr_lanes(lm_t m) { return (unsigned long long)__popcll(m); })
+QR_PF(__device__ __forceinline__ unsigned long long qr_lanes(bool m) { return (unsigned long long)__popcll(__ballot(m)); })
 
 /* what clip() needs to know about the candidate's surface space */
 template <bool DIV>
@@ -123,32 +116,10 @@ __device__ __forceinline__ V3 xform(BaseP B, u32 off, bool full, V3 in)
     return o;
 }
 
-#ifndef QR_CUT_ROOT2
-#define QR_CUT_ROOT2 0      /* solve_cell: a quadric's second root is divided only where a lane reads it (0: both roots always).  OFF: it
-                             * lost its A/B -- demo scene 1 at 1080p 1.8 % slower with it (profiles/r05_shade_solve_cuts.txt) */
-#endif
-#ifndef QR_CUT_XFORM2
-#define QR_CUT_XFORM2 1     /* diff and ray through one record's matrix: the coefficients loaded once, `full` decided once (0: two xform calls) */
-#endif
-#ifndef QR_CUT_BVSPH
-#define QR_CUT_BVSPH 1      /* walk_list: a bounding-volume array whose cull sphere every ray that is on misses sideways is skipped inside the
-                             * cull run, and a ray that misses it stays out of the volume test (0: arrays always end the run and only the
-                             * behind / beyond test is made, profiles/r22_array_cull.txt) */
-#endif
-/* -DQR_PROF -DQR_PROF_BVSPH_DRY (the count of profiles/r22_array_cull.txt): the walk of QR_CUT_BVSPH=0, which besides counts what
- * the cut would decide (qr_prof[50..61]) without acting on it.  The plain QR_PROF build walks as the product does. */
-#if defined(QR_PROF_BVSPH_DRY) && !defined(QR_PROF)
-#error "QR_PROF_BVSPH_DRY is a mode of the QR_PROF build"
-#endif
-#if QR_CUT_BVSPH && !defined(QR_PROF_BVSPH_DRY)
-#define QR_BVSPH_ACT 1
-#else
-#define QR_BVSPH_ACT 0
-#endif
-/* xform of `a` and of `b` with the same record: each with xform's operations in xform's order */
+/* xform of `a` and of `b` with the same record: each with xform's operations in xform's order, the coefficients loaded once and
+ * `full` decided once (two xform calls instead: demo scene 1 at 1080p 1.5 % slower, profiles/r05_shade_solve_cuts.txt) */
 __device__ __forceinline__ void xform2(BaseP B, u32 off, bool full, V3 a, V3 b, V3 &oa, V3 &ob)
 {
-#if QR_CUT_XFORM2
     const QR_CONST DSurf *p = (const QR_CONST DSurf *)(B + off);
     const float m00 = p->tci[0], m11 = p->tcj[1], m22 = p->tck[2];
     float a4 = m00 * a.x, b4 = m00 * b.x;
@@ -166,10 +137,6 @@ __device__ __forceinline__ void xform2(BaseP B, u32 off, bool full, V3 a, V3 b, 
     }
     oa.x = a4; oa.y = a5; oa.z = a6;
     ob.x = b4; ob.y = b5; ob.z = b6;
-#else
-    oa = xform(B, off, full, a);
-    ob = xform(B, off, full, b);
-#endif
 }
 
 __device__ __forceinline__ float sel3(float a, float b, float c, u32 i) { return i == 0 ? a : i == 1 ? b : c; }
@@ -318,24 +285,14 @@ __device__ __forceinline__ typename MK<DIV>::T clip(BaseP B, const SurfS &s, u32
         V3 cxyz = {0.0f, 0.0f, 0.0f};                   /* the hit in the cached clipper trnode's space */
         V3 pt = hit;                                    /* what a fast plane cell reads: the world hit, or cxyz while a trnode group lasts */
         u32 cp = s.clip;
-#if QR_CLIP_PREFETCH
-        /* the program's cells lie one behind the other: the next one is on its way while this one is evaluated (a lone
-         * wave in the tail of a frame otherwise waits out one scalar-cache round trip per cell).  The cell behind the END
-         * cell is read and dropped: programs are followed by other sections of the image or its tail padding. */
-        if constexpr (!DIV) cp = __builtin_amdgcn_readfirstlane(cp);
-        u32x8 cn = *(const QR_CONST u32x8 *)(B + cp);
-#endif
+        /* Each cell is loaded when it is evaluated.  Loading the next cell of the program meanwhile was tried: no change for a band
+         * of the slowest footprints rendered alone (92.3 / 92.6 us), 1.6 % slower frames (two more spilled scalar registers) -- the
+         * cells of a program share cache lines, the waits are elsewhere */
         for (;;)
         {
             if constexpr (!DIV) cp = __builtin_amdgcn_readfirstlane(cp);
-#if QR_CLIP_PREFETCH
-            const u32x8 cc = cn;
-            cp += (u32)sizeof(CClip);
-            if (cc.s0 != 0) cn = *(const QR_CONST u32x8 *)(B + cp);
-#else
             const u32x8 cc = *(const QR_CONST u32x8 *)(B + cp);
             cp += (u32)sizeof(CClip);
-#endif
             const u32 cop = cc.s0;
             if (cop == 0) break;
             QR_PROF_HIT(2);             /* clipper cells */
@@ -451,11 +408,9 @@ __device__ __forceinline__ bool bv_hit(const V3 &ry, const V3 &df, float sci0, f
     return cle(0.0f, x3);
 }
 
-#ifdef QR_WAVETIME
-__shared__ unsigned qr_wt_groups[2];    /* list groups walked by this wave: nearest-hit, shadow (tools/gpu_wavetime.py) */
-__shared__ unsigned long long qr_wt_shadow;     /* 100 MHz ticks spent in shadow traversals */
-__shared__ unsigned qr_wt_cells[4];     /* packet walks of this wave: cells looked at (nearest-hit, shadow), cells solved (nearest-hit, shadow) */
-#endif
+QR_WT(__shared__ unsigned qr_wt_groups[2];)     /* list groups walked by this wave: nearest-hit, shadow (tools/gpu_wavetime.py) */
+QR_WT(__shared__ unsigned long long qr_wt_shadow;)      /* 100 MHz ticks spent in shadow traversals */
+QR_WT(__shared__ unsigned qr_wt_cells[4];)      /* packet walks of this wave: cells looked at (nearest-hit, shadow), cells solved (nearest-hit, shadow) */
 
 /* per-lane state of one list walk */
 struct WalkState
@@ -520,12 +475,6 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
     {
         /* up to two candidate roots per lane, in the lane's own order */
         float ct0 = 0.0f, ct1 = 0.0f;
-#if QR_CUT_ROOT2
-        /* quadric without near-zero discriminant lanes: the second candidate's root as numerator and denominator, divided
-         * only when some lane still asks for it after the first candidate went through clip() */
-        bool lazy1 = false;
-        float ct1n = 0.0f, ct1d = 1.0f;
-#endif
         int   cs0 = 0, cs1 = 0;
         mask_t cm0 = K::none(), cm1 = K::none();
         int   ncand = 0;
@@ -623,23 +572,11 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
                     }
                 }
                 const bool inner_first = cgt(0.0f, a);      /* only read where xmask holds */
-                float t1, t2;
-#if QR_CUT_ROOT2
-                /* the roots meet only in the lanes of dmask (t1 - t2 below); without such a lane each candidate slot is its
-                 * own division of the operands selected per lane: the same operands, the same quotient bits */
-                lazy1 = !K::any(dmask);
-                if (lazy1)
-                {
-                    t1 = (inner_first ? t2n : t1n) / (inner_first ? t2d : t1d);     /* the first candidate's root */
-                    t2 = 0.0f;
-                    ct1n = inner_first ? t1n : t2n; ct1d = inner_first ? t1d : t2d;
-                }
-                else
-#endif
-                {
-                    t1 = t1n / t1d;
-                    t2 = t2n / t2d;
-                }
+                /* both roots are divided at once.  Dividing the second only where a lane still reads it after the first went through
+                 * clip() lost its A/B: demo scene 1 at 1080p 1.8 % slower, 11 -> 19 spilled scalar registers and a divergent division
+                 * in the candidate loop (profiles/r05_shade_solve_cuts.txt) */
+                float t1 = t1n / t1d;
+                float t2 = t2n / t2d;
                 const mask_t t1msk = K::of(cne(t1d, 0.0f));
                 const mask_t t2msk = K::of(cne(t2d, 0.0f));
                 if (K::any(dmask))
@@ -673,11 +610,7 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
                     mi2 = mi2 & K::inv(same & K::inv(so));
                 }
                 ncand = 2;
-#if QR_CUT_ROOT2
-                if (lazy1) ct0 = t1;
-                else
-#endif
-                { ct0 = inner_first ? t2 : t1; ct1 = inner_first ? t1 : t2; }
+                ct0 = inner_first ? t2 : t1; ct1 = inner_first ? t1 : t2;
                 cs0 = inner_first ? 1 : 0;   cs1 = inner_first ? 0 : 1;
                 const mask_t inf = K::of(inner_first);
                 cm0 = (inf & mi2) | (K::inv(inf) & mo); cm1 = (inf & mo) | (K::inv(inf) & mi2);
@@ -694,9 +627,6 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
             const int side = p == 0 ? cs0 : cs1;
             mask_t m = (p == 0 ? cm0 : cm1) & K::inv(done);
             if (!K::any(m)) continue;
-#if QR_CUT_ROOT2
-            if (p != 0 && lazy1) ct1 = ct1n / ct1d;
-#endif
             const float t = p == 0 ? ct0 : ct1;
             V3 loc;
             m = clip<DIV, CLIPL>(B, s, op, r, w.tbuf, ci, t, side, m, loc);
@@ -750,7 +680,9 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
  * max(tn, 0) > min(tf, tb1)  (max / min drop a NaN operand exactly where the three compares were false).
  */
 /*
- * Arrays in the run (QR_CUT_BVSPH).  A bounding-volume cell with a cull sphere (QR_OPF_CULL | QR_OPT_BV: s96 == 40 after the mask)
+ * Arrays in the run (profiles/r22_array_cull.txt; before it an array always ended the run and only the behind / beyond test was made:
+ * that walk, rebuilt for the A/B, took 0.04239 against 0.04182 ms per step on demo scene 1, 0.24317 against 0.22934 on demo scene 2 and
+ * 0.63214 against 0.62408 on the swarm).  A bounding-volume cell with a cull sphere (QR_OPF_CULL | QR_OPT_BV: s96 == 40 after the mask)
  * takes the solver cells' sphere test with R2 = R * R and the "origin outside" threshold 1.01 * R2 computed here: slot 2 of such
  * a cell is the array's end offset and slot 3 walk_pool's marker, never an R2.  When no ray that is on needs the array the cursor
  * becomes that end offset and the run goes on; otherwise the cell is handed out with the verdict per ray.  When every ray that is
@@ -765,7 +697,6 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
  * rule of the hand-out path rests on too.  Lanes that are off are compared by resume <= pos, never by equality: a jump cannot
  * strand one, and nesting puts their resume point at or behind the jump's target.
  */
-#if QR_BVSPH_ACT
 #ifdef QR_STATS
 /* the guarded diagnostic build counts, with s[96:97] still the rays that are on: arrays jumped; of them with rays waiting at an enclosing
  * array's end (off and not occluded); of them onto the list's END cell; arrays that leave by the all-inside exit with some ray on */
@@ -787,14 +718,13 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
             "s_cselect_b32 s98, 1, 0\n" \
             "s_add_u32 %[ni], %[ni], s98\n" \
             "s_branch qr_cull_out_%=\n"
-#define QR_RUN_NJ_OP , [am] "=&s"(am), [nj] "+s"(njl.jump), [nw] "+s"(njl.jwait), [ne] "+s"(njl.jend), [ni] "+s"(njl.ins)
+#define QR_RUN_NJ_OP , [nj] "+s"(njl.jump), [nw] "+s"(njl.jwait), [ne] "+s"(njl.jend), [ni] "+s"(njl.ins)
 #else
 #define QR_RUN_NJ_ASM
 #define QR_RUN_INS "qr_cull_out_%="
 #define QR_RUN_INS_ASM
-#define QR_RUN_NJ_OP , [am] "=&s"(am)
+#define QR_RUN_NJ_OP
 #endif
-#define QR_RUN_LEAVE "qr_cull_arr_%="
 #define QR_RUN_ARRAY \
             "qr_cull_arr_%=:\n" \
             "s_cmp_lg_u32 s96, 40\n" \
@@ -834,37 +764,20 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
             "s_mov_b32 %[pos], s90\n"                       /* the array's end */ \
             "s_branch qr_cull_top_%=\n" \
             QR_RUN_INS_ASM
-#else
-#define QR_RUN_NJ_OP
-#define QR_RUN_LEAVE "qr_cull_out_%="
-#define QR_RUN_ARRAY
-#endif
 
-#ifdef QR_STATS
-struct ArrJumps { u32 jump, jwait, jend, ins; };    /* arrays jumped in the run; of them with rays waiting / onto the END cell; all-inside exits */
-#endif
+struct ArrJumps { QR_ST(u32 jump, jwait, jend, ins;) };     /* statistics build: arrays jumped in the run; of them with rays waiting / onto the END cell; all-inside exits */
 
 template <bool BOXC>
 __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray &r, const WalkState &w,
-                                         float idx, float idy, float idz, float nox, float noy, float noz, float dd, float dde, float dlen
-#if QR_BVSPH_ACT
-                                         , lm_t &amiss
-#endif
-#if QR_BVSPH_ACT && defined(QR_STATS)
-                                         , ArrJumps &nj
-#endif
-                                         )
+                                         float idx, float idy, float idz, float nox, float noy, float noz, float dd, float dde, float dlen,
+                                         lm_t &amiss, [[maybe_unused]] ArrJumps &nj)
 {
     unsigned long long c01, c23, c45, c67;
     float t0, t1, t2, t3, t4, t5, t6;
     const float tb1 = w.tbuf * 1.00001f;
     u32 cur = __builtin_amdgcn_readfirstlane(pos);           /* wave-uniform by construction; says so to the compiler */
-#if QR_BVSPH_ACT
     unsigned long long am;                                   /* written on the array path only, read only for an array cell */
-#endif
-#if QR_BVSPH_ACT && defined(QR_STATS)
-    ArrJumps njl = {0, 0, 0, 0};                             /* this run's counts, in SGPRs of their own */
-#endif
+    QR_ST(ArrJumps njl = {0, 0, 0, 0};)                      /* this run's counts, in SGPRs of their own */
     if constexpr (BOXC)
     {
         asm volatile(
@@ -873,7 +786,7 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
             "s_waitcnt lgkmcnt(0)\n"
             "s_and_b32 s96, s88, 40\n"                      /* QR_OPF_CULL | QR_OPT_BV */
             "s_cmp_lg_u32 s96, 32\n"
-            "s_cbranch_scc1 " QR_RUN_LEAVE "\n"
+            "s_cbranch_scc1 qr_cull_arr_%=\n"
             "s_bitcmp0_b32 s88, 19\n"                       /* QR_OPF_BOX */
             "s_cbranch_scc1 qr_cull_sph_%=\n"
             "v_fma_f32 %[t0], s90, %[idx], %[nox]\n"
@@ -929,7 +842,7 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
             "s_mov_b64 %[c45], s[92:93]\n"
             "s_mov_b64 %[c67], s[94:95]\n"
             : [c01] "=&s"(c01), [c23] "=&s"(c23), [c45] "=&s"(c45), [c67] "=&s"(c67), [pos] "+s"(cur),
-              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6) QR_RUN_NJ_OP
+              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6), [am] "=&s"(am) QR_RUN_NJ_OP
             : [B] "s"(B), [idx] "v"(idx), [idy] "v"(idy), [idz] "v"(idz), [nox] "v"(nox), [noy] "v"(noy), [noz] "v"(noz), [tb1] "v"(tb1),
               [ox] "v"(r.org.x), [oy] "v"(r.org.y), [oz] "v"(r.org.z), [dx] "v"(r.dir.x), [dy] "v"(r.dir.y), [dz] "v"(r.dir.z),
               [dd] "v"(dd), [dde] "v"(dde), [dlen] "v"(dlen), [tbd] "v"(w.tbd), [res] "v"(w.resume), [osrf] "v"(r.osrf)
@@ -944,7 +857,7 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
             "s_waitcnt lgkmcnt(0)\n"
             "s_and_b32 s96, s88, 0x80028\n"                 /* QR_OPF_CULL | QR_OPT_BV | QR_OPF_BOX: a box cell is not culled here */
             "s_cmp_lg_u32 s96, 32\n"
-            "s_cbranch_scc1 " QR_RUN_LEAVE "\n"
+            "s_cbranch_scc1 qr_cull_arr_%=\n"
             "v_sub_f32 %[t0], s92, %[ox]\n"
             "v_sub_f32 %[t1], s93, %[oy]\n"
             "v_sub_f32 %[t2], s94, %[oz]\n"
@@ -978,19 +891,15 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
             "s_mov_b64 %[c45], s[92:93]\n"
             "s_mov_b64 %[c67], s[94:95]\n"
             : [c01] "=&s"(c01), [c23] "=&s"(c23), [c45] "=&s"(c45), [c67] "=&s"(c67), [pos] "+s"(cur),
-              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4) QR_RUN_NJ_OP
+              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4), [am] "=&s"(am) QR_RUN_NJ_OP
             : [B] "s"(B),
               [ox] "v"(r.org.x), [oy] "v"(r.org.y), [oz] "v"(r.org.z), [dx] "v"(r.dir.x), [dy] "v"(r.dir.y), [dz] "v"(r.dir.z),
               [dd] "v"(dd), [dde] "v"(dde), [dlen] "v"(dlen), [tbd] "v"(w.tbd), [res] "v"(w.resume), [osrf] "v"(r.osrf)
             : "vcc", "scc", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99");
     }
     pos = cur;
-#if QR_BVSPH_ACT
     amiss = am;
-#endif
-#if QR_BVSPH_ACT && defined(QR_STATS)
-    nj.jump += njl.jump; nj.jwait += njl.jwait; nj.jend += njl.jend; nj.ins += njl.ins;
-#endif
+    QR_ST(nj.jump += njl.jump; nj.jwait += njl.jwait; nj.jend += njl.jend; nj.ins += njl.ins;)
     c.s0 = (u32)c01; c.s1 = (u32)(c01 >> 32); c.s2 = (u32)c23; c.s3 = (u32)(c23 >> 32);
     c.s4 = (u32)c45; c.s5 = (u32)(c45 >> 32); c.s6 = (u32)c67; c.s7 = (u32)(c67 >> 32);
 }
@@ -1000,11 +909,7 @@ __device__ __forceinline__ void cull_run(BaseP B, u32 &pos, u32x8 &c, const Ray 
  * NOCULL (caller rays that the culls were not made for, see traverse): no sphere, box or bounding-volume cull -- every cell is
  * solved, as the reference walks its list.  Use with BOXC = false. */
 template <bool SHADOW, bool BOXC, bool NOCULL = false>
-__device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &h, bool &occluded
-#ifdef QR_STATS
-                                          , unsigned long long *stats
-#endif
-                                          )
+__device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &h, bool &occluded, [[maybe_unused]] WalkStats stats)
 {
     WalkState w;
     w.txyz = {0, 0, 0}; w.trijk = {0, 0, 0};
@@ -1032,20 +937,12 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
     u32 pos = __builtin_amdgcn_readfirstlane(head);
     QR_PROF_HIT(SHADOW ? 18 : 19);      /* packet walks */
     QR_CULL_FLOPS((BOXC && (c_frm(B)->img_flags & QR_IMG_BOXES)) ? 15 : 9);
-#ifdef QR_STATS
-    unsigned long long st_iter = 0, st_lanes = 0, st_skip = 0;
+    QR_ST(unsigned long long st_iter = 0, st_lanes = 0, st_skip = 0;)
     /* arrays with a cull sphere: handed out, of them with rays already occluded / waiting at an enclosing array's end / out of reach
      * for every ray that is on; handed out with some rays ruled out sideways while others go on, and those rays; jumped in the run */
-    u32 st_arr = 0, st_aocc = 0, st_await = 0, st_part = 0, st_plan = 0;
-    ArrJumps st_jump = {0, 0, 0, 0};
-#endif
-#ifdef QR_PROF
-    bool tn_open = false;               /* profiles/r22_array_cull.txt: trnode ranges that end without a member handed out */
-#endif
-#ifdef QR_PROF_BVSPH_DRY
-    constexpr int PA = SHADOW ? 50 : 56;    /* ... and what the array cut would decide, per walk kind */
-    lm_t qr_arr_side = 0;
-#endif
+    QR_ST(u32 st_arr = 0, st_aocc = 0, st_await = 0, st_part = 0, st_plan = 0;)
+    [[maybe_unused]] ArrJumps st_jump = {};
+    QR_PF(bool tn_open = false;)        /* profiles/r22_array_cull.txt: trnode ranges that end without a member handed out */
     for (;;)
     {
         /*
@@ -1060,9 +957,7 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
          * the walk's only cell load.
          */
         u32x8 c;
-#if QR_BVSPH_ACT
         lm_t arr_miss = 0;                      /* an array handed out by the run: the rays its cull sphere rules out */
-#endif
         if constexpr (NOCULL)
         {
             QR_GUARD_POS(1, pos, head, return);
@@ -1075,14 +970,7 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
          * instructions -- and the cursor is checked before the run loads its first cell and when it hands a cell out (the
          * statistics of culled cells are not kept in that build) */
         QR_GUARD_POS(1, pos, head, return);
-        cull_run<BOXC>(B, pos, c, r, w, idx, idy, idz, nox, noy, noz, dd, dde, dlen
-#if QR_BVSPH_ACT
-                       , arr_miss
-#endif
-#if QR_BVSPH_ACT && defined(QR_STATS)
-                       , st_jump
-#endif
-                       );
+        cull_run<BOXC>(B, pos, c, r, w, idx, idy, idz, nox, noy, noz, dd, dde, dlen, arr_miss, st_jump);
         QR_GUARD_POS(4, pos, head, return);
 #else
         for (;;)
@@ -1091,24 +979,15 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
              * new value), which keeps the cursor in an SGPR: with one readfirstlane here instead, it lived in a VGPR
              * and made the round trip v_mov / v_readfirstlane once per cell */
             QR_GUARD_POS(1, pos, head, return);
-#ifdef QR_WAVETIME
-            if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) qr_wt_cells[SHADOW ? 1 : 0]++;
-#endif
+            QR_WT(if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) qr_wt_cells[SHADOW ? 1 : 0]++;)
             c = *(const QR_CONST u32x8 *)(B + pos);
             QR_PROF_HIT(16);            /* cells loaded by packet walks */
-#ifdef QR_PROF
             /* a solver cell outside the node's space ends the range of the trnode cell before it */
-            if (tn_open && (c.s0 & QR_OPT_SOLVER) && !(c.s0 & QR_OPF_CACHED)) { QR_PROF_HIT(63); tn_open = false; }
-#endif
-#if QR_BVSPH_ACT
+            QR_PF(if (tn_open && (c.s0 & QR_OPT_SOLVER) && !(c.s0 & QR_OPF_CACHED)) { QR_PROF_HIT(63); tn_open = false; })
             /* an array with a cull sphere stays in the run (see QR_RUN_ARRAY): the sphere test with R2 and 1.01 R2 made here, and a
              * step to the array's end */
             const bool is_arr = (c.s0 & (QR_OPF_CULL | QR_OPT_BV)) == (QR_OPF_CULL | QR_OPT_BV);
             if (!is_arr && (c.s0 & (QR_OPF_CULL | QR_OPT_BV | (BOXC ? 0u : QR_OPF_BOX))) != QR_OPF_CULL) break;
-#else
-            const bool is_arr = false;
-            if ((c.s0 & (QR_OPF_CULL | QR_OPT_BV | (BOXC ? 0u : QR_OPF_BOX))) != QR_OPF_CULL) break;
-#endif
             lm_t miss;
             bool inside_all = false;            /* an array, and every ray that is on starts inside its sphere */
             if (BOXC && (c.s0 & QR_OPF_BOX))
@@ -1138,57 +1017,39 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
                 inside_all = is_arr && (LM(w.resume <= pos) & LM(oc2 > R2x)) == 0;
             }
             const lm_t need = LM(w.resume <= pos) & ~(miss & LM(c.s1 != r.osrf));
-#ifdef QR_STATS
-            if (!is_arr) { st_iter++; st_lanes += __popcll(LM(w.resume <= pos)); }     /* an array is counted where it is handed out or jumped */
-#endif
-#if QR_BVSPH_ACT
+            QR_ST(if (!is_arr) { st_iter++; st_lanes += __popcll(LM(w.resume <= pos)); })     /* an array is counted where it is handed out or jumped */
             /* as the written-out run: handed out with nobody ruled out when every ray that is on starts inside (or none is on: the
              * hand-out path then steps to the array's end) */
             if (is_arr) arr_miss = inside_all ? 0 : miss;
             if (inside_all)
             {
-#ifdef QR_STATS
-                if (LM(w.resume <= pos) != 0) st_jump.ins++;
-#endif
+                QR_ST(if (LM(w.resume <= pos) != 0) st_jump.ins++;)
                 break;
             }
-#endif
             if (need != 0) break;
             if (is_arr)
             {
-#ifdef QR_STATS
-                st_iter++; st_lanes += __popcll(LM(w.resume <= pos)); st_jump.jump++;
-                if (LM(w.resume > pos && w.resume != 0xFFFFFFFFu) != 0) st_jump.jwait++;
-                if (*(const QR_CONST u32 *)(B + c.s2) == 0) st_jump.jend++;
-#endif
+                QR_ST(st_iter++; st_lanes += __popcll(LM(w.resume <= pos)); st_jump.jump++;)
+                QR_ST(if (LM(w.resume > pos && w.resume != 0xFFFFFFFFu) != 0) st_jump.jwait++;)
+                QR_ST(if (*(const QR_CONST u32 *)(B + c.s2) == 0) st_jump.jend++;)
                 pos = __builtin_amdgcn_readfirstlane(c.s2);
                 continue;
             }
             QR_PROF_HIT(17);            /* culled without looking at the surface */
-#ifdef QR_STATS
-            st_skip++;
-#endif
+            QR_ST(st_skip++;)
             pos = __builtin_amdgcn_readfirstlane(pos + 32);
         }
 #endif
         }
         const u32 op = c.s0;
-#ifdef QR_PROF
-        if (tn_open && (op == 0 || (op & QR_OPT_TRNODE))) { QR_PROF_HIT(63); tn_open = false; }     /* the list or the next node ends the range */
-#endif
-#ifdef QR_PROF_BVSPH_DRY
-        qr_arr_side = 0;
-#endif
+        QR_PF(if (tn_open && (op == 0 || (op & QR_OPT_TRNODE))) { QR_PROF_HIT(63); tn_open = false; })     /* the list or the next node ends the range */
         if (op == 0) break;
         const u32 srf_off = c.s1;
         const lm_t on = LM(w.resume <= pos);
         u32 next = pos + 32;
         bool full = true;
-#ifdef QR_STATS
-        if (!((op & (QR_OPF_CULL | QR_OPT_BV)) == QR_OPF_CULL)) { st_iter++; st_lanes += __popcll(on); }
-#endif
+        QR_ST(if (!((op & (QR_OPF_CULL | QR_OPT_BV)) == QR_OPF_CULL)) { st_iter++; st_lanes += __popcll(on); })
         lm_t far = 0;                           /* bounding volume: lanes for which the whole array is out of reach */
-#if QR_BVSPH_ACT
         if ((op & (QR_OPF_CULL | QR_OPT_BV)) == (QR_OPF_CULL | QR_OPT_BV) && !NOCULL)
         {
             /* the run has tested the array's own conservative sphere (qr_compile.cpp) for every ray and hands its verdict out with
@@ -1196,54 +1057,22 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
              * hit by this ray: treated as a miss of the volume.  Such a ray stays out of the volume's space and test and waits at
              * the array's end.  (Testing it here again cost the swarm 3 % of its frame time, profiles/r22_array_cull.txt.) */
             far = on & arr_miss;
-#ifdef QR_STATS
-            st_arr++;
-            if (far != 0 && (on & ~far) != 0) { st_part++; st_plan += __popcll(far); }
-            if (LM(w.resume == 0xFFFFFFFFu) != 0) st_aocc++;                    /* ... reached with rays already occluded */
-            if (LM(w.resume > pos && w.resume != 0xFFFFFFFFu) != 0) st_await++;  /* ... with rays waiting at an enclosing array's end */
-#endif
+            QR_ST(st_arr++;)
+            QR_ST(if (far != 0 && (on & ~far) != 0) { st_part++; st_plan += __popcll(far); })
+            QR_ST(if (LM(w.resume == 0xFFFFFFFFu) != 0) st_aocc++;)                    /* ... reached with rays already occluded */
+            QR_ST(if (LM(w.resume > pos && w.resume != 0xFFFFFFFFu) != 0) st_await++;)  /* ... with rays waiting at an enclosing array's end */
             if (far != 0) { if (lane_of(far)) w.resume = c.s2; }
             full = (on & ~far) != 0;
         }
-        /* the walk without culls: as before the cut, an array with a sphere is entered when some ray is on */
+        /* the walk without culls: an array with a sphere is entered when some ray is on */
         else if ((op & (QR_OPF_CULL | QR_OPT_BV)) == (QR_OPF_CULL | QR_OPT_BV)) full = on != 0;
-#else
-        if ((op & (QR_OPF_CULL | QR_OPT_BV)) == (QR_OPF_CULL | QR_OPT_BV))
-        {
-            /* the array's own conservative sphere (qr_compile.cpp): entirely behind the origin, or entirely beyond
-             * the current depth bound -> nothing inside can be hit by this ray: treated as a miss of the volume */
-            const float R = u2f(c.s7);
-            const float ocx = u2f(c.s4) - r.org.x, ocy = u2f(c.s5) - r.org.y, ocz = u2f(c.s6) - r.org.z;
-            const float b = __builtin_fmaf(ocz, r.dir.z, __builtin_fmaf(ocy, r.dir.y, ocx * r.dir.x));
-            if constexpr (!NOCULL) far = on & (LM(__builtin_fmaf(R, dlen, b) < 0.0f) | LM(__builtin_fmaf(-R, dlen, b) > w.tbd));
-#ifdef QR_PROF_BVSPH_DRY
-            if constexpr (!NOCULL)
-            {
-                /* the rays that the solver cells' sphere test would rule out besides: counted below, not acted on */
-                const float R2 = R * R, R2x = 1.01f * R2;
-                const float oc2 = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, ocx * ocx));
-                qr_arr_side = on & ~far & LM(oc2 > R2x) & LM(__builtin_fmaf(oc2, dde, b * __builtin_fabsf(b)) < dd * (oc2 - R2));
-            }
-#endif
-#ifdef QR_STATS
-            st_arr++;
-#endif
-            if (far != 0) { if (lane_of(far)) w.resume = c.s2; }
-            full = (on & ~far) != 0;
-        }
-#endif
-#ifdef QR_PROF_BVSPH_DRY
-        if (op & QR_OPT_BV) { QR_PROF_HIT(PA + 0); if (!full) QR_PROF_HIT(PA + 1); }      /* (a) array cells reached, (b) left by `far` */
-#endif
 
         if (full)
         {
             if (op & QR_OPT_TRNODE)
             {
                 QR_PROF_HIT(20);
-#ifdef QR_PROF
-                QR_PROF_HIT(62); tn_open = true;
-#endif
+                QR_PF(QR_PROF_HIT(62); tn_open = true;)
                 QR_FLOPS_M(3 + ((op & QR_OPF_FULLM) ? 30 : 6), __popcll(on));
                 /* array element with a transform: diff and ray in its space, cached for the surfaces behind it */
                 if (lane_of(on))
@@ -1271,25 +1100,13 @@ __device__ __forceinline__ void walk_list(BaseP B, u32 head, const Ray &r, Hit &
                  * (tracer.cpp:4040-4054); rays that were off already wait for the end of an enclosing array,
                  * which lies at or behind this array's end (arrays nest, qr_compile.cpp) */
                 if (LM(w.resume <= pos) == 0) next = c.s2;
-#ifdef QR_PROF_BVSPH_DRY
-                {
-                    const bool nobody = LM(w.resume <= pos) == 0, sph_all = (on & ~far & ~qr_arr_side) == 0;
-                    if (nobody) QR_PROF_HIT(PA + 2);                                /* (c) the volume test run, no lane enters */
-                    if (sph_all) { QR_PROF_HIT(PA + 3); if (nobody) QR_PROF_HIT(PA + 5); }     /* (d) the sphere alone decides for the wave; of them in (c) */
-                    else if (qr_arr_side != 0) QR_PROF_ADD(PA + 4, __popcll(qr_arr_side));     /* (e) lanes ruled out while others go on */
-                }
-#endif
             }
             else
             {
                 SurfS s;
                 ld_surf(B, srf_off, s);
-#ifdef QR_WAVETIME
-                if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) qr_wt_cells[SHADOW ? 3 : 2]++;
-#endif
-#ifdef QR_PROF
-                if (op & QR_OPF_CACHED) tn_open = false;              /* a member of the node's range is handed out */
-#endif
+                QR_WT(if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) qr_wt_cells[SHADOW ? 3 : 2]++;)
+                QR_PF(if (op & QR_OPF_CACHED) tn_open = false;)       /* a member of the node's range is handed out */
                 if (lane_of(on)) solve_cell<SHADOW, false>(B, op, srf_off, s, r, dd, w, h);
                 if (SHADOW)
                 {
@@ -1365,11 +1182,7 @@ __device__ __forceinline__ bool div_culled(const u32x4 &c0, const u32x4 &c1, con
  * (a packet of width one).  Only for lists without clipper programs (QR_LISTF_DIV, set by the compiler).
  */
 template <bool SHADOW>
-__device__ __forceinline__ void walk_div(BaseP B, bool active, const Ray &r, Hit &h, bool &occluded
-#ifdef QR_STATS
-                                         , unsigned long long *stats
-#endif
-                                         )
+__device__ __forceinline__ void walk_div(BaseP B, bool active, const Ray &r, Hit &h, bool &occluded, [[maybe_unused]] WalkStats stats)
 {
     WalkState w;
     w.txyz = {0, 0, 0}; w.trijk = {0, 0, 0};
@@ -1381,9 +1194,7 @@ __device__ __forceinline__ void walk_div(BaseP B, bool active, const Ray &r, Hit
     w.tbd = w.tbuf * dd;
     u32 pos = active ? (r.list & ~31u) : 0u;    /* 0: the lane has finished */
     u32 p_op = 0, p_srf = 0;                    /* the candidate cell the lane stands on (p_op == 0: none) */
-#ifdef QR_STATS
-    unsigned long long st_iter = 0, st_lanes = 0, st_solve = 0, st_slanes = 0;
-#endif
+    QR_ST(unsigned long long st_iter = 0, st_lanes = 0, st_solve = 0, st_slanes = 0;)
     for (;;)
     {
         const lm_t pend = LM(p_op != 0);
@@ -1395,9 +1206,7 @@ __device__ __forceinline__ void walk_div(BaseP B, bool active, const Ray &r, Hit
              * one 64-byte load per lane: the cell and what follows it -- the extension of a bounding-volume cell, or
              * the next cell, which is then handled in the same round trip when the first one was culled (the walk is
              * bound by the latency of these dependent loads, not by arithmetic) */
-#ifdef QR_STATS
-            st_iter++; st_lanes += __popcll(adv);
-#endif
+            QR_ST(st_iter++; st_lanes += __popcll(adv);)
             if (lane_of(adv))
             {
                 QR_GUARD_POS(2, pos, r.list, return);
@@ -1452,9 +1261,7 @@ __device__ __forceinline__ void walk_div(BaseP B, bool active, const Ray &r, Hit
         else
         {
             /* ---- SOLVE ---- */
-#ifdef QR_STATS
-            st_solve++; st_slanes += __popcll(pend);
-#endif
+            QR_ST(st_solve++; st_slanes += __popcll(pend);)
             if (lane_of(pend))
             {
                 SurfS s;
@@ -1495,14 +1302,8 @@ __device__ __forceinline__ void walk_div(BaseP B, bool active, const Ray &r, Hit
 #ifndef QR_INCOH_DEN
 #define QR_INCOH_DEN 1
 #endif
-#ifndef QR_POOL
-#define QR_POOL 1          /* 0: walk_div without hand-over (A/B) */
-#endif
 #ifndef QR_POOL_MIN_IDLE
 #define QR_POOL_MIN_IDLE 12     /* hand-over round as soon as this many lanes have nothing to do (2: +2 %, 6: +1.5 % frame time) */
-#endif
-#ifndef QR_POOL_FLAT
-#define QR_POOL_FLAT 1             /* flat lists are cut in halves for idle lanes (0: hand-over only at the boundaries bounding volumes give) */
 #endif
 #ifndef QR_POOL_FLAT_MIN_BYTES
 #define QR_POOL_FLAT_MIN_BYTES 128u    /* a flat range of at least four cells gives its far half away */
@@ -1543,7 +1344,9 @@ __device__ __forceinline__ int lanes_below(lm_t m)
  * (t, cell offset) over the hits of all ranges of that ray -- the reference takes the first cell in list order among
  * equal depths (strict compare, tracer.cpp:1626), which is exactly that minimum, so the order in which ranges are
  * walked does not matter.  Depth tests inside a range use the range's own bound; the best depth known for the ray when
- * the range was taken only feeds the conservative sphere culls.
+ * the range was taken only feeds the conservative sphere culls.  With hand-over 39 (shadow) / 48 (secondary) of 64 lanes step, and
+ * a frame of that scene takes 72 M wave-steps instead of 393 M (DESIGN.md 4 "Per-lane walk with work hand-over"): world-space lists
+ * always come here, walk_div keeps the lists with transform state.
  */
 /*
  * One conservative test for either kind of cell (ours, not the reference's; a cell without QR_OPF_CULL carries R = +inf
@@ -1570,11 +1373,7 @@ __device__ __forceinline__ bool pool_cull(u32 srf, const u32x4 &c1, float r2, fl
 }
 
 template <bool SHADOW>
-__device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hit &h, bool &occluded
-#ifdef QR_STATS
-                                          , unsigned long long *stats
-#endif
-                                          )
+__device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hit &h, bool &occluded, [[maybe_unused]] WalkStats stats)
 {
     PoolLds &P = pool_lds();
     const int lane = (int)(threadIdx.x & 63u);
@@ -1592,10 +1391,10 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
     u32 pos = active ? (r.list & ~31u) : 0u;    /* 0: nothing to walk */
     u32 iend = 0xFFFFFFFFu;                     /* end of the range; the first range of a ray ends at the END cell */
     u32 give = 0;
-#if QR_POOL_FLAT
     /* a FLAT list (no bounding-volume cell: every 32 bytes a cell) tells its length in the word in front of it (qr_compile.cpp):
      * its range can be cut anywhere, and is -- in halves, whenever lanes idle (round 4: the shadow lists of hits on small
-     * objects are ten such cells, and a walk lasted as long as its slowest ray's ten) */
+     * objects are ten such cells, and a walk lasted as long as its slowest ray's ten; with hand-over only at the boundaries that
+     * bounding volumes give, the 10 000 object scene ran at 9 276 against 9 749 Mrays/s, profiles/r04_flat_list_halving.txt) */
     bool flat = false;
     if (pos != 0)
     {
@@ -1603,22 +1402,14 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
         flat = (lw & 1u) != 0;
         if (flat) iend = pos + (lw & ~31u);
     }
-#endif
     u32 p_op = 0, p_srf = 0, p_pos = 0;         /* the candidate cell the lane stands on (p_op == 0: none) */
     bool busy = active;
-#if defined(QR_STATS) && defined(QR_GUARD)
-    u32 g_prev = 0, g_how = 0;
-#define QR_G(x) x
-#else
-#define QR_G(x)
-#endif
+    QR_GD(u32 g_prev = 0, g_how = 0;)           /* the guard's record of how this lane came to its cursor */
     Hit lh; lh.t = 0.0f; lh.srf = 0; lh.side = 0; lh.loc = {0, 0, 0};
     u32 lh_pos = 0;
     P.key[lane] = SHADOW ? 0ull : (((unsigned long long)f2u(r.tmax) << 32) | 0xFFFFFFFFull);
     __syncthreads();
-#ifdef QR_STATS
-    unsigned long long st_iter = 0, st_lanes = 0, st_solve = 0, st_slanes = 0, st_give = 0;
-#endif
+    QR_ST(unsigned long long st_iter = 0, st_lanes = 0, st_solve = 0, st_slanes = 0, st_give = 0;)
     for (;;)
     {
         const lm_t pend = LM(p_op != 0);
@@ -1643,7 +1434,6 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
         if (work == 0) break;
 
         /* ---- hand-over ---- */
-#if QR_POOL_FLAT
         /* flat range: the boundary is its middle cell */
         if (flat && pos != 0 && p_op == 0) give = (iend - pos) >= QR_POOL_FLAT_MIN_BYTES ? pos + (((iend - pos) >> 6) << 5) : 0u;
         const bool can_give = pos != 0 && give > pos && (iend - give) >= (flat ? 32u : QR_POOL_MIN_BYTES);
@@ -1651,22 +1441,11 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
         const lm_t idle = ~work;
         if (givers != 0 && __popcll(idle) >= (__popcll(LM(can_give && flat)) != 0 ? QR_POOL_FLAT_MIN_IDLE : QR_POOL_MIN_IDLE))
         {
-#else
-        const bool can_give = pos != 0 && give > pos && (iend - give) >= QR_POOL_MIN_BYTES;
-        const lm_t givers = LM(can_give);
-        const lm_t idle = ~work;
-        if (givers != 0 && __popcll(idle) >= QR_POOL_MIN_IDLE)
-        {
-#endif
             const int n_g = __popcll(givers), n_i = __popcll(idle);
             const int rank_g = lanes_below(givers), rank_i = lanes_below(idle);
             if (can_give && rank_g < n_i)
             {
-#if QR_POOL_FLAT
                 P.give[rank_g] = u32x4{(u32)owner, give, iend, flat ? 1u : 0u};
-#else
-                P.give[rank_g] = u32x4{(u32)owner, give, iend, 0u};
-#endif
                 iend = give; give = 0;
             }
             __syncthreads();
@@ -1682,10 +1461,8 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
             if (tk)
             {
                 owner = src; pos = g.y; iend = g.z; give = 0; busy = true;
-#if QR_POOL_FLAT
                 flat = g.w != 0u;
-#endif
-                QR_G(g_prev = g.z; g_how = 8;)
+                QR_GD(g_prev = g.z; g_how = 8;)
                 cr.org = {ox, oy, oz}; cr.dir = {dx, dy, dz}; cr.tmin = tmn; cr.tmax = tmx;
                 cr.osrf = osf; cr.oflg = ofl; cr.ploc = {px, py, pz};
                 dd = dx * dx + dy * dy + dz * dz;
@@ -1697,18 +1474,14 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
                 w.tbd = cull_t * dd;
             }
             __syncthreads();                    /* slots are free again */
-#ifdef QR_STATS
-            st_give += (unsigned long long)(n_g < n_i ? n_g : n_i);
-#endif
+            QR_ST(st_give += (unsigned long long)(n_g < n_i ? n_g : n_i);)
             continue;
         }
 
         if (adv != 0 && __popcll(pend) < QR_DIV_BATCH)
         {
             /* ---- STEP (as walk_div) ---- */
-#ifdef QR_STATS
-            st_iter++; st_lanes += __popcll(adv);
-#endif
+            QR_ST(st_iter++; st_lanes += __popcll(adv);)
             if (lane_of(adv))
             {
                 QR_GUARD_POS(3, pos, ((unsigned long long)g_prev << 32) | g_how, return);
@@ -1726,9 +1499,7 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
                      * the exact test below and a lane that fails that test continues at a garbage offset (seen in the ISA,
                      * caught by the QR_GUARD build) */
                     u32 bv_end = a0.z;
-#ifndef QR_NO_BVEND_COPY        /* -DQR_NO_BVEND_COPY: the build without the copy, for the ISA comparison in DESIGN.md */
                     asm volatile("" : "+v"(bv_end));
-#endif
                     float b2, m, rhs;
                     const bool culled = (op & QR_OPF_BOX) == 0
                                      && pool_cull(srf_off, a1, is_bv ? u2f(b1.w) : u2f(a0.z), u2f(a0.w), is_bv, cr, dd, dde, dlen, w.tbd, b2, m, rhs);
@@ -1757,16 +1528,14 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
                     }
                 }
                 if (next >= iend) next = 0;
-                QR_G(g_prev = pos; g_how = (op & 0xFFFFFu) | ((next == a0.z ? 1u : 0u) << 24) | ((next == pos + 64 ? 1u : 0u) << 25);)
+                QR_GD(g_prev = pos; g_how = (op & 0xFFFFFu) | ((next == a0.z ? 1u : 0u) << 24) | ((next == pos + 64 ? 1u : 0u) << 25);)
                 pos = next;
             }
         }
         else
         {
             /* ---- SOLVE ---- */
-#ifdef QR_STATS
-            st_solve++; st_slanes += __popcll(pend);
-#endif
+            QR_ST(st_solve++; st_slanes += __popcll(pend);)
             if (lane_of(pend))
             {
                 SurfS s;
@@ -1818,9 +1587,6 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
 /* ------------------------------------------------------------------------------------------------------------ */
 /* walk_dda: nearest hit through the uniform grid of a long world-space list (CDda, qr_program.h)               */
 /* ------------------------------------------------------------------------------------------------------------ */
-#ifndef QR_DDA
-#define QR_DDA 1
-#endif
 #ifndef QR_DDA_KMAX
 #define QR_DDA_KMAX 64      /* segments per ray at most (4: +4 %, 16: +0.4 % frame time on the 10k scene) */
 #endif
@@ -1829,23 +1595,14 @@ __device__ __forceinline__ void walk_pool(BaseP B, bool active, const Ray &r, Hi
                              * segment behind it (16: +5 % frame time; 4 until stretches were re-split while the walk runs: with more
                              * lanes marching 6-8 are 0.6 % faster, 3 is 0.5 % slower) */
 #endif
-#ifndef QR_DDA_TWO_REFS
-#define QR_DDA_TWO_REFS 1   /* a step looks at two refs of the current cell when the first is culled (0: one, A/B) */
-#endif
 #ifndef QR_DDA_SPLIT_MAXOWN
 #define QR_DDA_SPLIT_MAXOWN 32
-#endif
-#ifndef QR_DDA_RESPLIT
-#define QR_DDA_RESPLIT 1        /* stretches are halved again while the walk runs, whenever enough lanes idle (0: only the split at the start) */
 #endif
 #ifndef QR_DDA_RESPLIT_IDLE
 #define QR_DDA_RESPLIT_IDLE 12     /* (4: -1.6 %, 8: -0.6 %, 32: -3 % against 12 on config 5) */
 #endif
 #ifndef QR_DDA_RESPLIT_CELLS
 #define QR_DDA_RESPLIT_CELLS 2  /* a lane only gives away the far half of a stretch of at least this many cells */
-#endif
-#ifndef QR_DDA_SPLIT
-#define QR_DDA_SPLIT 1    /* rays of a sparse wave are cut into segments marched by idle lanes */
 #endif
 
 /* bit pattern of the next float above a positive finite t (equal depths: an earlier cell of the list still wins) */
@@ -1868,11 +1625,7 @@ __device__ __forceinline__ float next_up(float t) { return u2f(f2u(t) + 1u); }
  * occupies lanes that had nothing to do: 11 -> 30 of 64 lanes stepping, and with solver rounds from 4 candidates on
  * an early hit ends the march of everything behind it.
  */
-__device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit &h
-#ifdef QR_STATS
-                                         , unsigned long long *stats
-#endif
-                                         )
+__device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit &h, [[maybe_unused]] WalkStats stats)
 {
     PoolLds &P = pool_lds();
     const int lane = (int)(threadIdx.x & 63u);
@@ -1924,9 +1677,7 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
     };
     P.key[lane] = ((unsigned long long)f2u(r.tmax) << 32) | 0xFFFFFFFFull;
     __syncthreads();
-#ifdef QR_STATS
-    unsigned long long st_iter = 0, st_lanes = 0, st_solve = 0, st_slanes = 0;
-#endif
+    QR_ST(unsigned long long st_iter = 0, st_lanes = 0, st_solve = 0, st_slanes = 0;)
 #pragma nounroll
     for (int pass = 0; pass < 2; pass++)
     {
@@ -1953,7 +1704,6 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
             if (n_own > QR_DDA_SPLIT_MAXOWN) K = 1;
             int seg = 0;
             march = enter;
-#if QR_DDA_SPLIT
             if (K > 1)
             {
                 const lm_t idle = ~owners;
@@ -1988,9 +1738,6 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
                 __syncthreads();
             }
             else K = 1;
-#else
-            K = 1;
-#endif
             if (march)
             {
                 /* this lane's segment of t, its first cell and the DDA increments */
@@ -2006,14 +1753,14 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
             const lm_t pend = LM(p_op != 0);
             const lm_t adv = (pass == 0 ? LM(rp < rend) : LM(march)) & ~pend;
             if ((adv | pend) == 0) break;
-#if QR_DDA_RESPLIT
             if (pass == 1)
             {
                 /* Stretches end at very different times (a hit right behind the start, or a march through the whole grid): as
                  * soon as QR_DDA_RESPLIT_IDLE lanes have nothing to march, lanes with a long stretch ahead hand its far half to
                  * them -- the walk lasts as long as its longest stretch, and that is halved.  The same split as the one at the
                  * start (the cell around the cut is looked at from both sides, hits meet in LDS as the minimum of depth and
-                 * original cell), only later. */
+                 * original cell), only later.  With the split at the start alone the 10 000 object scene ran at 9 034 against
+                 * 9 241 Mrays/s (profiles/r04_dda_resplit_sweep.txt). */
                 const lm_t idle = ~(LM(march) | pend);
                 const float cur_t = __builtin_fminf(tmx, __builtin_fminf(tmy, tmz));
                 const float lim = __builtin_fminf(t_far, __builtin_fminf(w.tbuf, u2f(((const volatile u32 *)&P.key[owner])[1])));
@@ -2060,12 +1807,9 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
                     continue;
                 }
             }
-#endif
             if (adv != 0 && __popcll(pend) < QR_DDA_BATCH)
             {
-#ifdef QR_STATS
-                st_iter++; st_lanes += __popcll(adv);
-#endif
+                QR_ST(st_iter++; st_lanes += __popcll(adv);)
                 if (lane_of(adv))
                 {
                     if (rp < rend)
@@ -2073,11 +1817,10 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
                         /* ---- next ref of the current cell (or of the up-front members) ---- */
                         const u32 ro = g2.w + rp * 32u;
                         const u32x4 a0 = *(const QR_CONST u32x4 *)(B + ro), a1 = *(const QR_CONST u32x4 *)(B + ro + 16);
-#if QR_DDA_TWO_REFS
                         /* the ref behind it travels in the same round trip (the array has two refs of slack) and is looked at in
-                         * this step when the first one is culled: the march is a chain of dependent loads, one per step */
+                         * this step when the first one is culled: the march is a chain of dependent loads, one per step (one ref a
+                         * step was 3 % slower on the 10 000 object scene, DESIGN.md 4 "Grid walk") */
                         const u32x4 c0 = *(const QR_CONST u32x4 *)(B + ro + 32), c1 = *(const QR_CONST u32x4 *)(B + ro + 48);
-#endif
                         rp++;
                         if (a0.y != last0 && a0.y != last1)
                         {
@@ -2086,7 +1829,6 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
                             if (!pool_cull(a0.y, a1, r2, r2 * 1.01f, false, cr, dd, dde, dlen, w.tbd, b2, m, rhs))
                             { p_op = a0.x; p_srf = a0.y; p_pos = a0.w; }
                         }
-#if QR_DDA_TWO_REFS
                         if (p_op == 0 && rp < rend)
                         {
                             rp++;
@@ -2098,7 +1840,6 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
                                 { p_op = c0.x; p_srf = c0.y; p_pos = c0.w; }
                             }
                         }
-#endif
                     }
                     else
                     {
@@ -2126,9 +1867,7 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
             else
             {
                 /* ---- SOLVE ---- */
-#ifdef QR_STATS
-                st_solve++; st_slanes += __popcll(pend);
-#endif
+                QR_ST(st_solve++; st_slanes += __popcll(pend);)
                 bool accepted = false;
                 if (lane_of(pend))
                 {
@@ -2197,11 +1936,7 @@ __device__ __forceinline__ void walk_dda(BaseP B, bool active, const Ray &r, Hit
  * order, with the same arithmetic.
  */
 template <bool SHADOW, bool DIVK, bool CALLER = false>
-__device__ __forceinline__ void traverse(BaseP B, bool active, bool coherent, const Ray &r, Hit &h, bool &occluded
-#ifdef QR_STATS
-                                         , unsigned long long *stats
-#endif
-                                         )
+__device__ __forceinline__ void traverse(BaseP B, bool active, bool coherent, const Ray &r, Hit &h, bool &occluded, WalkStats stats)
 {
     h.t = r.tmax; h.srf = 0; h.side = 0; h.loc = {0, 0, 0};
     occluded = false;
@@ -2218,9 +1953,7 @@ __device__ __forceinline__ void traverse(BaseP B, bool active, bool coherent, co
         const int leader = __ffsll((long long)pending) - 1;
         const u32 head = (u32)__builtin_amdgcn_readlane((int)r.list, leader);
         const lm_t mine = pending & LM(r.list == head);
-#ifdef QR_WAVETIME
-        if ((int)(threadIdx.x & 63u) == leader) qr_wt_groups[SHADOW ? 1 : 0]++;
-#endif
+        QR_WT(if ((int)(threadIdx.x & 63u) == leader) qr_wt_groups[SHADOW ? 1 : 0]++;)
         if constexpr (DIVK)
         {
         const int n_left = __popcll(pending), n_mine = __popcll(mine);
@@ -2233,33 +1966,15 @@ __device__ __forceinline__ void traverse(BaseP B, bool active, bool coherent, co
         {
             const lm_t go = CALLER ? go_c : (incoherent ? can_div : mine);
             pending &= ~go;
-#if QR_DDA
             /* nearest-hit rays on lists that carry a uniform grid */
             if (!SHADOW && (go & LM((r.list & QR_LISTF_DDA) == 0)) == 0)
             {
-                walk_dda(B, lane_of(go), r, h
-#ifdef QR_STATS
-                         , stats
-#endif
-                         );
+                walk_dda(B, lane_of(go), r, h, stats);
                 continue;
             }
-#endif
-#if QR_POOL
             /* hand-over needs lists without transform state (QR_LISTF_WORLD) */
-            if ((go & LM((r.list & QR_LISTF_WORLD) == 0)) == 0)
-            walk_pool<SHADOW>(B, lane_of(go), r, h, occluded
-#ifdef QR_STATS
-                              , stats
-#endif
-                              );
-            else
-#endif
-            walk_div<SHADOW>(B, lane_of(go), r, h, occluded
-#ifdef QR_STATS
-                             , stats
-#endif
-                             );
+            if ((go & LM((r.list & QR_LISTF_WORLD) == 0)) == 0) walk_pool<SHADOW>(B, lane_of(go), r, h, occluded, stats);
+            else walk_div<SHADOW>(B, lane_of(go), r, h, occluded, stats);
             continue;
         }
         }
@@ -2267,20 +1982,9 @@ __device__ __forceinline__ void traverse(BaseP B, bool active, bool coherent, co
         if (CALLER && (mine & nocull) != 0)
         {
             if (lane_of(mine))
-                walk_list<SHADOW, false, true>(B, head & ~31u, r, h, occluded
-#ifdef QR_STATS
-                                               , stats
-#endif
-                                               );
+                walk_list<SHADOW, false, true>(B, head & ~31u, r, h, occluded, stats);
         }
-        else if (lane_of(mine))
-        {
-            walk_list<SHADOW, !DIVK>(B, head & ~31u, r, h, occluded
-#ifdef QR_STATS
-                              , stats
-#endif
-                              );
-        }
+        else if (lane_of(mine)) walk_list<SHADOW, !DIVK>(B, head & ~31u, r, h, occluded, stats);
     }
 }
 

@@ -1,4 +1,4 @@
-"""Bounding-volume arrays in the packet walk's cull run (QR_CUT_BVSPH, csrc/qr_walk.hpp): an array whose cull sphere every ray that
+"""Bounding-volume arrays in the packet walk's cull run (cull_run and walk_list, csrc/qr_walk.hpp): an array whose cull sphere every ray that
 is on misses sideways is skipped inside the run, and a ray that misses it stays out of the volume test.  Frames must keep every
 bit, so each snapshot below is rendered by the oracle on the CPU and by the kernel -- the packet instance, the per-lane instance
 (QR_DIV=1), and both with the culls off (QR_CULL=0): equal pixels, first-hit ids and ray counts.  160 x 120 throughout.

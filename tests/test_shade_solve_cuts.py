@@ -1,14 +1,14 @@
-"""The hot-path cuts of shade() and solve_cell() (QR_CUT_* in csrc/qr_shade.hpp and csrc/qr_walk.hpp) against the oracle, on
-snapshots patched so that every cut's branches run -- the stock fixtures take few of them:
+"""The hot-path cuts of shade() and solve_cell() (csrc/qr_shade.hpp and csrc/qr_walk.hpp, profiles/r05_shade_solve_cuts.txt)
+against the oracle, on snapshots patched so that every cut's branches run -- the stock fixtures take few of them:
 
-  QR_CUT_TEXEL   every material a one-texel colour of its own (the colour comes finished from the image), masks of 7 / 8 / 10
+  texel colour   every material a one-texel colour of its own (the colour comes finished from the image), masks of 7 / 8 / 10
                  bits, gamma on and off (the squaring stays in the kernel);
-  QR_CUT_TEXLUT  the textures kept, with those masks: table loads, and the arithmetic for the 10-bit mask;
-  QR_CUT_RSQ     specular powers with and without fraction bits, diffuse off with specular on (the shared rsq then comes from
+  texel table    the textures kept, with those masks: table loads, and the arithmetic for the 10-bit mask;
+  shared rsq     specular powers with and without fraction bits, diffuse off with specular on (the shared rsq then comes from
                  the specular block alone), metal and plain blends;
-  QR_CUT_NDIR    surfaces that refract AND reflect with Fresnel on, and total inner reflection;
-  QR_CUT_XFORM2  scaled, rotated and sheared arrays: full matrices, own and cached transforms;
-  QR_CUT_ROOT2   quadrics with a raised d_eps: silhouette lanes with 0 <= d < d_eps beside lanes without.
+  shared ray     surfaces that refract AND reflect with Fresnel on, and total inner reflection;
+  xform2         scaled, rotated and sheared arrays: full matrices, own and cached transforms;
+  quadric roots  quadrics with a raised d_eps: silhouette lanes with 0 <= d < d_eps beside lanes without.
 
 Each patched snapshot is rendered by the oracle on the CPU and by the kernel -- the packet instance, the per-lane instance
 (QR_DIV=1) and qr_shade_rays on the camera's rays: pixels, first-hit ids and ray counts must be equal.  160 x 120 throughout.

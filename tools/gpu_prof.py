@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Walk statistics of one workload with the QR_PROF build: tools/gpu_stats.py NAME|synth:N:W:H:D [depth] (GPU box).
-Build first: make -C quadray-engine_amd/csrc variant NAME=prof EXTRA=-DQR_PROF
-(EXTRA="-DQR_PROF -DQR_PROF_BVSPH_DRY": the walk without the array cut, which counts what the cut would decide: profiles/r22_array_cull.txt)"""
+Build first: make -C quadray-engine_amd/csrc variant NAME=prof EXTRA=-DQR_PROF"""
 import os, sys, gzip
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["QR_LIB"] = os.path.join(ROOT, "quadray-engine_amd", "libqrhip_prof.so")
