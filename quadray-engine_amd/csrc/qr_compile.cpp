@@ -410,6 +410,8 @@ struct Builder
     uint32_t o_srf = 0, o_shd = 0, o_mat = 0, o_lgt = 0, o_tex = 0;
 
     std::vector<uint32_t> list_off;         /* surface list head -> byte offset of its program (0 unseen)   */
+    std::vector<uint32_t> shadow_off;       /* ... of its program as a shadow list, where that is another one (compile_list) */
+    bool drop_shadowless = true;            /* QR_SHADOWLESS=0: shadow lists keep the cells that cast no shadow */
     std::vector<uint32_t> light_off;        /* light list head  -> byte offset                               */
     std::vector<uint8_t> list_heavy;        /* surface list head -> 1 holds a reflective, 2 a non-opaque surface */
     struct ClipKey { int head, trnode, cdef; uint32_t off; };
@@ -431,6 +433,7 @@ struct Builder
         : v(v_), E(E_), bs(bs_), cull_mode(cm), blob(b), n_srf((int)v_.hdr->n_srf), n_elm((int)E_.size())
     {
         list_off.assign((size_t)n_elm + 1, 0); light_off.assign((size_t)n_elm + 1, 0); list_heavy.assign((size_t)n_elm + 1, 0);
+        shadow_off.assign((size_t)n_elm + 1, 0);
         chain_pos.assign((size_t)n_elm + 1, 0); chain_stamp.assign((size_t)n_elm + 1, -1);
     }
 
@@ -476,24 +479,44 @@ struct Builder
 
     struct Restart {};                      /* thrown by compile_list: a long chain in a build that assumed there is none */
 
-    uint32_t compile_list(int head)
+    /* a side that casts no shadow (CHECK_SHAD, tracer.cpp:549-589): a light's own body, plain transparency */
+    static bool no_shadow(int p) { return (p & QR_PROP_LIGHT) || ((p & QR_PROP_TRANSP) && !(p & QR_PROP_REFRACT)); }
+
+    /*
+     * as_shadow: the program is only ever walked by shadow rays (CLight::shadow).  A hit on a solver cell that casts no shadow
+     * (QR_OPF_NOSHAD) changes nothing in such a walk -- it occludes nobody, and a shadow walk keeps no depth -- so the cell is left
+     * out the way a marker element is: array ends and trnode ranges stay what they were.  Every shadow ray of the demo scenes aims at
+     * such a cell, the light's own body, which no cull removes: more than half of their shadow walks' solves
+     * (profiles/r25_own_surface_roots.txt).  A chain that is also a tile or side list keeps its full program beside this one;
+     * one without such a surface has a single program for both.
+     */
+    uint32_t compile_list(int head, bool as_shadow = false)
     {
         if (head == QR_NULL) return 0;
         if (E.size() + 1 > list_off.size())
         {
             /* chains appended by the shadow grids */
             const size_t n1 = E.size() + 1;
-            list_off.resize(n1, 0); light_off.resize(n1, 0); list_heavy.resize(n1, 0);
+            list_off.resize(n1, 0); light_off.resize(n1, 0); list_heavy.resize(n1, 0); shadow_off.resize(n1, 0);
             chain_pos.resize(n1, 0); chain_stamp.resize(n1, -1);
         }
-        if (list_off[head]) return list_off[head];
+        if (as_shadow && shadow_off[head]) return shadow_off[head];
+        if (!as_shadow && list_off[head]) return list_off[head];
         stamp++;
         int n = 0;
+        bool shadowless = false;
         for (int e = head; e != QR_NULL; e = E[e].next)
         {
             if ((size_t)n >= E.size()) throw Fail{QR_ERR_ARG, "cyclic list"};
             chain_stamp[e] = stamp; chain_pos[e] = n++;
+            if (as_shadow && drop_shadowless)
+            {
+                const qr_surface &q = v.srf[E[e].simd];
+                if (is_real(q) && no_shadow(q.props[0]) && no_shadow(q.props[1])) shadowless = true;
+            }
         }
+        if (as_shadow && !shadowless) return shadow_off[head] = compile_list(head);
+        uint32_t &memo_off = as_shadow ? shadow_off[head] : list_off[head];
         if (box_ok && n >= QR_LONG_CELLS) throw Restart{};
         /* The engine hands every screen tile a chain of its own, and most neighbours hold the same surfaces in the same order:
          * a chain whose elements (surface, kind, position of the array's last member) equal those of a chain compiled
@@ -502,6 +525,7 @@ struct Builder
         uint64_t dkey = 1469598103934665603ull;
         bool dedup = dedup_on;
         dk.clear();
+        if (as_shadow) { dk.push_back(-2); dkey = (dkey ^ 0xFFFFFFFEu) * 1099511628211ull; }       /* a key no full program has: theirs hold triples */
         for (int e = head; e != QR_NULL && dedup; e = E[e].next)
         {
             const qr_elem &el = E[e];
@@ -525,7 +549,7 @@ struct Builder
             {
                 const DedupEnt &d = dedup_ent[(size_t)hit];
                 dedup_last = hit;
-                list_off[head] = d.off; list_heavy[head] = d.heavy;
+                memo_off = d.off; list_heavy[head] = d.heavy;
                 return d.off;
             }
         }
@@ -581,7 +605,6 @@ struct Builder
                 if (ak == 0) op |= QR_OPF_KX; else if (ak == 1) op |= QR_OPF_KY;
                 if ((s.axes >> 10) & 1u) op |= QR_OPF_SGNK;
                 if (ai == 0) op |= QR_OPF_IX; else if (ai == 1) op |= QR_OPF_IY;
-                auto no_shadow = [](int p) { return (p & QR_PROP_LIGHT) || ((p & QR_PROP_TRANSP) && !(p & QR_PROP_REFRACT)); };
                 const bool n0 = no_shadow(s.props[0]), n1 = no_shadow(s.props[1]);
                 if (n0 && n1) op |= QR_OPF_NOSHAD; else if (n0 || n1) op |= QR_OPF_SIDESHAD;
                 if (s.clip != QR_NULL) op |= QR_OPF_CLIP;
@@ -602,6 +625,7 @@ struct Builder
                 }
             }
             t.op = op;
+            if (as_shadow && (op & QR_OPF_NOSHAD)) t.emit = false;
             lo_after[i] = local_obj;
         }
         /* static state must not depend on whether a ray walked through an array or skipped it (AR_skp:
@@ -716,7 +740,7 @@ struct Builder
         const uint32_t base = alloc((size_t)(ne + 1) * sizeof(CCell) + front, 64);
         const uint32_t off = base + (uint32_t)front;
         if (want_len) *at<uint32_t>(off - 4u) = (uint32_t)ne * (uint32_t)sizeof(CCell) | (pre_bv == 0 ? 1u : 0u);
-        list_off[head] = off;
+        memo_off = off;
         for (int i = 0; i < n; i++)
         {
             if (!ch[i].emit) continue;
@@ -794,7 +818,7 @@ struct Builder
             if (ch[i].emit && ((ch[i].op & QR_OPT_TRNODE) || (ch[i].op & QR_OPF_LOCAL))) world = false;
         if (world) lf |= QR_LISTF_WORLD;
         if (want_dda && world && (lf & QR_LISTF_DIV)) { build_dda(base, off, n); lf |= QR_LISTF_DDA; any_long = true; }
-        list_off[head] = off | lf;
+        memo_off = off | lf;
         list_heavy[head] = heavy;
         if (dedup) dedup_add(dkey, off | lf, heavy);
         return off | lf;
@@ -1060,7 +1084,7 @@ struct Builder
             CLight l;
             l.lgt = o_lgt + (uint32_t)E[e].simd * (uint32_t)sizeof(qr_light);
             const int sh = E[e].data, lg = E[e].simd;       /* copies: compile_grid appends to E */
-            l.shadow = compile_list(sh);
+            l.shadow = compile_list(sh, true);
             if (Egrow != nullptr && light_user[head] >= 0 && sh != QR_NULL)
                 if (const uint32_t g = compile_grid(light_user[head], lg, sh)) l.shadow = g;
             ls.push_back(l);
@@ -1118,6 +1142,8 @@ static int program_build_once(const qr_scene_view &v, const std::vector<qr_elem>
         {
             const char *de = getenv("QR_DDA");          /* 0 turns the uniform grids off */
             b.dda_min = de ? atoi(de) : 512;
+            const char *se = getenv("QR_SHADOWLESS");   /* 0 keeps the cells that cast no shadow in the shadow lists */
+            b.drop_shadowless = !(se && atoi(se) == 0);
         }
         if (want_grids)
         {

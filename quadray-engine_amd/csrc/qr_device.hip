@@ -601,6 +601,14 @@ extern "C" int qr_render_count(qr_device_scene *s, void *frame_dev, void *stream
         for (int i = 0; i < 8; i++) fprintf(stderr, " %llu", pf[40 + i]);
         fprintf(stderr, "\n");
         fprintf(stderr, "QR_PROF trnode cells reached %llu, ranges that end without a member handed out %llu\n", pf[62], pf[63]);
+        /* own-surface cells and cells that cast no shadow in the packet walks' solves (profiles/r25_own_surface_roots.txt) */
+        for (int k = 0; k < 3; k++)
+        {
+            static const char *kind[3] = { "shadow", "primary", "secondary" };
+            const unsigned long long *a = pf + 50 + 4 * k;
+            fprintf(stderr, "QR_PROF solves of %s packet walks: own-surface cells plane %llu quadric %llu two-plane %llu, cells that cast no shadow %llu\n",
+                    kind[k], a[0], a[1], a[2], a[3]);
+        }
         unsigned long long z[64] = {0};
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(qr_prof), z, sizeof(z)));
     }

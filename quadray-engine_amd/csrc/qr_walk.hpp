@@ -485,6 +485,11 @@ __device__ __forceinline__ void solve_cell(BaseP B, u32 op, u32 srf_off, const S
         QR_PROF_HIT(SHADOW ? 11 : 12);
         if (op & (QR_OPF_OWN | QR_OPF_CACHED)) QR_PROF_HIT(13);
         if (op & QR_OPF_CONIC) QR_PROF_HIT(14);
+        /* profiles/r25_own_surface_roots.txt, by kind of packet walk (shadow, primary, secondary): cells where every ray that is on is
+         * on its own surface, by solver; cells that cast no shadow */
+        QR_PF(if constexpr (!DIV) { const int pk = 50 + 4 * (SHADOW ? 0 : (r.osrf == 0 ? 1 : 2));
+              if (!K::any(K::of(srf_off != r.osrf))) QR_PROF_HIT(pk + ((op & QR_OPT_PLANE) ? 0 : ((op & QR_OPT_QUADRIC) ? 1 : 2)));
+              if (op & QR_OPF_NOSHAD) QR_PROF_HIT(pk + 3); })
         if (op & QR_OPT_PLANE)
         {
             /* PL_ptr 4062-4136 */
