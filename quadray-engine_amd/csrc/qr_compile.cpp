@@ -709,9 +709,10 @@ struct Builder
         for (int i = 0; i < n; i++) { emit_idx[i] = ne; if (ch[i].emit) { ne += (ch[i].op & QR_OPT_BV) ? 2 : 1; n_emitted++; } }
         emit_idx[n] = ne;
         /* uniform grid (CDda) for long world-space lists without clipper programs: decided before the cells are placed,
-         * the record sits in the 64 bytes in front of the program */
+         * the record sits in the 64 bytes in front of the program.  Not for a program of shadow rays alone (as_shadow here: the
+         * one with cells left out): only nearest-hit rays walk a grid (qr_walk.hpp traverse, !SHADOW) */
         bool want_dda = false;
-        if (dda_min > 0 && !has_trnode)
+        if (dda_min > 0 && !has_trnode && !as_shadow)
         {
             int n_small = 0; bool ok = true;
             for (int i = 0; i < n && ok; i++)

@@ -13,6 +13,14 @@ surface taken as the engine wrote it from the snapshots under tests/golden/ (SOU
                            test15_160).  Planes only: texture coordinates are written by the plane's material code alone
                            (oracle/qr_oracle.c, PL_mat), a textured quadric would show what the last plane hit left there
   lst                      light lists by synth._sides over the global list
+The lists are not the engine's.  Which light is entered on which side is its rule (synth._sides and qr_sides.cpp clip_side agree
+on every member, as bbox_side(lgt->bvbox, srf->shape) has it), but the shadow list behind every light is the GLOBAL list, where
+the engine's lsort -- and the product's list-building pass after it -- places on a side's shadow list only what bbox_side(box,
+srf->shape) sees from that side: geometry alone, no transparency, so the inner side of an open shape gets no caster that stands
+behind the shape's own wall.  While the wall casts a shadow it hides them anyway and build_lists(crowd) renders as the crowd does
+(test_crowd.py: test_bounds_and_lists_are_conservative); with members patched to cast none (tests/_noshad.py) the superset written
+here keeps shadows that the engine's lists drop: 8 / 75 / 1 pixels of the HIER / DENSE / OPEN crowd, narrowed to surfaces 250, 271
+and 310 of DENSE and pinned in tests/test_noshad_walks.py.
 For a record without its own transform (has_trm == 0) every other field is relative to pos (oracle/qr_oracle.c clip():
 hit - pos against min / max; qr_sides.cpp: bmin = min + pos) or is a pure shape coefficient: d_eps, t_eps, axes, conic,
 srf_t, c_def, smask stay as the engine set them.
