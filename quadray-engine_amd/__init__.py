@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "qr_gather_rays_async", "qr_gather_views_async", "qr_gather_hits_async",
     "qr_fan_rays_framed_async", "qr_fan_views_framed_async", "qr_fan_hits_framed_async",
     "qr_gather_rays_framed_async", "qr_gather_views_framed_async", "qr_gather_hits_framed_async",
-    "qr_atrous_views_async", "qr_pt_adapt_views_variance_async",
+    "qr_atrous_views_async", "qr_pt_adapt_views_variance_async", "qr_reproject_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -65,6 +65,7 @@ ATROUS_LUMA = 4             # the luminance stop against the variance,
 ATROUS_DEMODULATE = 8       # every colour read is divided by its own pixel's albedo,
 ATROUS_MODULATE = 16        # the output is multiplied by the centre pixel's albedo
 ATROUS_MAX_STEP = 64        # QR_ATROUS_MAX_STEP: the widest tap spacing of one pass
+REPROJ_DEMODULATE = 1       # qr_reproject_views_async flag: this frame's colour is divided by its own pixel's albedo
 
 
 class QrError(RuntimeError):
@@ -89,6 +90,15 @@ class AtrousParams(ctypes.Structure):
     """qr_atrous_params (include/qrhip.h), 32 bytes"""
     _fields_ = [("step", ctypes.c_int32), ("channels", ctypes.c_int32), ("normal_sq", ctypes.c_int32), ("flags", ctypes.c_uint32),
                 ("sigma_z", ctypes.c_float), ("sigma_l2", ctypes.c_float), ("eps_l", ctypes.c_float), ("alb_floor", ctypes.c_float)]
+
+
+class ReprojectParams(ctypes.Structure):
+    """qr_reproject_params (include/qrhip.h), 64 bytes"""
+    _fields_ = [("channels", ctypes.c_int32), ("flags", ctypes.c_uint32), ("off_x", ctypes.c_float), ("off_y", ctypes.c_float),
+                ("normal_min", ctypes.c_float), ("plane_max", ctypes.c_float), ("min_weight", ctypes.c_float),
+                ("alpha_min", ctypes.c_float), ("alpha_mom_min", ctypes.c_float), ("max_len", ctypes.c_float),
+                ("var_min_len", ctypes.c_float), ("unknown", ctypes.c_float), ("alb_floor", ctypes.c_float),
+                ("reserved", ctypes.c_uint32 * 3)]
 
 
 class RayCounts(ctypes.Structure):
@@ -158,6 +168,7 @@ def lib():
         getattr(L, name + "_reset").argtypes = [vp] + head + [vp]
     L.qr_pt_adapt_list_work_bytes.argtypes = [vp, i64, ctypes.POINTER(cu64)]
     L.qr_atrous_views_async.argtypes = [vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(AtrousParams), vp, vp, vp]
+    L.qr_reproject_views_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(ReprojectParams), vp, vp, vp, vp, vp]
     L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
     L.qr_frame_hash.argtypes = [vp, cu64]
@@ -689,6 +700,72 @@ class Scene:
             self._atrous_launch(c, v, hits, dims, 1 << k, per_pass[k], co, vo, stream)
             c, v = co, vo
         return c, v
+
+    @staticmethod
+    def _reproject_stops(**params):
+        from . import rays
+        try:
+            return rays.reproject_stops(**params)
+        except (ValueError, TypeError) as e:
+            raise QrError(str(e)) from None
+
+    def _reproject_args(self, colour, hits, prev, variance, out, colour_out, variance_out, coords):
+        """the tensors of reproject(): dtype and shape first, then contiguity and device.  Returns ((n, h, w, channels), the
+        previous triple or three None, out, colour_out, variance_out, coords) with the outputs that are wanted made."""
+        dev = self.device
+        if not (_fits(colour, "float32", (None, None, None, None)) and colour.shape[3] in (3, 4) and min(colour.shape) >= 1):
+            raise QrError("colour must be a float32 [N, H, W, 3] or [N, H, W, 4] tensor")
+        n, h, w, ch = (int(x) for x in colour.shape)
+        if not _fits(hits, "float32", (n, h, w, 12)):
+            raise QrError(f"hits must be a float32 [{n}, {h}, {w}, 12] tensor of qr_hit records (view_hits)")
+        if variance is not None and not _fits(variance, "float32", (n, h, w)):
+            raise QrError(f"variance must be None or a float32 [{n}, {h}, {w}] tensor")
+        if prev is None:
+            prev = (None, None, None)
+        elif not (isinstance(prev, (tuple, list)) and len(prev) == 3 and _fits(prev[0], "float32", (n, 16))
+                  and _fits(prev[1], "float32", (n, h, w, 12)) and _fits(prev[2], "float32", (n, h, w, 8))):
+            raise QrError(f"prev must be None or (views_prev float32 [{n}, 16], hits_prev float32 [{n}, {h}, {w}, 12], "
+                          f"history float32 [{n}, {h}, {w}, 8])")
+        for t, what in ((colour, "colour"), (hits, "hits"), (variance, "variance"), (prev[0], "views_prev"), (prev[1], "hits_prev"),
+                        (prev[2], "history")):
+            if t is not None and not _fits(t, None, None, dev):
+                raise QrError(f"{what} must be contiguous and on cuda:{dev}")
+        out = _fill("out", out, "float32", (n, h, w, 8), dev)
+        if prev[2] is not None and out.data_ptr() == prev[2].data_ptr():
+            raise QrError("out must not be the previous history: the taps read neighbours")
+        return ((n, h, w, ch), prev, out, _wanted("colour_out", colour_out, "float32", (n, h, w, ch), dev),
+                _wanted("variance_out", variance_out, "float32", (n, h, w), dev), _wanted("coords", coords, "float32", (n, h, w, 2), dev))
+
+    def _reproject_launch(self, colour, hits, variance, prev, dims, stops, out, colour_out, variance_out, coords, stream):
+        n, h, w, ch = dims
+        p = ReprojectParams(ch, *(stops[k] for k in ("flags", "off_x", "off_y", "normal_min", "plane_max", "min_weight", "alpha_min",
+                                                     "alpha_mom_min", "max_len", "var_min_len", "unknown", "alb_floor")))
+        _check(lib().qr_reproject_views_async(self._h, _ptr(colour), _ptr(hits), _ptr(variance), _ptr(prev[0]), _ptr(prev[1]),
+                                              _ptr(prev[2]), n, w, h, ctypes.byref(p), _ptr(out), _ptr(colour_out),
+                                              _ptr(variance_out), _ptr(coords), self._stream_ptr(stream)))
+
+    def reproject(self, colour, hits, prev=None, variance=None, out=None, colour_out=True, variance_out=True, coords=False,
+                  stream=None, **params):
+        """Temporal reprojection (qr_reproject_views_async; rays.reproject_pass is its arithmetic): blend this frame's noisy colour
+        (float32 [N, H, W, 3|4]) into the history of the frame before, fetched where this frame's hits (view_hits of the current
+        cameras) fall in the previous cameras and kept only on the same surface.  prev = (views_prev [N, 16], hits_prev, history
+        [N, H, W, 8]) of the frame before, None for a first frame; variance (float32 [N, H, W], PtAdaptiveViews.variance): what
+        a short history hands out.  out: the history tensor to write (a new one by default, never prev's); colour_out,
+        variance_out, coords: True (a new tensor), False or a tensor to fill.  params: normal_min, plane_max, min_weight,
+        alpha_min, alpha_mom_min, max_len, var_min_len, unknown, albedo_floor, demodulate, off as rays.reproject_stops takes
+        them -- starting points, not tuned.  Static scenes under a moving camera.  Returns (history, colour, variance), with
+        coords wanted (history, colour, variance, coords); what is not wanted is None.  Asynchronous on `stream`."""
+        stops = self._reproject_stops(**params)
+        dims, prev, out, colour_out, variance_out, cd = self._reproject_args(colour, hits, prev, variance, out, colour_out,
+                                                                             variance_out, coords)
+        self._reproject_launch(colour, hits, variance, prev, dims, stops, out, colour_out, variance_out, cd, stream)
+        return (out, colour_out, variance_out) if cd is None else (out, colour_out, variance_out, cd)
+
+    def temporal(self, n_views, width, height, channels=3, **params):
+        """A temporal accumulator over frames of n_views moving cameras at width x height (rays.temporal is its chain): returns
+        a Temporal whose step(colour, hits, views, variance=None) reprojects against the frame before.  params as for
+        reproject()."""
+        return Temporal(self, n_views, width, height, channels, **params)
 
     def _fan_args(self, dirs, eps, reach, shape, mask):
         """(dirs as a contiguous float32 [K, 4] tensor, K, eps, reach, open, mask or None) of an occlusion-fan call whose
@@ -1289,6 +1366,69 @@ class PtAdaptiveViews(_Adaptive):
                                              _ptr(counts), _ptr(opent), 0, Scene._stream_ptr(stream)))
         out = (frames,) + tuple(t for t in (mean, counts, opent) if t is not None)
         return out if len(out) > 1 else frames
+
+
+class Temporal:
+    """A temporal accumulation over the frames of moving cameras (Scene.temporal; include/qrhip.h qr_reproject_views_async;
+    rays.Temporal is its chain in numpy).
+
+    It owns two history tensors (float32 [N, H, W, 8]: c0 c1 c2 c3 m1 m2 len 0 per pixel) that it alternates between, and
+    clones of the last step's hit records and cameras: a copy of 48 B per pixel and step, on the step's stream, so that the
+    caller may reuse its own tensors at once.  `frames`: steps since the start or the last reset().  Static scenes under a
+    moving camera; the stops (normal_min, plane_max, ...: rays.reproject_stops) are starting points, not tuned."""
+
+    def __init__(self, scene, n_views, width, height, channels=3, **params):
+        if not (all(isinstance(x, int) and not isinstance(x, bool) and x >= 1 for x in (n_views, width, height)) and channels in (3, 4)):
+            raise QrError("n_views, width and height must be positive integers and channels 3 or 4")
+        self.scene, self.shape, self.channels = scene, (n_views, height, width), channels
+        self.params = scene._reproject_stops(**params)
+        self._hist = [_new("float32", self.shape + (8,), scene.device) for _ in range(2)]
+        self._cur, self._hits, self._views, self.frames = 0, None, None, 0
+
+    def reset(self):
+        """The next step is a first frame: every pixel fresh.  Nothing is launched."""
+        self._hits = self._views = None
+        self.frames = 0
+
+    def clone(self):
+        """A checkpoint: an accumulator with copies of the history, records and cameras (on the current stream) that continues
+        independently."""
+        other = Temporal(self.scene, self.shape[0], self.shape[2], self.shape[1], self.channels)
+        other.params = dict(self.params)
+        other._cur, other.frames = self._cur, self.frames
+        if self._hits is not None:
+            other._hist[self._cur].copy_(self._hist[self._cur])
+            other._hits, other._views = self._hits.clone(), self._views.clone()
+        return other
+
+    @property
+    def history(self):
+        """the entries after the last step, float32 [N, H, W, 8] (a view: the step after next overwrites it); None before the first"""
+        return None if self._hits is None else self._hist[self._cur]
+
+    @property
+    def length(self):
+        """the history length per pixel after the last step, a float32 [N, H, W] view of `history`; None before the first"""
+        return None if self._hits is None else self._hist[self._cur][..., 6]
+
+    def step(self, colour, hits, views, variance=None, stream=None):
+        """One frame: colour (float32 [N, H, W, channels]), hits (view_hits of `views`) and views (float32 [N, 16], this frame's
+        cameras) against the frame before; variance as for Scene.reproject.  Returns (colour, variance), new tensors: the
+        accumulated colour -- demodulated with demodulate=True: Scene.atrous(modulate=True) as the last filter pass multiplies
+        back -- and its variance, what Scene.denoise takes.  Asynchronous on `stream`."""
+        import torch
+        scn = self.scene
+        n, h, w = self.shape
+        if not (_fits(colour, "float32", (n, h, w, self.channels)) and _fits(views, "float32", (n, 16), scn.device)):
+            raise QrError(f"this accumulation holds float32 colour [{n}, {h}, {w}, {self.channels}] and views [{n}, 16] on cuda:{scn.device}")
+        prev = None if self._hits is None else (self._views, self._hits, self._hist[self._cur])
+        dims, prev, out, col, var, _ = scn._reproject_args(colour, hits, prev, variance, self._hist[self._cur ^ 1], True, True, False)
+        scn._reproject_launch(colour, hits, variance, prev, dims, self.params, out, col, var, None, stream)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            self._hits, self._views = hits.clone(), views.clone()
+        self._cur ^= 1
+        self.frames += 1
+        return col, var
 
 
 class MultiRender:

@@ -16,6 +16,7 @@
 #include "qr_layers.hpp"
 #include "qr_openlist.hpp"
 #include "qr_atrous.hpp"
+#include "qr_reproject.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstring>

@@ -1,6 +1,6 @@
 /*
  * qr_rayapi.hpp - host glue of the ray API (include/qrhip.h): ray queries, shading, views, path-traced rays and views,
- * the a-trous filter, open lists, hit records, fans, gather fans and hit layers.  Included by qr_device.hip (one
+ * the a-trous filter, temporal reprojection, open lists, hit records, fans, gather fans and hit layers.  Included by qr_device.hip (one
  * translation unit) after qr_device_scene, HIP_TRY, QR_TRY, need_scene and pt_seed_plane.
  *
  * Every check, grid and kernel choice is stated once, below; an entry point composes these in the order of its own
@@ -553,6 +553,53 @@ extern "C" int qr_atrous_views_async(qr_device_scene *s, const float *colour_in,
     const dim3 grid((unsigned)(phx * ap.tiles_x), (unsigned)(phy * ap.tiles_y), (unsigned)n_views), block(QR_ATROUS_BLOCK);
     pick(p->channels == 3, [&](auto three) {
         hipLaunchKernelGGL(qr_atrous_kernel<(decltype(three)::value ? 3 : 4)>, grid, block, 0, (hipStream_t)stream, ap);
+    });
+    return launched();
+}
+
+/* ---- temporal reprojection (qr_reproject.hpp): one lane per pixel, 32 x 8 pixel tiles, blockIdx.z the view ---- */
+
+extern "C" int qr_reproject_views_async(qr_device_scene *s, const float *colour_in, const qr_hit *hits, const float *var_in,
+                                        const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
+                                        int n_views, int width, int height, const qr_reproject_params *p,
+                                        float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream)
+{
+    QR_TRY(need_scene(s));
+    if (p == nullptr) return qr_fail(QR_ERR_ARG, "null reprojection parameters");
+    QR_TRY(view_size_args(n_views, width, height));
+    if (p->channels != 3 && p->channels != 4) return qr_fail(QR_ERR_ARG, "channels must be 3 or 4");
+    QR_TRY(flags_arg(p->flags, QR_REPROJ_DEMODULATE, "unknown reprojection flags"));
+    if (p->reserved[0] != 0u || p->reserved[1] != 0u || p->reserved[2] != 0u)
+        return qr_fail(QR_ERR_ARG, "the reserved words of the reprojection parameters must be 0");
+    if (!(std::fabs(p->off_x) <= FLT_MAX) || !(std::fabs(p->off_y) <= FLT_MAX)) return qr_fail(QR_ERR_ARG, "off_x and off_y must be finite");
+    if (p->normal_min != p->normal_min) return qr_fail(QR_ERR_ARG, "normal_min must not be NaN");
+    if (!(p->plane_max > 0.0f) || !(p->alb_floor > 0.0f)) return qr_fail(QR_ERR_ARG, "plane_max and alb_floor must be above 0");
+    if (!(p->min_weight >= 0.0f)) return qr_fail(QR_ERR_ARG, "min_weight must be 0 or more");
+    if (!(p->alpha_min >= 0.0f && p->alpha_min <= 1.0f) || !(p->alpha_mom_min >= 0.0f && p->alpha_mom_min <= 1.0f))
+        return qr_fail(QR_ERR_ARG, "alpha_min and alpha_mom_min must be 0..1");
+    if (!(p->max_len >= 1.0f) || !(p->var_min_len >= 1.0f)) return qr_fail(QR_ERR_ARG, "max_len and var_min_len must be 1 or more");
+    const int n_prev = (views_prev != nullptr) + (hits_prev != nullptr) + (hist_in != nullptr);
+    if (n_prev != 0 && n_prev != 3)
+        return qr_fail(QR_ERR_ARG, "views_prev, hits_prev and hist_in go together: all three or none (the first frame)");
+    if (n_views == 0) return QR_OK;
+    QR_TRY(need_ptrs({colour_in, hits, hist_out}));
+    QR_TRY(aligned_ptrs({hits, views_prev, hits_prev, hist_in, hist_out}, 16, "views, hits and history must be 16-byte aligned"));
+    QR_TRY(aligned_ptrs({colour_in, var_in, colour_out, var_out, coords_out}, 4, "colour, variance and coords must be 4-byte aligned"));
+    if (hist_in == hist_out) return qr_fail(QR_ERR_ARG, "the taps read neighbours' history: hist_out cannot be hist_in");
+    HIP_TRY(hipSetDevice(s->device));
+    ReprojP rp;
+    rp.colour_in = colour_in; rp.hits = (const f32x4 *)hits; rp.var_in = var_in;
+    rp.views_prev = views_prev; rp.hits_prev = (const f32x4 *)hits_prev; rp.hist_in = (const f32x4 *)hist_in;
+    rp.hist_out = (f32x4 *)hist_out; rp.colour_out = colour_out; rp.var_out = var_out; rp.coords_out = coords_out;
+    rp.width = width; rp.height = height; rp.flags = p->flags;
+    rp.off_x = p->off_x; rp.off_y = p->off_y; rp.normal_min = p->normal_min; rp.plane_max = p->plane_max;
+    rp.min_weight = p->min_weight; rp.alpha_min = p->alpha_min; rp.alpha_mom_min = p->alpha_mom_min;
+    rp.max_len = p->max_len; rp.var_min_len = p->var_min_len; rp.unknown = p->unknown; rp.alb_floor = p->alb_floor;
+    /* grid.x <= 512, grid.y <= 2048 at QR_VIEW_MAX_DIM */
+    const dim3 grid((unsigned)((width + QR_REPROJ_TW - 1) / QR_REPROJ_TW), (unsigned)((height + QR_REPROJ_TH - 1) / QR_REPROJ_TH),
+                    (unsigned)n_views), block(QR_REPROJ_BLOCK);
+    pick(p->channels == 3, [&](auto three) {
+        hipLaunchKernelGGL(qr_reproject_kernel<(decltype(three)::value ? 3 : 4)>, grid, block, 0, (hipStream_t)stream, rp);
     });
     return launched();
 }

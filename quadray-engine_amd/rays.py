@@ -74,6 +74,17 @@ and pt_adapt_view_variance state them in float32 numpy, operation for operation;
     views_acc = scn.pt_adaptive_views(views, w, h, min_samples=8, max_samples=8)
     _, mean = views_acc.step(8, mean=True)
     clean, var = scn.denoise(mean, scn.view_hits(views, w, h), views_acc.variance(), passes=5, plane=0.05, luma=4.0)
+
+Scene.temporal reuses the samples of the frames before under a moving camera (include/qrhip.h qr_reproject_views_async): every
+pixel of this frame's hit records is projected into the previous camera (project_to_view), the previous history is fetched there
+through four bilinear taps held to the same surface, and this frame's colour is blended in.  reproject_pass states one call,
+Temporal / temporal the accumulator's chain, in float32 numpy; reproject_stops is the host side of the arguments:
+
+    acc = scn.temporal(1, w, h, plane_max=0.02)     # about one pixel's footprint, world units
+    for view in camera_path:                        # float32 [1, 16] tensors
+        hits = scn.view_hits(view, w, h)
+        colour, var = acc.step(noisy_mean_of(view), hits, view, variance_of(view))
+        clean, _ = scn.denoise(colour, hits, var, passes=5, plane=0.05, luma=4.0)
 """
 import struct
 
@@ -1113,3 +1124,249 @@ def pt_adapt_view_variance(state, spp, unknown=1.0):
         for k in range(1, spp):
             acc = acc + v[..., k]
         return (acc * (f(1.0) / f(spp * spp))).astype(f)
+
+
+# ---- temporal reprojection (include/qrhip.h qr_reproject_views_async; Scene.reproject, Scene.temporal) ----
+
+REPROJ_DEMODULATE = 1                                                                               # QR_REPROJ_DEMODULATE
+REPROJ_NAN = np.array([0x7FC00000], dtype=np.uint32).view(np.float32)[0]                            # the NaN the call writes
+_REPROJ_FIELDS = ("flags", "off_x", "off_y", "normal_min", "plane_max", "min_weight", "alpha_min", "alpha_mom_min", "max_len",
+                  "var_min_len", "unknown", "alb_floor")
+
+
+def reproject_stops(normal_min=0.9, plane_max=None, min_weight=0.01, alpha_min=0.05, alpha_mom_min=0.2, max_len=32, var_min_len=4,
+                    unknown=1.0, albedo_floor=1 / 256, demodulate=False, off=(0, 0)):
+    """The host side of Scene.reproject's arguments: a dict of qr_reproject_params' fields (flags, off_x, off_y, normal_min,
+    plane_max, min_weight, alpha_min, alpha_mom_min, max_len, var_min_len, unknown, alb_floor), the floats as float32, that
+    reproject_pass takes as keywords.  The defaults are starting points, not tuned: normal_min 0.9; plane_max should be about one
+    pixel's footprint in world units at the scene's depth (None: +inf, the plane test only closes NaN); min_weight 0.01; and
+    SVGF's customary alpha_min 0.05, alpha_mom_min 0.2, max_len 32, var_min_len 4.  off: the sub-pixel offset of the records'
+    rays, the frame's (hor_a[0], ver_a[0]); (0, 0) without FSAA.  Raises ValueError for what the call would refuse."""
+    f = np.float32
+
+    def number(x, what):
+        try:
+            v = f(x)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a number") from None
+        if isinstance(x, (bool, str)):
+            raise ValueError(f"{what} must be a number")
+        return v
+    try:
+        off_x, off_y = off
+    except (TypeError, ValueError):
+        raise ValueError("off must be a pair of numbers") from None
+    p = dict(flags=REPROJ_DEMODULATE if demodulate else 0, off_x=number(off_x, "off"), off_y=number(off_y, "off"),
+             normal_min=number(normal_min, "normal_min"), plane_max=f(np.inf) if plane_max is None else number(plane_max, "plane_max"),
+             min_weight=number(min_weight, "min_weight"), alpha_min=number(alpha_min, "alpha_min"),
+             alpha_mom_min=number(alpha_mom_min, "alpha_mom_min"), max_len=number(max_len, "max_len"),
+             var_min_len=number(var_min_len, "var_min_len"), unknown=number(unknown, "unknown"),
+             alb_floor=number(albedo_floor, "albedo_floor"))
+    _reproject_params(p)
+    return p
+
+
+def _reproject_params(p):
+    """the refusals of qr_reproject_views_async that concern the parameters alone, as ValueError"""
+    if int(p["flags"]) & ~REPROJ_DEMODULATE:
+        raise ValueError("flags must be of REPROJ_*")
+    if not (np.isfinite(p["off_x"]) and np.isfinite(p["off_y"])):
+        raise ValueError("off must be finite")
+    if np.isnan(p["normal_min"]):
+        raise ValueError("normal_min must be a number, not NaN")
+    if not (p["plane_max"] > 0 and p["alb_floor"] > 0):
+        raise ValueError("plane_max and albedo_floor must be above 0")
+    if not p["min_weight"] >= 0:
+        raise ValueError("min_weight must be 0 or more")
+    if not (0 <= p["alpha_min"] <= 1 and 0 <= p["alpha_mom_min"] <= 1):
+        raise ValueError("alpha_min and alpha_mom_min must be 0..1")
+    if not (p["max_len"] >= 1 and p["var_min_len"] >= 1):
+        raise ValueError("max_len and var_min_len must be 1 or more")
+
+
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def _dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def project_to_view(view, pos, off=(0, 0), dtype=np.float32):
+    """The projection of qr_reproject_views_async, operation for operation: where world-space points pos [..., 3] fall in the
+    frame of `view` (a qr_view [16], or [..., 16] broadcast against pos).  With A = hor x ver, B = ver x dir, C = dir x hor, det
+    = (dir.x * A.x + dir.y * A.y) + dir.z * A.z and e = pos - org: den = e . A, nu = e . B, nv = e . C in that association, fx =
+    nu / den - off[0], fy = nv / den - off[1], front = (0 < den and 0 < det) or (den < 0 and det < 0).  Returns (xy [..., 2],
+    front [...]): pixel (x, y)'s own ray gives (x, y) to rounding; a point behind the eye is not front.  dtype: float32 is the
+    call's arithmetic; float64 evaluates the same text in double precision."""
+    f = np.dtype(dtype).type
+    v, pos = np.asarray(view).astype(f), np.asarray(pos).astype(f)
+    org, d, hor, ver = v[..., 0:3], v[..., 4:7], v[..., 8:11], v[..., 12:15]
+    with np.errstate(all="ignore"):
+        A, B, C = _cross(hor, ver), _cross(ver, d), _cross(d, hor)
+        det = _dot(d, A)
+        e = pos - org
+        den, nu, nv = _dot(e, A), _dot(e, B), _dot(e, C)
+        fx, fy = nu / den - f(off[0]), nv / den - f(off[1])
+        front = ((0 < den) & (0 < det)) | ((den < 0) & (det < 0))
+    return np.stack([fx, fy], axis=-1), front
+
+
+def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, off_y=0.0, normal_min=0.9, plane_max=np.inf,
+                   min_weight=0.01, alpha_min=0.05, alpha_mom_min=0.2, max_len=32.0, var_min_len=4.0, unknown=1.0, alb_floor=1 / 256,
+                   taps=None):
+    """The specification of one qr_reproject_views_async call in float32 numpy, every operation elementwise so that it rounds
+    once: colour float32 [N, H, W, C] (or [H, W, C]; C 3 or 4), hits float32 [N, H, W, 12] (this frame's qr_hit records),
+    variance float32 [N, H, W] or None, prev = None (the first frame) or (views_prev [N, 16], hits_prev [N, H, W, 12], history
+    [N, H, W, 8]), the rest as qr_reproject_params (reproject_stops gives them as a dict).  Returns (history' [N, H, W, 8],
+    colour' [N, H, W, C], variance' [N, H, W], coords [N, H, W, 2]), new arrays.
+
+    Per pixel p (include/qrhip.h has the full text): c = the colour, with REPROJ_DEMODULATE and id_p >= 0 channels 0..2 divided by
+    alb if alb > alb_floor else alb_floor; l = (r * 0.2126 + g * 0.7152) + b * 0.0722.  The fresh entry is (c, l, l * l, 1, 0)
+    with the variance variance[p] (unknown without one); a miss, the first frame, a point not in front of the previous camera
+    (project_to_view) give it, and NaN coords.  Else coords = (fx, fy), and inside -1 < fx < W, -1 < fy < H the four taps q =
+    (floor(fx) + i, floor(fy) + j), j outer, b = (wx if i else 1 - wx) * (wy if j else 1 - wy), are taken where q is inside the
+    frame, id_q == id_p, 1 <= len_q, normal_min < n_p . n_q, |n_p . (pos_q - pos_p)| <= plane_max and 0 < b: sw += b, sc += c_q
+    * b, s1 += m1_q * b, s2 += m2_q * b, sl += len_q * b.  Where min_weight < sw: len = min(sl / sw + 1, max_len), a = 1 / len,
+    c = (sc / sw) * (1 - max(a, alpha_min)) + c * max(a, alpha_min), m1 and m2 likewise with alpha_mom_min, the variance max(0,
+    m2 - m1 * m1) where var_min_len <= len; elsewhere the fresh entry.
+
+    taps: if a list is given, the four (taken bool [N, H, W], b float32 [N, H, W]) pairs are appended to it in tap order."""
+    f = np.float32
+    colour, variance, hits = _atrous_args(colour, variance, hits)
+    single = colour.ndim == 3
+    if single:
+        colour, hits = colour[None], hits[None]
+        variance = None if variance is None else variance[None]
+    par = dict(flags=int(flags), off_x=f(off_x), off_y=f(off_y), normal_min=f(normal_min), plane_max=f(plane_max),
+               min_weight=f(min_weight), alpha_min=f(alpha_min), alpha_mom_min=f(alpha_mom_min), max_len=f(max_len),
+               var_min_len=f(var_min_len), unknown=f(unknown), alb_floor=f(alb_floor))
+    _reproject_params(par)
+    n, h, w, ch = colour.shape
+    if prev is not None:
+        try:
+            views_prev, hits_prev, hist_in = prev
+        except (TypeError, ValueError):
+            raise ValueError("prev must be None or (views_prev, hits_prev, history)") from None
+        if single:
+            views_prev, hits_prev, hist_in = (np.asarray(a)[None] for a in (views_prev, hits_prev, hist_in))
+        views_prev, hits_prev, hist_in = np.asarray(views_prev), np.asarray(hits_prev), np.asarray(hist_in)
+        for a, shape, what in ((views_prev, (n, 16), "views_prev"), (hits_prev, (n, h, w, 12), "hits_prev"), (hist_in, (n, h, w, 8), "history")):
+            if a.dtype != f or a.shape != shape:
+                raise ValueError(f"{what} must be float32 {list(shape)}, got {a.dtype} {list(a.shape)}")
+    pos, _, nrm, ids, alb, _ = hit_fields(hits)
+    hit = ids >= 0
+    one, zero = f(1.0), f(0.0)
+    with np.errstate(all="ignore"):
+        a = np.where(alb > par["alb_floor"], alb, par["alb_floor"])                 # a NaN albedo gives the floor
+        col = np.zeros((n, h, w, 4), dtype=f)
+        col[..., :ch] = colour
+        if par["flags"] & REPROJ_DEMODULATE:
+            col[..., 0:3] = np.where(hit[..., None], col[..., 0:3] / a, col[..., 0:3])
+        lum = (col[..., 0] * f(0.2126) + col[..., 1] * f(0.7152)) + col[..., 2] * f(0.0722)
+        lum2 = lum * lum
+        var = np.full((n, h, w), par["unknown"], dtype=f) if variance is None else variance.copy()
+        hist = np.zeros((n, h, w, 8), dtype=f)
+        hist[..., 0:4], hist[..., 4], hist[..., 5], hist[..., 6] = col, lum, lum2, one
+        coords = np.full((n, h, w, 2), REPROJ_NAN, dtype=f)
+        if prev is not None:
+            xy, front = project_to_view(views_prev[:, None, None, :], pos, (par["off_x"], par["off_y"]))
+            front = front & hit
+            coords = np.where(front[..., None], xy, REPROJ_NAN).astype(f)
+            fx, fy = xy[..., 0], xy[..., 1]
+            window = front & (-one < fx) & (fx < f(w)) & (-one < fy) & (fy < f(h))
+            x0, y0 = np.floor(fx), np.floor(fy)
+            wx, wy = fx - x0, fy - y0
+            ix, iy = np.where(window, x0, zero).astype(np.int64), np.where(window, y0, zero).astype(np.int64)
+            pos_q, _, nrm_q, ids_q, _, _ = hit_fields(hits_prev)
+            vi = np.arange(n)[:, None, None]
+            sw, s1, s2, sl = (np.zeros((n, h, w), dtype=f) for _ in range(4))
+            sc = np.zeros((n, h, w, 4), dtype=f)
+            for j in (0, 1):
+                for i in (0, 1):
+                    qx, qy = ix + i, iy + j
+                    b = (wx if i else one - wx) * (wy if j else one - wy)
+                    ok = window & (qx >= 0) & (qx < w) & (qy >= 0) & (qy < h)
+                    qx, qy = np.clip(qx, 0, w - 1), np.clip(qy, 0, h - 1)
+                    hq, nq = hist_in[vi, qy, qx], nrm_q[vi, qy, qx]
+                    ok = ok & (ids_q[vi, qy, qx] == ids) & (one <= hq[..., 6])
+                    ok = ok & (par["normal_min"] < _dot(nrm, nq))
+                    ok = ok & (np.abs(_dot(nrm, pos_q[vi, qy, qx] - pos)) <= par["plane_max"]) & (0 < b)
+                    if taps is not None:
+                        taps.append((ok, np.where(ok, b, zero)))
+                    sw = np.where(ok, sw + b, sw)
+                    sc = np.where(ok[..., None], sc + hq[..., 0:4] * b[..., None], sc)
+                    s1 = np.where(ok, s1 + hq[..., 4] * b, s1)
+                    s2 = np.where(ok, s2 + hq[..., 5] * b, s2)
+                    sl = np.where(ok, sl + hq[..., 6] * b, sl)
+            keep = window & (par["min_weight"] < sw)
+            ln = sl / sw + one
+            ln = np.where(ln < par["max_len"], ln, par["max_len"])
+            al = one / ln
+            ac = np.where(al > par["alpha_min"], al, par["alpha_min"])
+            am = np.where(al > par["alpha_mom_min"], al, par["alpha_mom_min"])
+            cb = (sc / sw[..., None]) * (one - ac)[..., None] + col * ac[..., None]
+            m1 = (s1 / sw) * (one - am) + lum * am
+            m2 = (s2 / sw) * (one - am) + lum2 * am
+            v = m2 - m1 * m1
+            v = np.where(0 < v, v, zero)
+            hist[..., 0:ch] = np.where(keep[..., None], cb[..., 0:ch], col[..., 0:ch])
+            hist[..., 4], hist[..., 5], hist[..., 6] = np.where(keep, m1, lum), np.where(keep, m2, lum2), np.where(keep, ln, one)
+            var = np.where(keep & (par["var_min_len"] <= ln), v, var).astype(f)
+    out = (hist, hist[..., 0:ch].copy(), var, coords)
+    return tuple(o[0] for o in out) if single else out
+
+
+class Temporal:
+    """The accumulator's chain in numpy (temporal(); what Scene.temporal's Temporal computes on the GPU): two history arrays it
+    alternates between and copies of the last hit records and cameras.  step(colour, hits, views, variance=None) is one
+    reproject_pass against the frame before -- the first frame after the start or a reset() has none -- and returns (colour,
+    variance); history / length are the entry array [N, H, W, 8] and its length plane after the last step (None before the
+    first); clone() continues independently."""
+
+    def __init__(self, n_views, width, height, channels=3, **params):
+        if channels not in (3, 4) or min(int(n_views), int(width), int(height)) < 1:
+            raise ValueError("channels must be 3 or 4 and n_views, width, height at least 1")
+        self.shape, self.channels, self.params = (int(n_views), int(height), int(width)), int(channels), reproject_stops(**params)
+        self._hist = [np.zeros(self.shape + (8,), dtype=np.float32) for _ in range(2)]
+        self._cur, self._hits, self._views, self.frames = 0, None, None, 0
+
+    def reset(self):
+        """the next step is a first frame"""
+        self._hits = self._views = None
+        self.frames = 0
+
+    def clone(self):
+        other = Temporal(self.shape[0], self.shape[2], self.shape[1], self.channels)
+        other.params = dict(self.params)
+        other._hist = [a.copy() for a in self._hist]
+        other._cur, other.frames = self._cur, self.frames
+        other._hits = None if self._hits is None else self._hits.copy()
+        other._views = None if self._views is None else self._views.copy()
+        return other
+
+    @property
+    def history(self):
+        return None if self._hits is None else self._hist[self._cur]
+
+    @property
+    def length(self):
+        return None if self._hits is None else self._hist[self._cur][..., 6]
+
+    def step(self, colour, hits, views, variance=None):
+        colour, hits, views = np.asarray(colour), np.asarray(hits), np.asarray(views)
+        if colour.shape != self.shape + (self.channels,) or views.shape != (self.shape[0], 16) or views.dtype != np.float32:
+            raise ValueError(f"this accumulation holds float32 colour {list(self.shape) + [self.channels]} and views [{self.shape[0]}, 16]")
+        prev = None if self._hits is None else (self._views, self._hits, self._hist[self._cur])
+        hist, col, var, _ = reproject_pass(colour, hits, variance, prev, **self.params)
+        self._cur ^= 1
+        self._hist[self._cur][...] = hist
+        self._hits, self._views = hits.copy(), views.copy()
+        self.frames += 1
+        return col, var
+
+
+def temporal(n_views, width, height, channels=3, **params):
+    """The specification of Scene.temporal: a Temporal accumulator in numpy.  params: as reproject_stops takes them."""
+    return Temporal(n_views, width, height, channels, **params)

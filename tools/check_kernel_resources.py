@@ -30,6 +30,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
     than 168 VGPRs (128: the view instance with packet walks only);
   * a guided a-trous instance qr_atrous_kernel<CH> or qr_pt_adapt_var_kernel spills a vector register, has a private segment or
     uses more than 64 VGPRs, or a filter instance more LDS than its 36 x 12 staged entries (20736 B / 22464 B);
+  * a temporal reprojection instance qr_reproject_kernel<CH> spills a vector register, has a private segment, uses any LDS or
+    more than 96 (3 channels) / 80 (4 channels) VGPRs;
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
 usage: check_kernel_resources.py <file.s> [--print]
 """
@@ -124,8 +126,15 @@ LIMITS = {
     "16qr_atrous_kernelILi3EE": (64, 0, 0),
     "16qr_atrous_kernelILi4EE": (64, 0, 0),
     "22qr_pt_adapt_var_kernel": (64, 0, 0),
+    # temporal reprojection (qr_reproject.hpp qr_reproject_kernel<CH>): a projection and four gathered taps per pixel, bound by the
+    # bytes it moves: nothing spilled, no private segment, no LDS at all, and the registers of the build's assembly rounded up to
+    # the next occupancy step: 82 VGPRs -> 96 (5 waves per SIMD), 74 -> 80 (6 waves).  The registers are the sixteen quads of
+    # the four taps in flight at once, which is what the launch time rests on (qr_reproject.hpp)
+    "19qr_reproject_kernelILi3EE": (96, 0, 0),
+    "19qr_reproject_kernelILi4EE": (80, 0, 0),
 }
-LDS_LIMITS = {"16qr_atrous_kernelILi3EE": 20736, "16qr_atrous_kernelILi4EE": 22464}
+LDS_LIMITS = {"16qr_atrous_kernelILi3EE": 20736, "16qr_atrous_kernelILi4EE": 22464,
+              "19qr_reproject_kernelILi3EE": 0, "19qr_reproject_kernelILi4EE": 0}
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 
 
