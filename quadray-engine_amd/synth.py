@@ -161,8 +161,8 @@ def _tree(b, obj, ks, leaf):
 
 def _sides(r, lp):
     """Which side of surface record r a light at lp is entered on (2 outer, 1 inner, 3 both) -- the engine's rule
-    (RT_OPTS_2SIDED: lsort -> bbox_side -> clip_side, engine.cpp:2503-2533, rtgeom.cpp:939-995; the same rule as light_sides
-    in csrc/qr_compile.cpp): the sign of the quadric form at the light (margin 1e-4); a convex surface seen from inside shows
+    (RT_OPTS_2SIDED: lsort -> bbox_side -> clip_side, engine.cpp:2503-2533, rtgeom.cpp:939-995; the same rule as clip_side
+    of csrc/qr_sides.cpp, by which csrc/qr_lists.cpp enters lights): the sign of the quadric form at the light (margin 1e-4); a convex surface seen from inside shows
     its inner side only; from outside the outer side only, unless the surface is concave-capable with holes or the light
     stands outside its clip box."""
     f = r.view(np.float32)

@@ -1,4 +1,4 @@
-"""Colours at upload (csrc/qr_program.h QR_MATX_*, qr_compile.cpp material_colour): the image's copy of a material record whose
+"""Colours at upload (csrc/qr_program.h QR_MATX_*, qr_compile.hpp material_colour): the image's copy of a material record whose
 texture is ONE texel carries the finished colour, so that shade() skips the texel load, the three conversions and the three
 IEEE divisions by `clamp`.  The kernel takes the stored words as they are: they must be the bits its own arithmetic gives,
 

@@ -1,4 +1,4 @@
-"""The large-scene shadow walks on surfaces that cast no shadow (tests/_noshad.py; csrc/qr_compile.cpp compile_list(head,
+"""The large-scene shadow walks on surfaces that cast no shadow (tests/_noshad.py; csrc/qr_builder.cpp compile_list(head,
 as_shadow) leaves QR_OPF_NOSHAD cells out of the programs CLight::shadow points to, QR_SHADOWLESS=0 keeps them).
 
 tests/test_own_surface_roots.py holds that on fixtures of at most 240 objects; no large scene of the tree has a surface that

@@ -1,4 +1,4 @@
-"""Shadow lists without the cells that cast no shadow (csrc/qr_compile.cpp compile_list(head, as_shadow), QR_SHADOWLESS=0 keeps
+"""Shadow lists without the cells that cast no shadow (csrc/qr_builder.cpp compile_list(head, as_shadow), QR_SHADOWLESS=0 keeps
 them; profiles/r25_own_surface_roots.txt).
 
 The count that was asked for before anything was cut found a ray's own surface in few of the packet walks' solves, and a cell that

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Host-only: per-phase time of validate + compile of a snapshot (QR_COMPILE_TIMING ticks of csrc/qr_compile.cpp), and a hash
+"""Host-only: per-phase time of validate + compile of a snapshot (QR_COMPILE_TIMING ticks of csrc/qr_compile.cpp and qr_schedule.cpp), and a hash
 of the compiled image (QR_DUMP_IMAGE) so that a change to the compiler can be checked to leave the image byte for byte.
 usage: tools/host_compile_time.py [snapshot.qrs.gz | synth:N:W:H:DEPTH] [reps]"""
 import gzip, hashlib, importlib, os, re, subprocess, sys, tempfile
