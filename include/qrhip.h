@@ -1018,8 +1018,77 @@ int qr_reproject_views_async(qr_device_scene *scn, const float *colour_in, const
                              int n_views, int width, int height, const qr_reproject_params *p,
                              float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream);
 
+/*
+ * Guided upsampling: light computed on a COARSE lattice -- every factor-th pixel of the frame, 1/4 or 1/16 of the pixels --
+ * brought to the full frame by a joint-bilateral upsample guided by the full-resolution qr_hit records (qr_hit_views_async).
+ * The low-frequency light (a gather fan, path-traced samples) is traced for the lattice pixels only; with QR_UPSAMPLE_DEMODULATE
+ * and QR_UPSAMPLE_MODULATE the albedo is divided out on the lattice and multiplied back per full pixel, so textures stay sharp.
+ * A pure function of its inputs.
+ *   - The lattice, all in integers: factor s in 1..QR_UPSAMPLE_MAX_FACTOR, phase (px, py) with 0 <= px, py < s.  Coarse pixel
+ *     (X, Y) is full pixel (s * X + px, s * Y + py); the coarse frame is Wl = ceil((width - px) / s) by Hl = ceil((height - py) / s),
+ *     both at least 1 (a phase beyond the frame is refused).  The GUIDE of a coarse pixel is the FULL frame's record at that
+ *     pixel, hits[s * Y + py][s * X + px], always inside the frame: there is no coarse G-buffer argument.  (The records to trace
+ *     the coarse light from are the same strided slice: rays.py coarse_hits; the camera of the coarse frame: coarse_view.)
+ *   - colour_lo: float32 [n_views][Hl][Wl][channels], compact, channels 3 or 4.  var_lo: float32 [n_views][Hl][Wl] or NULL.
+ *     hits: qr_hit [n_views][height][width] (pos, nrm, id, alb are read).  colour_out: float32 [n_views][height][width][channels].
+ *     var_out: float32 [n_views][height][width], given iff var_lo is.  weight_out: float32 [n_views][height][width] or NULL.
+ *     All DEVICE memory; hits 16-byte, the floats 4-byte aligned.  Every pixel of every view is written to every output that is
+ *     given.  An output equal to an input is refused; any other overlap of an input and an output is undefined.
+ *   - The arithmetic is pinned as in qr_atrous_views_async: fp32, IEEE division, nothing fused, every parenthesis an order,
+ *     every comparison written so that a NaN closes a tap.  For full pixel p = (x, y) with record (pos_p, nrm_p, id_p, alb_p):
+ *       position X0 = floor_div(x - px, s) (-1 left of the first coarse column);  rx = (x - px) - X0 * s;
+ *                wx = (float)rx / (float)s;  Y0, ry, wy likewise.
+ *       taps     j = 0, 1 outer, i = 0, 1 inner;  Q = (X0 + i, Y0 + j), inside iff 0 <= Q.x < Wl && 0 <= Q.y < Hl;  its guide G is
+ *                the full record at Q's full pixel;  b = (i ? wx : 1.0f - wx) * (j ? wy : 1.0f - wy).
+ *       read     a coarse colour as read, c_Q, is divided, with QR_UPSAMPLE_DEMODULATE and id_G >= 0, in its first three
+ *                channels by alb_G > alb_floor ? alb_G : alb_floor (the filter's rule: a NaN albedo gives the floor; a fourth
+ *                channel is never divided).  var_Q = var_lo[Q].
+ *       guide    id_p < 0: the tap is eligible iff it is inside and id_G < 0; then g = 1.0f.  Otherwise it is eligible iff it is
+ *                inside, id_G >= 0 and, with QR_UPSAMPLE_SAME_ID, id_G == id_p;  g = 1.0f, then in this order
+ *                  QR_UPSAMPLE_NORMAL  d = (nrm_p.x * nrm_G.x + nrm_p.y * nrm_G.y) + nrm_p.z * nrm_G.z;  d = 0 < d ? d : 0;
+ *                                      d = d * d, normal_sq times;  g = g * d
+ *                  QR_UPSAMPLE_PLANE   e = pos_G - pos_p;  d = (nrm_p.x * e.x + nrm_p.y * e.y) + nrm_p.z * e.z;
+ *                                      t = fabsf(d) / sigma_z;  g = g * (1.0f / (1.0f + t * t))
+ *       stage 1  w = b * g;  an eligible tap is taken iff 0 < w;  in tap order, all sums from +0.0:
+ *                sc[k] += c_Q[k] * w per channel;  sw += w;  sv += var_Q * (w * w).
+ *                If 0 < sw: colour = sc[k] / sw, variance = sv / (sw * sw), weight = sw.
+ *       stage 2  when stage 1 took nothing: the same sums with w = g (a pixel whose only open taps have bilinear weight 0);
+ *                colour and variance as in stage 1, weight = +0.0f.
+ *       stage 3  when stage 2 took nothing: the nearest coarse pixel, Qx = X0 + (2 * rx >= s) clamped into 0..Wl - 1, Qy
+ *                likewise: its colour as read and its variance; weight = -1.0f.
+ *       modulate with QR_UPSAMPLE_MODULATE and id_p >= 0 the first three channels are then multiplied by
+ *                alb_p > alb_floor ? alb_p : alb_floor.
+ *     A non-finite coarse colour propagates by this arithmetic and is not special-cased.  quadray-engine_amd/rays.py
+ *     upsample_pass is this text in numpy, and the GPU reproduces it bit for bit.
+ *   - weight_out tells a host which pixels the lattice could not serve (weight <= 0: disocclusions, thin objects between lattice
+ *     points); it can trace exactly those through the ray-side calls.  On a flat guide without stops a pixel half way between
+ *     four lattice points gets a quarter of their variance.
+ *   - QR_ERR_ARG: a null or misaligned required pointer (colour_lo, hits, colour_out, the parameters), var_out without var_lo or
+ *     var_lo without var_out, an output equal to an input, factor outside 1..QR_UPSAMPLE_MAX_FACTOR, a phase outside
+ *     0..factor - 1 or beyond the frame (an empty coarse frame), channels other than 3 or 4, normal_sq outside 0..7, unknown flag
+ *     bits, sigma_z or alb_floor not above 0 (NaN included), n_views outside 0..QR_VIEW_MAX_VIEWS, a size outside
+ *     1..QR_VIEW_MAX_DIM.  A refused call launches nothing.  n_views == 0 returns QR_OK without a launch.
+ *   - The call reads nothing of the scene but its device: any mode, no QR_UPLOAD_RAY_QUERIES needed.  Asynchronous on `stream`.
+ */
+#define QR_UPSAMPLE_NORMAL      1u
+#define QR_UPSAMPLE_PLANE       2u
+#define QR_UPSAMPLE_SAME_ID     4u
+#define QR_UPSAMPLE_DEMODULATE  8u    /* divide the coarse colour by the albedo of its guide record */
+#define QR_UPSAMPLE_MODULATE    16u   /* multiply the result by the full pixel's albedo */
+#define QR_UPSAMPLE_MAX_FACTOR  16
+typedef struct qr_upsample_params {   /* 32 bytes */
+    int32_t  factor, phase_x, phase_y, channels;   /* channels 3 or 4 */
+    int32_t  normal_sq;                            /* 0..7: the normal stop is max(0, n.n')^(2^normal_sq) */
+    uint32_t flags;                                /* QR_UPSAMPLE_NORMAL | _PLANE | _SAME_ID | _DEMODULATE | _MODULATE */
+    float    sigma_z, alb_floor;                   /* plane stop, world units; the smallest albedo divided by: both > 0 */
+} qr_upsample_params;
+
+int qr_upsample_views_async(qr_device_scene *scn, const float *colour_lo, const float *var_lo, const qr_hit *hits,
+                            int n_views, int width, int height, const qr_upsample_params *p,
+                            float *colour_out, float *var_out, float *weight_out, void *stream);
+
 /* ------------------------------------------------------------------------ */
-/* 3. Misc                                                                  */
+/* 3. Misc                                                                 */
 /* ------------------------------------------------------------------------ */
 
 /*

@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "qr_gather_rays_async", "qr_gather_views_async", "qr_gather_hits_async",
     "qr_fan_rays_framed_async", "qr_fan_views_framed_async", "qr_fan_hits_framed_async",
     "qr_gather_rays_framed_async", "qr_gather_views_framed_async", "qr_gather_hits_framed_async",
-    "qr_atrous_views_async", "qr_pt_adapt_views_variance_async", "qr_reproject_views_async",
+    "qr_atrous_views_async", "qr_pt_adapt_views_variance_async", "qr_reproject_views_async", "qr_upsample_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -66,6 +66,12 @@ ATROUS_DEMODULATE = 8       # every colour read is divided by its own pixel's al
 ATROUS_MODULATE = 16        # the output is multiplied by the centre pixel's albedo
 ATROUS_MAX_STEP = 64        # QR_ATROUS_MAX_STEP: the widest tap spacing of one pass
 REPROJ_DEMODULATE = 1       # qr_reproject_views_async flag: this frame's colour is divided by its own pixel's albedo
+UPSAMPLE_NORMAL = 1         # qr_upsample_views_async flags: the normal stop,
+UPSAMPLE_PLANE = 2          # the plane-distance stop,
+UPSAMPLE_SAME_ID = 4        # a tap must be the pixel's own surface and side,
+UPSAMPLE_DEMODULATE = 8     # the coarse colour is divided by the albedo of its guide record,
+UPSAMPLE_MODULATE = 16      # the result is multiplied by the full pixel's albedo
+UPSAMPLE_MAX_FACTOR = 16    # QR_UPSAMPLE_MAX_FACTOR: the coarsest lattice
 
 
 class QrError(RuntimeError):
@@ -99,6 +105,12 @@ class ReprojectParams(ctypes.Structure):
                 ("alpha_min", ctypes.c_float), ("alpha_mom_min", ctypes.c_float), ("max_len", ctypes.c_float),
                 ("var_min_len", ctypes.c_float), ("unknown", ctypes.c_float), ("alb_floor", ctypes.c_float),
                 ("reserved", ctypes.c_uint32 * 3)]
+
+
+class UpsampleParams(ctypes.Structure):
+    """qr_upsample_params (include/qrhip.h), 32 bytes"""
+    _fields_ = [("factor", ctypes.c_int32), ("phase_x", ctypes.c_int32), ("phase_y", ctypes.c_int32), ("channels", ctypes.c_int32),
+                ("normal_sq", ctypes.c_int32), ("flags", ctypes.c_uint32), ("sigma_z", ctypes.c_float), ("alb_floor", ctypes.c_float)]
 
 
 class RayCounts(ctypes.Structure):
@@ -169,7 +181,8 @@ def lib():
     L.qr_pt_adapt_list_work_bytes.argtypes = [vp, i64, ctypes.POINTER(cu64)]
     L.qr_atrous_views_async.argtypes = [vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(AtrousParams), vp, vp, vp]
     L.qr_reproject_views_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(ReprojectParams), vp, vp, vp, vp, vp]
-    L.qr_snapshot_build_lists_c.argtypes = [vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
+    L.qr_upsample_views_async.argtypes = [vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(UpsampleParams), vp, vp, vp, vp]
+    L.qr_snapshot_build_lists_c.argtypes =[vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
     L.qr_frame_hash.argtypes = [vp, cu64]
     L.qr_frame_hash.restype = cu64
@@ -700,6 +713,59 @@ class Scene:
             self._atrous_launch(c, v, hits, dims, 1 << k, per_pass[k], co, vo, stream)
             c, v = co, vo
         return c, v
+
+    def upsample(self, colour_lo, hits, factor, phase=(0, 0), variance=None, normal_power=128, plane=None, same_id=False,
+                 demodulate=False, modulate=False, albedo_floor=1 / 256, out=None, variance_out=None, weight=False, stream=None):
+        """Guided upsampling (qr_upsample_views_async; rays.upsample_pass is its arithmetic): coarse light colour_lo (float32
+        [N, Hl, Wl, 3|4], computed for every factor-th pixel from `phase` = (px, py) on: hit_gather on rays.coarse_hits(hits,
+        factor, phase), or pt_views / pt_adaptive_views / render_views on rays.coarse_view at rays.coarse_size) brought to the
+        full frame of hits (view_hits, float32 [N, H, W, 12]) through the four lattice points around each pixel, weighted
+        bilinearly and by the guide: normal_power (None or a power of two 1..128), plane (sigma_z in world units, or None),
+        same_id (only taps of the pixel's own surface).  variance: float32 [N, Hl, Wl] or None.  demodulate divides the coarse
+        colour by its lattice pixel's albedo, modulate multiplies the result by the full pixel's; albedo_floor the smallest
+        albedo divided by.  The stops are starting points, not tuned.  out / variance_out: tensors to write; weight: True (a
+        new tensor), False or a tensor to fill with the taken taps' weight (0: only taps of bilinear weight 0; -1: no tap, the
+        nearest coarse pixel: what a host may trace again).  A wrong tensor is a ValueError.  Returns the colour, or a tuple of
+        the colour, the variance (with a variance) and the weight (when wanted).  Asynchronous on `stream`."""
+        from . import rays
+        dev = self.device
+        flags, nsq, sz, af = rays.upsample_stops(normal_power=normal_power, plane=plane, same_id=same_id, demodulate=demodulate,
+                                                 modulate=modulate, albedo_floor=albedo_floor)
+        if not (_fits(hits, "float32", (None, None, None, 12)) and min(hits.shape) >= 1):
+            raise ValueError("hits must be a float32 [N, H, W, 12] tensor of qr_hit records (view_hits) of the FULL frame")
+        n, h, w = (int(x) for x in hits.shape[:3])
+        wl, hl = rays.coarse_size(w, h, factor, phase)
+        if not (_fits(colour_lo, "float32", (n, hl, wl, None)) and colour_lo.shape[3] in (3, 4)):
+            raise ValueError(f"colour_lo must be a float32 [{n}, {hl}, {wl}, 3] or [{n}, {hl}, {wl}, 4] tensor: the coarse frame of "
+                             f"a {w} x {h} frame at factor {factor}, phase {tuple(phase)} (rays.coarse_size)")
+        ch = int(colour_lo.shape[3])
+        if variance is not None and not _fits(variance, "float32", (n, hl, wl)):
+            raise ValueError(f"variance must be None or a float32 [{n}, {hl}, {wl}] tensor")
+        if variance_out is not None and variance is None:
+            raise ValueError("variance_out needs a variance")
+        if out is not None and not _fits(out, "float32", (n, h, w, ch)):
+            raise ValueError(f"out must be None or a float32 [{n}, {h}, {w}, {ch}] tensor")
+        if variance_out is not None and not _fits(variance_out, "float32", (n, h, w)):
+            raise ValueError(f"variance_out must be None or a float32 [{n}, {h}, {w}] tensor")
+        if weight is None or isinstance(weight, bool):
+            weight = True if weight else None
+        elif not _fits(weight, "float32", (n, h, w)):
+            raise ValueError(f"weight must be True, False or a float32 [{n}, {h}, {w}] tensor")
+        for t, what in ((colour_lo, "colour_lo"), (hits, "hits"), (variance, "variance"), (out, "out"), (variance_out, "variance_out"),
+                        (weight, "weight")):
+            if t is not None and t is not True and not _fits(t, None, None, dev):
+                raise ValueError(f"{what} must be contiguous and on cuda:{dev}")
+        if out is None:
+            out = _new("float32", (n, h, w, ch), dev)
+        if variance is not None and variance_out is None:
+            variance_out = _new("float32", (n, h, w), dev)
+        if weight is True:
+            weight = _new("float32", (n, h, w), dev)
+        p = UpsampleParams(int(factor), int(phase[0]), int(phase[1]), ch, nsq, flags, float(sz), float(af))
+        _check(lib().qr_upsample_views_async(self._h, _ptr(colour_lo), _ptr(variance), _ptr(hits), n, w, h, ctypes.byref(p),
+                                             _ptr(out), _ptr(variance_out), _ptr(weight), self._stream_ptr(stream)))
+        got = (out,) + (() if variance is None else (variance_out,)) + (() if weight is None else (weight,))
+        return got[0] if len(got) == 1 else got
 
     @staticmethod
     def _reproject_stops(**params):

@@ -17,6 +17,7 @@
 #include "qr_openlist.hpp"
 #include "qr_atrous.hpp"
 #include "qr_reproject.hpp"
+#include "qr_upsample.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstring>

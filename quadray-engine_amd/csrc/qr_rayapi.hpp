@@ -557,6 +557,50 @@ extern "C" int qr_atrous_views_async(qr_device_scene *s, const float *colour_in,
     return launched();
 }
 
+/* ---- guided upsampling (qr_upsample.hpp): one lane per full pixel, 32 x 8 pixel tiles, blockIdx.z the view ---- */
+
+extern "C" int qr_upsample_views_async(qr_device_scene *s, const float *colour_lo, const float *var_lo, const qr_hit *hits,
+                                       int n_views, int width, int height, const qr_upsample_params *p,
+                                       float *colour_out, float *var_out, float *weight_out, void *stream)
+{
+    QR_TRY(need_scene(s));
+    if (p == nullptr) return qr_fail(QR_ERR_ARG, "null upsampling parameters");
+    QR_TRY(view_size_args(n_views, width, height));
+    if (p->factor < 1 || p->factor > QR_UPSAMPLE_MAX_FACTOR)
+        return qr_fail(QR_ERR_ARG, "factor must be 1.." + std::to_string(QR_UPSAMPLE_MAX_FACTOR));
+    if (p->phase_x < 0 || p->phase_x >= p->factor || p->phase_y < 0 || p->phase_y >= p->factor)
+        return qr_fail(QR_ERR_ARG, "phase_x and phase_y must be 0..factor - 1");
+    if (p->phase_x >= width || p->phase_y >= height) return qr_fail(QR_ERR_ARG, "the phase lies beyond the frame: the coarse frame is empty");
+    if (p->channels != 3 && p->channels != 4) return qr_fail(QR_ERR_ARG, "channels must be 3 or 4");
+    if (p->normal_sq < 0 || p->normal_sq > 7) return qr_fail(QR_ERR_ARG, "normal_sq must be 0..7");
+    QR_TRY(flags_arg(p->flags, QR_UPSAMPLE_NORMAL | QR_UPSAMPLE_PLANE | QR_UPSAMPLE_SAME_ID | QR_UPSAMPLE_DEMODULATE | QR_UPSAMPLE_MODULATE,
+                     "unknown upsampling flags"));
+    if (!(p->sigma_z > 0.0f) || !(p->alb_floor > 0.0f)) return qr_fail(QR_ERR_ARG, "sigma_z and alb_floor must be above 0");
+    if ((var_lo == nullptr) != (var_out == nullptr)) return qr_fail(QR_ERR_ARG, "var_lo and var_out go together: both or neither");
+    if (n_views == 0) return QR_OK;
+    QR_TRY(need_ptrs({colour_lo, colour_out, hits}));
+    QR_TRY(aligned_ptrs({hits}, 16, "hits must be 16-byte aligned"));
+    QR_TRY(aligned_ptrs({colour_lo, var_lo, colour_out, var_out, weight_out}, 4, "colour, variance and weight must be 4-byte aligned"));
+    for (const void *o : {(const void *)colour_out, (const void *)var_out, (const void *)weight_out})
+        for (const void *i : {(const void *)colour_lo, (const void *)var_lo, (const void *)hits})
+            if (o != nullptr && o == i) return qr_fail(QR_ERR_ARG, "a pixel reads its neighbours' lattice points: an output cannot be an input");
+    HIP_TRY(hipSetDevice(s->device));
+    UpsampleP up;
+    up.colour_lo = colour_lo; up.var_lo = var_lo; up.hits = (const f32x4 *)hits;
+    up.colour_out = colour_out; up.var_out = var_out; up.weight_out = weight_out;
+    up.width = width; up.height = height;
+    up.wl = (width - p->phase_x + p->factor - 1) / p->factor; up.hl = (height - p->phase_y + p->factor - 1) / p->factor;
+    up.factor = p->factor; up.phase_x = p->phase_x; up.phase_y = p->phase_y; up.normal_sq = p->normal_sq; up.flags = p->flags;
+    up.sigma_z = p->sigma_z; up.alb_floor = p->alb_floor;
+    /* grid.x <= 512, grid.y <= 2048 at QR_VIEW_MAX_DIM */
+    const dim3 grid((unsigned)((width + QR_UPS_TW - 1) / QR_UPS_TW), (unsigned)((height + QR_UPS_TH - 1) / QR_UPS_TH),
+                    (unsigned)n_views), block(QR_UPS_BLOCK);
+    pick(p->channels == 3, [&](auto three) {
+        hipLaunchKernelGGL(qr_upsample_kernel<(decltype(three)::value ? 3 : 4)>, grid, block, 0, (hipStream_t)stream, up);
+    });
+    return launched();
+}
+
 /* ---- temporal reprojection (qr_reproject.hpp): one lane per pixel, 32 x 8 pixel tiles, blockIdx.z the view ---- */
 
 extern "C" int qr_reproject_views_async(qr_device_scene *s, const float *colour_in, const qr_hit *hits, const float *var_in,

@@ -1370,3 +1370,197 @@ class Temporal:
 def temporal(n_views, width, height, channels=3, **params):
     """The specification of Scene.temporal: a Temporal accumulator in numpy.  params: as reproject_stops takes them."""
     return Temporal(n_views, width, height, channels, **params)
+
+
+# ---- guided upsampling (include/qrhip.h qr_upsample_views_async; Scene.upsample) ----
+
+UPSAMPLE_NORMAL, UPSAMPLE_PLANE, UPSAMPLE_SAME_ID, UPSAMPLE_DEMODULATE, UPSAMPLE_MODULATE = 1, 2, 4, 8, 16     # QR_UPSAMPLE_* flags
+UPSAMPLE_MAX_FACTOR = 16                                                                            # QR_UPSAMPLE_MAX_FACTOR
+
+
+def upsample_stops(normal_power=128, plane=None, same_id=False, demodulate=False, modulate=False, albedo_floor=1 / 256):
+    """The host side of Scene.upsample's arguments: (flags, normal_sq, sigma_z, alb_floor) as qr_upsample_params takes them.
+    normal_power: None (no normal stop) or a power of two 1..128, sent as its log2; plane: sigma_z in world units or None (sent
+    as 1.0); same_id: a tap must be the pixel's own surface and side; demodulate / modulate: divide the coarse colour by its
+    guide's albedo / multiply the result by the full pixel's.  Validates like atrous_stops: ValueError for anything else."""
+    flags, normal_sq, _, _, _, alb_floor = atrous_stops(normal_power=normal_power, albedo_floor=albedo_floor)
+    flags = UPSAMPLE_NORMAL if flags & ATROUS_NORMAL else 0
+    sigma_z = np.float32(1.0)
+    if plane is not None:
+        sigma_z = atrous_stops(normal_power=None, plane=plane)[2]
+        flags |= UPSAMPLE_PLANE
+    for on, bit, what in ((same_id, UPSAMPLE_SAME_ID, "same_id"), (demodulate, UPSAMPLE_DEMODULATE, "demodulate"),
+                          (modulate, UPSAMPLE_MODULATE, "modulate")):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"{what} must be True or False")
+        if on:
+            flags |= bit
+    return flags, normal_sq, sigma_z, alb_floor
+
+
+def _lattice(factor, phase):
+    """(s, px, py) of a lattice, validated"""
+    ok = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not ok(factor) or not 1 <= factor <= UPSAMPLE_MAX_FACTOR:
+        raise ValueError(f"factor must be an integer, 1..{UPSAMPLE_MAX_FACTOR}")
+    if not (isinstance(phase, (tuple, list)) and len(phase) == 2 and ok(phase[0]) and ok(phase[1])
+            and 0 <= phase[0] < factor and 0 <= phase[1] < factor):
+        raise ValueError("phase must be a pair of integers (px, py), each 0..factor - 1")
+    return int(factor), int(phase[0]), int(phase[1])
+
+
+def coarse_size(width, height, factor, phase=(0, 0)):
+    """(Wl, Hl) of the coarse frame of a width x height frame: coarse pixel (X, Y) is full pixel (factor * X + px, factor * Y + py),
+    Wl = ceil((width - px) / factor), Hl = ceil((height - py) / factor).  ValueError for a factor outside 1..UPSAMPLE_MAX_FACTOR,
+    a phase outside 0..factor - 1 or beyond the frame (the coarse frame would be empty)."""
+    s, px, py = _lattice(factor, phase)
+    if isinstance(width, bool) or isinstance(height, bool) or not isinstance(width, (int, np.integer)) \
+            or not isinstance(height, (int, np.integer)) or width < 1 or height < 1:
+        raise ValueError("width and height must be integers, at least 1")
+    if px >= width or py >= height:
+        raise ValueError(f"phase {(px, py)} lies beyond the {width} x {height} frame: the coarse frame is empty")
+    return (int(width) - px + s - 1) // s, (int(height) - py + s - 1) // s
+
+
+def coarse_hits(hits, factor, phase=(0, 0)):
+    """The coarse G-buffer: hits[:, py::factor, px::factor] of full-frame hit records (float32 [N, H, W, 12] or [H, W, 12], a numpy
+    array or a torch tensor), made contiguous -- the guides of qr_upsample_views_async, and the records to hand to hit_gather,
+    hit_occlusion and the other calls that take caller-supplied records, so that the coarse light is traced from exactly the
+    points it is later weighted by."""
+    s, px, py = _lattice(factor, phase)
+    if hits.ndim not in (3, 4) or hits.shape[-1] != 12:
+        raise ValueError(f"hits must be [N, H, W, 12] or [H, W, 12], got {list(hits.shape)}")
+    coarse_size(int(hits.shape[-2]), int(hits.shape[-3]), s, (px, py))
+    sub = hits[..., py::s, px::s, :]
+    return np.ascontiguousarray(sub) if isinstance(sub, np.ndarray) else sub.contiguous()
+
+
+def coarse_view(view, factor, phase=(0, 0)):
+    """The qr_view whose pixel (X, Y) looks where the full view's pixel (factor * X + px, factor * Y + py) looks: hor * factor,
+    ver * factor, dir + hor * px + ver * py computed in float64 and rounded once; org, t_min and t_max are kept.  For pt_views,
+    pt_adaptive_views and render_views at coarse_size.  At phase (0, 0) and a factor that is a power of two the coarse rays
+    are the full view's rays bit for bit (on a scene without FSAA); otherwise they differ by a few roundings.  On a scene with
+    FSAA the scene's sample offsets scale with hor and ver: a coarse sample then spreads over `factor` full pixels, and the
+    guide stays sample 0's full record."""
+    s, px, py = _lattice(factor, phase)
+    v = np.array(view, dtype=np.float32).reshape(16)
+    d, hor, ver = (v[k:k + 3].astype(np.float64) for k in (4, 8, 12))
+    v[4:7] = d + hor * px + ver * py
+    v[8:11] = hor * s
+    v[12:15] = ver * s
+    return v
+
+
+def upsample_pass(colour_lo, variance_lo, hits, factor, phase=(0, 0), flags=0, normal_sq=0, sigma_z=1.0, alb_floor=1 / 256, taps=None):
+    """The specification of qr_upsample_views_async in float32 numpy, every operation elementwise so that it rounds once:
+    colour_lo float32 [N, Hl, Wl, C] (or [Hl, Wl, C]; C 3 or 4), variance_lo float32 [N, Hl, Wl] or None, hits float32
+    [N, H, W, 12] -- the FULL frame's records, (Wl, Hl) = coarse_size(W, H, factor, phase) --, flags of UPSAMPLE_*, the rest
+    as qr_upsample_params.  Returns (colour [N, H, W, C], variance [N, H, W] or None, weight [N, H, W]), new arrays.
+
+    Per full pixel p = (x, y) (include/qrhip.h has the full text): X0 = floor_div(x - px, s), rx = (x - px) - X0 * s,
+    wx = float(rx) / float(s), rows likewise; taps j = 0, 1 outer, i = 0, 1 inner at Q = (X0 + i, Y0 + j) with the guide G = the
+    full record at (s * Q.x + px, s * Q.y + py) and b the bilinear weight.  A coarse colour is read divided by max(alb_G,
+    alb_floor) under DEMODULATE where id_G >= 0.  A miss pixel takes inside miss taps with g = 1; a hit pixel inside hit taps
+    (of its own id under SAME_ID) with g = the NORMAL stop times the PLANE stop.  Stage 1: w = b * g, taken iff 0 < w, colour =
+    sum(c * w) / sum(w), variance = sum(var * (w * w)) / (sum(w) * sum(w)), weight = sum(w).  Stage 2, when stage 1 took nothing:
+    w = g, weight = +0.0.  Stage 3, when stage 2 took nothing: the nearest coarse pixel (X0 + (2 * rx >= s), clamped), weight =
+    -1.0.  MODULATE multiplies channels 0..2 by max(alb_p, alb_floor) where id_p >= 0.
+
+    taps: if a list is given, the four (eligible bool [N, H, W], b float32 [H, W], g float32 [N, H, W], qy [H, W], qx [H, W])
+    tuples are appended in tap order (qy, qx clipped into the coarse frame): what a test needs to evaluate the same sums in
+    another precision."""
+    f = np.float32
+    s, px, py = _lattice(factor, phase)
+    colour_lo, hits = np.asarray(colour_lo), np.asarray(hits)
+    single = hits.ndim == 3
+    if single:
+        colour_lo, hits = colour_lo[None], hits[None]
+        variance_lo = None if variance_lo is None else np.asarray(variance_lo)[None]
+    if hits.dtype != np.float32 or hits.ndim != 4 or hits.shape[-1] != 12:
+        raise ValueError(f"hits must be float32 [N, H, W, 12] or [H, W, 12], got {hits.dtype} {list(hits.shape)}")
+    n, h, w = hits.shape[:3]
+    wl, hl = coarse_size(w, h, s, (px, py))
+    if colour_lo.dtype != np.float32 or colour_lo.ndim != 4 or colour_lo.shape[:3] != (n, hl, wl) or colour_lo.shape[3] not in (3, 4):
+        raise ValueError(f"colour_lo must be float32 [{n}, {hl}, {wl}, 3|4], got {colour_lo.dtype} {list(colour_lo.shape)}")
+    if variance_lo is not None:
+        variance_lo = np.asarray(variance_lo)
+        if variance_lo.dtype != np.float32 or variance_lo.shape != (n, hl, wl):
+            raise ValueError(f"variance_lo must be float32 [{n}, {hl}, {wl}], got {variance_lo.dtype} {list(variance_lo.shape)}")
+    flags, normal_sq = int(flags), int(normal_sq)
+    if not 0 <= normal_sq <= 7 or flags & ~31:
+        raise ValueError("normal_sq must be 0..7, flags of UPSAMPLE_*")
+    sigma_z, alb_floor = f(sigma_z), f(alb_floor)
+    if not (sigma_z > 0 and alb_floor > 0):
+        raise ValueError("sigma_z and alb_floor must be above 0")
+    ch = colour_lo.shape[3]
+    pos, _, nrm, ids, alb, _ = hit_fields(hits)
+    one, zero = f(1.0), f(0.0)
+    with np.errstate(all="ignore"):
+        guide = hits[:, py::s, px::s]                                       # [n, hl, wl, 12]: the full records at the lattice points
+        gpos, _, gnrm, gid, galb, _ = hit_fields(guide)
+        col = colour_lo.copy()
+        if flags & UPSAMPLE_DEMODULATE:
+            a = np.where(galb > alb_floor, galb, alb_floor)                 # a NaN albedo gives the floor
+            col[..., 0:3] = np.where((gid >= 0)[..., None], col[..., 0:3] / a, col[..., 0:3])
+        var = np.zeros((n, hl, wl), dtype=f) if variance_lo is None else variance_lo
+        ys, xs = np.mgrid[0:h, 0:w]
+        x0, y0 = (xs - px) // s, (ys - py) // s                             # floor division: -1 left of / above the lattice
+        rx, ry = (xs - px) - x0 * s, (ys - py) - y0 * s
+        wx, wy = rx.astype(f) / f(s), ry.astype(f) / f(s)
+        hit_p = ids >= 0
+        each = []
+        for j in (0, 1):
+            for i in (0, 1):
+                qx, qy = x0 + i, y0 + j
+                inside = (qx >= 0) & (qx < wl) & (qy >= 0) & (qy < hl)
+                qx, qy = np.clip(qx, 0, wl - 1), np.clip(qy, 0, hl - 1)
+                b = (wx if i else one - wx) * (wy if j else one - wy)
+                idg = gid[:, qy, qx]
+                g = np.ones((n, h, w), dtype=f)
+                if flags & UPSAMPLE_NORMAL:
+                    nq = gnrm[:, qy, qx]
+                    d = (nrm[..., 0] * nq[..., 0] + nrm[..., 1] * nq[..., 1]) + nrm[..., 2] * nq[..., 2]
+                    d = np.where(0 < d, d, zero)
+                    for _ in range(normal_sq):
+                        d = d * d
+                    g = g * d
+                if flags & UPSAMPLE_PLANE:
+                    e = gpos[:, qy, qx] - pos
+                    d = (nrm[..., 0] * e[..., 0] + nrm[..., 1] * e[..., 1]) + nrm[..., 2] * e[..., 2]
+                    t = np.abs(d) / sigma_z
+                    g = g * (one / (one + t * t))
+                ok = (idg >= 0) & ((idg == ids) if flags & UPSAMPLE_SAME_ID else True)
+                elig = inside[None] & np.where(hit_p, ok, idg < 0)
+                g = np.where(hit_p, g, one).astype(f)
+                each.append((elig, b, g, qy, qx))
+        if taps is not None:
+            taps.extend(each)
+        sums = []
+        for stage in (1, 2):
+            sc, sw, sv = np.zeros((n, h, w, ch), dtype=f), np.zeros((n, h, w), dtype=f), np.zeros((n, h, w), dtype=f)
+            for elig, b, g, qy, qx in each:
+                wt = b[None] * g if stage == 1 else g
+                take = elig & (0 < wt)
+                wt = np.where(take, wt, zero)
+                sc = np.where(take[..., None], sc + col[:, qy, qx] * wt[..., None], sc)
+                sw = np.where(take, sw + wt, sw)
+                sv = np.where(take, sv + var[:, qy, qx] * (wt * wt), sv)
+            sums.append((sc, sw, sv))
+        first = 0 < sums[0][1]
+        sc = np.where(first[..., None], sums[0][0], sums[1][0])
+        sw = np.where(first, sums[0][1], sums[1][1])
+        sv = np.where(first, sums[0][2], sums[1][2])
+        served = 0 < sw
+        nx = np.clip(x0 + (2 * rx >= s), 0, wl - 1)
+        ny = np.clip(y0 + (2 * ry >= s), 0, hl - 1)
+        out = np.where(served[..., None], sc / sw[..., None], col[:, ny, nx]).astype(f)
+        vout = np.where(served, sv / (sw * sw), var[:, ny, nx]).astype(f)
+        weight = np.where(first, sw, np.where(served, zero, f(-1.0))).astype(f)
+        if flags & UPSAMPLE_MODULATE:
+            a = np.where(alb > alb_floor, alb, alb_floor)
+            out[..., 0:3] = np.where(hit_p[..., None], out[..., 0:3] * a, out[..., 0:3])
+    if variance_lo is None:
+        vout = None
+    if single:
+        return out[0], None if vout is None else vout[0], weight[0]
+    return out, vout, weight
