@@ -171,6 +171,8 @@ typedef struct qr_program_info
     uint32_t n_grids;           /* shadow lists by hit position built for large planes        */
     uint32_t n_grid_lists;      /* lists in them                                              */
     uint32_t n_dda;             /* uniform grids built over long lists                        */
+    uint32_t n_pgrids;          /* packet shadow pyramids (not counted in n_grids)            */
+    uint32_t n_pgrid_nodes;     /* their nodes that hold a list, all levels                   */
 } qr_program_info;
 int qr_program_stats(const void *blob, uint64_t size, qr_program_info *info);
 /* qr_program_stats with upload flags (QR_UPLOAD_*): reports the image qr_scene_upload_ex would build with them.  Host only,

@@ -564,16 +564,11 @@ uint32_t Builder::compile_clip(int owner)
  */
 uint32_t Builder::compile_grid(int si, int lg, int sh)
 {
+    int a, b;
+    if (!grid_plane(si, a, b)) return 0;
     const qr_surface &s = v.srf[si];
-    if (!is_real(s) || s.srf_t[0] != 1 || s.has_trm != 0 || s.shift != 0) return 0;
-    const int k = (int)((s.axes >> 4) & 3);
-    if (k > 2) return 0;
-    const int a = k == 0 ? 1 : 0, b = k == 2 ? 1 : 2;
-    const bool fin = (s.minmax_t & (1u << a)) && (s.minmax_t & (1u << (3 + a))) && (s.minmax_t & (1u << b)) && (s.minmax_t & (1u << (3 + b)));
-    if (!fin) return 0;
     const double lo_a = s.min[a], hi_a = s.max[a], lo_b = s.min[b], hi_b = s.max[b];
     const double ea = hi_a - lo_a, eb = hi_b - lo_b;
-    if (!(ea > 1e-3) || !(eb > 1e-3) || !(ea < 1e18) || !(eb < 1e18)) return 0;
     /* long enough to be worth it? */
     int n_real = 0;
     for (int e = sh; e != QR_NULL && n_real < kn.grid_min; e = E[e].next) if (is_real(v.srf[E[e].simd])) n_real++;
@@ -624,6 +619,97 @@ uint32_t Builder::compile_grid(int si, int lg, int sh)
     return off | QR_LISTF_GRID;
 }
 
+/* compile_grid's geometric conditions: an untransformed plane with a finite clip rectangle; a, b: the in-plane components */
+bool Builder::grid_plane(int si, int &a, int &b) const
+{
+    const qr_surface &s = v.srf[si];
+    if (!is_real(s) || s.srf_t[0] != 1 || s.has_trm != 0 || s.shift != 0) return false;
+    const int k = (int)((s.axes >> 4) & 3);
+    if (k > 2) return false;
+    a = k == 0 ? 1 : 0; b = k == 2 ? 1 : 2;
+    const bool fin = (s.minmax_t & (1u << a)) && (s.minmax_t & (1u << (3 + a))) && (s.minmax_t & (1u << b)) && (s.minmax_t & (1u << (3 + b)));
+    if (!fin) return false;
+    const double ea = (double)s.max[a] - s.min[a], eb = (double)s.max[b] - s.min[b];
+    return ea > 1e-3 && eb > 1e-3 && ea < 1e18 && eb < 1e18;
+}
+
+/*
+ * Packet shadow pyramid for surface `si` (a plane as compile_grid takes them), light `lg` and shadow chain `sh`, in an image
+ * the packet instance serves: CGrid with QR_GRIDC_PYR, qr_program.h.  `top` is the chain's plain shadow program, the node of
+ * level L.  A node's list is what HullPred keeps of its PARENT's list for the node's own patch (centre, half diagonal + the
+ * padding of compile_grid for a cell of that size), so it is a sub-sequence of the parent's whatever the predicate's rounding.
+ * Returns the record's offset | QR_LISTF_GRID, or 0.
+ */
+uint32_t Builder::compile_pgrid(int si, int lg, int sh, uint32_t top)
+{
+    int a, b;
+    if (!grid_plane(si, a, b) || top == 0) return 0;
+    const qr_surface &s = v.srf[si];
+    int n_real = 0;
+    for (int e = sh; e != QR_NULL && n_real < kn.pgrid_min; e = E[e].next) if (is_real(v.srf[E[e].simd])) n_real++;
+    if (n_real < kn.pgrid_min) return 0;
+    const double lo_a = s.min[a], lo_b = s.min[b], ea = (double)s.max[a] - lo_a, eb = (double)s.max[b] - lo_b;
+    ListFilter lf(v, bs, *Egrow, sh);
+    const int L = kn.pgrid_levels, N = 1 << L, n_pos = (int)lf.ch.size();
+    CGrid g;
+    g.nx = g.ny = (uint32_t)N; g.comps = (uint32_t)a | ((uint32_t)b << 2) | QR_GRIDC_PYR | ((uint32_t)L << 8);
+    g.org_a = (float)lo_a; g.org_b = (float)lo_b;
+    g.inv_a = (float)(N / ea); g.inv_b = (float)(N / eb);
+    const uint32_t n_words = QR_PGRID_LEVEL_OFF((uint32_t)N, (uint32_t)L) + 1u;
+    std::vector<uint32_t> table(n_words, 0u);
+    table[n_words - 1] = top;
+    /* keep[node][position in the chain], level by level from the top: the parent's AND the node's own predicate.  The nodes of
+     * a level are filtered by worker threads, then appended and compiled in node order, as compile_grid does. */
+    std::vector<uint8_t> up((size_t)n_pos, 1), cur;
+    for (int l = L - 1; l >= 0; l--)
+    {
+        const int n = N >> l, n_nodes = n * n;
+        const double ca = ea / n, cb = eb / n;
+        const double pad_a = 2e-3 * ca + 1e-3, pad_b = 2e-3 * cb + 1e-3;
+        const double pr = __builtin_sqrt((0.5 * ca + pad_a) * (0.5 * ca + pad_a) + (0.5 * cb + pad_b) * (0.5 * cb + pad_b)) + 1e-3;
+        cur.assign((size_t)n_nodes * n_pos, 0);
+        std::vector<ListFilter::Run> runs((size_t)n_nodes);
+        std::vector<int> heads((size_t)n_nodes, QR_NULL);
+        const int np = n >> 1 ? n >> 1 : 1;             /* nodes per row of the level above (one node at level L) */
+        for_ranges(n_nodes, kn.threads(n_nodes), [&](int, int c0, int c1) {
+            for (int c = c0; c < c1; c++)
+            {
+                const int i = c % n, j = c / n;
+                double pc[3] = { s.pos[0], s.pos[1], s.pos[2] };
+                pc[a] += lo_a + (i + 0.5) * ca; pc[b] += lo_b + (j + 0.5) * cb;
+                const HullPred pred(v.lgt[lg].pos, pc, pr);
+                const uint8_t *par = l == L - 1 ? up.data() : up.data() + (size_t)((j >> 1) * np + (i >> 1)) * n_pos;
+                uint8_t *mine = cur.data() + (size_t)c * n_pos;
+                for (int q = 0; q < n_pos; q++)
+                {
+                    const ListFilter::Node &nd = lf.ch[(size_t)q];
+                    mine[q] = par[q] && (nd.head ? (!nd.bounded || pred(nd.bound, true)) : pred(nd.bound, nd.bounded));
+                }
+                /* the nodes keep their bounding-volume elements (flat_max -1): on the engine's chains a volume stands in front
+                 * of a trnode, and a wave that misses it skips the transform (profiles/r30_packet_shadow_pyramid.txt) */
+                heads[(size_t)c] = lf.filter_nodes_run([&](int q) { return mine[q] != 0; }, runs[(size_t)c], -1);
+            }
+        });
+        uint32_t *row = table.data() + QR_PGRID_LEVEL_OFF((uint32_t)N, (uint32_t)l);
+        for (int c = 0; c < n_nodes; c++)
+        {
+            if (heads[(size_t)c] == ListFilter::SOURCE_LIST) { row[c] = top; n_pgrid_nodes++; continue; }
+            const int h = lf.append(runs[(size_t)c], heads[(size_t)c]);
+            runs[(size_t)c] = ListFilter::Run();
+            row[c] = compile_list(h, true);
+            if (row[c]) n_pgrid_nodes++;
+        }
+        up.swap(cur);
+    }
+    n_pgrid_nodes++;                /* the top */
+    g.table = alloc(table.size() * 4, 4);
+    memcpy(at<uint32_t>(g.table), table.data(), table.size() * 4);
+    const uint32_t off = alloc(sizeof(CGrid), 32);
+    *at<CGrid>(off) = g;
+    n_pgrids++;
+    return off | QR_LISTF_GRID;
+}
+
 uint32_t Builder::compile_lights(int head)
 {
     if (head == QR_NULL) return 0;
@@ -636,7 +722,11 @@ uint32_t Builder::compile_lights(int head)
         const int sh = E[e].data, lg = E[e].simd;       /* copies: compile_grid appends to E */
         l.shadow = compile_list(sh, true);
         if (Egrow != nullptr && light_user[head] >= 0 && sh != QR_NULL)
-            if (const uint32_t g = compile_grid(light_user[head], lg, sh)) l.shadow = g;
+        {
+            const uint32_t g = kn.grid_min > 0 ? compile_grid(light_user[head], lg, sh) : 0u;
+            if (g) l.shadow = g;
+            else if (pgrid_ok) { if (const uint32_t pg = compile_pgrid(light_user[head], lg, sh, l.shadow)) l.shadow = pg; }
+        }
         ls.push_back(l);
     }
     ls.back().lgt |= QR_CLIGHT_LAST;

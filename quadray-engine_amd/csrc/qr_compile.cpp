@@ -14,7 +14,8 @@ using namespace qrc;
 static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 Knobs::Knobs()
-    : cull(env_int("QR_CULL", 3)), grid_min(env_int("QR_GRID", 256)), dda_min(env_int("QR_DDA", 512)),
+    : cull(env_int("QR_CULL", 3)), grid_min(env_int("QR_GRID", 256)),
+      pgrid_min(env_int("QR_PGRID", 12)), pgrid_levels(std::min(std::max(env_int("QR_PGRID_LEVELS", 4), 1), (int)QR_PGRID_LEVELS_MAX)), dda_min(env_int("QR_DDA", 512)),
       drop_shadowless(env_int("QR_SHADOWLESS", 1) != 0), boxes(env_int("QR_BOX", 1) != 0), dedup(env_int("QR_LIST_DEDUP", 1) != 0),
       host_threads(getenv("QR_HOST_THREADS") ? std::max(0, env_int("QR_HOST_THREADS", 0)) : -1),
       sides_exact_max(env_int("QR_SIDES_EXACT_MAX", QR_SIDES_EXACT_MAX))
@@ -34,9 +35,11 @@ int clear_run_max()
 
 /* shadow grids (CGrid) append filtered chains to the cell array: the build works on a copy then.  Only scenes with long
  * shadow lists on clipped planes get any, so the per-frame compile of the engine's scenes never copies. */
-bool wants_shadow_grids(const qr_scene_view &v, size_t n_elm, const Knobs &kn)
+bool wants_shadow_grids(const qr_scene_view &v, size_t n_elm, const Knobs &kn, bool pgrid_ok)
 {
-    if (kn.grid_min <= 0 || n_elm < (size_t)kn.grid_min) return false;
+    const bool grids = kn.grid_min > 0 && n_elm >= (size_t)kn.grid_min;
+    const bool pgrids = pgrid_ok && n_elm >= (size_t)kn.pgrid_min;     /* packet shadow pyramids (compile_pgrid) append chains too */
+    if (!grids && !pgrids) return false;
     for (int i = 0; i < (int)v.hdr->n_srf; i++)
     {
         const qr_surface &q = v.srf[i];
@@ -242,12 +245,13 @@ void finish(Builder &b, const Layout &l, const qr_frame &frm, size_t n_tiles, ui
     out.n_srf = hd.n_srf; out.n_mat = hd.n_mat; out.n_lgt = hd.n_lgt; out.n_tex = hd.n_texels; out.n_tiles = (uint32_t)n_tiles;
     out.off_lists = l.o_ord + (uint32_t)(l.n_sched * 8 + 16);
     b.st.bytes = out.blob.size(); b.st.n_grids = b.n_grids; b.st.n_grid_lists = b.n_grid_lists; b.st.n_dda = b.n_dda;
+    b.st.n_pgrids = b.n_pgrids; b.st.n_pgrid_nodes = b.n_pgrid_nodes;
     out.stats = b.st;
     out.has_long_lists = b.any_long;
     out.has_grids = b.n_grids != 0;
     /* box cells and a list the per-lane walkers take (possible only with lowered QR_DDA / QR_GRID thresholds: by default such a
      * list has QR_LONG_CELLS elements and has ended the first attempt already): build again without box cells */
-    if (b.box_ok && (b.any_long || b.n_grids != 0)) throw Builder::Restart{};
+    if ((b.box_ok || b.n_pgrids != 0) && (b.any_long || b.n_grids != 0)) throw Builder::Restart{};
     b.at<DevHeader>(0)->img_flags = b.any_box ? QR_IMG_BOXES : 0u;
     b.at<DevHeader>(0)->img_bytes = (uint32_t)out.blob.size();
 }
@@ -268,12 +272,15 @@ int program_build_once(const qr_scene_view &v, const std::vector<qr_elem> &E, co
         out.blob.reserve(sizeof(DevHeader) + (size_t)(hd.n_srf + 1) * (sizeof(DSurf) + sizeof(DShade)) + (size_t)(hd.n_mat + 1) * sizeof(qr_material)
                          + (size_t)hd.n_texels * 4 + T.size() * 4 + E.size() * 80 + (size_t)frm.frm_w * frm.frm_h / 8 + 65536);
         std::vector<qr_elem> Eg;
-        const bool want_grids = wants_shadow_grids(v, E.size(), kn);
+        /* packet shadow pyramids: only in an attempt that takes every list for short -- an image that turns out to need the
+         * per-lane instance is built again without them (finish) */
+        const bool pgrid_ok = kn.pgrid_min > 0 && assume_short && !(flags & QR_BUILD_NO_PGRID);
+        const bool want_grids = wants_shadow_grids(v, E.size(), kn, pgrid_ok);
         if (want_grids) Eg = E;
         timer.tick("pre");
         Builder b(v, want_grids ? Eg : E, bs, kn, out.blob);
         timer.tick("builder");
-        if (want_grids) { b.Egrow = &Eg; find_light_users(b, E.size()); }
+        if (want_grids) { b.Egrow = &Eg; b.pgrid_ok = pgrid_ok; find_light_users(b, E.size()); }
         const Layout l = fixed_layout(b, T.size(), frm);
         fill_materials(b, l.o_lut);
         timer.tick("fixed");
@@ -351,5 +358,6 @@ extern "C" int qr_program_stats_ex(const void *blob, uint64_t size, uint32_t fla
     info->bytes = p.stats.bytes; info->n_lists = p.stats.n_lists; info->n_cells = p.stats.n_cells;
     info->n_dropped = p.stats.n_dropped; info->n_clip_cells = p.stats.n_clip_cells; info->n_sched = p.n_sched;
     info->n_grids = p.stats.n_grids; info->n_grid_lists = p.stats.n_grid_lists; info->n_dda = p.stats.n_dda;
+    info->n_pgrids = p.stats.n_pgrids; info->n_pgrid_nodes = p.stats.n_pgrid_nodes;
     return QR_OK;
 }

@@ -39,6 +39,9 @@ struct Knobs
 {
     int    cull = 3;                        /* QR_CULL: cull cells on 0 nothing, 1 planes, 2 planes + open quadrics, 3 all */
     int    grid_min = 256;                  /* QR_GRID: shadow lists with at least this many surfaces get a grid (CGrid); 0 turns the grids off */
+    int    pgrid_min = 12;                  /* QR_PGRID: in images the packet instance serves, a clipped plane's shadow list with at least this many
+                                             * surfaces gets a pyramid of filtered lists (CGrid with QR_GRIDC_PYR); 0 turns them off */
+    int    pgrid_levels = 4;                /* QR_PGRID_LEVELS: L of the pyramids, 2^L x 2^L cells at level 0 (1..QR_PGRID_LEVELS_MAX) */
     int    dda_min = 512;                   /* QR_DDA: lists with at least this many bounded members get a uniform grid (CDda); 0 turns them off */
     double dda_cells = 2.0;                 /* QR_DDA_CELLS: grid cells per member: 0.5 .. 8 are within 5 % of each other on the 10k scene */
     bool   drop_shadowless = true;          /* QR_SHADOWLESS=0: shadow lists keep the cells that cast no shadow */
@@ -150,6 +153,8 @@ struct Builder
     int n_srf, n_elm;
     uint32_t o_srf = 0, o_shd = 0, o_mat = 0, o_lgt = 0, o_tex = 0;
     uint32_t n_dda = 0, n_grids = 0, n_grid_lists = 0;
+    uint32_t n_pgrids = 0, n_pgrid_nodes = 0;   /* packet shadow pyramids and their nodes with a list (n_grids counts plain CGrids only) */
+    bool pgrid_ok = false;                  /* the attempt takes every list for short: pyramids may be built (compile_pgrid) */
 
     std::vector<uint32_t> list_off;         /* surface list head -> byte offset of its program (0 unseen)   */
     std::vector<uint32_t> shadow_off;       /* ... of its program as a shadow list, where that is another one (compile_list) */
@@ -228,6 +233,8 @@ private:
     void emit_cells(int n, uint32_t off, bool has_trnode);
     void build_dda(uint32_t rec_off, uint32_t off, int n);
     uint32_t compile_grid(int si, int lg, int sh);
+    uint32_t compile_pgrid(int si, int lg, int sh, uint32_t top);
+    bool grid_plane(int si, int &a, int &b) const;
 };
 
 /*

@@ -8,7 +8,7 @@ static int diag_print_counters(qr_device_scene *s)
     static const char *const kind[3] = { "shadow", "primary", "secondary" };
     (void)s; (void)kind;
 #ifdef QR_PROF
-    unsigned long long pf[64];
+    unsigned long long pf[80];
     HIP_TRY(hipMemcpyFromSymbol(pf, HIP_SYMBOL(qr_prof), sizeof(pf)));
     static const char *nm[48] = { "candidates through clip()", "clipper programs run", "clipper cells", "  fast plane cells", "  trnode / trsame cells",
         "  generic plane tests", "  quadric tests", "", "solve: plane cells", "solve: quadric cells", "solve: two-plane cells", "solve in shadow walks", "solve in nearest-hit walks",
@@ -30,7 +30,11 @@ static int diag_print_counters(qr_device_scene *s)
         fprintf(stderr, "QR_PROF solves of %s packet walks: own-surface cells plane %llu quadric %llu two-plane %llu, cells that cast no shadow %llu\n",
                 kind[k], a[0], a[1], a[2], a[3]);
     }
-    unsigned long long z[64] = {0};
+    /* packet shadow pyramid (qr_shade.hpp): the level of the node a wave's vote chose, and the votes that ended on an empty node */
+    fprintf(stderr, "QR_PROF pyramid votes by level 0..7:");
+    for (int i = 0; i < 8; i++) fprintf(stderr, " %llu", pf[64 + i]);
+    fprintf(stderr, ", on an empty node (no walk) %llu\n", pf[72]);
+    unsigned long long z[80] = {0};
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(qr_prof), z, sizeof(z)));
 #endif
 #ifdef QR_STATS

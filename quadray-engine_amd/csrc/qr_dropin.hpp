@@ -218,7 +218,10 @@ extern "C" int qr_render0(const void *s_inf, const qr_abi_desc *abi)
         c.compiled = false;
         c.evict();
         static const bool rebin = env_tristate("QR_REBIN") == 1;
-        QR_TRY(build_program(v, devs[0], rebin, c.hp, c.prog, 0, want_blocks, false, 0));
+        /* no packet shadow pyramids in an image that is compiled for ONE frame: building them costs more host time than the
+         * frame's kernel gets back (profiles/r30_packet_shadow_pyramid.txt); QR_DROPIN_PGRID=1 builds them all the same */
+        static const bool pgrid = env_tristate("QR_DROPIN_PGRID") == 1;
+        QR_TRY(build_program(v, devs[0], rebin, c.hp, c.prog, 0, want_blocks, false, pgrid ? 0u : QR_BUILD_NO_PGRID));
         /* the finished image is verified offset by offset (qr_program_verify) on EVERY frame that was compiled: the layout
          * depends on list contents (programs shared by content, clear runs, box cells), so equal totals do not mean an equal
          * structure, and the product kernel checks no offset it loads.  The walk costs ~0.05 ms at 1080p since heads equal to

@@ -29,7 +29,7 @@ struct BSphere { float c[3]; float r; float lo[3] = { 1.0f, 1.0f, 1.0f }, hi[3] 
 
 #define QR_SCHED_PER_LANE 0xFFFFFFFEu       /* schedule entry: the footprint straddles tiles, look the list up per pixel */
 
-struct QrProgramStats { uint64_t bytes; uint32_t n_lists, n_cells, n_dropped, n_clip_cells, n_grids, n_grid_lists, n_dda; };
+struct QrProgramStats { uint64_t bytes; uint32_t n_lists, n_cells, n_dropped, n_clip_cells, n_grids, n_grid_lists, n_dda, n_pgrids, n_pgrid_nodes; };
 
 struct QrProgram
 {
@@ -54,7 +54,9 @@ void qr_bound_spheres(const qr_scene_view &v, std::vector<BSphere> &out);
 int  qr_program_build(const qr_scene_view &v, const std::vector<qr_elem> &E, const std::vector<int32_t> &T,
                       const qr_frame &frm, const std::vector<BSphere> &bs, QrProgram &out, std::string &err, int sched_blocks = 0,
                       bool verify = true,       /* verify: walk every offset of the finished image (qr_program_verify) before returning it */
-                      uint32_t flags = 0);      /* QR_UPLOAD_RAY_QUERIES: also compile the snapshot's global list for ray queries */
+                      uint32_t flags = 0);      /* QR_UPLOAD_RAY_QUERIES: also compile the snapshot's global list for ray queries;
+                                                 * QR_BUILD_NO_PGRID: no packet shadow pyramids (the per-frame compile of qr_render0) */
+#define QR_BUILD_NO_PGRID 0x10000u              /* internal: no public upload flag has this bit */
 int  qr_program_verify(const QrProgram &p, std::string &err);
 /* per-surface shadow / reflection / light lists from the global list and the surfaces' bounds (ssort / lsort's role) */
 int  qr_snapshot_build_lists(const qr_scene_view &v, std::vector<uint8_t> &out, std::string &err);

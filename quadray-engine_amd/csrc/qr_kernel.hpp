@@ -86,7 +86,7 @@ typedef uint32_t u32;
 /* -DQR_PROF builds: wave-level event counters in a device global, printed by qr_render_count (where does a frame's instruction
  * budget go: tools/gpu_prof.py) */
 #ifdef QR_PROF
-__device__ unsigned long long qr_prof[64];
+__device__ unsigned long long qr_prof[80];
 #define QR_PROF_HIT(i) do { if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) atomicAdd(&qr_prof[i], 1ull); } while (0)
 #define QR_PROF_ADD(i, n) do { if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) atomicAdd(&qr_prof[i], (unsigned long long)(n)); } while (0)
 /* algorithmic fp32 operations the kernel executes, with the weights of SURVEY.md 8(d) as oracle/qr_oracle.c applies them (FL()):

@@ -103,8 +103,9 @@ struct ListFilter
         return head == QR_NULL ? QR_NULL : head + base;
     }
 
+    /* flat_max: a run that keeps at most this many surfaces is written without its bounding-volume elements (-1: never) */
     template <typename Pred>
-    int filter_nodes_run(Pred keep, Run &run) const
+    int filter_nodes_run(Pred keep, Run &run, int flat_max = QR_FLAT_LIST_MAX) const
     {
         run.el.clear(); run.local.clear();
         std::vector<qr_elem> &R = run.el;
@@ -155,7 +156,7 @@ struct ListFilter
          * only skip work, tracer.cpp:3955-4054): written flat it is a fraction of the cells.  Trnode elements stay. */
         int kept = 0;
         for (int e = head; e != QR_NULL; e = R[e].next) if (is_real(v.srf[R[e].simd])) kept++;
-        if (kept <= QR_FLAT_LIST_MAX)
+        if (kept <= flat_max)
         {
             int nh = QR_NULL, nt = QR_NULL;
             for (int e = head; e != QR_NULL; )

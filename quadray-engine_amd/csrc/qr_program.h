@@ -100,11 +100,24 @@ struct CGrid                    /* 32 B, 32-byte aligned */
 {
     uint32_t table;             /* byte offset of nx * ny list offsets (row-major, b major; 0 = nothing can shadow that cell) */
     uint32_t nx, ny;            /* cells along component a / b, 1..QR_GRID_MAX each                                       */
-    uint32_t comps;             /* a | b << 2: which components of the local hit span the plane                           */
+    uint32_t comps;             /* a | b << 2: which components of the local hit span the plane; | QR_GRIDC_PYR | L << 8 below */
     float    org_a, org_b;      /* local coordinate of the rectangle's low corner                                         */
     float    inv_a, inv_b;      /* cells per unit                                                                         */
 };
 #define QR_GRID_MAX 64u
+/*
+ * Packet shadow pyramid (ours): a CGrid with QR_GRIDC_PYR in `comps` belongs to an image the packet kernel instance serves.
+ * nx = ny = N = 2^L, L = QR_GRIDC_LEVELS(comps).  `table` holds level 0 exactly as above -- the per-lane instance reads it as a
+ * plain CGrid -- and right behind it levels 1..L, (N >> l)^2 words each, row-major: node (i, j) of level l covers the level-0
+ * cells [i 2^l, (i + 1) 2^l) x [j 2^l, (j + 1) 2^l) and lists what can stand between the light and that patch, a sub-sequence
+ * of its parent's program.  Level L is one word, the surface's plain shadow program.  The packet instance takes ONE node for all
+ * lanes of a wave that send a shadow ray: the lowest one that covers all their level-0 cells (qr_shade.hpp).
+ */
+#define QR_GRIDC_PYR        16u
+#define QR_GRIDC_LEVELS(c)  (((c) >> 8) & 7u)
+#define QR_PGRID_LEVELS_MAX 6u
+/* words of the levels below l */
+#define QR_PGRID_LEVEL_OFF(n, l) ((4u * ((n) * (n) - ((n) >> (l)) * ((n) >> (l)))) / 3u)
 
 /*
  * Uniform grid over the members of a long world-space list (ours).  A ray through a sparse cloud of thousands of small

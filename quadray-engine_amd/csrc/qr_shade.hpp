@@ -589,6 +589,46 @@ __device__ __forceinline__ void shade(const Ctx &cx, bool act, bool coherent, co
                 }
             }
         }
+        else
+        {
+            /* packet shadow pyramid (CGrid with QR_GRIDC_PYR, qr_program.h): the lanes that send a shadow ray from one such plane
+             * walk ONE node's list, the lowest node that covers all their level-0 cells -- traverse forms no extra group.
+             * Lanes that face away from the light send no ray and stay out of the vote. */
+            if (any_lane((sl & QR_LISTF_GRID) != 0))
+            {
+                const bool pg = (sl & QR_LISTF_GRID) != 0;
+                const u32 rec = sl & ~31u;
+                if (pg) sl = 0u;
+                lm_t todo = LM(pg && lm);
+                while (todo != 0)
+                {
+                    /* one record at a time (a wave's hits on two such planes: two turns), read with one scalar load */
+                    const u32 r0 = (u32)__builtin_amdgcn_readlane((int)rec, __ffsll((long long)todo) - 1);
+                    const lm_t mine = todo & LM(rec == r0);
+                    todo &= ~mine;
+                    const u32x8 g = *(const QR_CONST u32x8 *)(B + r0);          /* CGrid: table, nx, ny, comps, org_a, org_b, inv_a, inv_b */
+                    const u32 n = g.s1, cp = g.s3, L = QR_GRIDC_LEVELS(cp);
+                    /* the level-0 cell, with the arithmetic and clamps of the per-lane arm above */
+                    const float la = (cp & 3u) == 0 ? h.loc.x : ((cp & 3u) == 1 ? h.loc.y : h.loc.z);
+                    const float lb = ((cp >> 2) & 3u) == 0 ? h.loc.x : (((cp >> 2) & 3u) == 1 ? h.loc.y : h.loc.z);
+                    int ia = cvt_floor((la - u2f(g.s4)) * u2f(g.s6)), ib = cvt_floor((lb - u2f(g.s5)) * u2f(g.s7));
+                    ia = ia < 0 ? 0 : (ia >= (int)n ? (int)n - 1 : ia);
+                    ib = ib < 0 ? 0 : (ib >= (int)n ? (int)n - 1 : ib);
+                    const u32 key = lane_of(mine) ? (u32)ia | ((u32)ib << 16) : 0u;
+                    const u32 k0 = (u32)__builtin_amdgcn_readlane((int)key, __ffsll((long long)mine) - 1);
+                    /* the level: the first at which no lane of `mine` differs from the leader in either index */
+                    const u32 d = lane_of(mine) ? key ^ k0 : 0u;
+                    const u32 dd = (d | (d >> 16)) & 0xFFFFu;
+                    u32 l = 0;
+                    while (l < L && any_lane((dd >> l) != 0u)) l++;
+                    const u32 node = QR_PGRID_LEVEL_OFF(n, l) + ((k0 >> 16) >> l) * (n >> l) + ((k0 & 0xFFFFu) >> l);
+                    const u32 w = *(const QR_CONST u32 *)(B + (g.s0 + node * 4u));
+                    QR_PROF_HIT(64 + (int)l);
+                    if (w == 0u) QR_PROF_HIT(72);
+                    if (lane_of(mine)) sl = w;
+                }
+            }
+        }
         sr.list = sl; sr.osrf = hsrf; sr.oflg = side; sr.ploc = h.loc;
         Hit sh; bool occ;
         if (COUNT) { if (lm) cnt.shadow++; }

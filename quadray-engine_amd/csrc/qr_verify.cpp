@@ -186,10 +186,46 @@ int qr_program_verify(const QrProgram &p, std::string &err)
                         const CGrid *g = (const CGrid *)(b.data() + go);
                         if (g->nx < 1 || g->nx > QR_GRID_MAX || g->ny < 1 || g->ny > QR_GRID_MAX) return bad("shadow grid size");
                         const uint32_t ca = g->comps & 3u, cb = (g->comps >> 2) & 3u;
-                        if ((g->comps >> 4) || ca > 2 || cb > 2 || ca == cb) return bad("shadow grid components");
-                        if ((g->table & 3) || g->table < p.off_lists || (size_t)g->table + (size_t)g->nx * g->ny * 4 > limit) return bad("shadow grid table");
+                        const bool pyr = (g->comps & QR_GRIDC_PYR) != 0;
+                        const uint32_t L = QR_GRIDC_LEVELS(g->comps);
+                        if ((g->comps & ~(15u | (pyr ? QR_GRIDC_PYR | (7u << 8) : 0u))) || ca > 2 || cb > 2 || ca == cb) return bad("shadow grid components");
+                        /* a pyramid: 2^L x 2^L cells, in an image of the packet instance alone */
+                        if (pyr && (L < 1 || L > QR_PGRID_LEVELS_MAX || g->nx != (1u << L) || g->ny != g->nx || p.has_grids || p.has_long_lists))
+                            return bad("shadow pyramid record");
+                        if (!pyr && !p.has_grids) return bad("shadow grid in an image that reports none");
+                        const size_t n_words = pyr ? QR_PGRID_LEVEL_OFF(g->nx, L) + 1u : (size_t)g->nx * g->ny;
+                        if ((g->table & 3) || g->table < p.off_lists || (size_t)g->table + n_words * 4 > limit) return bad("shadow grid table");
                         const uint32_t *tb = (const uint32_t *)(b.data() + g->table);
-                        for (uint32_t q = 0; q < g->nx * g->ny; q++) if (const char *m = check_list(tb[q])) return bad(m);
+                        for (size_t q = 0; q < n_words; q++) if (const char *m = check_list(tb[q])) return bad(m);
+                        if (pyr)
+                        {
+                            /* every node's program a sub-sequence of its parent's: the same cells (type, surface) in the same order */
+                            auto next_cell = [&](uint32_t &o) { const CCell *c = (const CCell *)(b.data() + o); o += (c->op & QR_OPT_BV) ? 64 : 32; return c; };
+                            auto sub_seq = [&](uint32_t child, uint32_t parent) {
+                                if (child == 0 || child == parent) return true;
+                                if (parent == 0) return false;
+                                uint32_t oc = child & ~31u, op = parent & ~31u;
+                                for (;;)
+                                {
+                                    const CCell *c = next_cell(oc);
+                                    if (c->op == 0) return true;
+                                    for (;;)
+                                    {
+                                        const CCell *q = next_cell(op);
+                                        if (q->op == 0) return false;
+                                        if ((q->op & QR_OPT_MASK) == (c->op & QR_OPT_MASK) && q->srf == c->srf) break;
+                                    }
+                                }
+                            };
+                            if (tb[n_words - 1] == 0) return bad("shadow pyramid without a top program");
+                            for (uint32_t l = 0; l < L; l++)
+                            {
+                                const uint32_t n = g->nx >> l, np = n >> 1;
+                                const uint32_t *row = tb + QR_PGRID_LEVEL_OFF(g->nx, l), *par = tb + QR_PGRID_LEVEL_OFF(g->nx, l + 1);
+                                for (uint32_t j = 0; j < n; j++) for (uint32_t i = 0; i < n; i++)
+                                    if (!sub_seq(row[j * n + i], par[(j >> 1) * np + (i >> 1)])) return bad("shadow pyramid node holds what its parent does not");
+                            }
+                        }
                     }
                     else if (const char *m = check_list(l->shadow)) return bad(m);
                     if (l->lgt & QR_CLIGHT_LAST) break;
