@@ -946,7 +946,8 @@ int qr_pt_adapt_views_variance_async(qr_device_scene *scn, const int32_t *state,
  * qr_hit records (qr_hit_views_async: pos is world space, so the current camera is not an argument) is projected into the
  * camera the previous frame was made with, the previous frame's history is fetched there through four bilinear taps, each
  * held to the same surface by the previous frame's records, and this frame's noisy colour is blended into it.  A pure
- * function of its inputs.  A surface point that moved fails the world-space tests and starts afresh: conservative.
+ * function of its inputs.  A surface point that moved fails the world-space tests and starts afresh: conservative
+ * (qr_reproject_moving_async below takes a per-surface motion table and keeps the history of objects that move).
  *   - colour_in: float32 [n_views][height][width][channels], channels 3 or 4.  hits, hits_prev: qr_hit [n_views][height][width]
  *     of this and of the previous frame (pos, nrm, id, alb are read).  var_in: float32 [n_views][height][width] or NULL, the
  *     variance handed out where the history is short.  views_prev: the n_views cameras hits_prev and hist_in were made with.
@@ -1019,6 +1020,48 @@ int qr_reproject_views_async(qr_device_scene *scn, const float *colour_in, const
                              const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
                              int n_views, int width, int height, const qr_reproject_params *p,
                              float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream);
+
+/*
+ * Temporal reprojection for ANIMATED scenes: qr_reproject_views_async with a per-surface motion table.  A scene patched by
+ * qr_hierarchy_apply keeps every surface at its record index from frame to frame, and id = surface << 1 | side in every qr_hit
+ * names it; row s of the table is the affine map that takes a world point on surface record s NOW to where that material
+ * point was in the previous frame, prev = A . pos + t, as three rows (a0 a1 a2 t) of four floats (the Python package's
+ * hierarchy_motion makes the table from the node tables of the two frames).  Each pixel's point and normal are moved before
+ * the projection and the tap tests, so a pixel on an object that turned finds its own history where the object was.
+ *   - Contract: that of qr_reproject_views_async, every word, plus the move step.  motion_dev: qr_motion [n_motion] in DEVICE
+ *     memory, 16-byte aligned.  motion_dev == NULL with n_motion == 0 is allowed and gives the static call's bits (it is the
+ *     static call).  qr_reproject_params is unchanged, its reserved words stay 0.
+ *   - The arithmetic is pinned like the rest: fp32, nothing fused, every parenthesis an order.  The static text with:
+ *       move     only with a table.  s = id_p >> 1.  s >= n_motion: a fresh entry, coords NaN (id_p < 0 is the miss rule as before).
+ *                r0, r1, r2 = the three quads of motion[s];
+ *                pos'.k = ((rk.x * pos.x + rk.y * pos.y) + rk.z * pos.z) + rk.w
+ *                nrm'.k =  (rk.x * nrm.x + rk.y * nrm.y) + rk.z * nrm.z          (not renormalised)
+ *       project  as before with e = pos' - org
+ *       taps     as before with nrm' in the normal test and nrm' . (pos_q - pos') in the plane test; id_q == id_p unchanged
+ *     Everything else is the static text word for word: reading and demodulating the colour by the pixel's OWN albedo, fresh
+ *     entries, blend, variance, outputs.  A NaN row ("no history": an array or bounding record, a surface that was re-scaled)
+ *     gives a NaN den, so the pixel is not in front and gets a fresh entry through the existing rule.
+ *   - The exact identity row 1 0 0 0  0 1 0 0  0 0 1 0 against no table: on records whose pos and nrm are finite every word of
+ *     hist_out, colour_out and var_out is the same, and coords_out is the same but for the sign of a zero.  x * 1 + y * 0 turns
+ *     a -0.0 coordinate into +0.0; from there it can reach an output only through e = pos' - org with a +0.0 org component and
+ *     nu (or nv) a sum of three zero products, where fx = -0.0 without the table becomes +0.0 with it (the taps, weights and
+ *     tests compare and subtract, which do not tell the zeros apart).  That is the one documented difference.  A record with
+ *     an infinite pos or nrm component is another matter: 0 * Inf is NaN, the moved vector is NaN, and the pixel is fresh
+ *     (pos) or takes no tap (nrm) where the static text may keep history.
+ *   - What this does NOT do: the history is the light the surface point received in the frames before.  Light that changes
+ *     because a shadow caster or a light moved -- not the surface under the pixel -- lags by the history length, as it does
+ *     for any temporal accumulation; deforming or re-scaled objects and surfaces whose record index changes between frames
+ *     get NaN rows or wrong ids and start afresh.  Clamping the history to the neighbourhood's colours is a follow-up, not
+ *     part of this call.
+ *   - QR_ERR_ARG: every refusal of qr_reproject_views_async, and: a null table with n_motion > 0, a table with n_motion == 0,
+ *     n_motion outside 0..(1 << 30), a table that is not 16-byte aligned.  A refused call launches nothing.
+ */
+typedef struct qr_motion { float row[3][4]; } qr_motion;   /* 48 bytes, 16-byte aligned */
+int qr_reproject_moving_async(qr_device_scene *scn, const float *colour_in, const qr_hit *hits, const float *var_in,
+                              const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
+                              const qr_motion *motion_dev, int n_motion,
+                              int n_views, int width, int height, const qr_reproject_params *p,
+                              float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream);
 
 /*
  * Guided upsampling: light computed on a COARSE lattice -- every factor-th pixel of the frame, 1/4 or 1/16 of the pixels --

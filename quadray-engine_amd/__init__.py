@@ -33,7 +33,8 @@ ABI_SYMBOLS = [
     "qr_gather_rays_async", "qr_gather_views_async", "qr_gather_hits_async",
     "qr_fan_rays_framed_async", "qr_fan_views_framed_async", "qr_fan_hits_framed_async",
     "qr_gather_rays_framed_async", "qr_gather_views_framed_async", "qr_gather_hits_framed_async",
-    "qr_atrous_views_async", "qr_pt_adapt_views_variance_async", "qr_reproject_views_async", "qr_upsample_views_async",
+    "qr_atrous_views_async", "qr_pt_adapt_views_variance_async", "qr_reproject_views_async", "qr_reproject_moving_async",
+    "qr_upsample_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
     # include/qr_hierarchy.h
@@ -106,6 +107,11 @@ class ReprojectParams(ctypes.Structure):
                 ("alpha_min", ctypes.c_float), ("alpha_mom_min", ctypes.c_float), ("max_len", ctypes.c_float),
                 ("var_min_len", ctypes.c_float), ("unknown", ctypes.c_float), ("alb_floor", ctypes.c_float),
                 ("reserved", ctypes.c_uint32 * 3)]
+
+
+class Motion(ctypes.Structure):
+    """qr_motion (include/qrhip.h), 48 bytes: one row of hierarchy_motion's table"""
+    _fields_ = [("row", (ctypes.c_float * 4) * 3)]
 
 
 class UpsampleParams(ctypes.Structure):
@@ -182,6 +188,7 @@ def lib():
     L.qr_pt_adapt_list_work_bytes.argtypes = [vp, i64, ctypes.POINTER(cu64)]
     L.qr_atrous_views_async.argtypes = [vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(AtrousParams), vp, vp, vp]
     L.qr_reproject_views_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(ReprojectParams), vp, vp, vp, vp, vp]
+    L.qr_reproject_moving_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.POINTER(ReprojectParams), vp, vp, vp, vp, vp]
     L.qr_upsample_views_async.argtypes = [vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(UpsampleParams), vp, vp, vp, vp]
     L.qr_snapshot_build_lists_c.argtypes =[vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
@@ -468,6 +475,57 @@ def hierarchy_records_after_apply(blob, nodes, opts):
             nodes[g]["srf"] = n_srf
             n_srf += 1
     return nodes
+
+
+def hierarchy_motion(nodes_prev, nodes_cur, opts, n_srf):
+    """The motion table of qr_reproject_moving_async (Scene.reproject(motion=), Temporal.step(motion=)) between two node tables
+    of one hierarchy: float32 [n_srf, 12], n_srf the record count of the CURRENT snapshot (after hierarchy_apply, which may
+    have appended transform-node records).  Row s is three rows (a0 a1 a2 t) of the affine map that takes a world point on
+    surface record s now to where that material point was in the previous frame: prev = A . pos + t.
+
+    In float64 from hierarchy_update of both tables: W(node) = mtx[node] where trnode is -1 or the node itself, else mtx[node]
+    @ mtx[trnode] (4 x 4 row-major, the position in row 3, applied to row vectors); X = inv(W_cur) @ W_prev, A = X[:3, :3].T,
+    t = X[3, :3], rounded once to float32.  A node whose two world matrices are bit-equal gets the exact identity row.  Rows of
+    quiet NaN ("no history": conservative, never wrong) go to records that no surface node (tag 0..8, srf >= 0) names -- arrays,
+    bounding volumes, appended transform-node records --, to surfaces whose A is not a rotation (max |A A^T - I| > 1e-4: a
+    scaler changed) and to surfaces whose W_cur is singular.  Both tables must have the same length, parents and tags."""
+    import numpy as np
+    prev = np.ascontiguousarray(nodes_prev, dtype=node_dtype())
+    cur = np.ascontiguousarray(nodes_cur, dtype=node_dtype())
+    if prev.shape != cur.shape or prev.ndim != 1:
+        raise ValueError("nodes_prev and nodes_cur must be node tables of the same length")
+    if not (np.array_equal(prev["parent"], cur["parent"]) and np.array_equal(prev["tag"], cur["tag"])):
+        raise ValueError("nodes_prev and nodes_cur must have the same parents and tags: one hierarchy at two times")
+    if isinstance(n_srf, bool) or not isinstance(n_srf, (int, np.integer)) or not 0 <= n_srf <= 1 << 30:
+        raise ValueError("n_srf must be the record count of the current snapshot, 0..2^30")
+
+    def world(nodes):
+        st = hierarchy_update(nodes, opts)
+        out = []
+        for i in range(len(nodes)):
+            m, t = st[i]["mtx"].reshape(4, 4).astype(np.float64), int(st[i]["trnode"])
+            out.append(m if t < 0 or t == i else m @ st[t]["mtx"].reshape(4, 4).astype(np.float64))
+        return out
+
+    table = np.full((int(n_srf), 12), np.array([0x7FC00000], dtype=np.uint32).view(np.float32)[0], dtype=np.float32)
+    wp, wc = world(prev), world(cur)
+    for i in range(len(cur)):
+        s = int(cur[i]["srf"])
+        if not (0 <= cur[i]["tag"] < 9 and 0 <= s < n_srf):
+            continue
+        if wp[i].tobytes() == wc[i].tobytes():
+            table[s] = (1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0)
+            continue
+        with np.errstate(all="ignore"):
+            try:
+                x = np.linalg.inv(wc[i]) @ wp[i]
+            except np.linalg.LinAlgError:
+                continue
+            rot = x[:3, :3].T
+            if not (np.isfinite(x).all() and np.abs(rot @ rot.T - np.eye(3)).max() <= 1e-4):
+                continue
+            table[s] = np.concatenate([rot, x[3, :3, None]], axis=1).reshape(12).astype(np.float32)
+    return table
 
 
 def program_stats(blob, flags=0):
@@ -803,16 +861,32 @@ class Scene:
         return ((n, h, w, ch), prev, out, _wanted("colour_out", colour_out, "float32", (n, h, w, ch), dev),
                 _wanted("variance_out", variance_out, "float32", (n, h, w), dev), _wanted("coords", coords, "float32", (n, h, w, 2), dev))
 
-    def _reproject_launch(self, colour, hits, variance, prev, dims, stops, out, colour_out, variance_out, coords, stream):
+    def _motion_arg(self, motion):
+        """the motion table of reproject() / Temporal.step(): None, or a contiguous float32 [n, 12] tensor (n >= 1) on the
+        scene's device (hierarchy_motion makes it); ValueError for anything else"""
+        if motion is None:
+            return None
+        motion = _need("motion", motion, "float32", (None, 12), self.device, error=ValueError)
+        if not 1 <= motion.shape[0] <= 1 << 30:
+            raise ValueError("motion must have 1..2^30 rows")
+        return motion
+
+    def _reproject_launch(self, colour, hits, variance, prev, dims, stops, out, colour_out, variance_out, coords, stream, motion=None):
         n, h, w, ch = dims
         p = ReprojectParams(ch, *(stops[k] for k in ("flags", "off_x", "off_y", "normal_min", "plane_max", "min_weight", "alpha_min",
                                                      "alpha_mom_min", "max_len", "var_min_len", "unknown", "alb_floor")))
-        _check(lib().qr_reproject_views_async(self._h, _ptr(colour), _ptr(hits), _ptr(variance), _ptr(prev[0]), _ptr(prev[1]),
-                                              _ptr(prev[2]), n, w, h, ctypes.byref(p), _ptr(out), _ptr(colour_out),
-                                              _ptr(variance_out), _ptr(coords), self._stream_ptr(stream)))
+        if motion is None:
+            _check(lib().qr_reproject_views_async(self._h, _ptr(colour), _ptr(hits), _ptr(variance), _ptr(prev[0]), _ptr(prev[1]),
+                                                  _ptr(prev[2]), n, w, h, ctypes.byref(p), _ptr(out), _ptr(colour_out),
+                                                  _ptr(variance_out), _ptr(coords), self._stream_ptr(stream)))
+        else:
+            _check(lib().qr_reproject_moving_async(self._h, _ptr(colour), _ptr(hits), _ptr(variance), _ptr(prev[0]), _ptr(prev[1]),
+                                                   _ptr(prev[2]), motion.data_ptr(), int(motion.shape[0]), n, w, h, ctypes.byref(p),
+                                                   _ptr(out), _ptr(colour_out), _ptr(variance_out), _ptr(coords),
+                                                   self._stream_ptr(stream)))
 
     def reproject(self, colour, hits, prev=None, variance=None, out=None, colour_out=True, variance_out=True, coords=False,
-                  stream=None, **params):
+                  stream=None, motion=None, **params):
         """Temporal reprojection (qr_reproject_views_async; rays.reproject_pass is its arithmetic): blend this frame's noisy colour
         (float32 [N, H, W, 3|4]) into the history of the frame before, fetched where this frame's hits (view_hits of the current
         cameras) fall in the previous cameras and kept only on the same surface.  prev = (views_prev [N, 16], hits_prev, history
@@ -820,18 +894,23 @@ class Scene:
         a short history hands out.  out: the history tensor to write (a new one by default, never prev's); colour_out,
         variance_out, coords: True (a new tensor), False or a tensor to fill.  params: normal_min, plane_max, min_weight,
         alpha_min, alpha_mom_min, max_len, var_min_len, unknown, albedo_floor, demodulate, off as rays.reproject_stops takes
-        them -- starting points, not tuned.  Static scenes under a moving camera.  Returns (history, colour, variance), with
-        coords wanted (history, colour, variance, coords); what is not wanted is None.  Asynchronous on `stream`."""
+        them -- starting points, not tuned.  motion=None: static scenes under a moving camera.  motion (float32 [n, 12] on
+        the scene's device, hierarchy_motion of the previous and the current node table; ValueError for anything else): an
+        animated scene patched by hierarchy_apply -- every pixel's point and normal are taken to where its surface was in the
+        previous frame before the projection and the tap tests (qr_reproject_moving_async).  Returns (history, colour,
+        variance), with coords wanted (history, colour, variance, coords); what is not wanted is None.  Asynchronous on
+        `stream`."""
+        motion = self._motion_arg(motion)
         stops = self._reproject_stops(**params)
         dims, prev, out, colour_out, variance_out, cd = self._reproject_args(colour, hits, prev, variance, out, colour_out,
                                                                              variance_out, coords)
-        self._reproject_launch(colour, hits, variance, prev, dims, stops, out, colour_out, variance_out, cd, stream)
+        self._reproject_launch(colour, hits, variance, prev, dims, stops, out, colour_out, variance_out, cd, stream, motion)
         return (out, colour_out, variance_out) if cd is None else (out, colour_out, variance_out, cd)
 
     def temporal(self, n_views, width, height, channels=3, **params):
         """A temporal accumulator over frames of n_views moving cameras at width x height (rays.temporal is its chain): returns
-        a Temporal whose step(colour, hits, views, variance=None) reprojects against the frame before.  params as for
-        reproject()."""
+        a Temporal whose step(colour, hits, views, variance=None, motion=None, scene=None) reprojects against the frame
+        before.  params as for reproject()."""
         return Temporal(self, n_views, width, height, channels, **params)
 
     def _fan_args(self, dirs, eps, reach, shape, mask):
@@ -1442,7 +1521,8 @@ class Temporal:
     It owns two history tensors (float32 [N, H, W, 8]: c0 c1 c2 c3 m1 m2 len 0 per pixel) that it alternates between, and
     clones of the last step's hit records and cameras: a copy of 48 B per pixel and step, on the step's stream, so that the
     caller may reuse its own tensors at once.  `frames`: steps since the start or the last reset().  Static scenes under a
-    moving camera; the stops (normal_min, plane_max, ...: rays.reproject_stops) are starting points, not tuned."""
+    moving camera, and with step(motion=, scene=) scenes animated through hierarchy_apply; the stops (normal_min, plane_max,
+    ...: rays.reproject_stops) are starting points, not tuned."""
 
     def __init__(self, scene, n_views, width, height, channels=3, **params):
         if not (all(isinstance(x, int) and not isinstance(x, bool) and x >= 1 for x in (n_views, width, height)) and channels in (3, 4)):
@@ -1478,19 +1558,25 @@ class Temporal:
         """the history length per pixel after the last step, a float32 [N, H, W] view of `history`; None before the first"""
         return None if self._hits is None else self._hist[self._cur][..., 6]
 
-    def step(self, colour, hits, views, variance=None, stream=None):
+    def step(self, colour, hits, views, variance=None, stream=None, motion=None, scene=None):
         """One frame: colour (float32 [N, H, W, channels]), hits (view_hits of `views`) and views (float32 [N, 16], this frame's
-        cameras) against the frame before; variance as for Scene.reproject.  Returns (colour, variance), new tensors: the
-        accumulated colour -- demodulated with demodulate=True: Scene.atrous(modulate=True) as the last filter pass multiplies
-        back -- and its variance, what Scene.denoise takes.  Asynchronous on `stream`."""
+        cameras) against the frame before; variance and motion as for Scene.reproject.  scene: the Scene to launch on, by
+        default the one the accumulator was made with -- an animated host uploads a new Scene every frame and may close the
+        old one; the reprojection reads nothing of a scene but its device, which must be the accumulator's (QrError).
+        Returns (colour, variance), new tensors: the accumulated colour -- demodulated with demodulate=True:
+        Scene.atrous(modulate=True) as the last filter pass multiplies back -- and its variance, what Scene.denoise takes.
+        Asynchronous on `stream`."""
         import torch
-        scn = self.scene
+        scn = self.scene if scene is None else scene
+        if not isinstance(scn, Scene) or scn.device != self.scene.device:
+            raise QrError(f"scene must be a Scene on the accumulator's device cuda:{self.scene.device}")
+        motion = scn._motion_arg(motion)
         n, h, w = self.shape
         if not (_fits(colour, "float32", (n, h, w, self.channels)) and _fits(views, "float32", (n, 16), scn.device)):
             raise QrError(f"this accumulation holds float32 colour [{n}, {h}, {w}, {self.channels}] and views [{n}, 16] on cuda:{scn.device}")
         prev = None if self._hits is None else (self._views, self._hits, self._hist[self._cur])
         dims, prev, out, col, var, _ = scn._reproject_args(colour, hits, prev, variance, self._hist[self._cur ^ 1], True, True, False)
-        scn._reproject_launch(colour, hits, variance, prev, dims, self.params, out, col, var, None, stream)
+        scn._reproject_launch(colour, hits, variance, prev, dims, self.params, out, col, var, None, stream, motion)
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
             self._hits, self._views = hits.clone(), views.clone()
         self._cur ^= 1

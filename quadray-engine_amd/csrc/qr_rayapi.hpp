@@ -603,10 +603,13 @@ extern "C" int qr_upsample_views_async(qr_device_scene *s, const float *colour_l
 
 /* ---- temporal reprojection (qr_reproject.hpp): one lane per pixel, 32 x 8 pixel tiles, blockIdx.z the view ---- */
 
-extern "C" int qr_reproject_views_async(qr_device_scene *s, const float *colour_in, const qr_hit *hits, const float *var_in,
-                                        const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
-                                        int n_views, int width, int height, const qr_reproject_params *p,
-                                        float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream)
+/* both entry points: every check of the static contract, then the table's, then the launch of the static kernel (no table) or
+ * of the moving one */
+static int reproject_launch(qr_device_scene *s, const float *colour_in, const qr_hit *hits, const float *var_in,
+                            const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
+                            const qr_motion *motion_dev, int n_motion,
+                            int n_views, int width, int height, const qr_reproject_params *p,
+                            float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream)
 {
     QR_TRY(need_scene(s));
     if (p == nullptr) return qr_fail(QR_ERR_ARG, "null reprojection parameters");
@@ -625,13 +628,18 @@ extern "C" int qr_reproject_views_async(qr_device_scene *s, const float *colour_
     const int n_prev = (views_prev != nullptr) + (hits_prev != nullptr) + (hist_in != nullptr);
     if (n_prev != 0 && n_prev != 3)
         return qr_fail(QR_ERR_ARG, "views_prev, hits_prev and hist_in go together: all three or none (the first frame)");
+    if (n_motion < 0 || n_motion > (1 << 30)) return qr_fail(QR_ERR_ARG, "n_motion must be 0..2^30");
+    if ((motion_dev != nullptr) != (n_motion > 0))
+        return qr_fail(QR_ERR_ARG, "motion_dev and n_motion go together: a table of n_motion >= 1 rows, or NULL and 0");
+    QR_TRY(aligned_ptrs({motion_dev}, 16, "the motion table must be 16-byte aligned"));
     if (n_views == 0) return QR_OK;
     QR_TRY(need_ptrs({colour_in, hits, hist_out}));
     QR_TRY(aligned_ptrs({hits, views_prev, hits_prev, hist_in, hist_out}, 16, "views, hits and history must be 16-byte aligned"));
     QR_TRY(aligned_ptrs({colour_in, var_in, colour_out, var_out, coords_out}, 4, "colour, variance and coords must be 4-byte aligned"));
     if (hist_in == hist_out) return qr_fail(QR_ERR_ARG, "the taps read neighbours' history: hist_out cannot be hist_in");
     HIP_TRY(hipSetDevice(s->device));
-    ReprojP rp;
+    ReprojMovingP mp;
+    ReprojP &rp = mp.r;
     rp.colour_in = colour_in; rp.hits = (const f32x4 *)hits; rp.var_in = var_in;
     rp.views_prev = views_prev; rp.hits_prev = (const f32x4 *)hits_prev; rp.hist_in = (const f32x4 *)hist_in;
     rp.hist_out = (f32x4 *)hist_out; rp.colour_out = colour_out; rp.var_out = var_out; rp.coords_out = coords_out;
@@ -639,13 +647,35 @@ extern "C" int qr_reproject_views_async(qr_device_scene *s, const float *colour_
     rp.off_x = p->off_x; rp.off_y = p->off_y; rp.normal_min = p->normal_min; rp.plane_max = p->plane_max;
     rp.min_weight = p->min_weight; rp.alpha_min = p->alpha_min; rp.alpha_mom_min = p->alpha_mom_min;
     rp.max_len = p->max_len; rp.var_min_len = p->var_min_len; rp.unknown = p->unknown; rp.alb_floor = p->alb_floor;
+    mp.motion = (const f32x4 *)motion_dev; mp.n_motion = (u32)n_motion;
     /* grid.x <= 512, grid.y <= 2048 at QR_VIEW_MAX_DIM */
     const dim3 grid((unsigned)((width + QR_REPROJ_TW - 1) / QR_REPROJ_TW), (unsigned)((height + QR_REPROJ_TH - 1) / QR_REPROJ_TH),
                     (unsigned)n_views), block(QR_REPROJ_BLOCK);
     pick(p->channels == 3, [&](auto three) {
-        hipLaunchKernelGGL(qr_reproject_kernel<(decltype(three)::value ? 3 : 4)>, grid, block, 0, (hipStream_t)stream, rp);
+        constexpr int CH = decltype(three)::value ? 3 : 4;
+        if (motion_dev == nullptr) hipLaunchKernelGGL(qr_reproject_kernel<CH>, grid, block, 0, (hipStream_t)stream, rp);
+        else hipLaunchKernelGGL(qr_reproj_moving_kernel<CH>, grid, block, 0, (hipStream_t)stream, mp);
     });
     return launched();
+}
+
+extern "C" int qr_reproject_views_async(qr_device_scene *s, const float *colour_in, const qr_hit *hits, const float *var_in,
+                                        const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
+                                        int n_views, int width, int height, const qr_reproject_params *p,
+                                        float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream)
+{
+    return reproject_launch(s, colour_in, hits, var_in, views_prev, hits_prev, hist_in, nullptr, 0, n_views, width, height, p,
+                            hist_out, colour_out, var_out, coords_out, stream);
+}
+
+extern "C" int qr_reproject_moving_async(qr_device_scene *s, const float *colour_in, const qr_hit *hits, const float *var_in,
+                                         const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
+                                         const qr_motion *motion_dev, int n_motion,
+                                         int n_views, int width, int height, const qr_reproject_params *p,
+                                         float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream)
+{
+    return reproject_launch(s, colour_in, hits, var_in, views_prev, hits_prev, hist_in, motion_dev, n_motion, n_views, width,
+                            height, p, hist_out, colour_out, var_out, coords_out, stream);
 }
 
 /* ---- open lists and indexed adaptive steps (qr_openlist.hpp, qr_kernel.hpp qr_pt_list_kernel): compaction on chip ---- */

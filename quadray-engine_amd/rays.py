@@ -85,6 +85,12 @@ Temporal / temporal the accumulator's chain, in float32 numpy; reproject_stops i
         hits = scn.view_hits(view, w, h)
         colour, var = acc.step(noisy_mean_of(view), hits, view, variance_of(view))
         clean, _ = scn.denoise(colour, hits, var, passes=5, plane=0.05, luma=4.0)
+
+For a scene animated through hierarchy_apply, step(..., motion=, scene=) takes the package's hierarchy_motion table of the two
+frames' node tables (move_hits is the step it adds: qr_reproject_moving_async) and the frame's own Scene:
+
+    table = torch.from_numpy(qr.hierarchy_motion(nodes_prev, nodes_cur, opts, n_srf)).cuda()
+    colour, var = acc.step(noisy, hits, view, motion=table, scene=scene_of_this_frame)
 """
 import struct
 
@@ -1213,9 +1219,34 @@ def project_to_view(view, pos, off=(0, 0), dtype=np.float32):
     return np.stack([fx, fy], axis=-1), front
 
 
+def _motion_table(motion):
+    """the motion table of reproject_pass / move_hits: float32 [n, 12], n >= 1 (ValueError otherwise)"""
+    m = np.asarray(motion)
+    if m.dtype != np.float32 or m.ndim != 2 or m.shape[1] != 12 or m.shape[0] < 1:
+        raise ValueError(f"motion must be float32 [n, 12] with n >= 1, got {m.dtype} {list(m.shape)}")
+    return m
+
+
+def move_hits(hits, motion):
+    """The move step of qr_reproject_moving_async in float32 numpy, operation for operation: hits float32 [..., 12] (qr_hit
+    records), motion float32 [n, 12] (row s = the three quads r0 r1 r2 of surface record s).  Returns (pos' [..., 3], nrm'
+    [..., 3], listed [...]): with s = id >> 1, pos'.k = ((rk.x * pos.x + rk.y * pos.y) + rk.z * pos.z) + rk.w and nrm'.k =
+    (rk.x * nrm.x + rk.y * nrm.y) + rk.z * nrm.z (not renormalised); listed is false for a miss (id < 0) and for s >= n, whose
+    pos' and nrm' are NaN: such a pixel gets a fresh entry."""
+    m = _motion_table(motion)
+    pos, _, nrm, ids, _, _ = hit_fields(np.asarray(hits))
+    listed = (ids >= 0) & ((ids >> 1) < len(m))
+    r = m[np.where(listed, ids >> 1, 0)].reshape(ids.shape + (3, 4))
+    with np.errstate(all="ignore"):
+        mp = ((r[..., 0] * pos[..., None, 0] + r[..., 1] * pos[..., None, 1]) + r[..., 2] * pos[..., None, 2]) + r[..., 3]
+        mn = (r[..., 0] * nrm[..., None, 0] + r[..., 1] * nrm[..., None, 1]) + r[..., 2] * nrm[..., None, 2]
+    return (np.where(listed[..., None], mp, REPROJ_NAN).astype(np.float32), np.where(listed[..., None], mn, REPROJ_NAN).astype(np.float32),
+            listed)
+
+
 def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, off_y=0.0, normal_min=0.9, plane_max=np.inf,
                    min_weight=0.01, alpha_min=0.05, alpha_mom_min=0.2, max_len=32.0, var_min_len=4.0, unknown=1.0, alb_floor=1 / 256,
-                   taps=None):
+                   taps=None, motion=None):
     """The specification of one qr_reproject_views_async call in float32 numpy, every operation elementwise so that it rounds
     once: colour float32 [N, H, W, C] (or [H, W, C]; C 3 or 4), hits float32 [N, H, W, 12] (this frame's qr_hit records),
     variance float32 [N, H, W] or None, prev = None (the first frame) or (views_prev [N, 16], hits_prev [N, H, W, 12], history
@@ -1232,8 +1263,14 @@ def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, o
     c = (sc / sw) * (1 - max(a, alpha_min)) + c * max(a, alpha_min), m1 and m2 likewise with alpha_mom_min, the variance max(0,
     m2 - m1 * m1) where var_min_len <= len; elsewhere the fresh entry.
 
+    motion: None is the static call.  A float32 [n, 12] table (qr_reproject_moving_async; move_hits is the step): pos and nrm of
+    the pixel are replaced by pos' and nrm' in the projection, the normal test and the plane test -- everything else, the
+    colour's demodulation by the pixel's own albedo included, is the static text; a surface beyond the table is fresh.
+
     taps: if a list is given, the four (taken bool [N, H, W], b float32 [N, H, W]) pairs are appended to it in tap order."""
     f = np.float32
+    if motion is not None:
+        motion = _motion_table(motion)
     colour, variance, hits = _atrous_args(colour, variance, hits)
     single = colour.ndim == 3
     if single:
@@ -1257,6 +1294,9 @@ def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, o
                 raise ValueError(f"{what} must be float32 {list(shape)}, got {a.dtype} {list(a.shape)}")
     pos, _, nrm, ids, alb, _ = hit_fields(hits)
     hit = ids >= 0
+    listed = hit
+    if motion is not None:
+        pos, nrm, listed = move_hits(hits, motion)                                   # beyond the table: fresh, as a miss is
     one, zero = f(1.0), f(0.0)
     with np.errstate(all="ignore"):
         a = np.where(alb > par["alb_floor"], alb, par["alb_floor"])                 # a NaN albedo gives the floor
@@ -1272,7 +1312,7 @@ def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, o
         coords = np.full((n, h, w, 2), REPROJ_NAN, dtype=f)
         if prev is not None:
             xy, front = project_to_view(views_prev[:, None, None, :], pos, (par["off_x"], par["off_y"]))
-            front = front & hit
+            front = front & listed
             coords = np.where(front[..., None], xy, REPROJ_NAN).astype(f)
             fx, fy = xy[..., 0], xy[..., 1]
             window = front & (-one < fx) & (fx < f(w)) & (-one < fy) & (fy < f(h))
@@ -1320,8 +1360,8 @@ def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, o
 
 class Temporal:
     """The accumulator's chain in numpy (temporal(); what Scene.temporal's Temporal computes on the GPU): two history arrays it
-    alternates between and copies of the last hit records and cameras.  step(colour, hits, views, variance=None) is one
-    reproject_pass against the frame before -- the first frame after the start or a reset() has none -- and returns (colour,
+    alternates between and copies of the last hit records and cameras.  step(colour, hits, views, variance=None, motion=None) is
+    one reproject_pass against the frame before -- the first frame after the start or a reset() has none -- and returns (colour,
     variance); history / length are the entry array [N, H, W, 8] and its length plane after the last step (None before the
     first); clone() continues independently."""
 
@@ -1354,12 +1394,12 @@ class Temporal:
     def length(self):
         return None if self._hits is None else self._hist[self._cur][..., 6]
 
-    def step(self, colour, hits, views, variance=None):
+    def step(self, colour, hits, views, variance=None, motion=None):
         colour, hits, views = np.asarray(colour), np.asarray(hits), np.asarray(views)
         if colour.shape != self.shape + (self.channels,) or views.shape != (self.shape[0], 16) or views.dtype != np.float32:
             raise ValueError(f"this accumulation holds float32 colour {list(self.shape) + [self.channels]} and views [{self.shape[0]}, 16]")
         prev = None if self._hits is None else (self._views, self._hits, self._hist[self._cur])
-        hist, col, var, _ = reproject_pass(colour, hits, variance, prev, **self.params)
+        hist, col, var, _ = reproject_pass(colour, hits, variance, prev, motion=motion, **self.params)
         self._cur ^= 1
         self._hist[self._cur][...] = hist
         self._hits, self._views = hits.copy(), views.copy()

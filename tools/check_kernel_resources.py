@@ -31,7 +31,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
   * a guided a-trous instance qr_atrous_kernel<CH> or qr_pt_adapt_var_kernel spills a vector register, has a private segment or
     uses more than 64 VGPRs, or a filter instance more LDS than its 36 x 12 staged entries (20736 B / 22464 B);
   * a temporal reprojection instance qr_reproject_kernel<CH> spills a vector register, has a private segment, uses any LDS or
-    more than 96 (3 channels) / 80 (4 channels) VGPRs;
+    more than 96 (3 channels) / 80 (4 channels) VGPRs, or an instance with a motion table qr_reproj_moving_kernel<CH> more than
+    those plus its 12 row words (108 / 92);
   * a guided upsampling instance qr_upsample_kernel<CH> spills a vector register, has a private segment, uses more than 64 VGPRs
     or more LDS than its 34 x 10 staged entries (14960 B / 16320 B);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
@@ -134,6 +135,11 @@ LIMITS = {
     # the four taps in flight at once, which is what the launch time rests on (qr_reproject.hpp)
     "19qr_reproject_kernelILi3EE": (96, 0, 0),
     "19qr_reproject_kernelILi4EE": (80, 0, 0),
+    # temporal reprojection with a motion table (qr_reproject.hpp qr_reproj_moving_kernel<CH>): the same pixel with the move step:
+    # nothing spilled, no private segment, no LDS, and the static instance's limit plus the 12 row words a lane may hold at once
+    # (108 / 92; the build's assembly has 80 / 74)
+    "23qr_reproj_moving_kernelILi3EE": (108, 0, 0),
+    "23qr_reproj_moving_kernelILi4EE": (92, 0, 0),
     # guided upsampling (qr_upsample.hpp qr_upsample_kernel<CH>): four taps out of LDS per full pixel, bound by the bytes it moves:
     # nothing spilled, no private segment, and the registers of the build's assembly (35 / 36 VGPRs) rounded up to the next
     # occupancy step, 64 (8 waves per SIMD, all a SIMD holds); no more LDS than 34 x 10 staged entries of 8 + CH planes, of which
@@ -143,6 +149,7 @@ LIMITS = {
 }
 LDS_LIMITS = {"16qr_atrous_kernelILi3EE": 20736, "16qr_atrous_kernelILi4EE": 22464,
               "19qr_reproject_kernelILi3EE": 0, "19qr_reproject_kernelILi4EE": 0,
+              "23qr_reproj_moving_kernelILi3EE": 0, "23qr_reproj_moving_kernelILi4EE": 0,
               "18qr_upsample_kernelILi3EE": 14960, "18qr_upsample_kernelILi4EE": 16320}
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 
