@@ -297,6 +297,56 @@ def _wanted(name, t, dtype, shape, dev):
     return _need(name, t, dtype, shape, dev, lead="True, False or a")
 
 
+# The image filters (atrous, denoise, upsample, reproject, Temporal.step): dtype and shape of every tensor first, then the
+# residency of all of them.  `error`: QrError, or ValueError for upsample.
+
+def _stops(fn, error, **kw):
+    """the stops of a filter through rays.<fn> (atrous_stops, upsample_stops, reproject_stops): what that refuses, as `error`"""
+    from . import rays
+    try:
+        return getattr(rays, fn)(**kw)
+    except (ValueError, TypeError) as e:
+        raise error(str(e)) from None
+
+
+def _plane(name, t, shape, error):
+    """an optional float32 tensor of a filter, an input or an output: dtype and shape alone"""
+    if t is not None and not _fits(t, "float32", shape):
+        raise error(f"{name} must be None or a float32 {list(shape)} tensor")
+
+
+def _frame_inputs(colour, hits, variance, error=QrError, lattice=None):
+    """The frame inputs of a filter, dtype and shape alone: colour [N, H, W, 3|4], hits [N, H, W, 12], variance None or [N, H, W].
+    lattice=(factor, phase): colour (called colour_lo) and variance are the coarse frame of the full frame of hits, which then
+    comes first.  Returns (n, h, w, channels) of the full frame."""
+    if lattice is None:
+        if not (_fits(colour, "float32", (None, None, None, None)) and colour.shape[3] in (3, 4) and min(colour.shape) >= 1):
+            raise error("colour must be a float32 [N, H, W, 3] or [N, H, W, 4] tensor")
+        n, h, w, ch = (int(x) for x in colour.shape)
+        if not _fits(hits, "float32", (n, h, w, 12)):
+            raise error(f"hits must be a float32 [{n}, {h}, {w}, 12] tensor of qr_hit records (view_hits)")
+        lo = (n, h, w)
+    else:
+        from . import rays
+        if not (_fits(hits, "float32", (None, None, None, 12)) and min(hits.shape) >= 1):
+            raise error("hits must be a float32 [N, H, W, 12] tensor of qr_hit records (view_hits) of the FULL frame")
+        n, h, w = (int(x) for x in hits.shape[:3])
+        wl, hl = rays.coarse_size(w, h, *lattice)
+        if not (_fits(colour, "float32", (n, hl, wl, None)) and colour.shape[3] in (3, 4)):
+            raise error(f"colour_lo must be a float32 [{n}, {hl}, {wl}, 3] or [{n}, {hl}, {wl}, 4] tensor: the coarse frame of "
+                        f"a {w} x {h} frame at factor {lattice[0]}, phase {tuple(lattice[1])} (rays.coarse_size)")
+        ch, lo = int(colour.shape[3]), (n, hl, wl)
+    _plane("variance", variance, lo, error)
+    return n, h, w, ch
+
+
+def _resident(dev, error, *tensors):
+    """the residency pass: every (tensor, name) that is given is contiguous and on cuda:dev"""
+    for t, what in tensors:
+        if t is not None and not _fits(t, None, None, dev):
+            raise error(f"{what} must be contiguous and on cuda:{dev}")
+
+
 _FAN_FNS = {}       # (fan | gather, rays | hits | views, plain) -> the library's entry point, looked up once
 
 
@@ -690,32 +740,14 @@ class Scene:
 
     def _atrous_args(self, colour, hits, variance, out, variance_out):
         """the tensors of atrous() / denoise(): dtype and shape first, then contiguity and device.  Returns (n, h, w, channels)."""
-        if not (_fits(colour, "float32", (None, None, None, None)) and colour.shape[3] in (3, 4) and min(colour.shape) >= 1):
-            raise QrError("colour must be a float32 [N, H, W, 3] or [N, H, W, 4] tensor")
-        n, h, w, ch = (int(x) for x in colour.shape)
-        if not _fits(hits, "float32", (n, h, w, 12)):
-            raise QrError(f"hits must be a float32 [{n}, {h}, {w}, 12] tensor of qr_hit records (view_hits)")
-        if variance is not None and not _fits(variance, "float32", (n, h, w)):
-            raise QrError(f"variance must be None or a float32 [{n}, {h}, {w}] tensor")
-        if out is not None and not _fits(out, "float32", (n, h, w, ch)):
-            raise QrError(f"out must be None or a float32 [{n}, {h}, {w}, {ch}] tensor")
-        if variance_out is not None:
-            if variance is None:
-                raise QrError("variance_out needs a variance")
-            if not _fits(variance_out, "float32", (n, h, w)):
-                raise QrError(f"variance_out must be None or a float32 [{n}, {h}, {w}] tensor")
-        for t, what in ((colour, "colour"), (hits, "hits"), (variance, "variance"), (out, "out"), (variance_out, "variance_out")):
-            if t is not None and not _fits(t, None, None, self.device):
-                raise QrError(f"{what} must be contiguous and on cuda:{self.device}")
-        return n, h, w, ch
-
-    @staticmethod
-    def _atrous_stops(**stops):
-        from . import rays
-        try:
-            return rays.atrous_stops(**stops)
-        except (ValueError, TypeError) as e:
-            raise QrError(str(e)) from None
+        dims = _frame_inputs(colour, hits, variance)
+        _plane("out", out, dims, QrError)
+        if variance_out is not None and variance is None:
+            raise QrError("variance_out needs a variance")
+        _plane("variance_out", variance_out, dims[:3], QrError)
+        _resident(self.device, QrError, (colour, "colour"), (hits, "hits"), (variance, "variance"), (out, "out"),
+                  (variance_out, "variance_out"))
+        return dims
 
     def _atrous_launch(self, colour, variance, hits, dims, step, stops, out, variance_out, stream):
         n, h, w, ch = dims
@@ -736,13 +768,13 @@ class Scene:
         tuned.  out / variance_out: tensors to write, neither the inputs.  Returns colour_out, or (colour_out, variance_out) with
         a variance.  Asynchronous on `stream`."""
         import torch
-        stops = self._atrous_stops(normal_power=normal_power, plane=plane, luma=luma, luma_eps=luma_eps, demodulate=demodulate,
-                                   modulate=modulate, albedo_floor=albedo_floor)
+        stops = _stops("atrous_stops", QrError, normal_power=normal_power, plane=plane, luma=luma, luma_eps=luma_eps,
+                       demodulate=demodulate, modulate=modulate, albedo_floor=albedo_floor)
         if isinstance(step, bool) or not isinstance(step, numbers.Integral) or not 1 <= step <= ATROUS_MAX_STEP:
             raise QrError(f"step must be an integer, 1..{ATROUS_MAX_STEP}")
         dims = self._atrous_args(colour, hits, variance, out, variance_out)
         if out is None:
-            out = torch.empty_like(colour)
+            out = torch.empty_like(colour)              # not _new: torch.empty with its keywords cost 0.7 us more per tensor
         if variance is not None and variance_out is None:
             variance_out = torch.empty_like(variance)
         self._atrous_launch(colour, variance, hits, dims, int(step), stops, out, variance_out, stream)
@@ -760,7 +792,7 @@ class Scene:
             raise QrError("passes must be an integer, 1..7")
         if "demodulate" in stops or "modulate" in stops:
             raise QrError("denoise sets demodulate and modulate itself (albedo=True)")
-        per_pass = [self._atrous_stops(demodulate=bool(albedo) and k == 0, modulate=bool(albedo) and k == passes - 1, **stops)
+        per_pass = [_stops("atrous_stops", QrError, demodulate=bool(albedo) and k == 0, modulate=bool(albedo) and k == passes - 1, **stops)
                     for k in range(passes)]
         dims = self._atrous_args(colour, hits, variance, None, None)
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
@@ -772,6 +804,22 @@ class Scene:
             self._atrous_launch(c, v, hits, dims, 1 << k, per_pass[k], co, vo, stream)
             c, v = co, vo
         return c, v
+
+    def _upsample_args(self, colour_lo, hits, factor, phase, variance, out, variance_out, weight):
+        """the tensors of upsample(), as _atrous_args takes its own but with ValueError.  Returns ((n, h, w, channels), the
+        weight to fill: a tensor, a new one, or None)."""
+        n, h, w, _ = dims = _frame_inputs(colour_lo, hits, variance, ValueError, (factor, phase))
+        if variance_out is not None and variance is None:
+            raise ValueError("variance_out needs a variance")
+        _plane("out", out, dims, ValueError)
+        _plane("variance_out", variance_out, (n, h, w), ValueError)
+        if weight is None or isinstance(weight, bool):
+            weight = True if weight else None
+        elif not _fits(weight, "float32", (n, h, w)):
+            raise ValueError(f"weight must be True, False or a float32 [{n}, {h}, {w}] tensor")
+        _resident(self.device, ValueError, (colour_lo, "colour_lo"), (hits, "hits"), (variance, "variance"), (out, "out"),
+                  (variance_out, "variance_out"), (None if weight is True else weight, "weight"))
+        return dims, _new("float32", (n, h, w), self.device) if weight is True else weight
 
     def upsample(self, colour_lo, hits, factor, phase=(0, 0), variance=None, normal_power=128, plane=None, same_id=False,
                  demodulate=False, modulate=False, albedo_floor=1 / 256, out=None, variance_out=None, weight=False, stream=None):
@@ -786,80 +834,38 @@ class Scene:
         new tensor), False or a tensor to fill with the taken taps' weight (0: only taps of bilinear weight 0; -1: no tap, the
         nearest coarse pixel: what a host may trace again).  A wrong tensor is a ValueError.  Returns the colour, or a tuple of
         the colour, the variance (with a variance) and the weight (when wanted).  Asynchronous on `stream`."""
-        from . import rays
-        dev = self.device
-        flags, nsq, sz, af = rays.upsample_stops(normal_power=normal_power, plane=plane, same_id=same_id, demodulate=demodulate,
-                                                 modulate=modulate, albedo_floor=albedo_floor)
-        if not (_fits(hits, "float32", (None, None, None, 12)) and min(hits.shape) >= 1):
-            raise ValueError("hits must be a float32 [N, H, W, 12] tensor of qr_hit records (view_hits) of the FULL frame")
-        n, h, w = (int(x) for x in hits.shape[:3])
-        wl, hl = rays.coarse_size(w, h, factor, phase)
-        if not (_fits(colour_lo, "float32", (n, hl, wl, None)) and colour_lo.shape[3] in (3, 4)):
-            raise ValueError(f"colour_lo must be a float32 [{n}, {hl}, {wl}, 3] or [{n}, {hl}, {wl}, 4] tensor: the coarse frame of "
-                             f"a {w} x {h} frame at factor {factor}, phase {tuple(phase)} (rays.coarse_size)")
-        ch = int(colour_lo.shape[3])
-        if variance is not None and not _fits(variance, "float32", (n, hl, wl)):
-            raise ValueError(f"variance must be None or a float32 [{n}, {hl}, {wl}] tensor")
-        if variance_out is not None and variance is None:
-            raise ValueError("variance_out needs a variance")
-        if out is not None and not _fits(out, "float32", (n, h, w, ch)):
-            raise ValueError(f"out must be None or a float32 [{n}, {h}, {w}, {ch}] tensor")
-        if variance_out is not None and not _fits(variance_out, "float32", (n, h, w)):
-            raise ValueError(f"variance_out must be None or a float32 [{n}, {h}, {w}] tensor")
-        if weight is None or isinstance(weight, bool):
-            weight = True if weight else None
-        elif not _fits(weight, "float32", (n, h, w)):
-            raise ValueError(f"weight must be True, False or a float32 [{n}, {h}, {w}] tensor")
-        for t, what in ((colour_lo, "colour_lo"), (hits, "hits"), (variance, "variance"), (out, "out"), (variance_out, "variance_out"),
-                        (weight, "weight")):
-            if t is not None and t is not True and not _fits(t, None, None, dev):
-                raise ValueError(f"{what} must be contiguous and on cuda:{dev}")
+        flags, nsq, sz, af = _stops("upsample_stops", ValueError, normal_power=normal_power, plane=plane, same_id=same_id,
+                                    demodulate=demodulate, modulate=modulate, albedo_floor=albedo_floor)
+        (n, h, w, ch), weight = self._upsample_args(colour_lo, hits, factor, phase, variance, out, variance_out, weight)
         if out is None:
-            out = _new("float32", (n, h, w, ch), dev)
+            out = _new("float32", (n, h, w, ch), self.device)
         if variance is not None and variance_out is None:
-            variance_out = _new("float32", (n, h, w), dev)
-        if weight is True:
-            weight = _new("float32", (n, h, w), dev)
+            variance_out = _new("float32", (n, h, w), self.device)
         p = UpsampleParams(int(factor), int(phase[0]), int(phase[1]), ch, nsq, flags, float(sz), float(af))
         _check(lib().qr_upsample_views_async(self._h, _ptr(colour_lo), _ptr(variance), _ptr(hits), n, w, h, ctypes.byref(p),
                                              _ptr(out), _ptr(variance_out), _ptr(weight), self._stream_ptr(stream)))
         got = (out,) + (() if variance is None else (variance_out,)) + (() if weight is None else (weight,))
         return got[0] if len(got) == 1 else got
 
-    @staticmethod
-    def _reproject_stops(**params):
-        from . import rays
-        try:
-            return rays.reproject_stops(**params)
-        except (ValueError, TypeError) as e:
-            raise QrError(str(e)) from None
-
     def _reproject_args(self, colour, hits, prev, variance, out, colour_out, variance_out, coords):
         """the tensors of reproject(): dtype and shape first, then contiguity and device.  Returns ((n, h, w, channels), the
-        previous triple or three None, out, colour_out, variance_out, coords) with the outputs that are wanted made."""
+        previous triple or three None, (out, colour_out, variance_out, coords)) with the outputs that are wanted made."""
         dev = self.device
-        if not (_fits(colour, "float32", (None, None, None, None)) and colour.shape[3] in (3, 4) and min(colour.shape) >= 1):
-            raise QrError("colour must be a float32 [N, H, W, 3] or [N, H, W, 4] tensor")
-        n, h, w, ch = (int(x) for x in colour.shape)
-        if not _fits(hits, "float32", (n, h, w, 12)):
-            raise QrError(f"hits must be a float32 [{n}, {h}, {w}, 12] tensor of qr_hit records (view_hits)")
-        if variance is not None and not _fits(variance, "float32", (n, h, w)):
-            raise QrError(f"variance must be None or a float32 [{n}, {h}, {w}] tensor")
+        n, h, w, ch = _frame_inputs(colour, hits, variance)
         if prev is None:
             prev = (None, None, None)
         elif not (isinstance(prev, (tuple, list)) and len(prev) == 3 and _fits(prev[0], "float32", (n, 16))
                   and _fits(prev[1], "float32", (n, h, w, 12)) and _fits(prev[2], "float32", (n, h, w, 8))):
             raise QrError(f"prev must be None or (views_prev float32 [{n}, 16], hits_prev float32 [{n}, {h}, {w}, 12], "
                           f"history float32 [{n}, {h}, {w}, 8])")
-        for t, what in ((colour, "colour"), (hits, "hits"), (variance, "variance"), (prev[0], "views_prev"), (prev[1], "hits_prev"),
-                        (prev[2], "history")):
-            if t is not None and not _fits(t, None, None, dev):
-                raise QrError(f"{what} must be contiguous and on cuda:{dev}")
+        _resident(dev, QrError, (colour, "colour"), (hits, "hits"), (variance, "variance"), (prev[0], "views_prev"), (prev[1], "hits_prev"),
+                  (prev[2], "history"))
         out = _fill("out", out, "float32", (n, h, w, 8), dev)
         if prev[2] is not None and out.data_ptr() == prev[2].data_ptr():
             raise QrError("out must not be the previous history: the taps read neighbours")
-        return ((n, h, w, ch), prev, out, _wanted("colour_out", colour_out, "float32", (n, h, w, ch), dev),
-                _wanted("variance_out", variance_out, "float32", (n, h, w), dev), _wanted("coords", coords, "float32", (n, h, w, 2), dev))
+        return (n, h, w, ch), prev, (out, _wanted("colour_out", colour_out, "float32", (n, h, w, ch), dev),
+                                     _wanted("variance_out", variance_out, "float32", (n, h, w), dev),
+                                     _wanted("coords", coords, "float32", (n, h, w, 2), dev))
 
     def _motion_arg(self, motion):
         """the motion table of reproject() / Temporal.step(): None, or a contiguous float32 [n, 12] tensor (n >= 1) on the
@@ -871,19 +877,14 @@ class Scene:
             raise ValueError("motion must have 1..2^30 rows")
         return motion
 
-    def _reproject_launch(self, colour, hits, variance, prev, dims, stops, out, colour_out, variance_out, coords, stream, motion=None):
+    def _reproject_launch(self, colour, hits, variance, prev, dims, stops, outs, stream, motion=None):
         n, h, w, ch = dims
         p = ReprojectParams(ch, *(stops[k] for k in ("flags", "off_x", "off_y", "normal_min", "plane_max", "min_weight", "alpha_min",
                                                      "alpha_mom_min", "max_len", "var_min_len", "unknown", "alb_floor")))
-        if motion is None:
-            _check(lib().qr_reproject_views_async(self._h, _ptr(colour), _ptr(hits), _ptr(variance), _ptr(prev[0]), _ptr(prev[1]),
-                                                  _ptr(prev[2]), n, w, h, ctypes.byref(p), _ptr(out), _ptr(colour_out),
-                                                  _ptr(variance_out), _ptr(coords), self._stream_ptr(stream)))
-        else:
-            _check(lib().qr_reproject_moving_async(self._h, _ptr(colour), _ptr(hits), _ptr(variance), _ptr(prev[0]), _ptr(prev[1]),
-                                                   _ptr(prev[2]), motion.data_ptr(), int(motion.shape[0]), n, w, h, ctypes.byref(p),
-                                                   _ptr(out), _ptr(colour_out), _ptr(variance_out), _ptr(coords),
-                                                   self._stream_ptr(stream)))
+        fn, table = (lib().qr_reproject_views_async, ()) if motion is None else \
+            (lib().qr_reproject_moving_async, (motion.data_ptr(), int(motion.shape[0])))
+        _check(fn(self._h, _ptr(colour), _ptr(hits), _ptr(variance), _ptr(prev[0]), _ptr(prev[1]), _ptr(prev[2]), *table, n, w, h,
+                  ctypes.byref(p), *map(_ptr, outs), self._stream_ptr(stream)))
 
     def reproject(self, colour, hits, prev=None, variance=None, out=None, colour_out=True, variance_out=True, coords=False,
                   stream=None, motion=None, **params):
@@ -901,11 +902,10 @@ class Scene:
         variance), with coords wanted (history, colour, variance, coords); what is not wanted is None.  Asynchronous on
         `stream`."""
         motion = self._motion_arg(motion)
-        stops = self._reproject_stops(**params)
-        dims, prev, out, colour_out, variance_out, cd = self._reproject_args(colour, hits, prev, variance, out, colour_out,
-                                                                             variance_out, coords)
-        self._reproject_launch(colour, hits, variance, prev, dims, stops, out, colour_out, variance_out, cd, stream, motion)
-        return (out, colour_out, variance_out) if cd is None else (out, colour_out, variance_out, cd)
+        stops = _stops("reproject_stops", QrError, **params)
+        dims, prev, outs = self._reproject_args(colour, hits, prev, variance, out, colour_out, variance_out, coords)
+        self._reproject_launch(colour, hits, variance, prev, dims, stops, outs, stream, motion)
+        return outs[:3] if outs[3] is None else outs
 
     def temporal(self, n_views, width, height, channels=3, **params):
         """A temporal accumulator over frames of n_views moving cameras at width x height (rays.temporal is its chain): returns
@@ -1528,7 +1528,7 @@ class Temporal:
         if not (all(isinstance(x, int) and not isinstance(x, bool) and x >= 1 for x in (n_views, width, height)) and channels in (3, 4)):
             raise QrError("n_views, width and height must be positive integers and channels 3 or 4")
         self.scene, self.shape, self.channels = scene, (n_views, height, width), channels
-        self.params = scene._reproject_stops(**params)
+        self.params = _stops("reproject_stops", QrError, **params)
         self._hist = [_new("float32", self.shape + (8,), scene.device) for _ in range(2)]
         self._cur, self._hits, self._views, self.frames = 0, None, None, 0
 
@@ -1575,13 +1575,13 @@ class Temporal:
         if not (_fits(colour, "float32", (n, h, w, self.channels)) and _fits(views, "float32", (n, 16), scn.device)):
             raise QrError(f"this accumulation holds float32 colour [{n}, {h}, {w}, {self.channels}] and views [{n}, 16] on cuda:{scn.device}")
         prev = None if self._hits is None else (self._views, self._hits, self._hist[self._cur])
-        dims, prev, out, col, var, _ = scn._reproject_args(colour, hits, prev, variance, self._hist[self._cur ^ 1], True, True, False)
-        scn._reproject_launch(colour, hits, variance, prev, dims, self.params, out, col, var, None, stream, motion)
+        dims, prev, outs = scn._reproject_args(colour, hits, prev, variance, self._hist[self._cur ^ 1], True, True, False)
+        scn._reproject_launch(colour, hits, variance, prev, dims, self.params, outs, stream, motion)
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
             self._hits, self._views = hits.clone(), views.clone()
         self._cur ^= 1
         self.frames += 1
-        return col, var
+        return outs[1], outs[2]
 
 
 class MultiRender:

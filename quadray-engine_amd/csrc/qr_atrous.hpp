@@ -36,6 +36,16 @@ struct AtrousP
 /* max(alb, floor) as the header writes it: a NaN albedo gives the floor */
 __device__ __forceinline__ float qr_atrous_alb(float alb, float floor) { return alb > floor ? alb : floor; }
 
+/* the first three channels of c divided by the albedo ha of a record, each floored: this file, qr_upsample.hpp and
+ * qr_reproject_pixel.hpp.  The multiply, the normal stop and the plane stop stay written out in the two kernels that have them:
+ * as functions they moved qr_atrous_kernel's register allocation. */
+__device__ __forceinline__ void qr_albedo_divide(float *c, const f32x4 ha, float floor)
+{
+    c[0] = c[0] / qr_atrous_alb(ha.x, floor);
+    c[1] = c[1] / qr_atrous_alb(ha.y, floor);
+    c[2] = c[2] / qr_atrous_alb(ha.z, floor);
+}
+
 template <int CH>
 __global__ __launch_bounds__(QR_ATROUS_BLOCK)
 void qr_atrous_kernel(const AtrousP p)
@@ -69,12 +79,7 @@ void qr_atrous_kernel(const AtrousP p)
 #pragma unroll
             for (int k = 0; k < CH; k++) c[k] = p.colour_in[px * CH + k];
             if ((flags & QR_ATROUS_DEMODULATE) && id >= 0)
-            {
-                const f32x4 ha = h[2];
-                c[0] = c[0] / qr_atrous_alb(ha.x, p.alb_floor);
-                c[1] = c[1] / qr_atrous_alb(ha.y, p.alb_floor);
-                c[2] = c[2] / qr_atrous_alb(ha.z, p.alb_floor);
-            }
+                qr_albedo_divide(c, h[2], p.alb_floor);
 #pragma unroll
             for (int k = 0; k < CH; k++) l_col[k][e] = c[k];
             l_lum[e] = (c[0] * 0.2126f + c[1] * 0.7152f) + c[2] * 0.0722f;

@@ -100,6 +100,40 @@ static int aligned_ptrs(std::initializer_list<const void *> ps, unsigned align, 
     return QR_OK;
 }
 
+/* the 16-byte pointers of a call, then its 4-byte ones, each list with its own message */
+static int aligned_16_and_4(std::initializer_list<const void *> wide, const char *wide_msg,
+                            std::initializer_list<const void *> words, const char *words_msg)
+{
+    QR_TRY(aligned_ptrs(wide, 16, wide_msg));
+    return aligned_ptrs(words, 4, words_msg);
+}
+
+/* the image filters' parameter blocks (a-trous, upsampling, reprojection): msg names the block */
+static int need_params(const void *p, const char *msg)
+{
+    if (p == nullptr) return qr_fail(QR_ERR_ARG, msg);
+    return QR_OK;
+}
+
+static int channels_arg(int channels)
+{
+    if (channels != 3 && channels != 4) return qr_fail(QR_ERR_ARG, "channels must be 3 or 4");
+    return QR_OK;
+}
+
+static int normal_sq_arg(int normal_sq)
+{
+    if (normal_sq < 0 || normal_sq > 7) return qr_fail(QR_ERR_ARG, "normal_sq must be 0..7");
+    return QR_OK;
+}
+
+/* two optional arguments that go together */
+static int both_or_neither(bool a, bool b, const char *msg)
+{
+    if (a != b) return qr_fail(QR_ERR_ARG, msg);
+    return QR_OK;
+}
+
 static int put_bytes(uint64_t *bytes_out, uint64_t bytes)
 {
     if (bytes_out == nullptr) return qr_fail(QR_ERR_ARG, "null argument");
@@ -122,6 +156,12 @@ static dim3 footprint_grid(const qr_device_scene *s, int width, int height, int 
 {
     const Footprints f = footprints(s, width, height);
     return dim3((unsigned)f.cols, (unsigned)f.rows, (unsigned)n_views);
+}
+
+/* one lane per pixel in tw x th pixel tiles, blockIdx.z the view: 32 x 8 tiles give grid.x <= 512, grid.y <= 2048 at QR_VIEW_MAX_DIM */
+static dim3 tile_grid(int width, int height, int n_views, int tw, int th)
+{
+    return dim3((unsigned)((width + tw - 1) / tw), (unsigned)((height + th - 1) / th), (unsigned)n_views);
 }
 
 static ViewsP views_params(const qr_view *views, int width, int height, float *depth = nullptr)
@@ -150,6 +190,12 @@ static int launched()
 template <class F> static void pick(bool flag, F &&f)
 {
     if (flag) f(std::true_type{}); else f(std::false_type{});
+}
+
+/* f(std::integral_constant<int, 3>) or <int, 4>: the channels of a filtered frame, checked by channels_arg */
+template <class F> static void pick_channels(int channels, F &&f)
+{
+    pick(channels == 3, [&](auto three) { f(std::integral_constant<int, decltype(three)::value ? 3 : 4>{}); });
 }
 
 /* The instance of a launch over views, chosen as the frame launch chooses its own: per-lane walks only where some list
@@ -524,20 +570,20 @@ extern "C" int qr_atrous_views_async(qr_device_scene *s, const float *colour_in,
                                      float *colour_out, float *var_out, void *stream)
 {
     QR_TRY(need_scene(s));
-    if (p == nullptr) return qr_fail(QR_ERR_ARG, "null filter parameters");
+    QR_TRY(need_params(p, "null filter parameters"));
     QR_TRY(view_size_args(n_views, width, height));
     if (p->step < 1 || p->step > QR_ATROUS_MAX_STEP) return qr_fail(QR_ERR_ARG, "step must be 1.." + std::to_string(QR_ATROUS_MAX_STEP));
-    if (p->channels != 3 && p->channels != 4) return qr_fail(QR_ERR_ARG, "channels must be 3 or 4");
-    if (p->normal_sq < 0 || p->normal_sq > 7) return qr_fail(QR_ERR_ARG, "normal_sq must be 0..7");
+    QR_TRY(channels_arg(p->channels));
+    QR_TRY(normal_sq_arg(p->normal_sq));
     QR_TRY(flags_arg(p->flags, QR_ATROUS_NORMAL | QR_ATROUS_PLANE | QR_ATROUS_LUMA | QR_ATROUS_DEMODULATE | QR_ATROUS_MODULATE,
                      "unknown filter flags"));
     if (!(p->sigma_z > 0.0f) || !(p->sigma_l2 > 0.0f) || !(p->eps_l > 0.0f) || !(p->alb_floor > 0.0f))
         return qr_fail(QR_ERR_ARG, "sigma_z, sigma_l2, eps_l and alb_floor must be above 0");
-    if ((var_in == nullptr) != (var_out == nullptr)) return qr_fail(QR_ERR_ARG, "var_in and var_out go together: both or neither");
+    QR_TRY(both_or_neither(var_in != nullptr, var_out != nullptr, "var_in and var_out go together: both or neither"));
     if (n_views == 0) return QR_OK;
     QR_TRY(need_ptrs({colour_in, colour_out, hits}));
-    QR_TRY(aligned_ptrs({hits}, 16, "hits must be 16-byte aligned"));
-    QR_TRY(aligned_ptrs({colour_in, colour_out, var_in, var_out}, 4, "colour and variance must be 4-byte aligned"));
+    QR_TRY(aligned_16_and_4({hits}, "hits must be 16-byte aligned",
+                            {colour_in, colour_out, var_in, var_out}, "colour and variance must be 4-byte aligned"));
     if (colour_in == colour_out || (var_in != nullptr && var_in == var_out))
         return qr_fail(QR_ERR_ARG, "a pass reads neighbours: it cannot run in place");
     HIP_TRY(hipSetDevice(s->device));
@@ -551,8 +597,8 @@ extern "C" int qr_atrous_views_async(qr_device_scene *s, const float *colour_in,
     ap.tiles_y = ((height + p->step - 1) / p->step + QR_ATROUS_TH - 1) / QR_ATROUS_TH;
     /* grid.y = phy * tiles_y <= height / 8 + 2 * step: far below 65535 at QR_VIEW_MAX_DIM */
     const dim3 grid((unsigned)(phx * ap.tiles_x), (unsigned)(phy * ap.tiles_y), (unsigned)n_views), block(QR_ATROUS_BLOCK);
-    pick(p->channels == 3, [&](auto three) {
-        hipLaunchKernelGGL(qr_atrous_kernel<(decltype(three)::value ? 3 : 4)>, grid, block, 0, (hipStream_t)stream, ap);
+    pick_channels(p->channels, [&](auto ch) {
+        hipLaunchKernelGGL(qr_atrous_kernel<decltype(ch)::value>, grid, block, 0, (hipStream_t)stream, ap);
     });
     return launched();
 }
@@ -564,23 +610,23 @@ extern "C" int qr_upsample_views_async(qr_device_scene *s, const float *colour_l
                                        float *colour_out, float *var_out, float *weight_out, void *stream)
 {
     QR_TRY(need_scene(s));
-    if (p == nullptr) return qr_fail(QR_ERR_ARG, "null upsampling parameters");
+    QR_TRY(need_params(p, "null upsampling parameters"));
     QR_TRY(view_size_args(n_views, width, height));
     if (p->factor < 1 || p->factor > QR_UPSAMPLE_MAX_FACTOR)
         return qr_fail(QR_ERR_ARG, "factor must be 1.." + std::to_string(QR_UPSAMPLE_MAX_FACTOR));
     if (p->phase_x < 0 || p->phase_x >= p->factor || p->phase_y < 0 || p->phase_y >= p->factor)
         return qr_fail(QR_ERR_ARG, "phase_x and phase_y must be 0..factor - 1");
     if (p->phase_x >= width || p->phase_y >= height) return qr_fail(QR_ERR_ARG, "the phase lies beyond the frame: the coarse frame is empty");
-    if (p->channels != 3 && p->channels != 4) return qr_fail(QR_ERR_ARG, "channels must be 3 or 4");
-    if (p->normal_sq < 0 || p->normal_sq > 7) return qr_fail(QR_ERR_ARG, "normal_sq must be 0..7");
+    QR_TRY(channels_arg(p->channels));
+    QR_TRY(normal_sq_arg(p->normal_sq));
     QR_TRY(flags_arg(p->flags, QR_UPSAMPLE_NORMAL | QR_UPSAMPLE_PLANE | QR_UPSAMPLE_SAME_ID | QR_UPSAMPLE_DEMODULATE | QR_UPSAMPLE_MODULATE,
                      "unknown upsampling flags"));
     if (!(p->sigma_z > 0.0f) || !(p->alb_floor > 0.0f)) return qr_fail(QR_ERR_ARG, "sigma_z and alb_floor must be above 0");
-    if ((var_lo == nullptr) != (var_out == nullptr)) return qr_fail(QR_ERR_ARG, "var_lo and var_out go together: both or neither");
+    QR_TRY(both_or_neither(var_lo != nullptr, var_out != nullptr, "var_lo and var_out go together: both or neither"));
     if (n_views == 0) return QR_OK;
     QR_TRY(need_ptrs({colour_lo, colour_out, hits}));
-    QR_TRY(aligned_ptrs({hits}, 16, "hits must be 16-byte aligned"));
-    QR_TRY(aligned_ptrs({colour_lo, var_lo, colour_out, var_out, weight_out}, 4, "colour, variance and weight must be 4-byte aligned"));
+    QR_TRY(aligned_16_and_4({hits}, "hits must be 16-byte aligned",
+                            {colour_lo, var_lo, colour_out, var_out, weight_out}, "colour, variance and weight must be 4-byte aligned"));
     for (const void *o : {(const void *)colour_out, (const void *)var_out, (const void *)weight_out})
         for (const void *i : {(const void *)colour_lo, (const void *)var_lo, (const void *)hits})
             if (o != nullptr && o == i) return qr_fail(QR_ERR_ARG, "a pixel reads its neighbours' lattice points: an output cannot be an input");
@@ -592,11 +638,9 @@ extern "C" int qr_upsample_views_async(qr_device_scene *s, const float *colour_l
     up.wl = (width - p->phase_x + p->factor - 1) / p->factor; up.hl = (height - p->phase_y + p->factor - 1) / p->factor;
     up.factor = p->factor; up.phase_x = p->phase_x; up.phase_y = p->phase_y; up.normal_sq = p->normal_sq; up.flags = p->flags;
     up.sigma_z = p->sigma_z; up.alb_floor = p->alb_floor;
-    /* grid.x <= 512, grid.y <= 2048 at QR_VIEW_MAX_DIM */
-    const dim3 grid((unsigned)((width + QR_UPS_TW - 1) / QR_UPS_TW), (unsigned)((height + QR_UPS_TH - 1) / QR_UPS_TH),
-                    (unsigned)n_views), block(QR_UPS_BLOCK);
-    pick(p->channels == 3, [&](auto three) {
-        hipLaunchKernelGGL(qr_upsample_kernel<(decltype(three)::value ? 3 : 4)>, grid, block, 0, (hipStream_t)stream, up);
+    const dim3 grid = tile_grid(width, height, n_views, QR_UPS_TW, QR_UPS_TH), block(QR_UPS_BLOCK);
+    pick_channels(p->channels, [&](auto ch) {
+        hipLaunchKernelGGL(qr_upsample_kernel<decltype(ch)::value>, grid, block, 0, (hipStream_t)stream, up);
     });
     return launched();
 }
@@ -612,9 +656,9 @@ static int reproject_launch(qr_device_scene *s, const float *colour_in, const qr
                             float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream)
 {
     QR_TRY(need_scene(s));
-    if (p == nullptr) return qr_fail(QR_ERR_ARG, "null reprojection parameters");
+    QR_TRY(need_params(p, "null reprojection parameters"));
     QR_TRY(view_size_args(n_views, width, height));
-    if (p->channels != 3 && p->channels != 4) return qr_fail(QR_ERR_ARG, "channels must be 3 or 4");
+    QR_TRY(channels_arg(p->channels));
     QR_TRY(flags_arg(p->flags, QR_REPROJ_DEMODULATE, "unknown reprojection flags"));
     if (p->reserved[0] != 0u || p->reserved[1] != 0u || p->reserved[2] != 0u)
         return qr_fail(QR_ERR_ARG, "the reserved words of the reprojection parameters must be 0");
@@ -629,13 +673,13 @@ static int reproject_launch(qr_device_scene *s, const float *colour_in, const qr
     if (n_prev != 0 && n_prev != 3)
         return qr_fail(QR_ERR_ARG, "views_prev, hits_prev and hist_in go together: all three or none (the first frame)");
     if (n_motion < 0 || n_motion > (1 << 30)) return qr_fail(QR_ERR_ARG, "n_motion must be 0..2^30");
-    if ((motion_dev != nullptr) != (n_motion > 0))
-        return qr_fail(QR_ERR_ARG, "motion_dev and n_motion go together: a table of n_motion >= 1 rows, or NULL and 0");
+    QR_TRY(both_or_neither(motion_dev != nullptr, n_motion > 0,
+                           "motion_dev and n_motion go together: a table of n_motion >= 1 rows, or NULL and 0"));
     QR_TRY(aligned_ptrs({motion_dev}, 16, "the motion table must be 16-byte aligned"));
     if (n_views == 0) return QR_OK;
     QR_TRY(need_ptrs({colour_in, hits, hist_out}));
-    QR_TRY(aligned_ptrs({hits, views_prev, hits_prev, hist_in, hist_out}, 16, "views, hits and history must be 16-byte aligned"));
-    QR_TRY(aligned_ptrs({colour_in, var_in, colour_out, var_out, coords_out}, 4, "colour, variance and coords must be 4-byte aligned"));
+    QR_TRY(aligned_16_and_4({hits, views_prev, hits_prev, hist_in, hist_out}, "views, hits and history must be 16-byte aligned",
+                            {colour_in, var_in, colour_out, var_out, coords_out}, "colour, variance and coords must be 4-byte aligned"));
     if (hist_in == hist_out) return qr_fail(QR_ERR_ARG, "the taps read neighbours' history: hist_out cannot be hist_in");
     HIP_TRY(hipSetDevice(s->device));
     ReprojMovingP mp;
@@ -648,11 +692,9 @@ static int reproject_launch(qr_device_scene *s, const float *colour_in, const qr
     rp.min_weight = p->min_weight; rp.alpha_min = p->alpha_min; rp.alpha_mom_min = p->alpha_mom_min;
     rp.max_len = p->max_len; rp.var_min_len = p->var_min_len; rp.unknown = p->unknown; rp.alb_floor = p->alb_floor;
     mp.motion = (const f32x4 *)motion_dev; mp.n_motion = (u32)n_motion;
-    /* grid.x <= 512, grid.y <= 2048 at QR_VIEW_MAX_DIM */
-    const dim3 grid((unsigned)((width + QR_REPROJ_TW - 1) / QR_REPROJ_TW), (unsigned)((height + QR_REPROJ_TH - 1) / QR_REPROJ_TH),
-                    (unsigned)n_views), block(QR_REPROJ_BLOCK);
-    pick(p->channels == 3, [&](auto three) {
-        constexpr int CH = decltype(three)::value ? 3 : 4;
+    const dim3 grid = tile_grid(width, height, n_views, QR_REPROJ_TW, QR_REPROJ_TH), block(QR_REPROJ_BLOCK);
+    pick_channels(p->channels, [&](auto ch) {
+        constexpr int CH = decltype(ch)::value;
         if (motion_dev == nullptr) hipLaunchKernelGGL(qr_reproject_kernel<CH>, grid, block, 0, (hipStream_t)stream, rp);
         else hipLaunchKernelGGL(qr_reproj_moving_kernel<CH>, grid, block, 0, (hipStream_t)stream, mp);
     });

@@ -29,13 +29,7 @@
 #pragma unroll
     for (int k = 0; k < CH; k++) c[k] = p.colour_in[px * CH + k];
     if constexpr (CH == 3) c[3] = 0.0f;
-    if ((p.flags & QR_REPROJ_DEMODULATE) && id_p >= 0)
-    {
-        const f32x4 ha = h[2];
-        c[0] = c[0] / qr_atrous_alb(ha.x, p.alb_floor);
-        c[1] = c[1] / qr_atrous_alb(ha.y, p.alb_floor);
-        c[2] = c[2] / qr_atrous_alb(ha.z, p.alb_floor);
-    }
+    if ((p.flags & QR_REPROJ_DEMODULATE) && id_p >= 0) qr_albedo_divide(c, h[2], p.alb_floor);
     const float l = (c[0] * 0.2126f + c[1] * 0.7152f) + c[2] * 0.0722f;
     const float l2 = l * l;
     const float v_fresh = p.var_in != nullptr ? p.var_in[px] : p.unknown;

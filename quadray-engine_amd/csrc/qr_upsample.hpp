@@ -76,12 +76,7 @@ void qr_upsample_kernel(const UpsampleP p)
 #pragma unroll
             for (int k = 0; k < CH; k++) c[k] = p.colour_lo[lo * CH + k];
             if ((flags & QR_UPSAMPLE_DEMODULATE) && id >= 0)
-            {
-                const f32x4 ha = h[2];
-                c[0] = c[0] / qr_atrous_alb(ha.x, p.alb_floor);
-                c[1] = c[1] / qr_atrous_alb(ha.y, p.alb_floor);
-                c[2] = c[2] / qr_atrous_alb(ha.z, p.alb_floor);
-            }
+                qr_albedo_divide(c, h[2], p.alb_floor);
             if (has_var) var = p.var_lo[lo];
             if (flags & QR_UPSAMPLE_PLANE)
             {

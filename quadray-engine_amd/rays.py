@@ -954,36 +954,44 @@ ATROUS_MAX_STEP = 64                                                            
 ATROUS_H = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16], dtype=np.float32)                       # the 1-D kernel: binary fractions
 
 
+def _stop_number(x, what):
+    """a stop of atrous_stops and upsample_stops as float32: ValueError for what float32 does not convert and for what is not a
+    finite float32 above 0"""
+    try:
+        v = np.float32(x)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a number") from None
+    if not (v > 0 and np.isfinite(v)):
+        raise ValueError(f"{what} must be a finite float32 above 0")
+    return v
+
+
+def _normal_power(normal_power):
+    """(is the normal stop on?, normal_sq): None is no stop, a power of two 1..128 is sent as its log2"""
+    if normal_power is None:
+        return False, 0
+    if isinstance(normal_power, bool) or not isinstance(normal_power, (int, np.integer)) or normal_power not in (1, 2, 4, 8, 16, 32, 64, 128):
+        raise ValueError("normal_power must be None or a power of two, 1..128")
+    return True, int(normal_power).bit_length() - 1
+
+
 def atrous_stops(normal_power=128, plane=None, luma=None, luma_eps=1e-6, demodulate=False, modulate=False, albedo_floor=1 / 256):
     """The host side of Scene.atrous' arguments: (flags, normal_sq, sigma_z, sigma_l2, eps_l, alb_floor) as qr_atrous_params
     takes them.  normal_power: None (no normal stop) or a power of two 1..128, sent as its log2; plane: sigma_z or None; luma:
     the tolerance in standard deviations or None, sigma_l2 = float32(luma) * float32(luma); a stop that is off sends 1.0.
     Raises ValueError for anything else."""
-    flags, normal_sq = 0, 0
-    if normal_power is not None:
-        if isinstance(normal_power, bool) or not isinstance(normal_power, (int, np.integer)) or normal_power not in (1, 2, 4, 8, 16, 32, 64, 128):
-            raise ValueError("normal_power must be None or a power of two, 1..128")
-        flags |= ATROUS_NORMAL
-        normal_sq = int(normal_power).bit_length() - 1
-
-    def positive(x, what):
-        try:
-            v = np.float32(x)
-        except (TypeError, ValueError):
-            raise ValueError(f"{what} must be a number") from None
-        if not (v > 0 and np.isfinite(v)):
-            raise ValueError(f"{what} must be a finite float32 above 0")
-        return v
+    normal, normal_sq = _normal_power(normal_power)
+    flags = ATROUS_NORMAL if normal else 0
     sigma_z = sigma_l2 = np.float32(1.0)
     if plane is not None:
-        sigma_z = positive(plane, "plane")
+        sigma_z = _stop_number(plane, "plane")
         flags |= ATROUS_PLANE
     if luma is not None:
-        t = positive(luma, "luma")
+        t = _stop_number(luma, "luma")
         with np.errstate(over="ignore", under="ignore"):
-            sigma_l2 = positive(t * t, "luma squared")
+            sigma_l2 = _stop_number(t * t, "luma squared")
         flags |= ATROUS_LUMA
-    eps_l, alb_floor = positive(luma_eps, "luma_eps"), positive(albedo_floor, "albedo_floor")
+    eps_l, alb_floor = _stop_number(luma_eps, "luma_eps"), _stop_number(albedo_floor, "albedo_floor")
     if demodulate:
         flags |= ATROUS_DEMODULATE
     if modulate:
@@ -1150,7 +1158,7 @@ def reproject_stops(normal_min=0.9, plane_max=None, min_weight=0.01, alpha_min=0
     rays, the frame's (hor_a[0], ver_a[0]); (0, 0) without FSAA.  Raises ValueError for what the call would refuse."""
     f = np.float32
 
-    def number(x, what):
+    def number(x, what):            # its own copy: any finite value, no bool or str; through _stop_number the call cost 0.5 us more
         try:
             v = f(x)
         except (TypeError, ValueError):
@@ -1423,11 +1431,11 @@ def upsample_stops(normal_power=128, plane=None, same_id=False, demodulate=False
     normal_power: None (no normal stop) or a power of two 1..128, sent as its log2; plane: sigma_z in world units or None (sent
     as 1.0); same_id: a tap must be the pixel's own surface and side; demodulate / modulate: divide the coarse colour by its
     guide's albedo / multiply the result by the full pixel's.  Validates like atrous_stops: ValueError for anything else."""
-    flags, normal_sq, _, _, _, alb_floor = atrous_stops(normal_power=normal_power, albedo_floor=albedo_floor)
-    flags = UPSAMPLE_NORMAL if flags & ATROUS_NORMAL else 0
-    sigma_z = np.float32(1.0)
+    normal, normal_sq = _normal_power(normal_power)
+    flags = UPSAMPLE_NORMAL if normal else 0
+    alb_floor, sigma_z = _stop_number(albedo_floor, "albedo_floor"), np.float32(1.0)
     if plane is not None:
-        sigma_z = atrous_stops(normal_power=None, plane=plane)[2]
+        sigma_z = _stop_number(plane, "plane")
         flags |= UPSAMPLE_PLANE
     for on, bit, what in ((same_id, UPSAMPLE_SAME_ID, "same_id"), (demodulate, UPSAMPLE_DEMODULATE, "demodulate"),
                           (modulate, UPSAMPLE_MODULATE, "modulate")):

@@ -1,5 +1,6 @@
 """The case table of tests/test_api_refusals.py and tools/record_api_refusals.py: for every entry point of the ray API
-(qr_trace_rays_async .. qr_layer_views_async, include/qrhip.h) a good call, the single bad arguments the function checks,
+(qr_trace_rays_async .. qr_layer_views_async and the image filters after them, qr_upsample_views_async ..
+qr_reproject_moving_async, include/qrhip.h) a good call, the single bad arguments the function checks,
 and every pair of them that can be applied together.  A case records (status, qr_last_error()); the pairs pin which refusal
 wins when two apply.
 
@@ -16,12 +17,14 @@ QR_OK, QR_ERR_DEVICE = 0, -4
 SLOT = 1 << 19              # bytes of device memory behind every good pointer
 NAN, INF = float("nan"), float("inf")
 VIEW_MAX_VIEWS, VIEW_MAX_DIM = 65535, 16384
-ATROUS_FLAGS = 31
+ATROUS_FLAGS = UPSAMPLE_FLAGS = 31
+REPROJ_FLAGS = 1
 
 
 # ------------------------------------------------------------------------------------------------------- arguments
 # An argument is (name, kind, good value, single bad values).  Kinds: "s" scene handle, "i" int, "q" int64, "f" float,
-# "u" uint32 flags, "p" device pointer, "o" uint64 *bytes_out, "a" qr_atrous_params *, "st" stream.
+# "u" uint32 flags, "p" device pointer, "o" uint64 *bytes_out, "a" a parameter block (its good value: the binding's structure
+# class by name and the good field values; an override "p.field" sets one field), "st" stream.
 
 def S():
     return ("s", "s", "query", [("null", None)])
@@ -104,6 +107,21 @@ def _fan(name, src, views, framed, gather):
               zero=[dict(n_views=0) if views else dict(n=0)], noquery=True, pt=gather)
 
 
+def PARAMS(cls, **good):
+    return ("p", "a", (cls, good), [])
+
+
+def _few_flags(allowed):
+    """the flags word of a parameter block, thinned: the lowest unknown bit and bit 31"""
+    low = min(b for b in range(32) if not (allowed >> b) & 1)
+    return [(f"p.bit{b}", {"p.flags": 1 << b}) for b in (low, 31)]
+
+
+def _floats(*fields_and_bad):
+    """[(tag, override)]: per field of the parameter block its single bad values"""
+    return [(f"{f}{b!r}", {"p." + f: b}) for f, *bad in fields_and_bad for b in bad]
+
+
 def _atrous():
     par = [("p.null", {"p": None}),
            ("step0", {"p.step": 0}), ("step65", {"p.step": 65}), ("channels2", {"p.channels": 2}), ("channels5", {"p.channels": 5}),
@@ -115,8 +133,54 @@ def _atrous():
     par += [("var_in.alone", {"var_in": "null", "var": 0}), ("var_out.alone", {"var_out": "null", "var": 0}),
             ("colour.inplace", {"colour_out": "=colour_in"}), ("var.inplace", {"var_out": "=var_in"})]
     return fn("qr_atrous_views_async",
-              [S(), P("colour_in", 4), P("var_in", 4, False), P("hits", 16), VIEWS(False), ("p", "a", "good", []),
+              [S(), P("colour_in", 4), P("var_in", 4, False), P("hits", 16), VIEWS(False),
+               PARAMS("AtrousParams", step=1, channels=3, normal_sq=0, flags=0, sigma_z=1.0, sigma_l2=1.0, eps_l=1.0, alb_floor=1.0),
                P("colour_out", 4), P("var_out", 4, False), STREAM], extra=par, zero=[dict(n_views=0)])
+
+
+def _upsample():
+    par = [("p.null", {"p": None}), ("factor0", {"p.factor": 0}), ("factor17", {"p.factor": 17}),
+           ("phase_x-1", {"p.phase_x": -1}), ("phase_x2", {"p.phase_x": 2}), ("phase_y-1", {"p.phase_y": -1}), ("phase_y2", {"p.phase_y": 2}),
+           # inside the lattice of factor 16, beyond the 9 x 13 frame
+           ("phase_x.beyond", {"p.factor": 16, "p.phase_x": WIDTH}), ("phase_y.beyond", {"p.factor": 16, "p.phase_y": HEIGHT}),
+           ("channels2", {"p.channels": 2}), ("channels5", {"p.channels": 5}),
+           ("normal_sq-1", {"p.normal_sq": -1}), ("normal_sq8", {"p.normal_sq": 8})]
+    par += _few_flags(UPSAMPLE_FLAGS) + _floats(("sigma_z", 0.0, NAN), ("alb_floor", 0.0, NAN))
+    # as in _atrous(): one of the pair alone is refused, both null is a good call
+    par += [("var_lo.alone", {"var_lo": "null", "var": 0}), ("var_out.alone", {"var_out": "null", "var": 0}),
+            ("colour_out.is_colour_lo", {"colour_out": "=colour_lo"}), ("var_out.is_var_lo", {"var_out": "=var_lo"}),
+            ("weight_out.is_hits", {"weight_out": "=hits"})]
+    return fn("qr_upsample_views_async",
+              [S(), P("colour_lo", 4), P("var_lo", 4, False), P("hits", 16), VIEWS(False),
+               PARAMS("UpsampleParams", factor=2, phase_x=0, phase_y=0, channels=3, normal_sq=0, flags=0, sigma_z=1.0, alb_floor=1.0),
+               P("colour_out", 4), P("var_out", 4, False), P("weight_out", 4, False), STREAM], extra=par, zero=[dict(n_views=0)])
+
+
+def _reproject(moving):
+    par = [("p.null", {"p": None}), ("channels2", {"p.channels": 2}), ("channels5", {"p.channels": 5})]
+    par += _few_flags(REPROJ_FLAGS)
+    par += [(f"reserved{i}", {"p.reserved": tuple(int(j == i) for j in range(3))}) for i in range(3)]
+    par += _floats(("off_x", NAN, INF), ("off_y", NAN), ("normal_min", NAN), ("plane_max", 0.0, NAN), ("alb_floor", 0.0, NAN),
+                   ("min_weight", -1.0, NAN), ("alpha_min", 1.5, NAN), ("alpha_mom_min", -0.5, NAN), ("max_len", 0.5, NAN),
+                   ("var_min_len", 0.5, NAN))
+    # the previous triple: all three is the good call and none a good first frame, so one or two alone are never applied
+    # together ("prev" is no argument)
+    trio = ("views_prev", "hits_prev", "hist_in")
+    par += [(f"{a}.missing", {a: "null", "prev": 0}) for a in trio]
+    par += [(f"{a}.alone", {**{b: "null" for b in trio if b != a}, "prev": 0}) for a in trio]
+    par.append(("hist_out.is_hist_in", {"hist_out": "=hist_in"}))
+    table = []
+    if moving:
+        table = [P("motion_dev", 16, False), I("n_motion", 3, -1, (1 << 30) + 1)]
+        # a table without rows and rows without a table: both together are the static call, a good one ("motion" is no argument)
+        par += [("n_motion.missing", {"n_motion": 0, "motion": 0}), ("motion_dev.missing", {"motion_dev": "null", "motion": 0})]
+    return fn("qr_reproject_moving_async" if moving else "qr_reproject_views_async",
+              [S(), P("colour_in", 4), P("hits", 16), P("var_in", 4, False), P("views_prev", 16, False), P("hits_prev", 16, False),
+               P("hist_in", 16, False)] + table + [VIEWS(False),
+               PARAMS("ReprojectParams", channels=3, flags=0, off_x=0.0, off_y=0.0, normal_min=0.5, plane_max=1.0, min_weight=0.5,
+                      alpha_min=0.5, alpha_mom_min=0.5, max_len=2.0, var_min_len=2.0, unknown=1.0, alb_floor=1.0),
+               P("hist_out", 16), P("colour_out", 4, False), P("var_out", 4, False), P("coords_out", 4, False), STREAM],
+              extra=par, zero=[dict(n_views=0)])
 
 
 FUNCTIONS = [
@@ -166,8 +230,12 @@ FUNCTIONS = [
                                P("hits", 16, False), FLAGS(1), STREAM], zero=[dict(n=0)], noquery=True),
     fn("qr_layer_views_async", [S(), P("views", 16), VIEWS(True), I("k", 4, 0, 65), P("count", 4), P("t", 4, False), P("id", 4, False),
                                 P("hits", 16, False), FLAGS(0), STREAM], zero=[dict(n_views=0)], noquery=True),
+    _upsample(), _reproject(False), _reproject(True),
 ]
-assert len({f["name"] for f in FUNCTIONS}) == len(FUNCTIONS) == 38
+assert len({f["name"] for f in FUNCTIONS}) == len(FUNCTIONS) == 41
+# The recordings under tests/golden, each with the functions it holds.  The three image filters that came after the first
+# recording have a file of their own, so that the first one stands as it was recorded, byte for byte.
+RECORDINGS = {"api_refusals.json": FUNCTIONS[:38], "api_refusals_filters.json": FUNCTIONS[38:]}
 
 
 # ----------------------------------------------------------------------------------------------------------- cases
@@ -251,9 +319,9 @@ class Rig:
                 if v is None:
                     argv.append(None)
                 else:
-                    p = dict(step=1, channels=3, normal_sq=0, flags=0, sigma_z=1.0, sigma_l2=1.0, eps_l=1.0, alb_floor=1.0)
-                    p.update({k[2:]: x for k, x in over.items() if k.startswith("p.")})
-                    argv.append(ctypes.byref(self.qr.AtrousParams(**p)))
+                    cls, fields = v
+                    fields = {**fields, **{k[2:]: x for k, x in over.items() if k.startswith("p.")}}
+                    argv.append(ctypes.byref(getattr(self.qr, cls)(**fields)))
             elif kind == "st":
                 argv.append(self.stream)
             else:
@@ -266,11 +334,11 @@ def open_rigs(qr, load_blob):
     return {fx: Rig(qr, load_blob(fx), fx == FIXTURES[0]) for fx in FIXTURES}
 
 
-def run(rigs, visit):
-    """Every case of every function on every fixture: visit(fixture, function, case id, (status, message)) right after each
+def run(rigs, visit, functions=FUNCTIONS):
+    """Every case of every one of `functions` on every fixture: visit(fixture, function, case id, (status, message)) right after each
     call.  A call that got as far as the device (QR_OK with elements, or a device error) ends the run at once."""
     for fixture, rig in rigs.items():
-        for f in FUNCTIONS:
+        for f in functions:
             for cid, over, zero in cases(f):
                 if over.get("s") in ("noquery", "pt") and len(rig.scenes) == 1:
                     continue                                     # those two scenes exist for the first fixture alone

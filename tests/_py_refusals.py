@@ -1,6 +1,7 @@
 """The case table of tests/test_py_refusals.py and tools/record_py_refusals.py: the Python-level twin of _api_refusals.py.
-For every public method of Scene from trace() through render_views_mean() and for the four accumulators (constructor,
-step, open_list, variance, clone) a good call, the single bad arguments that the method or the library behind it refuses,
+For every public method of Scene from trace() through render_views_mean(), for the four accumulators (constructor,
+step, open_list, variance, clone) and, after them, for the image filters upsample() and reproject() and for Temporal
+(constructor, step, clone) a good call, the single bad arguments that the method or the library behind it refuses,
 and every pair of them that can be applied together.  A case records (exception type name, str(exception)), or ("ok", the
 shapes and dtypes of what came back) for a call of no elements; the pairs pin which refusal wins when two apply.
 
@@ -16,6 +17,13 @@ SLOTS = WIDTH * HEIGHT                                          # the fixture ha
 NAN, INF = float("nan"), float("inf")
 OMIT = ("omit",)            # the argument is not passed at all
 OTHER = {"float32": "float64", "int32": "int64"}
+
+
+class Same:
+    """The very tensor that member `index` of the call's tuple argument `name` is."""
+
+    def __init__(self, name, index):
+        self.name, self.index = name, index
 
 
 # ------------------------------------------------------------------------------------------------------- arguments
@@ -246,6 +254,73 @@ FUNCTIONS = [
        zero=[("acc0", dict(acc="zero"))]),
     fn("PtAdaptiveViews.clone", ("acc", "PtAdaptiveViews", "clone"), [A("acc", "query")], zero=[("clone", {})]),
 ]
+
+
+# The image filters that came after the recording of the functions above: appended, so that the earlier cases keep their places.
+# The frame is the table's, 2 views of 9 x 13; upsample() at factor 2, phase (0, 0): a coarse frame of 5 x 7.
+FACTOR, W_LO, H_LO = 2, 5, 7
+FRAME = (N_VIEWS, HEIGHT, WIDTH)
+COLOUR, RECORDS, VARIANCE = T(F32, *FRAME, 3), T(F32, *FRAME, 12), T(F32, *FRAME)
+HISTORY, MOTION = T(F32, *FRAME, 8), T(F32, 3, 12)
+PREV = (VIEWS, RECORDS, HISTORY)
+# a colour of 4 channels is a good one: no `last` kind, as in _atrous_tensors()
+A_COLOUR = ("colour", COLOUR, kinds(COLOUR, rank=(HEIGHT, WIDTH, 3)) + [("channels5", T(F32, *FRAME, 5)), ("empty", T(F32, 0, HEIGHT, WIDTH, 3))])
+A_MOTION = kinds(MOTION, last=True) + [("rows0", T(F32, 0, 12))]
+REPROJ_STOPS = [A("normal_min", 0.9, NAN), A("plane_max", None, 0.0), A("min_weight", 0.01, -1), A("alpha_min", 0.05, 2),
+                A("alpha_mom_min", 0.2, -1), A("max_len", 32, 0), A("var_min_len", 4, 0.5), A("unknown", 1.0, "x"),
+                A("albedo_floor", 1 / 256, 0.0), A("off", (0, 0), 5, (NAN, 0), ("('x', 0)", ("x", 0))), A("nonsense", OMIT, 1)]
+
+
+def _upsample():
+    lo, var_lo = T(F32, N_VIEWS, H_LO, W_LO, 3), T(F32, N_VIEWS, H_LO, W_LO)
+    return fn("upsample", ("scene", "upsample"),
+              [A("s", "query"),
+               ("colour_lo", lo, kinds(lo, rank=(H_LO, W_LO, 3), rows=True) + [("channels5", T(F32, N_VIEWS, H_LO, W_LO, 5))]),
+               ("hits", RECORDS, kinds(RECORDS, rank=(HEIGHT, WIDTH, 12), last=True, rows=True) + [("empty", T(F32, 0, HEIGHT, WIDTH, 12))]),
+               A("factor", FACTOR, 0, 17, 1.5, True), A("phase", (0, 0), (2, 0), (0, -1), (0.5, 0), 1),
+               TA("variance", var_lo, rows=True), A("normal_power", 128, 3), A("plane", None, 0.0), A("same_id", False, 1),
+               A("demodulate", False, 1), A("modulate", False, "x"), A("albedo_floor", 1 / 256, 0.0),
+               TA("out", COLOUR, given=False, last=True, rows=True), TA("variance_out", VARIANCE, given=False, rows=True),
+               ("weight", False, kinds(VARIANCE, rows=True)), A("nonsense", OMIT, 1)],
+              # inside the lattice of factor 16 and beyond the 9 x 13 frame
+              extra=[("phase.beyond_x", dict(factor=16, phase=(WIDTH, 0))), ("phase.beyond_y", dict(factor=16, phase=(0, HEIGHT))),
+                     ("variance_out.alone", dict(variance=None, variance_out=VARIANCE))])
+
+
+def _prev_bad():
+    """prev with one member of each bad kind, of the wrong length and of no length at all"""
+    how = (("views_prev", dict(last=True, rows=True)), ("hits_prev", dict(last=True, rows=True)), ("history", dict(last=True, rows=True)))
+    out = [(f"{name}.{tag}", PREV[:i] + (bad,) + PREV[i + 1:]) for i, (name, kw) in enumerate(how) for tag, bad in kinds(PREV[i], **kw)]
+    return out + [("len2", PREV[:2]), ("len4", PREV + (HISTORY,)), ("5", 5)]
+
+
+def _reproject(moving):
+    """reproject() has no refusal for a variance_out without a variance (it hands out `unknown`), so there is no such case"""
+    motion = TA("motion", MOTION, last=True) if moving else ("motion", None, A_MOTION)
+    if moving:
+        motion = (motion[0], motion[1], A_MOTION)
+    return fn("reproject[motion]" if moving else "reproject", ("scene", "reproject"),
+              [A("s", "query"), A_COLOUR, TA("hits", RECORDS, last=True, rows=True), ("prev", PREV, _prev_bad()),
+               TA("variance", VARIANCE, rows=True), TA("out", HISTORY, given=False, last=True, rows=True),
+               ("colour_out", True, kinds(COLOUR, last=True, rows=True)), ("variance_out", True, kinds(VARIANCE, rows=True)),
+               ("coords", False, kinds(T(F32, *FRAME, 2), last=True, rows=True)), motion]
+              # with a table the stops are the same code: one of them, the unknown keyword and the pair of numbers
+              + (REPROJ_STOPS[:1] + REPROJ_STOPS[-2:] if moving else REPROJ_STOPS),
+              # it names prev, so that it meets no other prev
+              extra=[("out.is_history", dict(out=Same("prev", 2), prev=PREV))])
+
+
+FUNCTIONS += [
+    _upsample(), _reproject(False), _reproject(True),
+    fn("Temporal", ("new", "Temporal"),
+       [A("n_views", N_VIEWS, 0, 1.5, True), A("width", WIDTH, 0), A("height", HEIGHT, 0), A("channels", 3, 5)] + REPROJ_STOPS),
+    # the reprojection needs no ray-query list, so a step on the other scene is a good call: scene= takes what is no Scene
+    fn("Temporal.step", ("acc", "Temporal", "step"),
+       [A("acc", "query"), TA("colour", COLOUR, rank=(HEIGHT, WIDTH, 3), last=True, rows=True), TA("hits", RECORDS, last=True, rows=True),
+        TA("views", VIEWS, last=True, rows=True), TA("variance", VARIANCE, rows=True), ("motion", None, A_MOTION),
+        A("scene", None, 7, "query")]),
+    fn("Temporal.clone", ("acc", "Temporal", "clone"), [A("acc", "query")], zero=[("clone", {})]),
+]
 assert len({f["name"] for f in FUNCTIONS}) == len(FUNCTIONS)
 
 
@@ -270,8 +345,13 @@ def cases(f):
     return out
 
 
-def table_digest():
-    return hashlib.sha1("\n".join(f"{f['name']}:{i}" for f in FUNCTIONS for i, _, _ in cases(f)).encode()).hexdigest()[:16]
+def table_digest(functions):
+    return hashlib.sha1("\n".join(f"{f['name']}:{i}" for f in functions for i, _, _ in cases(f)).encode()).hexdigest()[:16]
+
+
+# The recordings under tests/golden, each with the functions it holds.  The image filters and Temporal, which came after the first
+# recording, have a file of their own, so that the first one stands as it was recorded, byte for byte.
+RECORDINGS = {"py_refusals.json": FUNCTIONS[:-6], "py_refusals_filters.json": FUNCTIONS[-6:]}
 
 
 # --------------------------------------------------------------------------------------------------------- calling
@@ -282,6 +362,8 @@ def describe(x):
         return repr(x)
     if isinstance(x, (tuple, list)):
         return "(" + ", ".join(describe(y) for y in x) + ")"
+    if hasattr(x, "history"):                                            # a Temporal
+        return f"Temporal(shape={list(x.shape)}, channels={x.channels}, frames={x.frames}, history={describe(x.history)})"
     if hasattr(x, "state"):                                              # an accumulator
         held = f", samples={x.samples}" if hasattr(x, "samples") else ""
         return f"{type(x).__name__}(state={describe(x.state)}{held})"
@@ -306,6 +388,7 @@ class Rig:
         self.accs["zero"] = {"PtViews": scn.pt_views(views0, WIDTH, HEIGHT), "PtRays": scn.pt_rays(0),
                              "PtAdaptive": scn.pt_adaptive(0, 1, 4, 0.01),
                              "PtAdaptiveViews": scn.pt_adaptive_views(views0, WIDTH, HEIGHT, 1, 4, 0.01)}
+        self.accs["query"]["Temporal"] = scn.temporal(N_VIEWS, WIDTH, HEIGHT)
 
     def close(self):
         for s in self.scenes.values():
@@ -313,6 +396,8 @@ class Rig:
 
     def make(self, name, v):
         """one tensor per argument name and description: no case writes one, and no two arguments of a call share one"""
+        if isinstance(v, tuple) and any(isinstance(x, T) for x in v):
+            return tuple(self.make(f"{name}[{i}]", x) for i, x in enumerate(v))
         if not isinstance(v, T):
             return v
         key = (name,) + v.key()
@@ -323,7 +408,7 @@ class Rig:
     def call(self, f, over):
         """(type name, text) of one call of f with the overrides applied to the good call"""
         kw = {name: self.make(name, over.get(name, good)) for name, good, _ in f["args"]}
-        kw = {k: v for k, v in kw.items() if v is not OMIT}
+        kw = {k: kw[v.name][v.index] if isinstance(v, Same) else v for k, v in kw.items() if v is not OMIT}
         target = f["target"]
         try:
             if target[0] == "scene":
@@ -340,10 +425,10 @@ class Rig:
             return (type(e).__name__, str(e))
 
 
-def run(rig, visit):
-    """Every case of every function: visit(function, case id, outcome) right after each call.  A call that returns although it
+def run(rig, visit, functions=FUNCTIONS):
+    """Every case of every one of `functions`: visit(function, case id, outcome) right after each call.  A call that returns although it
     has elements ends the run at once."""
-    for f in FUNCTIONS:
+    for f in functions:
         for cid, over, zero in cases(f):
             got = rig.call(f, over)
             if got[0] == "ok" and not zero:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host cost of a call through the Python binding: on demo01_160, at the sizes of tests/_py_refusals.py
-(64 rays, 2 views of 9x13, 4 directions), CALLS back-to-back calls of each method with one synchronise at the end, in
+(64 rays, 2 views of 9x13, 4 directions; the image filters on those 2 frames), CALLS back-to-back calls of each method with one synchronise at the end, in
 microseconds per call.  The kernels behind these sizes are tiny, so the figure is what the binding and the library's host
 glue cost.
 
@@ -58,6 +58,13 @@ def main():
     adaptive = scn.pt_adaptive(N_RAYS, 1, 4, 0.01)
     index, count = adaptive.open_list()
     adaptive_views = scn.pt_adaptive_views(views, WIDTH, HEIGHT, 1, 4, 0.01)
+    # the image filters: the frame's own hit records, a flat colour and variance, upsampling from factor 2, phase (0, 0)
+    records = scn.view_hits(views, WIDTH, HEIGHT)
+    colour = torch.full((N_VIEWS, HEIGHT, WIDTH, 3), 0.5, device=dev)
+    variance = torch.full((N_VIEWS, HEIGHT, WIDTH), 0.25, device=dev)
+    colour_lo, variance_lo = colour[:, ::2, ::2].contiguous(), variance[:, ::2, ::2].contiguous()
+    prev = (views.clone(), records.clone(), torch.zeros((N_VIEWS, HEIGHT, WIDTH, 8), device=dev))
+    temporal = scn.temporal(N_VIEWS, WIDTH, HEIGHT)
 
     calls = {
         "trace": lambda: scn.trace(rays),
@@ -69,6 +76,11 @@ def main():
         "PtRays.step": lambda: pt_rays.step(rays),
         "PtAdaptive.step[list]": lambda: adaptive.step(rays, index=index, count=count),
         "PtAdaptiveViews.step[mean,counts,open]": lambda: adaptive_views.step(mean=True, counts=True, open=True),
+        "atrous[variance]": lambda: scn.atrous(colour, records, variance),
+        "denoise[2 passes]": lambda: scn.denoise(colour, records, variance, passes=2),
+        "upsample[variance,weight]": lambda: scn.upsample(colour_lo, records, 2, variance=variance_lo, weight=True),
+        "reproject[prev]": lambda: scn.reproject(colour, records, prev=prev, variance=variance),
+        "Temporal.step": lambda: temporal.step(colour, records, views, variance),
     }
     out = {}
     for name, call in calls.items():
