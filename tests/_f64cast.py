@@ -5,7 +5,7 @@ Domain: the real surfaces of a snapshot (tests/_rayq.py real_surfaces) as synth.
 axis-aligned, untransformed, without clipper lists, any axis map whose three 2-bit fields are a permutation of 0, 1, 2 -- and
 nothing else of the snapshot: no element list, bounding volume, tile or grid.  A transform (has_trm), shift, a clipper list, a
 trnode, a malformed axis map or a record with a solver whose tag lies outside 0..8 is an error (Domain.__init__ asserts), never
-a skipped surface.
+a skipped surface.  tests/_f64xform.py carries the caster to transforms, trnodes and clipper lists (XDomain, a subclass).
 
 Geometry, with loc = org + t * dir - pos, in world axes (sci and scj are stored per world axis; the axis map matters to planes
 alone):

@@ -8,6 +8,11 @@ directions, the side a hit names, hit point and normal, "layer j + 1 is the next
 the interval" are the project's own contract, stated twice by the same hands.  The caster states it a third time, in float64,
 from the surfaces alone: no list, hierarchy, tile or grid.  CPU tests hold the oracle to it, GPU tests the kernels.
 
+Domain: untransformed, unclipped surfaces, as tests/_f64cast.py states and asserts (test_caster_refuses_scenes_outside_its_domain).
+Own transforms, surfaces under a trnode and clipper lists -- the fixture scenes -- are covered by tests/test_f64_fixtures.py with
+tests/_f64xform.py, a subclass of this caster that returns its arrays bit for bit on this domain.  Still outside both: a
+transform node under another one and has_trm == 1, which no scene of either file holds.
+
 Margins (tests/_f64cast.py, stated once there): position 1e-3 scene units, t 1e-4 relative, grazing |disc| < 1e-4 (B^2 + |AC|), apex
 1e-2.  Two roots count as apart when they differ by twice a root's margin (each carries its own error).  The crowd scenes are
 cast with grazing at 1e-5 and the noise rule at 4 ulps (the same place says why); the synthetic scenes as committed.
