@@ -1051,8 +1051,8 @@ int qr_reproject_views_async(qr_device_scene *scn, const float *colour_in, const
  *   - What this does NOT do: the history is the light the surface point received in the frames before.  Light that changes
  *     because a shadow caster or a light moved -- not the surface under the pixel -- lags by the history length, as it does
  *     for any temporal accumulation; deforming or re-scaled objects and surfaces whose record index changes between frames
- *     get NaN rows or wrong ids and start afresh.  Clamping the history to the neighbourhood's colours is a follow-up, not
- *     part of this call.
+ *     get NaN rows or wrong ids and start afresh.  Clamping the history to the neighbourhood's colours removes that lag:
+ *     qr_reproject_clamped_async below is this call with the clamp step.
  *   - QR_ERR_ARG: every refusal of qr_reproject_views_async, and: a null table with n_motion > 0, a table with n_motion == 0,
  *     n_motion outside 0..(1 << 30), a table that is not 16-byte aligned.  A refused call launches nothing.
  */
@@ -1062,6 +1062,71 @@ int qr_reproject_moving_async(qr_device_scene *scn, const float *colour_in, cons
                               const qr_motion *motion_dev, int n_motion,
                               int n_views, int width, int height, const qr_reproject_params *p,
                               float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream);
+
+/*
+ * Temporal reprojection with a CLAMP: qr_reproject_moving_async whose fetched history colour is held, per channel and before it
+ * is blended, to a box made of THIS frame's colours in the (2 * radius + 1)^2 neighbourhood of the pixel -- the neighbourhood's
+ * minimum and maximum (QR_CLAMP_MINMAX), or its mean +- gamma standard deviations (QR_CLAMP_VARIANCE, variance clipping).  Light
+ * that changed although the surface under the pixel did not (a shadow that moved on) no longer trails by the history length: the
+ * stale colour is pulled into what the frame shows around the pixel.  With QR_CLAMP_SHORTEN a pixel whose history had to be
+ * moved also has its history length cut to short_len, so that it converges at the fresh rate and hands out var_in again;
+ * moved_out reports how far each pixel's history was moved.
+ *   - Contract: that of qr_reproject_moving_async, every word (a null table with n_motion 0 is the static call), plus the clamp
+ *     step.  clamp == NULL with moved_out == NULL IS qr_reproject_moving_async: the same launch, the same bits.  clamp == NULL
+ *     with moved_out given is refused.  moved_out: float32 [n_views][height][width] in DEVICE memory, 4-byte aligned, or NULL.
+ *     qr_reproject_params is unchanged.
+ *   - The arithmetic is pinned like the rest: fp32, nothing fused, IEEE division, every parenthesis an order.  The text of
+ *     qr_reproject_moving_async with one step between taps and blend:
+ *       clamp    only where the pixel keeps history (min_weight < sw; id_p >= 0 is implied).  A neighbour q = (x + i, y + j),
+ *                -radius <= i, j <= radius, is VALID iff it lies inside the frame of the same view and id_q >= 0 (hits, this
+ *                frame's records); the pixel itself is valid, so the count n >= 1.  A neighbour's colour v[k] is its colour
+ *                after its own `read` step: with QR_REPROJ_DEMODULATE its first three channels divided by q's own albedo under
+ *                the rule of `read`; a fourth channel is never divided.  Order: rows j = -radius..radius ascending; within a
+ *                row i = -radius..radius ascending, the row's partials first, then the rows' partials folded in j order -- so
+ *                that a separable evaluation (a row pass, then a column pass) and a direct one give the same bits.
+ *                QR_CLAMP_VARIANCE: all sums start at +0.0.  Per row rn (an integer count), r1[k] += v[k], r2[k] += v[k] * v[k]
+ *                over the valid entries; then n += rn, t1[k] += r1[k], t2[k] += r2[k].  An invalid entry or an empty row may be
+ *                skipped or added as +0.0: the bits are the same, since no sum here can be -0.0 (each starts at +0.0, and
+ *                x + y is -0.0 only when both are).  nf = (float)n;  mu = t1[k] / nf;  v = t2[k] / nf - mu * mu;
+ *                v = 0 < v ? v : 0;  sd = sqrtf(v), correctly rounded;  w = gamma * sd;  lo = mu - w;  hi = mu + w.
+ *                QR_CLAMP_MINMAX: a row's lo starts at +inf and its hi at -inf;  lo = v < lo ? v : lo;  hi = hi < v ? v : hi
+ *                over the row's valid entries; the same two statements, with the row's lo and hi for v, fold the rows into a
+ *                box that also starts at (+inf, -inf).  The comparison form decides: a NaN colour never enters the box (every
+ *                comparison with it is false), and of two zeros the one met first stays (-0.0 < +0.0 is false).  A
+ *                neighbourhood whose valid colours are all NaN leaves the box at (+inf, -inf), which takes a finite history to
+ *                -inf: the frame itself shows no number there.
+ *                Per channel in order:  hc = sc[k] / sw;  h1 = hc < lo ? lo : hc;  h2 = hi < h1 ? hi : h1 (a NaN bound clamps
+ *                nothing);  d = fabsf(h2 - hc);  moved = d > moved ? d : moved, from moved = +0.0.
+ *       blend    as before with two changes.  With QR_CLAMP_SHORTEN and 0 < moved:  len = len < short_len ? len : short_len,
+ *                after the max_len cap and before a = 1.0f / len.  c[k] = h2 * (1.0f - ac) + c[k] * ac: h2 in place of
+ *                sc[k] / sw.  The moments m1 and m2 are blended UNCHANGED: after a clamp the variance they give is stale, and
+ *                that is what QR_CLAMP_SHORTEN is for -- a short_len below var_min_len makes var_min_len <= len fail, and
+ *                the pixel hands out the fresh rule's variance.
+ *       output   as before, and moved_out[p] = -1.0f where the entry is fresh, by any rule; otherwise moved.
+ *     quadray-engine_amd/rays.py reproject_pass(clamp=, moved=) is this text in numpy, and the GPU reproduces it bit for bit.
+ *   - Starting points, not tuned (rays.py clamp_stops): variance mode, radius 1, gamma 1.
+ *   - QR_ERR_ARG: every refusal of qr_reproject_moving_async, checked first and in its order (n_views == 0 returns QR_OK
+ *     there, before the block is looked at); then: moved_out without a block; both mode bits or neither; unknown flag bits; a
+ *     reserved word not 0; radius outside 1..QR_CLAMP_MAX_RADIUS; gamma negative or NaN (in both modes); short_len NaN, or below
+ *     1 with QR_CLAMP_SHORTEN; moved_out not 4-byte aligned.  A refused call launches nothing.
+ */
+#define QR_CLAMP_MINMAX    1u
+#define QR_CLAMP_VARIANCE  2u          /* exactly one of the two */
+#define QR_CLAMP_SHORTEN   4u
+#define QR_CLAMP_MAX_RADIUS 3
+typedef struct qr_clamp_params {       /* 32 bytes, 8 words */
+    uint32_t flags;           /* QR_CLAMP_MINMAX or QR_CLAMP_VARIANCE, and QR_CLAMP_SHORTEN */
+    int32_t  radius;          /* 1..QR_CLAMP_MAX_RADIUS */
+    float    gamma;           /* VARIANCE: the box's half-width in standard deviations; >= 0, not NaN, in both modes */
+    float    short_len;       /* SHORTEN: the history length of a pixel that was moved, >= 1; otherwise any value but NaN */
+    uint32_t reserved[4];     /* must be 0 */
+} qr_clamp_params;
+int qr_reproject_clamped_async(qr_device_scene *scn, const float *colour_in, const qr_hit *hits, const float *var_in,
+                               const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
+                               const qr_motion *motion_dev, int n_motion,
+                               int n_views, int width, int height, const qr_reproject_params *p, const qr_clamp_params *clamp,
+                               float *hist_out, float *colour_out, float *var_out, float *coords_out, float *moved_out,
+                               void *stream);
 
 /*
  * Guided upsampling: light computed on a COARSE lattice -- every factor-th pixel of the frame, 1/4 or 1/16 of the pixels --

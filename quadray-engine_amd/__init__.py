@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "qr_fan_rays_framed_async", "qr_fan_views_framed_async", "qr_fan_hits_framed_async",
     "qr_gather_rays_framed_async", "qr_gather_views_framed_async", "qr_gather_hits_framed_async",
     "qr_atrous_views_async", "qr_pt_adapt_views_variance_async", "qr_reproject_views_async", "qr_reproject_moving_async",
+    "qr_reproject_clamped_async",
     "qr_upsample_views_async",
     "qr_frame_register", "qr_frame_unregister",
     "qr_frame_hash", "qr_last_error", "qr_version", "qr_device_count", "qr_kernel_name", "qr_capture_index",
@@ -67,6 +68,10 @@ ATROUS_DEMODULATE = 8       # every colour read is divided by its own pixel's al
 ATROUS_MODULATE = 16        # the output is multiplied by the centre pixel's albedo
 ATROUS_MAX_STEP = 64        # QR_ATROUS_MAX_STEP: the widest tap spacing of one pass
 REPROJ_DEMODULATE = 1       # qr_reproject_views_async flag: this frame's colour is divided by its own pixel's albedo
+CLAMP_MINMAX = 1            # qr_reproject_clamped_async flags: the box is the neighbourhood's minimum and maximum,
+CLAMP_VARIANCE = 2          # or its mean +- gamma standard deviations (exactly one of the two);
+CLAMP_SHORTEN = 4           # a pixel whose history was moved has its history length cut to short_len
+CLAMP_MAX_RADIUS = 3        # QR_CLAMP_MAX_RADIUS: the widest neighbourhood of the box
 UPSAMPLE_NORMAL = 1         # qr_upsample_views_async flags: the normal stop,
 UPSAMPLE_PLANE = 2          # the plane-distance stop,
 UPSAMPLE_SAME_ID = 4        # a tap must be the pixel's own surface and side,
@@ -107,6 +112,12 @@ class ReprojectParams(ctypes.Structure):
                 ("alpha_min", ctypes.c_float), ("alpha_mom_min", ctypes.c_float), ("max_len", ctypes.c_float),
                 ("var_min_len", ctypes.c_float), ("unknown", ctypes.c_float), ("alb_floor", ctypes.c_float),
                 ("reserved", ctypes.c_uint32 * 3)]
+
+
+class ClampParams(ctypes.Structure):
+    """qr_clamp_params (include/qrhip.h), 32 bytes"""
+    _fields_ = [("flags", ctypes.c_uint32), ("radius", ctypes.c_int32), ("gamma", ctypes.c_float), ("short_len", ctypes.c_float),
+                ("reserved", ctypes.c_uint32 * 4)]
 
 
 class Motion(ctypes.Structure):
@@ -189,6 +200,8 @@ def lib():
     L.qr_atrous_views_async.argtypes = [vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(AtrousParams), vp, vp, vp]
     L.qr_reproject_views_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(ReprojectParams), vp, vp, vp, vp, vp]
     L.qr_reproject_moving_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.POINTER(ReprojectParams), vp, vp, vp, vp, vp]
+    L.qr_reproject_clamped_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.POINTER(ReprojectParams),
+                                             ctypes.POINTER(ClampParams), vp, vp, vp, vp, vp, vp]
     L.qr_upsample_views_async.argtypes = [vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(UpsampleParams), vp, vp, vp, vp]
     L.qr_snapshot_build_lists_c.argtypes =[vp, cu64, ctypes.POINTER(vp), ctypes.POINTER(cu64)]
     L.qr_free.argtypes = [vp]
@@ -877,17 +890,42 @@ class Scene:
             raise ValueError("motion must have 1..2^30 rows")
         return motion
 
-    def _reproject_launch(self, colour, hits, variance, prev, dims, stops, outs, stream, motion=None):
+    @staticmethod
+    def _clamp_arg(clamp, moved=None):
+        """the clamp block of reproject() / Temporal before any tensor is looked at: None, or a rays.clamp_stops dict, returned
+        as (flags, radius, gamma, short_len); ValueError for what the call would refuse and for a moved plane without a block"""
+        from . import rays
+        if clamp is not None:
+            return rays._clamp_params(clamp)
+        if not (moved is False or moved is None):
+            raise ValueError("moved needs a clamp")
+        return None
+
+    def _moved_arg(self, moved, dims):
+        """the moved plane of reproject(): False or None (None), True (a new tensor) or a float32 [N, H, W] tensor to fill"""
+        try:
+            return _wanted("moved", moved, "float32", dims[:3], self.device)
+        except QrError as e:
+            raise ValueError(str(e)) from None
+
+    def _reproject_launch(self, colour, hits, variance, prev, dims, stops, outs, stream, motion=None, clamp=None, moved=None):
         n, h, w, ch = dims
         p = ReprojectParams(ch, *(stops[k] for k in ("flags", "off_x", "off_y", "normal_min", "plane_max", "min_weight", "alpha_min",
                                                      "alpha_mom_min", "max_len", "var_min_len", "unknown", "alb_floor")))
+        if clamp is not None:
+            c = ClampParams(int(clamp[0]), int(clamp[1]), float(clamp[2]), float(clamp[3]))
+            table = (None, 0) if motion is None else (motion.data_ptr(), int(motion.shape[0]))
+            _check(lib().qr_reproject_clamped_async(self._h, _ptr(colour), _ptr(hits), _ptr(variance), _ptr(prev[0]), _ptr(prev[1]),
+                                                    _ptr(prev[2]), *table, n, w, h, ctypes.byref(p), ctypes.byref(c),
+                                                    *map(_ptr, outs), _ptr(moved), self._stream_ptr(stream)))
+            return
         fn, table = (lib().qr_reproject_views_async, ()) if motion is None else \
             (lib().qr_reproject_moving_async, (motion.data_ptr(), int(motion.shape[0])))
         _check(fn(self._h, _ptr(colour), _ptr(hits), _ptr(variance), _ptr(prev[0]), _ptr(prev[1]), _ptr(prev[2]), *table, n, w, h,
                   ctypes.byref(p), *map(_ptr, outs), self._stream_ptr(stream)))
 
     def reproject(self, colour, hits, prev=None, variance=None, out=None, colour_out=True, variance_out=True, coords=False,
-                  stream=None, motion=None, **params):
+                  stream=None, motion=None, clamp=None, moved=False, **params):
         """Temporal reprojection (qr_reproject_views_async; rays.reproject_pass is its arithmetic): blend this frame's noisy colour
         (float32 [N, H, W, 3|4]) into the history of the frame before, fetched where this frame's hits (view_hits of the current
         cameras) fall in the previous cameras and kept only on the same surface.  prev = (views_prev [N, 16], hits_prev, history
@@ -898,20 +936,28 @@ class Scene:
         them -- starting points, not tuned.  motion=None: static scenes under a moving camera.  motion (float32 [n, 12] on
         the scene's device, hierarchy_motion of the previous and the current node table; ValueError for anything else): an
         animated scene patched by hierarchy_apply -- every pixel's point and normal are taken to where its surface was in the
-        previous frame before the projection and the tap tests (qr_reproject_moving_async).  Returns (history, colour,
-        variance), with coords wanted (history, colour, variance, coords); what is not wanted is None.  Asynchronous on
-        `stream`."""
+        previous frame before the projection and the tap tests (qr_reproject_moving_async).  clamp: None, or a
+        rays.clamp_stops block (qr_reproject_clamped_async; a bad one is a ValueError): the fetched history colour is held to
+        the box of this frame's colours around the pixel before it is blended, so that light which changed on a surface that
+        did not move -- a shadow that went on -- does not trail.  moved (it needs a clamp): True for a new float32 [N, H, W]
+        tensor, or a tensor to fill, with how far each pixel's history was moved (-1: a fresh entry).  Returns (history,
+        colour, variance), with coords wanted (history, colour, variance, coords); what is not wanted is None; with moved, the
+        result is extended by that one tensor.  Asynchronous on `stream`."""
         motion = self._motion_arg(motion)
         stops = _stops("reproject_stops", QrError, **params)
+        clamp = self._clamp_arg(clamp, moved)
         dims, prev, outs = self._reproject_args(colour, hits, prev, variance, out, colour_out, variance_out, coords)
-        self._reproject_launch(colour, hits, variance, prev, dims, stops, outs, stream, motion)
-        return outs[:3] if outs[3] is None else outs
+        moved = self._moved_arg(moved, dims)
+        self._reproject_launch(colour, hits, variance, prev, dims, stops, outs, stream, motion, clamp, moved)
+        got = outs[:3] if outs[3] is None else outs
+        return got if moved is None else got + (moved,)
 
-    def temporal(self, n_views, width, height, channels=3, **params):
+    def temporal(self, n_views, width, height, channels=3, clamp=None, **params):
         """A temporal accumulator over frames of n_views moving cameras at width x height (rays.temporal is its chain): returns
         a Temporal whose step(colour, hits, views, variance=None, motion=None, scene=None) reprojects against the frame
-        before.  params as for reproject()."""
-        return Temporal(self, n_views, width, height, channels, **params)
+        before.  params as for reproject(); clamp: None or a rays.clamp_stops block applied on every step (ValueError for a
+        bad one)."""
+        return Temporal(self, n_views, width, height, channels, clamp=clamp, **params)
 
     def _fan_args(self, dirs, eps, reach, shape, mask):
         """(dirs as a contiguous float32 [K, 4] tensor, K, eps, reach, open, mask or None) of an occlusion-fan call whose
@@ -1521,14 +1567,17 @@ class Temporal:
     It owns two history tensors (float32 [N, H, W, 8]: c0 c1 c2 c3 m1 m2 len 0 per pixel) that it alternates between, and
     clones of the last step's hit records and cameras: a copy of 48 B per pixel and step, on the step's stream, so that the
     caller may reuse its own tensors at once.  `frames`: steps since the start or the last reset().  Static scenes under a
-    moving camera, and with step(motion=, scene=) scenes animated through hierarchy_apply; the stops (normal_min, plane_max,
+    moving camera, and with step(motion=, scene=) scenes animated through hierarchy_apply; with clamp= (a rays.clamp_stops
+    block) every step holds the history to the frame's neighbourhood colours (qr_reproject_clamped_async); the stops (normal_min, plane_max,
     ...: rays.reproject_stops) are starting points, not tuned."""
 
-    def __init__(self, scene, n_views, width, height, channels=3, **params):
+    def __init__(self, scene, n_views, width, height, channels=3, clamp=None, **params):
         if not (all(isinstance(x, int) and not isinstance(x, bool) and x >= 1 for x in (n_views, width, height)) and channels in (3, 4)):
             raise QrError("n_views, width and height must be positive integers and channels 3 or 4")
         self.scene, self.shape, self.channels = scene, (n_views, height, width), channels
         self.params = _stops("reproject_stops", QrError, **params)
+        self._clamp = Scene._clamp_arg(clamp)
+        self.clamp = None if clamp is None else dict(clamp)
         self._hist = [_new("float32", self.shape + (8,), scene.device) for _ in range(2)]
         self._cur, self._hits, self._views, self.frames = 0, None, None, 0
 
@@ -1540,7 +1589,7 @@ class Temporal:
     def clone(self):
         """A checkpoint: an accumulator with copies of the history, records and cameras (on the current stream) that continues
         independently."""
-        other = Temporal(self.scene, self.shape[0], self.shape[2], self.shape[1], self.channels)
+        other = Temporal(self.scene, self.shape[0], self.shape[2], self.shape[1], self.channels, clamp=self.clamp)
         other.params = dict(self.params)
         other._cur, other.frames = self._cur, self.frames
         if self._hits is not None:
@@ -1576,7 +1625,7 @@ class Temporal:
             raise QrError(f"this accumulation holds float32 colour [{n}, {h}, {w}, {self.channels}] and views [{n}, 16] on cuda:{scn.device}")
         prev = None if self._hits is None else (self._views, self._hits, self._hist[self._cur])
         dims, prev, outs = scn._reproject_args(colour, hits, prev, variance, self._hist[self._cur ^ 1], True, True, False)
-        scn._reproject_launch(colour, hits, variance, prev, dims, self.params, outs, stream, motion)
+        scn._reproject_launch(colour, hits, variance, prev, dims, self.params, outs, stream, motion, self._clamp)
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
             self._hits, self._views = hits.clone(), views.clone()
         self._cur ^= 1

@@ -647,13 +647,13 @@ extern "C" int qr_upsample_views_async(qr_device_scene *s, const float *colour_l
 
 /* ---- temporal reprojection (qr_reproject.hpp): one lane per pixel, 32 x 8 pixel tiles, blockIdx.z the view ---- */
 
-/* both entry points: every check of the static contract, then the table's, then the launch of the static kernel (no table) or
- * of the moving one */
+/* the three entry points: every check of the static contract, then the table's, then the clamp block's, then the launch of
+ * the static kernel (no table), of the moving one, or -- with a block -- of the clamp kernel with or without a table */
 static int reproject_launch(qr_device_scene *s, const float *colour_in, const qr_hit *hits, const float *var_in,
                             const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
                             const qr_motion *motion_dev, int n_motion,
-                            int n_views, int width, int height, const qr_reproject_params *p,
-                            float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream)
+                            int n_views, int width, int height, const qr_reproject_params *p, const qr_clamp_params *clamp,
+                            float *hist_out, float *colour_out, float *var_out, float *coords_out, float *moved_out, void *stream)
 {
     QR_TRY(need_scene(s));
     QR_TRY(need_params(p, "null reprojection parameters"));
@@ -681,8 +681,25 @@ static int reproject_launch(qr_device_scene *s, const float *colour_in, const qr
     QR_TRY(aligned_16_and_4({hits, views_prev, hits_prev, hist_in, hist_out}, "views, hits and history must be 16-byte aligned",
                             {colour_in, var_in, colour_out, var_out, coords_out}, "colour, variance and coords must be 4-byte aligned"));
     if (hist_in == hist_out) return qr_fail(QR_ERR_ARG, "the taps read neighbours' history: hist_out cannot be hist_in");
+    if (clamp == nullptr && moved_out != nullptr) return qr_fail(QR_ERR_ARG, "moved_out needs a clamp block");
+    if (clamp != nullptr)
+    {
+        const uint32_t mode = clamp->flags & (QR_CLAMP_MINMAX | QR_CLAMP_VARIANCE);
+        if (mode != QR_CLAMP_MINMAX && mode != QR_CLAMP_VARIANCE)
+            return qr_fail(QR_ERR_ARG, "a clamp is QR_CLAMP_MINMAX or QR_CLAMP_VARIANCE: exactly one of the two");
+        QR_TRY(flags_arg(clamp->flags, QR_CLAMP_MINMAX | QR_CLAMP_VARIANCE | QR_CLAMP_SHORTEN, "unknown clamp flags"));
+        if (clamp->reserved[0] != 0u || clamp->reserved[1] != 0u || clamp->reserved[2] != 0u || clamp->reserved[3] != 0u)
+            return qr_fail(QR_ERR_ARG, "the reserved words of the clamp block must be 0");
+        if (clamp->radius < 1 || clamp->radius > QR_CLAMP_MAX_RADIUS)
+            return qr_fail(QR_ERR_ARG, "radius must be 1.." + std::to_string(QR_CLAMP_MAX_RADIUS));
+        if (!(clamp->gamma >= 0.0f)) return qr_fail(QR_ERR_ARG, "gamma must be 0 or more");
+        if (clamp->short_len != clamp->short_len || ((clamp->flags & QR_CLAMP_SHORTEN) && !(clamp->short_len >= 1.0f)))
+            return qr_fail(QR_ERR_ARG, "short_len must not be NaN, and 1 or more with QR_CLAMP_SHORTEN");
+        QR_TRY(aligned_ptrs({moved_out}, 4, "moved_out must be 4-byte aligned"));
+    }
     HIP_TRY(hipSetDevice(s->device));
-    ReprojMovingP mp;
+    ReprojClampP cp;
+    ReprojMovingP &mp = cp.m;
     ReprojP &rp = mp.r;
     rp.colour_in = colour_in; rp.hits = (const f32x4 *)hits; rp.var_in = var_in;
     rp.views_prev = views_prev; rp.hits_prev = (const f32x4 *)hits_prev; rp.hist_in = (const f32x4 *)hist_in;
@@ -693,9 +710,18 @@ static int reproject_launch(qr_device_scene *s, const float *colour_in, const qr
     rp.max_len = p->max_len; rp.var_min_len = p->var_min_len; rp.unknown = p->unknown; rp.alb_floor = p->alb_floor;
     mp.motion = (const f32x4 *)motion_dev; mp.n_motion = (u32)n_motion;
     const dim3 grid = tile_grid(width, height, n_views, QR_REPROJ_TW, QR_REPROJ_TH), block(QR_REPROJ_BLOCK);
+    if (clamp != nullptr)
+    {
+        cp.cl.moved_out = moved_out; cp.cl.flags = clamp->flags; cp.cl.radius = clamp->radius;
+        cp.cl.gamma = clamp->gamma; cp.cl.short_len = clamp->short_len;
+    }
     pick_channels(p->channels, [&](auto ch) {
         constexpr int CH = decltype(ch)::value;
-        if (motion_dev == nullptr) hipLaunchKernelGGL(qr_reproject_kernel<CH>, grid, block, 0, (hipStream_t)stream, rp);
+        if (clamp != nullptr)
+            pick(motion_dev != nullptr, [&](auto moving) {
+                hipLaunchKernelGGL((qr_reproj_clamp_kernel<CH, decltype(moving)::value>), grid, block, 0, (hipStream_t)stream, cp);
+            });
+        else if (motion_dev == nullptr) hipLaunchKernelGGL(qr_reproject_kernel<CH>, grid, block, 0, (hipStream_t)stream, rp);
         else hipLaunchKernelGGL(qr_reproj_moving_kernel<CH>, grid, block, 0, (hipStream_t)stream, mp);
     });
     return launched();
@@ -707,7 +733,7 @@ extern "C" int qr_reproject_views_async(qr_device_scene *s, const float *colour_
                                         float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream)
 {
     return reproject_launch(s, colour_in, hits, var_in, views_prev, hits_prev, hist_in, nullptr, 0, n_views, width, height, p,
-                            hist_out, colour_out, var_out, coords_out, stream);
+                            nullptr, hist_out, colour_out, var_out, coords_out, nullptr, stream);
 }
 
 extern "C" int qr_reproject_moving_async(qr_device_scene *s, const float *colour_in, const qr_hit *hits, const float *var_in,
@@ -717,7 +743,19 @@ extern "C" int qr_reproject_moving_async(qr_device_scene *s, const float *colour
                                          float *hist_out, float *colour_out, float *var_out, float *coords_out, void *stream)
 {
     return reproject_launch(s, colour_in, hits, var_in, views_prev, hits_prev, hist_in, motion_dev, n_motion, n_views, width,
-                            height, p, hist_out, colour_out, var_out, coords_out, stream);
+                            height, p, nullptr, hist_out, colour_out, var_out, coords_out, nullptr, stream);
+}
+
+extern "C" int qr_reproject_clamped_async(qr_device_scene *s, const float *colour_in, const qr_hit *hits, const float *var_in,
+                                          const qr_view *views_prev, const qr_hit *hits_prev, const float *hist_in,
+                                          const qr_motion *motion_dev, int n_motion,
+                                          int n_views, int width, int height, const qr_reproject_params *p,
+                                          const qr_clamp_params *clamp,
+                                          float *hist_out, float *colour_out, float *var_out, float *coords_out, float *moved_out,
+                                          void *stream)
+{
+    return reproject_launch(s, colour_in, hits, var_in, views_prev, hits_prev, hist_in, motion_dev, n_motion, n_views, width,
+                            height, p, clamp, hist_out, colour_out, var_out, coords_out, moved_out, stream);
 }
 
 /* ---- open lists and indexed adaptive steps (qr_openlist.hpp, qr_kernel.hpp qr_pt_list_kernel): compaction on chip ---- */

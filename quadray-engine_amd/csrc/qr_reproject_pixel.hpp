@@ -12,11 +12,16 @@
  * normal.  The bound test s < n_motion guards the address: a lane beyond the table loads row 0 (a table has at least one) and
  * ignores it; a miss loads nothing.  Neighbouring lanes mostly share a surface, so a wave's row loads fall into one or a few
  * cache lines.
+ *
+ * CLAMP: the clamp step of qr_reproject_clamped_async between the taps and the blend.  In scope with it: the block `cl`
+ * (ReprojClampArgs) and the planes l_col, l_ok that qr_reproj_clamp_kernel staged and synchronised on BEFORE this text, so that the
+ * early return below comes after the kernel's one barrier.  The kernels without the step name the three as constants that the
+ * discarded statements never read.
  */
     const int tid = (int)threadIdx.x;
     const int W = p.width, H = p.height;
     const int x = (int)blockIdx.x * QR_REPROJ_TW + tid % QR_REPROJ_TW, y = (int)blockIdx.y * QR_REPROJ_TH + tid / QR_REPROJ_TW;
-    if (x >= W || y >= H) return;                           /* past the frame's edge: nothing in this kernel synchronises */
+    if (x >= W || y >= H) return;                           /* past the frame's edge: nothing after this point synchronises (CLAMP: the staging and its barrier lie before this text) */
     const int view = __builtin_amdgcn_readfirstlane((int)blockIdx.z);
     const size_t view_px = (size_t)view * (size_t)W * (size_t)H;
     const size_t px = view_px + (size_t)y * (size_t)W + (size_t)x;
@@ -36,6 +41,7 @@
 
     const float qnan = u2f(0x7FC00000u);
     float m1 = l, m2 = l2, len = 1.0f, var = v_fresh, cx = qnan, cy = qnan;
+    [[maybe_unused]] float moved = -1.0f;                   /* CLAMP: -1 where the entry is fresh, by any rule */
 
     if (p.views_prev != nullptr && id_p >= 0)
     {
@@ -131,12 +137,37 @@
                 }
                 if (p.min_weight < sw)
                 {
+                    float h2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if constexpr (CLAMP)
+                    {
+                        /* clamp: the fetched colour held to the box of this frame's colours around the pixel, out of LDS */
+                        float lo[CH], hi[CH];
+                        qr_clamp_box<CH>(l_col, l_ok, tid, cl.radius, cl.flags, cl.gamma, lo, hi);
+                        moved = 0.0f;
+#pragma unroll
+                        for (int k = 0; k < CH; k++)
+                        {
+                            const float hc = sc[k] / sw;
+                            const float h1 = hc < lo[k] ? lo[k] : hc;
+                            h2[k] = hi[k] < h1 ? hi[k] : h1;
+                            const float d = fabsf(h2[k] - hc);
+                            moved = d > moved ? d : moved;
+                        }
+                    }
                     len = sl / sw + 1.0f;
                     len = len < p.max_len ? len : p.max_len;
+                    if constexpr (CLAMP)
+                    {
+                        if ((cl.flags & QR_CLAMP_SHORTEN) && 0.0f < moved) len = len < cl.short_len ? len : cl.short_len;
+                    }
                     const float a = 1.0f / len;
                     const float ac = a > p.alpha_min ? a : p.alpha_min, am = a > p.alpha_mom_min ? a : p.alpha_mom_min;
 #pragma unroll
-                    for (int k = 0; k < CH; k++) c[k] = (sc[k] / sw) * (1.0f - ac) + c[k] * ac;
+                    for (int k = 0; k < CH; k++)
+                    {
+                        if constexpr (CLAMP) c[k] = h2[k] * (1.0f - ac) + c[k] * ac;
+                        else c[k] = (sc[k] / sw) * (1.0f - ac) + c[k] * ac;
+                    }
                     m1 = (s1 / sw) * (1.0f - am) + l * am;
                     m2 = (s2 / sw) * (1.0f - am) + l2 * am;
                     if (p.var_min_len <= len)
@@ -160,3 +191,7 @@
     }
     if (p.var_out != nullptr) p.var_out[px] = var;
     if (p.coords_out != nullptr) { p.coords_out[px * 2] = cx; p.coords_out[px * 2 + 1] = cy; }
+    if constexpr (CLAMP)
+    {
+        if (cl.moved_out != nullptr) cl.moved_out[px] = moved;
+    }

@@ -91,6 +91,12 @@ frames' node tables (move_hits is the step it adds: qr_reproject_moving_async) a
 
     table = torch.from_numpy(qr.hierarchy_motion(nodes_prev, nodes_cur, opts, n_srf)).cuda()
     colour, var = acc.step(noisy, hits, view, motion=table, scene=scene_of_this_frame)
+
+Light that changes on a surface that stands still (the shadow of an object that moved on) trails by the history length unless
+the fetched history is held to the colours this frame shows around the pixel (clamp_box is the box, clamp_stops the block:
+qr_reproject_clamped_async):
+
+    acc = scn.temporal(1, w, h, plane_max=0.02, clamp=clamp_stops("variance", radius=1, gamma=1.0, short_len=1))
 """
 import struct
 
@@ -1198,6 +1204,99 @@ def _reproject_params(p):
         raise ValueError("max_len and var_min_len must be 1 or more")
 
 
+CLAMP_MINMAX, CLAMP_VARIANCE, CLAMP_SHORTEN = 1, 2, 4                                               # QR_CLAMP_*
+CLAMP_MAX_RADIUS = 3                                                                                # QR_CLAMP_MAX_RADIUS
+
+
+def clamp_stops(mode="variance", radius=1, gamma=1.0, short_len=None):
+    """The clamp block of Scene.reproject(clamp=) / reproject_pass(clamp=) as a dict of qr_clamp_params' fields (flags, radius,
+    gamma, short_len; include/qrhip.h qr_reproject_clamped_async): the fetched history colour is held to a box of this frame's
+    colours in the (2 * radius + 1)^2 neighbourhood of the pixel.  mode: "variance" (the mean +- gamma standard deviations) or
+    "minmax" (the neighbourhood's minimum and maximum; gamma is not used).  radius 1..CLAMP_MAX_RADIUS.  short_len: None, or the
+    history length (>= 1) a pixel whose history was moved is cut to (CLAMP_SHORTEN).  Starting points, not tuned.  Raises
+    ValueError for what the call would refuse."""
+    modes = {"variance": CLAMP_VARIANCE, "minmax": CLAMP_MINMAX}
+    if not isinstance(mode, str) or mode not in modes:
+        raise ValueError('mode must be "variance" or "minmax"')
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)):
+        raise ValueError(f"radius must be an integer, 1..{CLAMP_MAX_RADIUS}")
+    for x, what in ((gamma, "gamma"), (short_len, "short_len")):
+        if x is not None and (isinstance(x, (bool, str)) or not isinstance(x, (int, float, np.integer, np.floating))):
+            raise ValueError(f"{what} must be a number")
+    c = dict(flags=modes[mode] | (0 if short_len is None else CLAMP_SHORTEN), radius=int(radius), gamma=np.float32(gamma),
+             short_len=np.float32(1.0 if short_len is None else short_len))
+    _clamp_params(c)
+    return c
+
+
+def _clamp_params(c):
+    """the refusals of qr_reproject_clamped_async that concern the clamp block alone, as ValueError; returns (flags, radius,
+    gamma, short_len)"""
+    try:
+        flags, radius, gamma, short_len = int(c["flags"]), int(c["radius"]), np.float32(c["gamma"]), np.float32(c["short_len"])
+        extra = set(c) - {"flags", "radius", "gamma", "short_len"}
+    except (TypeError, KeyError, ValueError):
+        raise ValueError("clamp must be None or a dict of flags, radius, gamma and short_len (clamp_stops)") from None
+    if extra:
+        raise ValueError("clamp must be None or a dict of flags, radius, gamma and short_len (clamp_stops)")
+    if flags & (CLAMP_MINMAX | CLAMP_VARIANCE) not in (CLAMP_MINMAX, CLAMP_VARIANCE):
+        raise ValueError("a clamp is CLAMP_MINMAX or CLAMP_VARIANCE: exactly one of the two")
+    if flags & ~(CLAMP_MINMAX | CLAMP_VARIANCE | CLAMP_SHORTEN):
+        raise ValueError("clamp flags must be of CLAMP_*")
+    if not 1 <= radius <= CLAMP_MAX_RADIUS:
+        raise ValueError(f"radius must be 1..{CLAMP_MAX_RADIUS}")
+    if not gamma >= 0:
+        raise ValueError("gamma must be 0 or more")
+    if np.isnan(short_len) or (flags & CLAMP_SHORTEN and not short_len >= 1):
+        raise ValueError("short_len must not be NaN, and 1 or more with CLAMP_SHORTEN")
+    return flags, radius, gamma, short_len
+
+
+def clamp_box(col, valid, flags, radius, gamma=1.0):
+    """The box of the clamp step (include/qrhip.h qr_reproject_clamped_async) in float32 numpy, operation for operation: col
+    float32 [N, H, W, C], the colours after the read step; valid bool [N, H, W] (id >= 0).  Returns (lo, hi [N, H, W, C], n
+    [N, H, W]): per pixel over the valid neighbours within `radius` inside the frame of the same view, a row's partials first (i
+    ascending), then the rows' folded (j ascending).  CLAMP_VARIANCE: mu -+ gamma * sqrt(max(0, t2 / n - mu * mu)); CLAMP_MINMAX:
+    lo = v if v < lo else lo, hi = v if hi < v else hi from (+inf, -inf), per row and again over the rows.  A pixel without a
+    valid neighbour (n = 0: it is a miss itself) gets what the statements give; the call never looks at it."""
+    f = np.float32
+    r = int(radius)
+    n, h, w, ch = col.shape
+    colp = np.zeros((n, h + 2 * r, w + 2 * r, ch), dtype=f)
+    colp[:, r:r + h, r:r + w] = col
+    okp = np.zeros((n, h + 2 * r, w + 2 * r), dtype=bool)
+    okp[:, r:r + h, r:r + w] = valid
+    cnt = np.zeros((n, h, w), dtype=np.int64)
+    with np.errstate(all="ignore"):
+        if flags & CLAMP_VARIANCE:
+            t1, t2 = np.zeros((n, h, w, ch), dtype=f), np.zeros((n, h, w, ch), dtype=f)
+            for j in range(-r, r + 1):
+                r1, r2 = np.zeros((n, h, w, ch), dtype=f), np.zeros((n, h, w, ch), dtype=f)
+                for i in range(-r, r + 1):
+                    v, ok = colp[:, r + j:r + j + h, r + i:r + i + w], okp[:, r + j:r + j + h, r + i:r + i + w]
+                    cnt += ok
+                    r1 = np.where(ok[..., None], r1 + v, r1)
+                    r2 = np.where(ok[..., None], r2 + v * v, r2)
+                t1, t2 = t1 + r1, t2 + r2
+            nf = cnt.astype(f)[..., None]
+            mu = t1 / nf
+            var = t2 / nf - mu * mu
+            var = np.where(0 < var, var, f(0.0))
+            wd = f(gamma) * np.sqrt(var)
+            return (mu - wd).astype(f), (mu + wd).astype(f), cnt
+        lo, hi = np.full((n, h, w, ch), np.inf, dtype=f), np.full((n, h, w, ch), -np.inf, dtype=f)
+        for j in range(-r, r + 1):
+            rl, rh = np.full((n, h, w, ch), np.inf, dtype=f), np.full((n, h, w, ch), -np.inf, dtype=f)
+            for i in range(-r, r + 1):
+                v, ok = colp[:, r + j:r + j + h, r + i:r + i + w], okp[:, r + j:r + j + h, r + i:r + i + w]
+                cnt += ok
+                rl = np.where(ok[..., None] & (v < rl), v, rl)
+                rh = np.where(ok[..., None] & (rh < v), v, rh)
+            lo = np.where(rl < lo, rl, lo)
+            hi = np.where(hi < rh, rh, hi)
+        return lo, hi, cnt
+
+
 def _cross(a, b):
     return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
                      a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
@@ -1254,7 +1353,7 @@ def move_hits(hits, motion):
 
 def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, off_y=0.0, normal_min=0.9, plane_max=np.inf,
                    min_weight=0.01, alpha_min=0.05, alpha_mom_min=0.2, max_len=32.0, var_min_len=4.0, unknown=1.0, alb_floor=1 / 256,
-                   taps=None, motion=None):
+                   taps=None, motion=None, clamp=None, moved=False):
     """The specification of one qr_reproject_views_async call in float32 numpy, every operation elementwise so that it rounds
     once: colour float32 [N, H, W, C] (or [H, W, C]; C 3 or 4), hits float32 [N, H, W, 12] (this frame's qr_hit records),
     variance float32 [N, H, W] or None, prev = None (the first frame) or (views_prev [N, 16], hits_prev [N, H, W, 12], history
@@ -1275,10 +1374,20 @@ def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, o
     the pixel are replaced by pos' and nrm' in the projection, the normal test and the plane test -- everything else, the
     colour's demodulation by the pixel's own albedo included, is the static text; a surface beyond the table is fresh.
 
+    clamp: None, or a clamp block (clamp_stops; qr_reproject_clamped_async): where the pixel keeps history the fetched colour hc =
+    sc / sw is held per channel to the box (lo, hi) of clamp_box over this frame's demodulated colours, h2 = min(max(hc, lo), hi)
+    in the header's comparison form, which takes its place in the blend; with CLAMP_SHORTEN a pixel whose history was moved
+    (0 < max |h2 - hc|) has its length cut to short_len after the max_len cap.  moved=True (it needs a clamp) appends a fifth array
+    [N, H, W]: -1 where the entry is fresh, else that maximum.  With the defaults the 4-tuple and the bits are the unclamped call's.
+
     taps: if a list is given, the four (taken bool [N, H, W], b float32 [N, H, W]) pairs are appended to it in tap order."""
     f = np.float32
     if motion is not None:
         motion = _motion_table(motion)
+    if clamp is not None:
+        clamp = _clamp_params(clamp)
+    elif moved:
+        raise ValueError("moved needs a clamp")
     colour, variance, hits = _atrous_args(colour, variance, hits)
     single = colour.ndim == 3
     if single:
@@ -1318,6 +1427,7 @@ def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, o
         hist = np.zeros((n, h, w, 8), dtype=f)
         hist[..., 0:4], hist[..., 4], hist[..., 5], hist[..., 6] = col, lum, lum2, one
         coords = np.full((n, h, w, 2), REPROJ_NAN, dtype=f)
+        mv_out = np.full((n, h, w), -1.0, dtype=f)
         if prev is not None:
             xy, front = project_to_view(views_prev[:, None, None, :], pos, (par["off_x"], par["off_y"]))
             front = front & listed
@@ -1349,12 +1459,26 @@ def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, o
                     s2 = np.where(ok, s2 + hq[..., 5] * b, s2)
                     sl = np.where(ok, sl + hq[..., 6] * b, sl)
             keep = window & (par["min_weight"] < sw)
+            hc = sc / sw[..., None]
             ln = sl / sw + one
             ln = np.where(ln < par["max_len"], ln, par["max_len"])
+            if clamp is not None:
+                cflags, radius, gamma, short_len = clamp
+                lo, hi, _ = clamp_box(col, hit, cflags, radius, gamma)
+                h1 = np.where(hc < lo, lo, hc)
+                h2 = np.where(hi < h1, hi, h1)
+                d = np.abs(h2 - hc)
+                mv = np.zeros((n, h, w), dtype=f)
+                for k in range(ch):
+                    mv = np.where(d[..., k] > mv, d[..., k], mv)
+                if cflags & CLAMP_SHORTEN:
+                    ln = np.where(0 < mv, np.where(ln < short_len, ln, short_len), ln)
+                hc = h2
+                mv_out = np.where(keep, mv, f(-1.0)).astype(f)
             al = one / ln
             ac = np.where(al > par["alpha_min"], al, par["alpha_min"])
             am = np.where(al > par["alpha_mom_min"], al, par["alpha_mom_min"])
-            cb = (sc / sw[..., None]) * (one - ac)[..., None] + col * ac[..., None]
+            cb = hc * (one - ac)[..., None] + col * ac[..., None]
             m1 = (s1 / sw) * (one - am) + lum * am
             m2 = (s2 / sw) * (one - am) + lum2 * am
             v = m2 - m1 * m1
@@ -1363,20 +1487,25 @@ def reproject_pass(colour, hits, variance=None, prev=None, flags=0, off_x=0.0, o
             hist[..., 4], hist[..., 5], hist[..., 6] = np.where(keep, m1, lum), np.where(keep, m2, lum2), np.where(keep, ln, one)
             var = np.where(keep & (par["var_min_len"] <= ln), v, var).astype(f)
     out = (hist, hist[..., 0:ch].copy(), var, coords)
+    if moved:
+        out = out + (mv_out,)
     return tuple(o[0] for o in out) if single else out
 
 
 class Temporal:
     """The accumulator's chain in numpy (temporal(); what Scene.temporal's Temporal computes on the GPU): two history arrays it
     alternates between and copies of the last hit records and cameras.  step(colour, hits, views, variance=None, motion=None) is
-    one reproject_pass against the frame before -- the first frame after the start or a reset() has none -- and returns (colour,
+    one reproject_pass (with the accumulator's clamp block, if it was given one) against the frame before -- the first frame after the start or a reset() has none -- and returns (colour,
     variance); history / length are the entry array [N, H, W, 8] and its length plane after the last step (None before the
     first); clone() continues independently."""
 
-    def __init__(self, n_views, width, height, channels=3, **params):
+    def __init__(self, n_views, width, height, channels=3, clamp=None, **params):
         if channels not in (3, 4) or min(int(n_views), int(width), int(height)) < 1:
             raise ValueError("channels must be 3 or 4 and n_views, width, height at least 1")
         self.shape, self.channels, self.params = (int(n_views), int(height), int(width)), int(channels), reproject_stops(**params)
+        if clamp is not None:
+            _clamp_params(clamp)
+        self.clamp = None if clamp is None else dict(clamp)
         self._hist = [np.zeros(self.shape + (8,), dtype=np.float32) for _ in range(2)]
         self._cur, self._hits, self._views, self.frames = 0, None, None, 0
 
@@ -1386,7 +1515,7 @@ class Temporal:
         self.frames = 0
 
     def clone(self):
-        other = Temporal(self.shape[0], self.shape[2], self.shape[1], self.channels)
+        other = Temporal(self.shape[0], self.shape[2], self.shape[1], self.channels, clamp=self.clamp)
         other.params = dict(self.params)
         other._hist = [a.copy() for a in self._hist]
         other._cur, other.frames = self._cur, self.frames
@@ -1407,7 +1536,7 @@ class Temporal:
         if colour.shape != self.shape + (self.channels,) or views.shape != (self.shape[0], 16) or views.dtype != np.float32:
             raise ValueError(f"this accumulation holds float32 colour {list(self.shape) + [self.channels]} and views [{self.shape[0]}, 16]")
         prev = None if self._hits is None else (self._views, self._hits, self._hist[self._cur])
-        hist, col, var, _ = reproject_pass(colour, hits, variance, prev, motion=motion, **self.params)
+        hist, col, var, _ = reproject_pass(colour, hits, variance, prev, motion=motion, clamp=self.clamp, **self.params)
         self._cur ^= 1
         self._hist[self._cur][...] = hist
         self._hits, self._views = hits.copy(), views.copy()
@@ -1415,9 +1544,10 @@ class Temporal:
         return col, var
 
 
-def temporal(n_views, width, height, channels=3, **params):
-    """The specification of Scene.temporal: a Temporal accumulator in numpy.  params: as reproject_stops takes them."""
-    return Temporal(n_views, width, height, channels, **params)
+def temporal(n_views, width, height, channels=3, clamp=None, **params):
+    """The specification of Scene.temporal: a Temporal accumulator in numpy.  params: as reproject_stops takes them; clamp: None
+    or a clamp_stops block applied on every step."""
+    return Temporal(n_views, width, height, channels, clamp=clamp, **params)
 
 
 # ---- guided upsampling (include/qrhip.h qr_upsample_views_async; Scene.upsample) ----

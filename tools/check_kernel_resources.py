@@ -33,6 +33,8 @@ Reads the code-object metadata of the -save-temps assembly (qr_device-hip-amdgcn
   * a temporal reprojection instance qr_reproject_kernel<CH> spills a vector register, has a private segment, uses any LDS or
     more than 96 (3 channels) / 80 (4 channels) VGPRs, or an instance with a motion table qr_reproj_moving_kernel<CH> more than
     those plus its 12 row words (108 / 92);
+  * a clamped reprojection instance qr_reproj_clamp_kernel<CH, MOVING> spills a vector register, has a private segment, uses more
+    than 96 (3 channels) / 80 (4 channels) VGPRs or more LDS than its 38 x 14 staged entries of CH + 1 planes (8512 B / 10640 B);
   * a guided upsampling instance qr_upsample_kernel<CH> spills a vector register, has a private segment, uses more than 64 VGPRs
     or more LDS than its 34 x 10 staged entries (14960 B / 16320 B);
   * the hand-written cull loop's fixed scalar registers s[88:99] (qr_walk.hpp cull_run) are missing from its clobber list.
@@ -140,6 +142,14 @@ LIMITS = {
     # (108 / 92; the build's assembly has 80 / 74)
     "23qr_reproj_moving_kernelILi3EE": (108, 0, 0),
     "23qr_reproj_moving_kernelILi4EE": (92, 0, 0),
+    # temporal reprojection with a clamp (qr_reproject.hpp qr_reproj_clamp_kernel<CH, MOVING>): the same pixel behind a staged
+    # neighbourhood and a box out of LDS: nothing spilled, no private segment, no more LDS than (32 + 6) x (8 + 6) staged entries
+    # of CH + 1 planes, and the registers of the build's assembly rounded up to the next occupancy step: 84 / 82 VGPRs -> 96
+    # (5 waves per SIMD), 78 / 76 -> 80 (6 waves), the steps of the instances without the clamp
+    "22qr_reproj_clamp_kernelILi3ELb0EE": (96, 0, 0),
+    "22qr_reproj_clamp_kernelILi3ELb1EE": (96, 0, 0),
+    "22qr_reproj_clamp_kernelILi4ELb0EE": (80, 0, 0),
+    "22qr_reproj_clamp_kernelILi4ELb1EE": (80, 0, 0),
     # guided upsampling (qr_upsample.hpp qr_upsample_kernel<CH>): four taps out of LDS per full pixel, bound by the bytes it moves:
     # nothing spilled, no private segment, and the registers of the build's assembly (35 / 36 VGPRs) rounded up to the next
     # occupancy step, 64 (8 waves per SIMD, all a SIMD holds); no more LDS than 34 x 10 staged entries of 8 + CH planes, of which
@@ -150,6 +160,8 @@ LIMITS = {
 LDS_LIMITS = {"16qr_atrous_kernelILi3EE": 20736, "16qr_atrous_kernelILi4EE": 22464,
               "19qr_reproject_kernelILi3EE": 0, "19qr_reproject_kernelILi4EE": 0,
               "23qr_reproj_moving_kernelILi3EE": 0, "23qr_reproj_moving_kernelILi4EE": 0,
+              "22qr_reproj_clamp_kernelILi3ELb0EE": 8512, "22qr_reproj_clamp_kernelILi3ELb1EE": 8512,
+              "22qr_reproj_clamp_kernelILi4ELb0EE": 10640, "22qr_reproj_clamp_kernelILi4ELb1EE": 10640,
               "18qr_upsample_kernelILi3EE": 14960, "18qr_upsample_kernelILi4EE": 16320}
 KEYS = ("name", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")
 

@@ -34,8 +34,47 @@ STEPS = {"demo2_1080p": 300, "test18_1080p": 300}   # s
 FRAMES, SAMPLES, PASSES, REPS, FRAC = 8, 2, 5, 20, 0.37
 
 
-def torch_reproject(torch, col, hits, var, prev, p):
-    """rays.reproject_pass in torch operations on the device: one rounding per operation, the taps as gathers by index"""
+def torch_clamp_box(torch, c, hit, flags, r, gamma):
+    """rays.clamp_box in torch operations on the device: the box of every pixel from zero-padded shifted views, a row's partials
+    first, then the rows folded"""
+    n, h, w, ch = c.shape
+    cp = torch.zeros((n, h + 2 * r, w + 2 * r, ch), dtype=c.dtype, device=c.device)
+    cp[:, r:r + h, r:r + w] = c
+    okp = torch.zeros((n, h + 2 * r, w + 2 * r), dtype=torch.bool, device=c.device)
+    okp[:, r:r + h, r:r + w] = hit
+    inf = torch.full_like(c, float("inf"))
+    if flags & 2:
+        t1, t2, cnt = torch.zeros_like(c), torch.zeros_like(c), torch.zeros((n, h, w), dtype=torch.int32, device=c.device)
+    else:
+        lo, hi = inf.clone(), -inf
+    for j in range(2 * r + 1):
+        if flags & 2:
+            r1, r2 = torch.zeros_like(c), torch.zeros_like(c)
+        else:
+            rl, rh = inf.clone(), -inf
+        for i in range(2 * r + 1):
+            v, ok = cp[:, j:j + h, i:i + w], okp[:, j:j + h, i:i + w]
+            if flags & 2:
+                cnt = cnt + ok
+                r1, r2 = torch.where(ok[..., None], r1 + v, r1), torch.where(ok[..., None], r2 + v * v, r2)
+            else:
+                rl, rh = torch.where(ok[..., None] & (v < rl), v, rl), torch.where(ok[..., None] & (rh < v), v, rh)
+        if flags & 2:
+            t1, t2 = t1 + r1, t2 + r2
+        else:
+            lo, hi = torch.where(rl < lo, rl, lo), torch.where(hi < rh, rh, hi)
+    if flags & 2:
+        nf = cnt.float()[..., None]
+        mu = t1 / nf
+        vv = t2 / nf - mu * mu
+        wd = torch.sqrt(torch.where(vv > 0, vv, torch.zeros_like(vv))) * gamma
+        lo, hi = mu - wd, mu + wd
+    return lo, hi
+
+
+def torch_reproject(torch, col, hits, var, prev, p, clamp=None):
+    """rays.reproject_pass in torch operations on the device: one rounding per operation, the taps as gathers by index.  clamp: a
+    rays.clamp_stops block; the result is then extended by the moved plane"""
     n, h, w, ch = col.shape
     f = lambda k: float(p[k])
     ids = hits.view(torch.int32)[..., 7]
@@ -53,7 +92,7 @@ def torch_reproject(torch, col, hits, var, prev, p):
     hist = torch.zeros((n, h, w, 8), dtype=col.dtype, device=col.device)
     hist[..., 0:4], hist[..., 4], hist[..., 5], hist[..., 6] = c, lum, lum2, one
     if prev is None:
-        return hist, hist[..., 0:ch].contiguous(), vfresh.clone()
+        return (hist, hist[..., 0:ch].contiguous(), vfresh.clone()) + (() if clamp is None else (-one,))
     views, hq_all, gq_all = prev
     v = views[:, None, None, :]
     org, d, hor, ver = v[..., 0:3], v[..., 4:7], v[..., 8:11], v[..., 12:15]
@@ -91,10 +130,23 @@ def torch_reproject(torch, col, hits, var, prev, p):
     keep = window & (sw > f("min_weight"))
     ln = sl / sw + one
     ln = torch.where(ln < f("max_len"), ln, torch.full_like(ln, f("max_len")))
+    hc, mv = sc / sw[..., None], None
+    if clamp is not None:
+        lo, hi = torch_clamp_box(torch, c, hit, int(clamp["flags"]), int(clamp["radius"]), float(clamp["gamma"]))
+        h1 = torch.where(hc < lo, lo, hc)
+        h2 = torch.where(hi < h1, hi, h1)
+        d = (h2 - hc).abs()
+        mv = zero.clone()
+        for k in range(ch):
+            mv = torch.where(d[..., k] > mv, d[..., k], mv)
+        if int(clamp["flags"]) & 4:
+            short = torch.full_like(ln, float(clamp["short_len"]))
+            ln = torch.where(mv > 0, torch.where(ln < short, ln, short), ln)
+        hc = h2
     al = one / ln
     ac = torch.where(al > f("alpha_min"), al, torch.full_like(al, f("alpha_min")))
     am = torch.where(al > f("alpha_mom_min"), al, torch.full_like(al, f("alpha_mom_min")))
-    cb = (sc / sw[..., None]) * (one - ac)[..., None] + c * ac[..., None]
+    cb = hc * (one - ac)[..., None] + c * ac[..., None]
     m1 = (s1 / sw) * (one - am) + lum * am
     m2 = (s2 / sw) * (one - am) + lum2 * am
     vv = m2 - m1 * m1
@@ -102,7 +154,7 @@ def torch_reproject(torch, col, hits, var, prev, p):
     hist[..., 0:ch] = torch.where(keep[..., None], cb[..., 0:ch], c[..., 0:ch])
     hist[..., 4], hist[..., 5], hist[..., 6] = torch.where(keep, m1, lum), torch.where(keep, m2, lum2), torch.where(keep, ln, one)
     vout = torch.where(keep & (ln >= f("var_min_len")), vv, vfresh)
-    return hist, hist[..., 0:ch].contiguous(), vout
+    return (hist, hist[..., 0:ch].contiguous(), vout) + (() if clamp is None else (torch.where(keep, mv, -one),))
 
 
 def launch_bytes(n, h, w, ch, variance):
