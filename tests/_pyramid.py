@@ -16,6 +16,7 @@ import importlib
 import numpy as np
 
 import _noshad
+import _rayq
 from _noshad import _need
 
 HALF = 8.0
@@ -123,6 +124,157 @@ def scene(query=None, width=160, height=96, depth=2):
     return _SCENES[key]
 
 
+# ------------------------------------------------------------------------------------------------ the room
+#
+# A room open to the front and the right (160 x 96, its camera inside), for tests/test_pyramid_vote.py: four clipped, untransformed
+# planes of all three normal axes, every one with a pos far from its rectangle, a rectangle twice to four times as long as wide
+# and min != -max, so that no two of the numbers the vote reads (comps, org, inv, the local hit) can be exchanged unnoticed:
+#
+#   plane    axes   k  world rectangle                 pos              min .. max about pos (in-plane)     extent
+#   floor    0x024  2  x 10..22, y 5..11 at z = 2      (30, 4, 2)       (-20, 1) .. (-8, 7)                 12 x 6
+#   back     0x418  1  x 10..22, z 2..5  at y = 11     (-15, 11, 1)     (25, 1) .. (37, 4)                  12 x 3
+#   left     0x009  0  y 5..11,  z 2..5  at x = 10     (10, -9, 8)      (14, -6) .. (20, -3)                6 x 3
+#   ceiling  0x421  2  x 10..22, y 5..11 at z = 5      (3.5, 25, 5)     (6.5, -20) .. (18.5, -14)           12 x 6
+#
+# The axis words are the engine's own, read from plane records of the committed fixtures (ROOM_AXES); 0x418 and 0x421 carry the
+# plane sign (bit 10): their outer sides face the room.  Floor and back wall meet along y = 11, z = 2, which the camera sees.
+# Every plane has a shadow chain of its own with 17 of the 18 solver surfaces of the room (and the trnode's cell; each plane
+# leaves another one out): spheres and cylinders, one metal, one plainly transparent, a sphere and a cylinder under a rotated
+# trnode, a sphere over the shared edge and one over the floor's centre lines.  Every plane's light list -- one list, both sides, so that it has one user -- names all
+# three lights: a hit on the side that faces away from a light still reads the pyramid record and stays out of the vote.
+#   light 0  low over the floor's front left corner          light 1  0.6 behind the left wall, on its inner side
+#   light 2  central, under the ceiling
+
+ROOM_AXES = dict(floor=("lists/test15_160", 6, 0x024), back=("lists/test16_160", 14, 0x418),
+                 left=("lists/test16_160", 3, 0x009), ceiling=("lists/test16_160", 6, 0x421))
+ROOM_PLANES = dict(floor=((30.0, 4.0, 2.0), (-20.0, 1.0, 0.0), (-8.0, 7.0, 0.0), 0x1B),
+                   back=((-15.0, 11.0, 1.0), (25.0, 0.0, 1.0), (37.0, 0.0, 4.0), 0x2D),
+                   left=((10.0, -9.0, 8.0), (0.0, 14.0, -6.0), (0.0, 20.0, -3.0), 0x36),
+                   ceiling=((3.5, 25.0, 5.0), (6.5, -20.0, 0.0), (18.5, -14.0, 0.0), 0x1B))
+ROOM_LIGHTS = [(10.6, 5.6, 2.5), (9.4, 8.5, 3.4), (16.0, 8.0, 4.6)]
+ROOM_EYE, ROOM_TARGET = (20.5, 6.0, 4.0), (12.5, 10.5, 2.6)
+ROOM_BOX = ((10.0, 5.0, 2.0), (22.0, 11.0, 5.0))
+
+_ROOMS = {}
+
+
+def axis_word(plane):
+    """the axis word of the fixture's plane record ROOM_AXES names"""
+    import _crowd
+    name, rec, want = ROOM_AXES[plane]
+    r = _crowd._snapshot(name)[0][rec]
+    _need(int(r.view(np.int32)[37]) == 0 and int(r[15]) == 0 and int(r[19]) == 0 and int(r[23]) == want, "fixture record", name, rec, hex(int(r[23])))
+    return int(r[23])
+
+
+def set_camera(fr, eye, target, width, pov=1.0, up=(0.0, 0.0, 1.0)):
+    """qr_frame words of a camera at `eye` looking at `target`, the image plane one unit wide at distance pov (synth._frame)"""
+    eye, target = np.asarray(eye, dtype=np.float64), np.asarray(target, dtype=np.float64)
+    fwd = target - eye; fwd /= np.linalg.norm(fwd)
+    right = np.cross(fwd, up); right /= np.linalg.norm(right)
+    down = np.cross(fwd, right)
+    hor, ver = right / width, down / width
+    h = int(fr[32])
+    ff = fr.view(np.float32)
+    ff[1:4] = fwd * pov - hor * (0.5 * width) - ver * (0.5 * h)
+    ff[4:7], ff[7:10], ff[24], ff[25:28] = hor, ver, pov, eye
+    return fr
+
+
+def room(query=None, levels=None, width=160, height=96, depth=0):
+    """the room's snapshot; query as in scene(); levels: QR_PGRID_LEVELS of the compile, handed back as info["env"] (the value
+    an environment variable has: a string) for _noshad.env -- the snapshot itself does not depend on it.  Returns (blob,
+    dict(planes={name: surface}, node=, members=, transparent=, metal=, shadow_chain=[all occluders],
+    shadow_chains={plane: [its own chain]}, env={...}))"""
+    key = (None if query is None else tuple(query), width, height, depth)
+    env = {} if levels is None else {"QR_PGRID_LEVELS": str(int(levels))}
+    if key in _ROOMS:
+        blob, info = _ROOMS[key]
+        return blob, dict(info, env=env)
+    S = _synth()
+    b = S._Builder()
+    PLAIN = S.P_DIFFUSE | S.P_OPAQUE | S.P_NORMAL
+    METAL = S.P_SPECULAR | S.P_DIFFUSE | S.P_REFLECT | S.P_OPAQUE | S.P_NORMAL | S.P_METAL
+    CLEAR = (S.P_DIFFUSE | S.P_NORMAL | S.P_TRANSP) & ~(S.P_REFRACT | S.P_OPAQUE)
+    cols = [b.material(c) for c in (0xD04040, 0x40B040, 0x4060D0, 0xD0C040, 0xB050C0, 0x40C0C0)]
+    inner = b.material(0x808080)
+    metal_m = b.material(0xC0C0C0, l_dff=0.5, l_spc=0.5, l_pow=512, c_rfl=0.5, ext_2=81.0)
+    clear = b.material(0xA0D0F0, c_trn=0.6, c_rfr=1.0)
+    planes = {}
+    for name, col in (("floor", 0x909090), ("back", 0xA09080), ("left", 0x8090A0), ("ceiling", 0xB0B0B0)):
+        pos, mn, mx, mm = ROOM_PLANES[name]
+        planes[name] = b.surface(S.TAG_PLANE, (1, 1, 1), pos, mn=mn, mx=mx, minmax_t=mm, mats=(b.material(col), inner), props=(PLAIN, PLAIN))
+        b.srf[planes[name]][23] = axis_word(name)                               # the engine's own word, from the fixture ROOM_AXES names
+
+    def sphere(p, r, mats=None, props=(PLAIN, PLAIN)):
+        return b.surface(S.TAG_SPHERE, (2, 3, 3), p, sci=(1, 1, 1, np.float32(r) * np.float32(r)), mn=(-r, -r, -r), mx=(r, r, r),
+                         mats=mats or (cols[len(b.srf) % 6], inner), props=props)
+
+    def cylinder(p, r, h):
+        return b.surface(S.TAG_CYLINDER, (2, 3, 3), p, sci=(1, 1, 0, np.float32(r) * np.float32(r)), mn=(-r, -r, 0.0), mx=(r, r, h),
+                         minmax_t=0x24, mats=(cols[len(b.srf) % 6], inner), props=(PLAIN, PLAIN))
+
+    occ = [sphere((16.0, 8.0, 3.0), 0.6),                                       # over the floor's (and the ceiling's) centre lines
+           sphere((14.0, 10.6, 2.5), 0.35),                                     # over the edge floor / back wall
+           sphere((11.5, 6.3, 2.3), 0.25), cylinder((12.2, 5.8, 2.0), 0.2, 1.0), sphere((11.0, 7.5, 2.35), 0.3),   # near the low light
+           sphere((17.0, 10.3, 3.5), 0.4), cylinder((20.5, 10.2, 2.0), 0.3, 1.8),                                    # before the back wall
+           sphere((10.7, 9.0, 3.6), 0.35), cylinder((11.2, 10.2, 2.0), 0.25, 2.2),                                   # before the left wall
+           sphere((15.0, 7.5, 4.4), 0.4), sphere((19.0, 8.5, 4.5), 0.3),                                             # under the ceiling
+           cylinder((16.5, 6.0, 2.0), 0.3, 1.2), sphere((21.3, 6.0, 2.4), 0.4), sphere((13.5, 9.3, 2.4), 0.4),
+           sphere((18.5, 7.0, 2.9), 0.5, mats=(metal_m, inner), props=(METAL, PLAIN)),
+           sphere((13.0, 7.0, 3.2), 0.5, mats=(clear, clear), props=(CLEAR, CLEAR))]
+    metal, transparent = occ[-2], occ[-1]
+    M = _rot(0.7, 0.35)
+    node = b.surface(-1, (0, 0, 0), (19.5, 9.5, 3.2), real=False)
+    members = [sphere((0.5, 0.1, 0.2), 0.35), cylinder((-0.4, -0.2, -0.4), 0.25, 0.9)]
+    for i in [node] + members:
+        r = b.srf[i]
+        f = r.view(np.float32)
+        f[12:15], f[16:19], f[20:23] = M[0], M[1], M[2]
+        r[15], r[19] = 2, 1
+        r[39] = np.uint32(node)
+    occ += members
+
+    def chain(surfaces):
+        cells = [b.cell(s) for s in surfaces]
+        for k, s in enumerate(surfaces):
+            if s == node:
+                last = [j for j in range(k + 1, len(surfaces)) if surfaces[j] in members]
+                _need(last and last == list(range(k + 1, k + 1 + len(last))), "the node's members must follow it")
+                b.elm[cells[k]][1] = cells[last[-1]]
+        return b.link(cells)
+
+    shadow_chain = occ[:-2] + [node] + members
+    # a plane's chain leaves one occluder out, each plane another: a lane that walked another plane's list would lose it
+    left_out = dict(floor=occ[5], back=occ[13], left=occ[12], ceiling=occ[11])
+    shadow_chains = {planes[name]: [x for x in shadow_chain if x != left_out[name]] for name in planes}
+    glist = chain(list(planes.values()) + shadow_chain)
+    lights = [b.light(p, c, a_lnr=0.05) for p, c in zip(ROOM_LIGHTS, ((1.0, 0.95, 0.9), (0.7, 0.8, 0.6), (0.6, 0.7, 0.8)))]
+    lpos32 = [b.lgt[l].view(np.float32)[1:4].copy() for l in lights]
+    shared = {}
+    for i, r in enumerate(b.srf):
+        if not 0 <= int(r[37].view(np.int32)) < S.TAG_BOUND:
+            continue
+        if i in planes.values():                                                # one list of all three lights for both sides
+            sh = chain(shadow_chains[i])
+            ll = b.link([b.cell(l, data=sh) for l in lights])
+            r[44:48] = np.array([ll, glist, ll, glist], dtype=np.int32).view(np.uint32)
+            continue
+        at = r
+        if i in members:
+            at = r.copy()
+            at.view(np.float32)[0:3] = b.srf[node].view(np.float32)[0:3] + M.T @ r.view(np.float32)[0:3]
+        lo, li = S._light_lists(b, shared, lpos32, at, [(l, glist) for l in lights])
+        r[44:48] = np.array([lo, glist, li, glist], dtype=np.int32).view(np.uint32)
+    fr = set_camera(S._frame(width, height, depth, 0, False, 6.0, glist), ROOM_EYE, ROOM_TARGET, width)
+    if query is not None:
+        fr[38] = np.uint32(chain(list(query)) & 0xFFFFFFFF) if len(query) else np.uint32(0xFFFFFFFF)
+    blob = S._serialise(b, fr, glist)
+    _ROOMS[key] = (blob, dict(planes=planes, node=node, members=members, transparent=transparent, metal=metal, shadow_chain=shadow_chain,
+                               shadow_chains=shadow_chains))
+    return blob, dict(_ROOMS[key][1], env=env)
+
+
 # ------------------------------------------------------------------------------------------------ the image reader
 
 class Pyramid:
@@ -130,6 +282,7 @@ class Pyramid:
 
     def __init__(self, im, word):
         g = word & ~31
+        self.rec = g
         _need(word & 31 == LISTF_GRID, "shadow word flags", hex(word))
         self.table, self.nx, self.ny, comps = (im.word(g + 4 * k) for k in range(4))
         f = im.img[g // 4 + 4:g // 4 + 8].view(np.float32)
@@ -211,3 +364,282 @@ def check_pyramid(im, p, head):
                 elif op & OPF_CACHED:
                     _need(cur is not None and int(s[srf, S_TRNODE]) == cur, "node", (l, i, j), "surface", srf, "without its trnode's cell")
     return n_lists
+
+
+# ------------------------------------------------------------------------------------------------ the vote, stated in numpy
+#
+# The packet arm of the light loop (csrc/qr_shade.hpp) for ONE wave, in float32 numpy.  Used to build inputs and to count the
+# lanes a wrong vote would light (witnesses); no GPU output is ever compared with it.
+
+MUTANTS = ("no_climb", "one_short", "swap_ab", "swap_inv", "world", "first_record", "levels4", "no_clamp_hi")
+BORDER = 1e-3                                                   # of a level-0 cell: a witness lane keeps this far from every cell border
+
+
+def level_off(n, l):
+    """QR_PGRID_LEVEL_OFF: words in front of level l of a pyramid with n x n cells at level 0"""
+    return 4 * (n * n - (n >> l) ** 2) // 3
+
+
+def cell_index(p, loc, mutant=None):
+    """(ia, ib) of local hits float32 [m, 3]: floor((loc[a] - org_a) * inv_a) in single float32 operations, clamped to [0, n)"""
+    f = np.float32
+    a, b = (p.comp[1], p.comp[0]) if mutant == "swap_ab" else p.comp
+    inv = (p.inv[1], p.inv[0]) if mutant == "swap_inv" else p.inv
+    x = np.asarray(loc, dtype=f)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ia = np.floor((x[:, a] - f(p.org[0])) * f(inv[0])).astype(np.int64)
+        ib = np.floor((x[:, b] - f(p.org[1])) * f(inv[1])).astype(np.int64)
+    n = p.nx
+    ia = np.where(ia < 0, 0, ia if mutant == "no_clamp_hi" else np.where(ia >= n, n - 1, ia))
+    ib = np.where(ib < 0, 0, np.where(ib >= n, n - 1, ib))
+    return ia, ib
+
+
+def vote(p, loc, sends, mutant=None, world=None):
+    """the node (l, i, j) the wave walks for record p and its word (None: the mutant reads past the table): loc float32 [64, 3]
+    local hits, sends bool [64] the lanes that vote (at least one); world: the world hits the mutant `world` takes for local"""
+    sends = np.asarray(sends, dtype=bool)
+    ia, ib = cell_index(p, world if mutant == "world" else loc, mutant)
+    lead = int(np.nonzero(sends)[0][0])
+    ia0, ib0 = int(ia[lead]), int(ib[lead])
+    n, L = (16, 4) if mutant == "levels4" else (p.nx, p.L)
+    d = ((ia ^ ia0) | (ib ^ ib0))[sends]
+    l = 0
+    while l < L and ((d >> l) != 0).any():
+        l += 1
+    if mutant == "no_climb":
+        l = 0
+    if mutant == "one_short" and l > 0:
+        l -= 1
+    i, j = ia0 >> l, ib0 >> l
+    index = level_off(n, l) + j * (n >> l) + i
+    word = p.im.word(p.table + 4 * index) if index <= level_off(p.nx, p.L) else None
+    return (l, i, j), word
+
+
+def sends_to(rec, lpos):
+    """the kernel's lm of hit records [m, 12] for a light at lpos: 0 < dot(light - hit, nrm) in its operation order"""
+    f = np.float32
+    pos, nrm = rec[:, 0:3].astype(f), rec[:, 4:7].astype(f)
+    x1, x2, x3 = ((f(lpos[k]) - pos[:, k]) * nrm[:, k] for k in range(3))
+    return (x1 + x2) + x3 > 0
+
+
+def vote_wave(im, pyr, rec, lights, inside=None, mutant=None):
+    """the vote of one wave over the lanes that lie on pyramid planes: rec float32 [64, 12] the oracle's hit records of its
+    primary rays (a lane past the end: inside False), lights [n, 3] the lights' positions.  Returns {light: (voting lanes bool [64], word per lane int64 [64] (-1: the
+    mutant read past the table), level per lane)}; a lane's record is that of its (surface, side, light)."""
+    f = np.float32
+    ids = rec.view(np.int32)[:, 7]
+    ok = (ids >= 0) if inside is None else (ids >= 0) & inside
+    spos = im.s.view(np.float32)[:, 0:3]
+    out = {}
+    for lgt in range(len(lights)):
+        lm = sends_to(rec, lights[lgt])
+        recs = [pyr.get((int(i) >> 1, int(i) & 1, lgt)) if o else None for i, o in zip(ids, ok)]
+        todo = np.array([r is not None for r in recs]) & lm
+        votes, words, levels = todo.copy(), np.zeros(64, dtype=np.int64), np.full(64, -1)
+        first = None
+        while todo.any():
+            p = recs[int(np.nonzero(todo)[0][0])][0]
+            mine = todo & np.array([r is not None and r[0].rec == p.rec for r in recs])
+            todo &= ~mine
+            loc = rec[:, 0:3].astype(f) - spos[np.maximum(ids, 0) >> 1].astype(f)
+            (l, _, _), w = vote(p, loc, mine, mutant, world=rec[:, 0:3])
+            if mutant == "first_record":
+                first = (l, w) if first is None else first
+                l, w = first
+            words[mine], levels[mine] = (-1 if w is None else w), l
+        out[lgt] = (votes, words, levels)
+    return out
+
+
+def border_clear(p, loc, hi_rim=False):
+    """bool [m]: the local hits that keep BORDER of a level-0 cell away from every cell border (float64); hi_rim: those that lie
+    ON the rim line max[a] instead (unclamped ia == n, which is exact arithmetic on the room's numbers) and keep BORDER in b"""
+    a, b = p.comp
+    x = np.asarray(loc, dtype=np.float64)
+    ua, ub = (x[:, a] - p.org[0]) * p.inv[0], (x[:, b] - p.org[1]) * p.inv[1]
+    cb = (np.abs(ub - np.round(ub)) >= BORDER) & (ub > 0) & (ub < p.nx)
+    return cb & (cell_index(p, loc, "no_clamp_hi")[0] >= p.nx) if hi_rim else cb & (np.abs(ua - np.round(ua)) >= BORDER)
+
+
+# ------------------------------------------------------------------------------------------------ constructed waves
+#
+# A wave of the packet instance is an 8 x 8 footprint of a camera (lane = 8 (y & 7) + (x & 7), csrc/qr_kernel.hpp pixel_of_view),
+# so its 64 hits are placed through the camera: a view that looks straight at a plane from `off` in front of it, hor and ver
+# along the plane's two in-plane axes, puts pixel (x, y) on the plane at (u0 + x pitch_a, v0 + y pitch_b) -- every hit at t = 1,
+# an exact lattice where the numbers are binary fractions, as the room's are.
+
+def plane_geometry(blob, srf):
+    """(k, a, b, pos, lo, hi, towards the room) of a room plane: grid_plane's components, min / max about pos"""
+    s, f = _rayq.surfaces(blob)
+    k = (int(s[srf, 23]) >> 4) & 3
+    a, b = (1 if k == 0 else 0), (1 if k == 2 else 2)
+    pos = f[srf, 0:3].astype(np.float64)
+    lo, hi = f[srf, 4:7].astype(np.float64), f[srf, 8:11].astype(np.float64)
+    mid = 0.5 * (np.asarray(ROOM_BOX[0]) + np.asarray(ROOM_BOX[1]))
+    return k, a, b, pos, lo, hi, (1.0 if mid[k] > pos[k] else -1.0)
+
+
+def lattice_view(blob, srf, n, per_cell, cell0, shift, w, h, off=0.3):
+    """a qr_view whose pixel (x, y) hits plane `srf` at level-0 cell coordinates cell0 + (shift + (x, y)) / per_cell of a pyramid
+    with n x n cells: per_cell pixels a cell; shift 0.5: pixel centres, no hit on a border; shift 0: a pixel column on every
+    border.  The eye stands `off` in front of the window's centre."""
+    k, a, b, pos, lo, hi, sgn = plane_geometry(blob, srf)
+    ca, cb = (hi[a] - lo[a]) / n, (hi[b] - lo[b]) / n
+    pa, pb = ca / per_cell, cb / per_cell
+    u0 = pos[a] + lo[a] + cell0[0] * ca + shift[0] * pa
+    v0 = pos[b] + lo[b] + cell0[1] * cb + shift[1] * pb
+    eye = np.zeros(3); eye[a], eye[b], eye[k] = u0 + 0.5 * (w - 1) * pa, v0 + 0.5 * (h - 1) * pb, pos[k] + sgn * off
+    d = np.zeros(3); d[a], d[b], d[k] = u0 - eye[a], v0 - eye[b], -sgn * off
+    v = np.zeros(16, dtype=np.float32)
+    v[0:3], v[4:7], v[7] = eye, d, np.finfo(np.float32).max
+    v[8 + a], v[12 + b] = pa, pb
+    return v
+
+
+def vote_views(blob, info, levels):
+    """[(label, view, width, height)]: the lattices of every room plane for a pyramid of `levels`.  Per plane
+      cells     8 pixels a cell, pixel centres: every footprint inside ONE level-0 cell
+      straddle  the same, moved by half a footprint both ways: every footprint over a border in a, in b and over a corner of four
+                cells -- at the window's middle the borders of the top bit
+      rows      moved in b alone: footprints over a border in b only (cells that differ in one bit of ib and not of ia)
+      borders   shift 0: a pixel column and row on every cell border and on the rectangle's rim, the corners included
+      wide      2 pixels a cell: a footprint spans 4 x 4 cells, from an odd cell: the ancestor is two or three levels up
+      rim       1 pixel a cell from two cells outside the rectangle: lanes that miss next to lanes in the rim cells (levels 4)
+      corner    the four corners at shift 0, from one cell outside: hits on the rim lines themselves -- on max[a], max[b] the
+                unclamped index is n, the upper clamp; on min[a], min[b] it is floor(0) = 0, and a hit below is clipped away,
+                so the lower clamp is unreachable -- and misses beyond them (levels 4)
+    Windows hold at most 8 x 8 cells (64 x 64 pixels) around the rectangle's middle, where all bits of a cell index flip."""
+    n = 1 << levels
+    c = min(n, 8)
+    lo = (n - c) // 2
+    out = []
+    for name, srf in info["planes"].items():
+        px = 8 * c
+        out.append((f"{name} cells", lattice_view(blob, srf, n, 8, (lo, lo), (0.5, 0.5), px, px), px, px))
+        out.append((f"{name} straddle", lattice_view(blob, srf, n, 8, (lo, lo), (-3.5, -3.5), px + 8, px + 8), px + 8, px + 8))
+        out.append((f"{name} rows", lattice_view(blob, srf, n, 8, (lo, lo), (0.5, -3.5), px, px + 8), px, px + 8))
+        out.append((f"{name} borders", lattice_view(blob, srf, n, 8, (lo, lo), (0.0, 0.0), px + 8, px + 8), px + 8, px + 8))
+        if n >= 8:
+            out.append((f"{name} wide", lattice_view(blob, srf, n, 2, (lo + 1, lo + 1), (0.5, 0.5), 16, 16), 16, 16))
+        if levels == 4:
+            out.append((f"{name} rim", lattice_view(blob, srf, n, 1, (-2, -2), (0.5, 0.5), 24, 24), 24, 24))
+            for i, j in ((-1, -1), (n - 4, -1), (-1, n - 4), (n - 4, n - 4)):
+                out.append((f"{name} corner {i} {j}", lattice_view(blob, srf, n, 8, (i, j), (0.0, 0.0), 40, 40), 40, 40))
+    return out
+
+
+def room_views(rays_mod, blob, w, h):
+    """[(label, view)] of the four cameras of the room: its own; one grazing the back wall; one looking along the edge floor /
+    back wall, whose footprints hold lanes of both planes; one outside the floor's front right corner"""
+    return [("own", rays_mod.view_of(blob)),
+            ("grazing", rays_mod.look_at((21.5, 10.7, 3.5), (11.0, 10.95, 3.0), (0, 0, 1), 50.0, w, h)),
+            ("edge", rays_mod.look_at((21.5, 10.3, 2.6), (10.5, 11.0, 2.0), (0, 0, 1), 40.0, w, h)),
+            ("corner", rays_mod.look_at((23.5, 3.5, 3.8), (20.0, 7.0, 2.0), (0, 0, 1), 55.0, w, h))]
+
+
+def footprints(width, height):
+    """(index int64 [n_waves, 64] into the row-major rays of a width x height view, inside bool [n_waves, 64]): lane 8 (y & 7) +
+    (x & 7) of the footprint (x >> 3, y >> 3), footprints row by row"""
+    fx, fy = -(-width // 8), -(-height // 8)
+    lane = np.arange(64)
+    x = (np.arange(fx)[None, :, None] * 8 + (lane & 7)[None, None, :]) + np.zeros((fy, 1, 1), dtype=np.int64)
+    y = (np.arange(fy)[:, None, None] * 8 + (lane >> 3)[None, None, :]) + np.zeros((1, fx, 1), dtype=np.int64)
+    inside = (x < width) & (y < height)
+    idx = np.where(inside, y * width + x, 0)
+    return idx.reshape(-1, 64), inside.reshape(-1, 64)
+
+
+def shadow_rays(rec, lpos):
+    """the shadow rays hit -> light of hit records [m, 12], interval (0, 1)"""
+    r = np.zeros((len(rec), 8), dtype=np.float32)
+    r[:, 0:3] = rec[:, 0:3]
+    r[:, 4:7] = np.asarray(lpos, dtype=np.float32) - rec[:, 0:3]
+    r[:, 7] = 1.0
+    return r
+
+
+def witnesses(oracle, im, pyr, lights, rec, inside, whole, blob_of, mutants=(None,) + MUTANTS, threads=16):
+    """{mutant: [(wave, lane, surface, light)]}: the lanes of the waves rec [n_waves, 64, 12] that a wrong vote would light --
+    the shadow ray is occluded through its plane's whole chain (whole: {plane: snapshot}) and not through the list of the node the mutant picks
+    (blob_of(kept surfaces) -> snapshot; nothing where the word is 0); lanes within BORDER of a cell border and lanes whose
+    mutant reads past the table are left out.  None is the correct vote: it must have no witness.  no_clamp_hi differs from the
+    correct vote only ON the rim line max[a], so its witnesses are counted there and nowhere else (border_clear, hi_rim)."""
+    spos = im.s.view(np.float32)[:, 0:3]
+    flat = rec.reshape(-1, 12)
+    ids = flat.view(np.int32)[:, 7]
+    want = [np.zeros(len(flat), dtype=bool) for _ in lights]
+    for srf, blob in whole.items():
+        on = np.nonzero((ids >= 0) & ((ids >> 1) == srf))[0]
+        for lgt, l in enumerate(lights):
+            want[lgt][on] = oracle.trace_rays(blob, shadow_rays(flat[on], l), "occluded", threads=threads)
+    want = [w.reshape(-1, 64) for w in want]
+    clear, rim = np.zeros((len(rec), 64, len(lights)), dtype=bool), np.zeros((len(rec), 64, len(lights)), dtype=bool)
+    loc = flat[:, 0:3] - spos[np.maximum(ids, 0) >> 1]
+    by_rec = {}
+    for (srf, side, lgt), (p, _) in pyr.items():
+        by_rec.setdefault((srf, lgt), p)
+    for (srf, lgt), p in by_rec.items():
+        on = (ids >= 0) & ((ids >> 1) == srf)
+        c = np.zeros(len(flat), dtype=bool)
+        c[on] = border_clear(p, loc[on])
+        clear[:, :, lgt] |= c.reshape(-1, 64)
+        c = np.zeros(len(flat), dtype=bool)
+        c[on] = border_clear(p, loc[on], hi_rim=True)
+        rim[:, :, lgt] |= c.reshape(-1, 64)
+    kept_of = {}
+    out = {}
+    right = [vote_wave(im, pyr, rec[w], lights, inside[w]) for w in range(len(rec))]
+    for m in mutants:
+        groups = {}
+        for w in range(len(rec)):
+            v = right[w] if m is None else vote_wave(im, pyr, rec[w], lights, inside[w], m)
+            for lgt, (votes, words, _) in v.items():
+                cand = votes & want[lgt][w] & (rim if m == "no_clamp_hi" else clear)[w, :, lgt] & (words >= 0)
+                if m is not None:
+                    cand &= words != right[w][lgt][1]
+                for lane in np.nonzero(cand)[0]:
+                    word = int(words[lane])
+                    if word not in kept_of:
+                        kept_of[word] = tuple(s for _, s, _ in cells(im, word)) if word else ()
+                    groups.setdefault(kept_of[word], []).append((w, int(lane), lgt))
+        found = []
+        for kept, lanes in groups.items():
+            if kept:
+                rays = np.concatenate([shadow_rays(rec[w, lane][None], lights[lgt]) for w, lane, lgt in lanes])
+                got = oracle.trace_rays(blob_of(kept), rays, "occluded", threads=threads)
+            else:
+                got = np.zeros(len(lanes), dtype=bool)
+            found += [(w, lane, int(rec[w, lane].view(np.int32)[7]) >> 1, lgt) for (w, lane, lgt), g in zip(lanes, got) if not g]
+        out[m] = found
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ lattices over a node's patch
+
+def axis_points(a0, a1, lo, hi, thin=False):
+    """across one side of a node's patch: its ends, one ulp either side of them, eight points between (thin: two), kept inside
+    the rectangle [lo, hi]"""
+    f = np.float32
+    ends = [f(a0), np.nextafter(f(a0), f(-np.inf)), np.nextafter(f(a0), f(np.inf)), f(a1), np.nextafter(f(a1), f(-np.inf)), np.nextafter(f(a1), f(np.inf))]
+    pts = np.array(ends + list(np.linspace(a0, a1, 4 if thin else 10, dtype=np.float32)[1:-1]), dtype=np.float32)
+    return np.unique(np.clip(pts, f(lo), f(hi)))
+
+
+def node_shadow_rays(p, geo, l, i, j, light, thin=False):
+    """shadow rays (0, 1) towards `light` from a lattice over the patch of node (l, i, j) of pyramid p on the plane `geo`
+    (plane_geometry: k, a, b, pos, min, max about pos), in world space; thin: fewer interior points, every border point and its
+    two ulp neighbours kept"""
+    k, a, b, pos, lo, hi = geo[:6]
+    sa, sb = (hi[a] - lo[a]) / p.n(l), (hi[b] - lo[b]) / p.n(l)
+    wa, wb = pos[a] + lo[a], pos[b] + lo[b]
+    xs = axis_points(wa + i * sa, wa + (i + 1) * sa, wa, pos[a] + hi[a], thin)
+    ys = axis_points(wb + j * sb, wb + (j + 1) * sb, wb, pos[b] + hi[b], thin)
+    _need(len(xs) * len(ys) <= 64 * 64, "a node's lattice")
+    r = np.zeros((len(xs) * len(ys), 8), dtype=np.float32)
+    r[:, a], r[:, b], r[:, k] = np.repeat(xs, len(ys)), np.tile(ys, len(xs)), pos[k]
+    r[:, 4:7] = np.asarray(light, dtype=np.float32) - r[:, 0:3]
+    r[:, 7] = 1.0                                               # (0, 1): between the plane and the light
+    return r

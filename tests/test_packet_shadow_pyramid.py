@@ -103,24 +103,9 @@ def test_long_lists_get_no_pyramid(qr):
 
 # ---- conservativeness, by the oracle alone -------------------------------------------------------------------------
 
-def _axis_points(a0, a1):
-    """across one side of a node's patch: its ends, one ulp either side of them, eight points between, kept inside the rectangle"""
-    f = np.float32
-    ends = [f(a0), np.nextafter(f(a0), f(-np.inf)), np.nextafter(f(a0), f(np.inf)), f(a1), np.nextafter(f(a1), f(-np.inf)), np.nextafter(f(a1), f(np.inf))]
-    pts = np.array(ends + list(np.linspace(a0, a1, 10, dtype=np.float32)[1:-1]), dtype=np.float32)
-    return np.unique(np.clip(pts, f(-P.HALF), f(P.HALF)))
-
-
-def _shadow_rays(p, l, i, j, light):
-    size = 2.0 * P.HALF / p.n(l)
-    xs = _axis_points(-P.HALF + i * size, -P.HALF + (i + 1) * size)
-    ys = _axis_points(-P.HALF + j * size, -P.HALF + (j + 1) * size)
-    assert len(xs) * len(ys) <= 64 * 64
-    r = np.zeros((len(xs) * len(ys), 8), dtype=np.float32)
-    r[:, 0], r[:, 1] = np.repeat(xs, len(ys)), np.tile(ys, len(xs))
-    r[:, 4:7] = np.asarray(light, dtype=np.float32) - r[:, 0:3]
-    r[:, 7] = 1.0                                               # (0, 1): between the floor and the light
-    return r
+def _shadow_rays(p, geo, l, i, j, light):
+    """the lattice over a node's patch (tests/_pyramid.py node_shadow_rays), on the plane whose a, b, pos and min / max `geo` holds"""
+    return P.node_shadow_rays(p, geo, l, i, j, light)
 
 
 @pytest.mark.parametrize("level", [0, 2])
@@ -133,11 +118,13 @@ def test_nodes_lose_no_occluder(qr, oracle, tmp_path, level):
     n_rays = n_occ = n_short = 0
     for (srf, side, lgt), (p, head) in sorted(pyr.items()):
         assert p.comp == (0, 1) and p.org == (-P.HALF, -P.HALF)
+        geo = P.plane_geometry(blob, srf)
+        assert geo[:3] == (2, 0, 1) and (geo[3] == 0).all() and (geo[4][:2] == -P.HALF).all() and (geo[5][:2] == P.HALF).all()
         by_list = {}
         for (i, j) in p.nodes(level):
             w = p.node(level, i, j)
             kept = tuple(s for _, s, _ in P.cells(im, w)) if w else ()
-            by_list.setdefault(kept, []).append(_shadow_rays(p, level, i, j, P.LIGHTS[lgt]))
+            by_list.setdefault(kept, []).append(_shadow_rays(p, geo, level, i, j, P.LIGHTS[lgt]))
         for kept, rays in by_list.items():
             rays = np.concatenate(rays)
             want = oracle.trace_rays(whole, rays, "occluded", threads=8)
